@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- leapfrog-steps x chains / second of the fused ensemble-HMC hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 With N > 1 and no launcher in the environment (WORLD_SIZE unset) this script starts the N ranks
 itself -- `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
@@ -17,18 +17,30 @@ L leapfrog steps with L+1 gradient evaluations, both Hamiltonians, Metropolis
 accept/reject, and the store of the position AND momentum sample slabs.  Inputs are
 resident in HBM when the timed region starts.  With N > 1 every rank owns its own 65 536
 chains (weak scaling, C4 = 8 x 65 536); the only collective is the RCCL all-gather of sample
-slabs, measured AFTER the timed region: blocking (allgather_ms, bytes, GB/s) and overlapped with the
+slabs, measured with --full AFTER the timed region: blocking (allgather_ms, bytes, GB/s) and overlapped with the
 sampling of the next chunk (collection.overlapped: the exposed time).
 
 value = K * L * N_total_chains / t, t = max over ranks of the barrier-bracketed wall time of
-the K steps that follow EXACTLY W warm-up steps.  `value_steady` is the same measurement repeated
-once the chip has run >= SETTLE iterations in all (its clock needs ~30 ms of this work to settle;
-DESIGN.md section 5); the two agree when W >= SETTLE.
+the K steps that follow EXACTLY W warm-up steps; ms_per_step = t / K.  A plain run does only
+that: set-up, W warm-up steps, the K timed steps, the outputs (--dump-outputs) and the JSON line.
+The sample slabs take at most SLAB_BYTES of device memory: longer runs cycle through them (slab_count).
 
-At N = 1 the same JSON line also carries, under "other_workloads", the lines of BASELINE configs C3
-(Rosenbrock d=32, 262 144 chains; PBBI_KDK_FMA and reference operation order), C5 (d=4096 dense,
-fp32, 8 192 chains), of a dense Gaussian at d=256 (fp64, the streamed-P kernel) and of C2 through the class API's default rng="numpy" mode, measured after the headline (`--no-extras` skips them; `--workload c3|c5|
-stream|parity` prints one of them as its own line instead).
+--dump-outputs DIR writes what the last timed step computed on rank 0, for a fixed sample of
+DUMP_CHAINS chains (RandomState(0), sorted; all chains when there are fewer): DIR/samples.npy and
+DIR/momenta.npy (D, n) float64, DIR/reject.npy (n,) float64.  The inputs depend on the arguments
+only, so two builds can be compared file for file.
+
+--full adds everything else, measured after the headline:
+  - `value_steady`: the same measurement repeated once the chip has run >= SETTLE iterations in
+    all (its clock needs ~30 ms of this work to settle); the two agree when
+    W >= SETTLE.  The roofline block uses both.
+  - N = 1: the CPU baseline (`--no-cpu-baseline` skips it) and, under "other_workloads", the lines
+    of C2 with the f64 draw, BASELINE configs C3 (Rosenbrock d=32, 262 144 chains; PBBI_KDK_FMA and
+    reference operation order), C5 (d=4096 dense, fp32, 8 192 chains), of a dense Gaussian at
+    d=256 (fp64, the streamed-P kernel) and of C2 through the class API's default rng="numpy"
+    mode (`--no-extras` skips them).
+  - N > 1: the all-gather of sample slabs (collection).
+`--workload c3|c5|stream|parity|dense|gist` prints one of the other workloads as its own line instead.
 """
 import argparse
 import json
@@ -52,6 +64,25 @@ FP64_MFMA_PEAK_TFLOPS = 78.6   # MI355X fp64 matrix = fp64 vector peak (BASELINE
 FP32_MFMA_PEAK_TFLOPS = 157.3
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8 TB/s spec
 UNIT = "leapfrog-steps*chains/s"
+DUMP_CHAINS = 16384  # --dump-outputs: 2 x 16 MiB of float64 slabs at D = 128 (a whole slab is 64 MiB)
+SLAB_BYTES = 16 << 30  # device memory for the sample / momentum / decision slabs of one workload
+
+
+def slab_count(K, bytes_per_iteration):
+    """Slabs to allocate for runs of K iterations: K while they fit in SLAB_BYTES (C2: 128 iterations), else a
+    ring that longer runs pass through in chunks of that many iterations, one pbbi_hmc_run per chunk (the
+    chains' state and draws continue from chunk to chunk: the samples are those of one run)."""
+    return max(1, min(K, SLAB_BYTES // int(bytes_per_iteration)))
+
+
+def chunk_sizes(K, S_alloc):
+    """The pbbi_hmc_run calls of a run of K iterations through S_alloc slabs (run() in the workloads)."""
+    return [S_alloc] * (K // S_alloc) + ([K % S_alloc] if K % S_alloc else [])
+
+
+def dump_chain_index(n):
+    """The chains --dump-outputs writes: a fixed sample (RandomState(0)) of n, sorted."""
+    return np.sort(np.random.RandomState(0).permutation(n)[:min(n, DUMP_CHAINS)])
 
 
 def precision_matrix(d):
@@ -143,9 +174,10 @@ def cpu_baseline(Pm, L, seconds_target=4.0):
 RETRY_STALLED = False   # set for the embedded extra lines (main): see timed_runs
 
 
-def timed_runs(run, K, W, settle, barrier=lambda: None, reduce_max=lambda t: t):
-    """W warm-up steps, then K timed steps (`first`); then further untimed steps until `settle`
-    have run in all, then K timed steps again (`steady`).  run(S, iter0) enqueues S iterations.
+def timed_runs(run, K, W, settle, barrier=lambda: None, reduce_max=lambda t: t, steady=True, after_first=None):
+    """W warm-up steps, then K timed steps (`first`), then after_first(); with `steady`, further
+    untimed steps until `settle` have run in all, then K timed steps again (`steady`, else None).
+    run(S, iter0) enqueues S iterations.
     Each timing is (wall seconds max over ranks, HIP-event milliseconds on the launch stream).
     The supplementary lines measured later in the same process (RETRY_STALLED) repeat a timing ONCE when its wall
     time is more than 1.5 x its device time: a second workload in one process meets a single ~65 ms device-wide
@@ -176,6 +208,10 @@ def timed_runs(run, K, W, settle, barrier=lambda: None, reduce_max=lambda t: t):
     if RETRY_STALLED and first[0] * 1e3 > 1.5 * first[1] + 1.0:
         first = once(done)
         done += K
+    if after_first is not None:
+        after_first()
+    if not steady:
+        return first, None
     if done < settle:
         run(settle - done, done)
         done = settle
@@ -203,7 +239,7 @@ def bench_c3(args, exact_order):
     _lib.call("pbbi_philox_normal", 7, _lib.STREAM_POSITION, 0, 0, d, N, N, 0.1, None, _lib.F64, 0,
               q.data_ptr(), stream)
     q += 1.0  # q0 ~ N(1, 0.1^2): trajectories stay finite
-    S_alloc = max(K, 1)
+    S_alloc = slab_count(K, (2 * d * 8 + 1) * N)
     samples = torch.empty((S_alloc, d, N), dtype=torch.float64, device="cuda")
     momenta = torch.empty((S_alloc, d, N), dtype=torch.float64, device="cuda")
     reject = torch.empty((S_alloc, N), dtype=torch.uint8, device="cuda")
@@ -219,7 +255,7 @@ def bench_c3(args, exact_order):
     # pbbi_hmc_run fuses up to 16 consecutive iterations into ONE launch of k_ros2_hmc (the chain stays
     # in registers); ks / kss are per ITERATION, a launch covers K / n_launches of them
     fuse = int(os.environ.get("PBBI_FUSE_ITERS", "16"))
-    n_launches = -(-K // max(fuse, 1))
+    n_launches = sum(-(-s // max(fuse, 1)) for s in chunk_sizes(K, S_alloc))
     ks, kss = ev * 1e-3 / K, evs * 1e-3 / K
     bytes_alg = bytes_per_step_chain(d, L) * L * N
     ipl = K / n_launches
@@ -283,7 +319,7 @@ def bench_stream(args):
     _lib.call("pbbi_philox_normal", 7, _lib.STREAM_POSITION, 0, 0, d, N, N, 0.1, None, code, 0,
               q.data_ptr(), stream)
     q += 1.0
-    S_alloc = max(K, 1)
+    S_alloc = slab_count(K, (2 * d * w + 1) * N)
     samples = torch.empty((S_alloc, d, N), dtype=tdt, device="cuda")
     momenta = torch.empty((S_alloc, d, N), dtype=tdt, device="cuda")
     reject = torch.empty((S_alloc, N), dtype=torch.uint8, device="cuda")
@@ -333,7 +369,7 @@ def bench_dense(args):
     stream = torch.cuda.current_stream().cuda_stream
     q = torch.empty((d, N), dtype=torch.float64, device="cuda")
     _lib.call("pbbi_philox_normal", 7, _lib.STREAM_POSITION, 0, 0, d, N, N, 1.0, None, _lib.F64, 0, q.data_ptr(), stream)
-    S_alloc = max(K, 1)
+    S_alloc = slab_count(K, (2 * d * 8 + 1) * N)
     samples = torch.empty((S_alloc, d, N), dtype=torch.float64, device="cuda")
     momenta = torch.empty((S_alloc, d, N), dtype=torch.float64, device="cuda")
     reject = torch.empty((S_alloc, N), dtype=torch.uint8, device="cuda")
@@ -351,7 +387,8 @@ def bench_dense(args):
     carried = "carried between iterations: yes" in route
     ks, kss = ev * 1e-3 / K, evs * 1e-3 / K
     flops_alg = flops_per_step_chain(d, L) * L * N
-    flops_exec = (2.0 * d * d * ((L + 1.0 / K) if carried else L + 1) + 11.0 * d * L + 8.0 * d) * N
+    runs = len(chunk_sizes(K, S_alloc))   # each pbbi_hmc_run forms g(q_0) once: L + 1 mat-vecs in its first iteration
+    flops_exec = (2.0 * d * d * ((L + runs / K) if carried else L + 1) + 11.0 * d * L + 8.0 * d) * N
     traffic = src = None
     if d == 256 and N == 65536 and carried:  # the committed --pmc passes of tools/run_profiles_dstream.sh
         traffic, src = profile_json("r*_pmc_dense_d256.json", "hbm_bytes_per_iteration")
@@ -429,7 +466,7 @@ def bench_c5(args):
     q = torch.empty((d, N), dtype=torch.float32, device="cuda")
     _lib.call("pbbi_philox_normal", 7, _lib.STREAM_POSITION, 0, 0, d, N, N, 1.0, None, _lib.F32, 0,
               q.data_ptr(), stream)
-    S_alloc = max(K, 1)
+    S_alloc = slab_count(K, (2 * d * 4 + 1) * N)
     samples = torch.empty((S_alloc, d, N), dtype=torch.float32, device="cuda")
     momenta = torch.empty((S_alloc, d, N), dtype=torch.float32, device="cuda")
     reject = torch.empty((S_alloc, N), dtype=torch.uint8, device="cuda")
@@ -525,7 +562,7 @@ def bench_c2(args, rank, world, local_rank):
     q_state = torch.empty((D, N), dtype=torch.float64, device=f"cuda:{dev}")
     _lib.call("pbbi_philox_normal", seed, _lib.STREAM_POSITION, 0, chain0, D, N, N, 1.0, None,
               _lib.F64, dev, q_state.data_ptr(), stream)
-    S_alloc = max(K, 1)
+    S_alloc = slab_count(K, (2 * D * 8 + 1) * N)
     samples = torch.empty((S_alloc, D, N), dtype=torch.float64, device=f"cuda:{dev}")
     momenta = torch.empty((S_alloc, D, N), dtype=torch.float64, device=f"cuda:{dev}")
     reject = torch.empty((S_alloc, N), dtype=torch.uint8, device=f"cuda:{dev}")
@@ -548,7 +585,18 @@ def bench_c2(args, rank, world, local_rank):
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             return float(tt.item())
         return t
-    (t, dev_ms), (ts, dev_ms_s) = timed_runs(run, K, W, SETTLE, barrier, reduce_max)
+
+    dumped = {}
+
+    def capture():
+        # the last timed step is in slab (K - 1) % S_alloc (the steady run of --full reuses the slabs afterwards)
+        last = (K - 1) % S_alloc
+        ii = torch.from_numpy(dump_chain_index(N)).to(samples.device)
+        dumped.update(samples=samples[last][:, ii].cpu().numpy(), momenta=momenta[last][:, ii].cpu().numpy(),
+                      reject=reject[last][ii].cpu().numpy().astype(np.float64))
+    full = args.full
+    (t, dev_ms), steady = timed_runs(run, K, W, SETTLE, barrier, reduce_max, steady=full,
+                                     after_first=capture if rank == 0 and args.dump_outputs else None)
     accept = 1.0 - float(reject[:K].float().mean().item())
 
     # sample collection (outside the timed loop): (1) ONE blocking all-gather of a chunk of slabs over
@@ -556,7 +604,7 @@ def bench_c2(args, rank, world, local_rank):
     # (distributed.OverlappedGather: side stream, two send / two receive buffers) against the same sampling
     # without any collection -- the difference is what the collection costs when it is overlapped
     collect = None
-    if world > 1:
+    if world > 1 and full:
         from physicsbasedbayesianinference_amd.distributed import OverlappedGather, gather_blocks
         c = max(1, min(K, 8))                       # slabs per chunk: 8 x 64 MiB per rank at C2
         n_chunks = 4
@@ -601,26 +649,6 @@ def bench_c2(args, rank, world, local_rank):
     if rank != 0:
         return None
     total_chains = N * world
-    kernel_s = dev_ms * 1e-3 / K  # average launch duration from HIP events on the launch stream
-    kernel_ss = dev_ms_s * 1e-3 / K
-    flops_launch = flops_per_step_chain(D, L) * L * N
-    bytes_launch = bytes_per_step_chain(D, L) * L * N
-    traffic, traffic_src = profile_json("r*_pmc.json", "k_dense_hmc_hbm_bytes_per_iteration")
-    # pbbi_hmc_run carries the gradient of the chain's position from one iteration to the next (an
-    # accepted chain starts from the point whose gradient the last mat-vec just formed, a rejected one from
-    # the point it started at) and covers up to PBBI_DENSE_FUSE (64) iterations per launch: L mat-vecs per
-    # iteration are EXECUTED where SURVEY 8d's algorithmic figure counts L + 1.  Both rates are reported.
-    carried = os.environ.get("PBBI_NO_CARRY") is None
-    fuse_max = max(1, int(os.environ.get("PBBI_DENSE_FUSE", "64"))) if carried else 1
-    # a timed run = one pbbi_hmc_run of K iterations in equal fused launches (the first iteration of the run
-    # forms g(q_0) inside its launch: L + 1 mat-vecs once per run, counted below)
-    n_launch = -(-K // fuse_max) if (fuse_max > 1 and K > 1) else K
-    fuse = K / n_launch
-    matvecs = (L + 1.0 / K) if carried else L + 1  # per iteration, averaged over the timed run
-    flops_exec = (2.0 * D * D * matvecs + 11.0 * D * L + 8.0 * D) * N
-    # both sample slabs + decisions written; the carried gradient read and g(q_new) written; the position is
-    # read once per launch (the momentum is drawn in the kernel: SURVEY 8d's figure counts a read for it)
-    bytes_exec = ((2.0 * D * 8 + 1) * N + D * 8.0 * N / fuse + 2.0 * D * 8 * N) if carried else bytes_launch
     out = {
         "metric": "leapfrog-steps*chains/sec (node); d=128 Gaussian, ensemble=65536",
         "value": K * L * total_chains / t,
@@ -634,9 +662,6 @@ def bench_c2(args, rank, world, local_rank):
         "vs_baseline": None,
         "dtype": "f64",
         "data": "synthetic",
-        "value_steady": K * L * total_chains / ts,
-        "ms_per_step_steady": ts * 1e3 / K,
-        "steady_after_steps": max(SETTLE, W + K),
         "config": {"workload": "C2: d=128 dense-precision Gaussian, fp64, L=10 leapfrog steps "
                                "per HMC iteration, in-kernel Philox momentum + Metropolis",
                    "chains_per_gpu": N, "total_chains": total_chains, "D": D, "L": L,
@@ -644,23 +669,55 @@ def bench_c2(args, rank, world, local_rank):
                    "accept_rate": accept,
                    "draw": "f64 (PBBI_DRAW_F64: double-precision Box-Muller, bit-identical to the oracle)" if f64
                    else "f32 (single-precision Box-Muller on the transcendental unit; momenta only)"},
-        "roofline": roofline(
-            "mfma", "k_dense_hmc<8, full, hmc, zero-mean" + (", carried gradient, fused iterations>" if carried else ">"),
-            FP64_MFMA_PEAK_TFLOPS, "TFLOP/s", kernel_s, kernel_ss, flops_exec, flops_launch,
-            ("the L gradient mat-vecs + updates + energies an iteration performs (the gradient at the chain's "
-             "position is carried between iterations, bit-identical samples); frac_algorithmic = SURVEY 8d's count "
-             "with L + 1 mat-vecs") if carried else "L + 1 gradient mat-vecs + updates + energies (SURVEY 8d)",
-            traffic=traffic, traffic_source=traffic_src,
-            algorithmic_bytes_per_iteration=bytes_launch, required_bytes_per_iteration=bytes_exec,
-            iterations_per_launch=fuse, launch_ms=kernel_s * 1e3 * fuse, launch_ms_steady=kernel_ss * 1e3 * fuse,
-            hbm_required_GBs=bytes_exec / kernel_s / 1e9,
-            hbm_frac_of_8TBs=bytes_exec / kernel_s / 1e9 / HBM_PEAK_GBS),
     }
+    if full:
+        ts, dev_ms_s = steady
+        kernel_s = dev_ms * 1e-3 / K  # average launch duration from HIP events on the launch stream
+        kernel_ss = dev_ms_s * 1e-3 / K
+        flops_launch = flops_per_step_chain(D, L) * L * N
+        bytes_launch = bytes_per_step_chain(D, L) * L * N
+        traffic, traffic_src = profile_json("r*_pmc.json", "k_dense_hmc_hbm_bytes_per_iteration")
+        # pbbi_hmc_run carries the gradient of the chain's position from one iteration to the next (an
+        # accepted chain starts from the point whose gradient the last mat-vec just formed, a rejected one from
+        # the point it started at) and covers up to PBBI_DENSE_FUSE (64) iterations per launch: L mat-vecs per
+        # iteration are EXECUTED where SURVEY 8d's algorithmic figure counts L + 1.  Both rates are reported.
+        carried = os.environ.get("PBBI_NO_CARRY") is None
+        fuse_max = max(1, int(os.environ.get("PBBI_DENSE_FUSE", "64"))) if carried else 1
+        # a timed run = one pbbi_hmc_run per chunk of the slab ring, each in equal fused launches (the first
+        # iteration of a pbbi_hmc_run forms g(q_0) inside its launch: L + 1 mat-vecs once per call, counted below)
+        chunks = chunk_sizes(K, S_alloc)
+        n_launch = sum(-(-s // fuse_max) if (fuse_max > 1 and s > 1) else s for s in chunks)
+        fuse = K / n_launch
+        matvecs = (L + len(chunks) / K) if carried else L + 1  # per iteration, averaged over the timed run
+        flops_exec = (2.0 * D * D * matvecs + 11.0 * D * L + 8.0 * D) * N
+        # both sample slabs + decisions written; the carried gradient read and g(q_new) written; the position is
+        # read once per launch (the momentum is drawn in the kernel: SURVEY 8d's figure counts a read for it)
+        bytes_exec = ((2.0 * D * 8 + 1) * N + D * 8.0 * N / fuse + 2.0 * D * 8 * N) if carried else bytes_launch
+        out.update({
+            "value_steady": K * L * total_chains / ts,
+            "ms_per_step_steady": ts * 1e3 / K,
+            "steady_after_steps": max(SETTLE, W + K),
+            "roofline": roofline(
+                "mfma", "k_dense_hmc<8, full, hmc, zero-mean" + (", carried gradient, fused iterations>" if carried else ">"),
+                FP64_MFMA_PEAK_TFLOPS, "TFLOP/s", kernel_s, kernel_ss, flops_exec, flops_launch,
+                ("the L gradient mat-vecs + updates + energies an iteration performs (the gradient at the chain's "
+                 "position is carried between iterations, bit-identical samples); frac_algorithmic = SURVEY 8d's count "
+                 "with L + 1 mat-vecs") if carried else "L + 1 gradient mat-vecs + updates + energies (SURVEY 8d)",
+                traffic=traffic, traffic_source=traffic_src,
+                algorithmic_bytes_per_iteration=bytes_launch, required_bytes_per_iteration=bytes_exec,
+                iterations_per_launch=fuse, launch_ms=kernel_s * 1e3 * fuse, launch_ms_steady=kernel_ss * 1e3 * fuse,
+                hbm_required_GBs=bytes_exec / kernel_s / 1e9,
+                hbm_frac_of_8TBs=bytes_exec / kernel_s / 1e9 / HBM_PEAK_GBS),
+        })
     if collect is not None:
         out["allgather_ms"] = collect["allgather_ms"]
         out["collection"] = collect
     del samples, momenta, reject   # (left in torch's cache: the f64-draw line re-uses the same blocks)
-    if world == 1 and not args.no_cpu_baseline:
+    if dumped:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in dumped.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+    if world == 1 and full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(Pm, L)
     return out
 
@@ -687,16 +744,22 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=100,
                     help="untimed iterations before the timed ones; `value` is measured after exactly "
-                         "this many (~100 = 35 ms lets the chip settle its clock; value_steady reports "
-                         "the settled rate whatever W is)")
+                         "this many (~100 = 35 ms lets the chip settle its clock; with --full, value_steady "
+                         "reports the settled rate whatever W is)")
     ap.add_argument("--chains", type=int, default=N_PER_GPU, help="chains per GPU (C2, stream, parity)")
     ap.add_argument("--chains-c3", type=int, default=262144)
     ap.add_argument("--chains-c5", type=int, default=8192)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="c2: also the steady-state rate, the roofline, the CPU baseline and the other workloads "
+                         "(N = 1), the sample collection (N > 1); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="c2: write the last timed step's samples / momenta / reject decisions of a fixed sample "
+                         "of rank 0's chains to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="N = 1: skip the C3 / C5 lines embedded under other_workloads")
+                    help="--full, N = 1: skip the lines embedded under other_workloads")
     ap.add_argument("--workload", default="c2", choices=["c2", "c3", "c5", "stream", "parity", "dense", "gist"],
-                    help="c2 (default, the BASELINE metric, with C3/C5 embedded at N = 1); c3 / c5 / "
+                    help="c2 (default, the BASELINE metric, with C3/C5 embedded at N = 1 under --full); c3 / c5 / "
                          "stream / parity print that workload's own line")
     ap.add_argument("--exact-order", action="store_true",
                     help="--workload c3 / stream: the bit-exact velocity-Verlet kernels instead of PBBI_KDK_FMA")
@@ -716,6 +779,8 @@ def main():
         args.workload = "parity"
     if args.steps < 1 or args.warmup < 0 or args.gpus < 1:
         ap.error("--steps >= 1, --warmup >= 0, --gpus >= 1")
+    if args.dump_outputs and args.workload != "c2":
+        ap.error("--dump-outputs goes with --workload c2")
 
     if args.workload != "c2":
         fn = {"c3": lambda: bench_c3(args, args.exact_order), "c5": lambda: bench_c5(args), "dense": lambda: bench_dense(args), "gist": lambda: bench_gist(args),
@@ -750,11 +815,11 @@ def main():
             dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
     try:
         out = bench_c2(args, rank, world, local_rank)
-        if rank == 0 and world == 1 and not args.no_extras:
+        if rank == 0 and world == 1 and args.full and not args.no_extras:
             extras = {}
             def c2_f64():
                 a2 = argparse.Namespace(**vars(args))
-                a2.draw, a2.no_cpu_baseline = "f64", True
+                a2.draw, a2.no_cpu_baseline, a2.dump_outputs = "f64", True, None
                 return bench_c2(a2, rank, world, local_rank)
             global RETRY_STALLED
             RETRY_STALLED = True

@@ -347,6 +347,86 @@ def test_bench_self_launches_the_ranks(monkeypatch):
     assert len(calls) == 1
 
 
+def test_bench_plain_run_times_the_steps_asked_for_and_dumps_the_last(monkeypatch, tmp_path, capsys):
+    """The C2 line with the device calls stubbed: a plain run enqueues exactly W warm-up and K timed iterations
+    and prints the headline only; --dump-outputs writes the last timed iteration's slabs for a fixed sample of
+    the chains; --full adds the steady rate and the roofline and dumps the same iteration; a run longer than the
+    slabs that fit in SLAB_BYTES goes through them in chunks and still dumps its last iteration."""
+    import importlib
+    import json
+    import time
+    import types
+    import torch
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    import physicsbasedbayesianinference_amd as P
+    from physicsbasedbayesianinference_amd import _lib
+    tensors, runs = {}, []
+    real_empty = torch.empty
+
+    def empty(*a, device=None, **k):
+        t = real_empty(*a, **k)
+        tensors[t.data_ptr()] = t
+        return t
+
+    class Event:
+        def __init__(self, **k):
+            self.t = 0.0
+
+        def record(self):
+            self.t = time.perf_counter()
+
+        def elapsed_time(self, other):
+            return (other.t - self.t) * 1e3
+
+    def call(name, *a):
+        if name == "pbbi_hmc_run":   # slab i of a run starting at iteration it0 holds it0 + i
+            s, it0 = a[12], a[15]
+            runs.append((s, it0))
+            for i in range(s):
+                tensors[a[4]][i].fill_(it0 + i)
+                tensors[a[5]][i].fill_(-(it0 + i))
+                tensors[a[6]][i].fill_((it0 + i) % 2)
+    monkeypatch.setattr(torch, "empty", empty)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    monkeypatch.setattr(torch.cuda, "Event", Event)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda: types.SimpleNamespace(cuda_stream=0))
+    monkeypatch.setattr(torch.cuda, "set_device", lambda d: None)
+    monkeypatch.setattr(_lib, "load", lambda: None)
+    monkeypatch.setattr(_lib, "call", call)
+    monkeypatch.setattr(P, "GaussianDense", lambda *a, **k: types.SimpleNamespace(handle=None))
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    n = bench.DUMP_CHAINS + 5
+    lines = {}
+    for mode in ("plain", "full", "ring"):
+        if mode == "ring":   # room for two iterations' slabs
+            monkeypatch.setattr(bench, "SLAB_BYTES", 2 * (2 * bench.D * 8 + 1) * n + 1)
+        runs.clear()
+        argv = ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2", "--chains", str(n),
+                "--dump-outputs", str(tmp_path / mode)]
+        monkeypatch.setattr(sys, "argv", argv + (["--full", "--no-cpu-baseline", "--no-extras"] if mode == "full" else []))
+        assert bench.main() == 0
+        lines[mode] = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+        if mode == "ring":
+            assert runs == [(2, 0), (2, 2), (1, 4)]
+        else:
+            assert runs[:2] == [(2, 0), (3, 2)]
+        d = {f: np.load(tmp_path / mode / (f + ".npy")) for f in ("samples", "momenta", "reject")}
+        assert d["samples"].shape == d["momenta"].shape == (bench.D, bench.DUMP_CHAINS)
+        assert d["reject"].shape == (bench.DUMP_CHAINS,) and all(a.dtype == np.float64 for a in d.values())
+        assert np.all(d["samples"] == 4) and np.all(d["momenta"] == -4) and np.all(d["reject"] == 0)
+        if mode == "full":
+            assert runs[-1] == (3, bench.SETTLE)   # the steady run after SETTLE iterations in all
+    plain, full = lines["plain"], lines["full"]
+    assert plain["steps"] == 3 and plain["warmup"] == 2 and plain["ms_per_step"] > 0 and plain["higher_is_better"]
+    assert plain["dtype"] == "f64" and plain["unit"] == bench.UNIT
+    assert not {"value_steady", "roofline", "cpu_baseline", "other_workloads"} & set(plain)
+    assert {"value_steady", "ms_per_step_steady", "roofline"} <= set(full)
+    idx = bench.dump_chain_index(n)
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n and len(idx) == bench.DUMP_CHAINS
+    assert list(bench.dump_chain_index(7)) == list(range(7))
+
+
 def test_warmup_key_and_flag_values_match_the_header():
     """The Python constants mirror include/pbbi.h (flags, streams) and the warm-up key differs from any seed."""
     from physicsbasedbayesianinference_amd import _lib

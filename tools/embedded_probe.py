@@ -5,7 +5,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
 from physicsbasedbayesianinference_amd import _lib
-a = argparse.Namespace(chains=65536, steps=100, warmup=100, no_cpu_baseline=True, draw="f32")
+a = argparse.Namespace(chains=65536, steps=100, warmup=100, no_cpu_baseline=True, draw="f32", full=True,
+                       dump_outputs=None)
 for k in range(3):
     a.draw = "f64" if k == 1 else "f32"
     t0 = time.perf_counter()

@@ -32,7 +32,8 @@ def timed_sync(*a, **k):
 
 
 torch.cuda.synchronize = timed_sync
-a = argparse.Namespace(chains=65536, steps=100, warmup=100, no_cpu_baseline=(variant == "nocpu"), draw="f32")
+a = argparse.Namespace(chains=65536, steps=100, warmup=100, no_cpu_baseline=(variant == "nocpu"), draw="f32",
+                       full=True, dump_outputs=None)
 o = bench.bench_c2(a, 0, 1, 0)
 print("headline value %.4g steady %.4g" % (o["value"], o["value_steady"]), flush=True)
 if variant == "sleep":

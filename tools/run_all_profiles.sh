@@ -10,7 +10,7 @@ R=$O/prof_$tag
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/kt_c3 -- python3 bench.py --workload c3 > $R/kt_c3.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/kt_c3x -- python3 bench.py --workload c3 --exact-order > $R/kt_c3x.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/kt_c5 -- python3 bench.py --workload c5 > $R/kt_c5.log 2>&1
-python3 bench.py > $O/bench_${tag}.json 2> $O/bench_${tag}.err
+python3 bench.py --full > $O/bench_${tag}.json 2> $O/bench_${tag}.err
 python3 bench.py --workload c3 > $O/bench_${tag}_c3.json 2>> $O/bench_${tag}.err
 python3 bench.py --workload c3 --exact-order > $O/bench_${tag}_c3_exact.json 2>> $O/bench_${tag}.err
 python3 bench.py --workload c5 > $O/bench_${tag}_c5.json 2>> $O/bench_${tag}.err

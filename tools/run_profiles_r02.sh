@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-2 profiles.  Run on the GPU box (via gpurun):  tools/run_profiles_r02.sh [tag]
-#   kt        rocprofv3 --kernel-trace --stats of the DEFAULT bench.py run (C2 headline + C3 / C5 extras)
+#   kt        rocprofv3 --kernel-trace --stats of the bench.py --full run (C2 headline + C3 / C5 extras)
 #   pmc_*     separate --pmc passes (SQ set, FETCH_SIZE, WRITE_SIZE) over small fixed workloads
 # Summarise with tools/summarize_profiles_r02.py <tag> -> profiles/<tag>_*
 set -e
@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 R=$PWD/gpurun_out/prof_$tag
 rm -rf $R
 mkdir -p $R
-rocprofv3 --kernel-trace --stats --output-format csv -d $R/kt -- python3 bench.py --no-cpu-baseline > $R/kt.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $R/kt -- python3 bench.py --full --no-cpu-baseline > $R/kt.log 2>&1
 tail -c 400 $R/kt.log | head -c 300; echo
 SQ="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAIT_ANY"
 for w in workload c3 c5; do
