@@ -21,6 +21,7 @@ UTURN_STOP = 16
 DRAW_F64 = 32            # momenta drawn in double precision (include/pbbi.h)
 STREAM_MOMENTUM, STREAM_POSITION, STREAM_UNIFORM, STREAM_STEPS = 0, 1, 2, 3
 STREAM_SWAP = 4
+STREAM_RESAMPLE = 5      # the stage uniform of systematic resampling (pbbi_smc_resample_systematic)
 STREAM_DRAW_F64 = 0x100  # OR-ed into pbbi_philox_normal's rng_stream: the draw DRAW_F64 selects
 
 
@@ -81,6 +82,12 @@ PROTOTYPES = {
     "pbbi_reduce_min": [_vp, _i64, _i, _i, _vp, _vp],
     "pbbi_canonical_weights": [_vp, _i64, _d, _vp, _i, _i, _vp, _vp, _vp],
     "pbbi_scale_inverse": [_vp, _i64, _vp, _i, _i, _vp],
+    # tempered SMC (smc.py)
+    "pbbi_smc_ess_scan": [_vp, _vp, _vp, _vp, _d, _i64, _i64, _i, _i, _vp, _i, _i, _vp, _vp],
+    "pbbi_smc_next_beta": [_vp, _vp, _vp, _vp, _d, _i64, _i64, _i, _d, _vp, _vp, _i, _i, _vp],
+    "pbbi_smc_reweight": [_vp, _vp, _vp, _d, _i64, _i64, _i, _vp, _vp, _vp, _vp, _i, _i, _vp],
+    "pbbi_smc_resample_systematic": [_vp, _i64, _u64, _u64, _vp, _vp, _i64, _i, _vp, _d, _vp, _vp, _vp, _vp, _i, _i,
+                                     _vp],
 }
 
 _lib = None
