@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "pbbi_internal.h"
+#include "pbbi_chain.h"
 #include "pbbi_rng.h"
 
 namespace {
@@ -767,7 +768,7 @@ __global__ void k_big_decide(const T* pp_old_part, const T* pp_new_part, int n_s
     const T newH = T(0.5) * pn / m + (T(0.5) * xn + cst);
     const T ratio = exp((oldH - newH) * beta);
     const T u = rng ? (T)rng_uniform(seed, iter, chain0 + (uint64_t)n) : u_in[n];
-    const bool rej = (ratio == ratio) && (u > (ratio < T(1) ? ratio : T(1)));
+    const bool rej = metropolis_reject(ratio, u);
     reject[n] = rej ? 1 : 0;
     if (ratio_out) ratio_out[n] = ratio;
 }

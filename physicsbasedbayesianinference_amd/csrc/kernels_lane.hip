@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "pbbi_buf.h"
+#include "pbbi_chain.h"
 #include "pbbi_internal.h"
 #include "pbbi_rng.h"
 
@@ -315,8 +316,7 @@ __global__ void __launch_bounds__(BLOCK) k_lane_hmc(HmcPrm<T> prm, Pot pot) {
         const T U_new = pot.U(q);
         const T newH = kinetic<T, DMAX>(p, m) + U_new;  // p -> -p leaves dot(p,p) unchanged
         const T ratio = exp((oldH - newH) * (T)pbbi_accept_beta(prm.flags, prm.kT));  // src/HMC.py:115
-        // mask = u > min(1, ratio); NaN ratio compares False => accepted (src/HMC.py:168-173)
-        const bool reject = (ratio == ratio) && (u > (ratio < T(1) ? ratio : T(1)));
+        const bool reject = metropolis_reject(ratio, u);
         U_cur = reject ? U_old : U_new;
         if (reject) {
 #pragma unroll
@@ -437,7 +437,7 @@ __global__ void __launch_bounds__(BLOCK) k_lane_dyn_hmc(DynPrm<T> dp, Pot pot) {
                                                               (prm.flags & PBBI_UTURN_STOP) != 0);
     const T newH = hamiltonian<T, Pot, DMAX>(pot, q, p, m);
     const T ratio = exp((oldH - newH) * (T)pbbi_accept_beta(prm.flags, prm.kT));  // src/HMC.py:115
-    const bool reject = (ratio == ratio) && (u > (ratio < T(1) ? ratio : T(1)));
+    const bool reject = metropolis_reject(ratio, u);
     if (reject) {
 #pragma unroll
         for (int d = 0; d < DMAX; ++d) q[d] = load_row<T, FULL>(bq, voff, rin, d, D);  // :175
@@ -515,7 +515,7 @@ __global__ void __launch_bounds__(BLOCK) k_lane_gist_hmc(DynPrm<T> dp, Pot pot) 
     const double hr = (double)exp((oldH - newH) * (T)pbbi_accept_beta(prm.flags, prm.kT));
     const double ratio = (L <= tau_b) ? hr * ((double)tau_f / (double)tau_b) : 0.0;
     const double u = rng_uniform(prm.seed, prm.iter, chain);
-    const bool reject = (ratio == ratio) && (u > (ratio < 1.0 ? ratio : 1.0));
+    const bool reject = metropolis_reject(ratio, u);
     if (reject) {
         load_q();
 #pragma unroll

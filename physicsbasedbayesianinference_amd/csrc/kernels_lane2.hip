@@ -20,6 +20,7 @@
 #include <cstdlib>
 
 #include "pbbi_buf.h"
+#include "pbbi_chain.h"
 #include "pbbi_internal.h"
 #include "pbbi_rng.h"
 
@@ -373,7 +374,7 @@ __device__ __forceinline__ void ros2_tile(const Ros2Prm& prm, const Ros2<FULL>& 
     RSTAMP(n0 / CHAINS_PER_BLOCK, 3);
     const double ratio = exp((oldH - newH) * pbbi_accept_beta(prm.flags, prm.kT));  // src/HMC.py:115
     const double u = prm.rng ? rng_uniform(prm.seed, prm.iter, chain) : prm.u_in[n0 + cc];
-    const bool reject = (ratio == ratio) && (u > (ratio < 1.0 ? ratio : 1.0));
+    const bool reject = metropolis_reject(ratio, u);
     U_carry = reject ? U_old : U_new;  // U of the position the chain holds now (both lanes of a chain decide alike)
     if constexpr (!KDK && !DYN) a_valid = (__builtin_amdgcn_ballot_w64(reject) == 0);
     if (reject) {

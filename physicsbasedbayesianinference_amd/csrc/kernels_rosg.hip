@@ -15,6 +15,7 @@
 #include <cstdlib>
 
 #include "pbbi_buf.h"
+#include "pbbi_chain.h"
 #include "pbbi_internal.h"
 #include "pbbi_rng.h"
 
@@ -49,16 +50,6 @@ __device__ __forceinline__ double part_sum(double x) {  // sum over the G lanes 
     return x;
 }
 
-// Where the iterations of a fused run put their results (pbbi_hmc_run, IterArgs::fuse_*; as Ros2Run in
-// kernels_lane2.hip).
-struct RosgRun {
-    int S;            // iterations in this launch (1: plain pbbi_hmc_iter semantics)
-    int wrap2;        // position slabs alternate between slab 0 and 1 of q_base (burn-in)
-    int64_t slab0;    // index of the first iteration's position slab
-    int64_t slab;     // elements per slab (D * N)
-    double* q_base;   // slab 0 of the position slabs
-};
-
 // run.S > 1: the wave keeps its chains in registers for run.S consecutive iterations, and the potential
 // energy of the position an iteration starts from is the one the previous iteration formed (carried in a
 // register, the same value), as in k_ros2_hmc.
@@ -66,7 +57,7 @@ struct RosgRun {
 // kick's shuffles need the whole wave), a finished chain is frozen by per-lane coefficients -- drift step 0,
 // kick 0 -- its last kick is its own half kick, the wave stops with its longest chain.
 template <int G, bool UNIT, bool FULL, int METHOD, bool DYN = false>
-__global__ void __launch_bounds__(64, 3) k_rosg_hmc(RosgPrm prm, RosgRun run) {
+__global__ void __launch_bounds__(64, 3) k_rosg_hmc(RosgPrm prm, ChainRun run) {
     static_assert(!DYN || METHOD == PBBI_LEAPFROG, "per-chain lengths: Leapfrog");
     constexpr int CPW = 64 / G;  // chains per wave
     const int lane = threadIdx.x;
@@ -223,7 +214,7 @@ __global__ void __launch_bounds__(64, 3) k_rosg_hmc(RosgPrm prm, RosgRun run) {
     const double newH = kinetic() + U_new;
     const double ratio = exp((oldH - newH) * pbbi_accept_beta(prm.flags, prm.kT));  // src/HMC.py:115
     const double u = prm.rng ? rng_uniform(prm.seed, iter_k, chain) : prm.u_in[n0 + cc];
-    const bool reject = (ratio == ratio) && (u > (ratio < 1.0 ? ratio : 1.0));
+    const bool reject = metropolis_reject(ratio, u);
     U_carry = reject ? U_old : U_new;  // (all lanes of a chain decide alike)
     if (reject) {
 #pragma unroll
@@ -390,7 +381,7 @@ __global__ void __launch_bounds__(64, 2) k_rosg_exact_hmc(RosgPrm prm) {
     const double newH = hamiltonian();
     const double ratio = exp((oldH - newH) * pbbi_accept_beta(prm.flags, prm.kT));  // src/HMC.py:115
     const double u = prm.rng ? rng_uniform(prm.seed, prm.iter, chain) : prm.u_in[n0 + cc];
-    const bool reject = (ratio == ratio) && (u > (ratio < 1.0 ? ratio : 1.0));
+    const bool reject = metropolis_reject(ratio, u);
     if (reject) {
 #pragma unroll
         for (int j = 0; j < DL; ++j) q[j] = buf_load<double>(bq, vin, (uint32_t)j * rin);  // :175
@@ -436,8 +427,7 @@ template <int G>
 void launch(const IterArgs& a, const RosgPrm& prm, bool full) {
     constexpr int CPW = 64 / G;
     const dim3 grid((unsigned)((a.N + CPW - 1) / CPW)), block(64);
-    RosgRun run{1, 0, 0, (int64_t)a.pot->D * a.N, (double*)a.q_out};
-    if (a.fuse_S > 1) run = RosgRun{a.fuse_S, a.fuse_wrap2, a.fuse_slab0, (int64_t)a.pot->D * a.N, (double*)a.fuse_q_base};
+    const ChainRun run = chain_run(a);
 #define ROSG_LAUNCH(U_, M_)                                                                          \
     {                                                                                                \
         if (full) hipLaunchKernelGGL((k_rosg_hmc<G, U_, true, M_>), grid, block, 0, a.stream, prm, run);  \

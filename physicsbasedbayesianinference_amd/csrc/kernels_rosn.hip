@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "pbbi_buf.h"
+#include "pbbi_chain.h"
 #include "pbbi_internal.h"
 #include "pbbi_rng.h"
 
@@ -169,7 +170,7 @@ __global__ void __launch_bounds__(64 * GMAX, (GMAX <= 4 ? 3 : 1)) k_rosn_hmc(Ros
     for (int g = 0; g < G; ++g) dsum += dH[g * 64 + c];
     const double ratio = exp(dsum * pbbi_accept_beta(prm.flags, prm.kT));  // src/HMC.py:115
     const double u = prm.rng ? rng_uniform(prm.seed, prm.iter, chain) : prm.u_in[n0 + cc];
-    const bool reject = (ratio == ratio) && (u > (ratio < 1.0 ? ratio : 1.0));
+    const bool reject = metropolis_reject(ratio, u);
     if (reject) {
 #pragma unroll
         for (int j = 0; j < DL; ++j) q[j] = ld(bq, j);  // :175

@@ -20,6 +20,7 @@
 #include <cstdlib>
 
 #include "pbbi_buf.h"
+#include "pbbi_chain.h"
 #include "pbbi_internal.h"
 #include "pbbi_rng.h"
 
@@ -49,17 +50,6 @@ struct SepPrm {
     int32_t* steps_out;
 };
 
-// Where the iterations of a fused run put their results (pbbi_hmc_run, IterArgs::fuse_*; as Ros2Run in
-// kernels_lane2.hip): iteration k of the launch writes position slab (slab0 + k), modulo 2 for a burn-in's
-// two scratch slabs, momentum slab k, ratio / reject rows k.
-struct SepRun {
-    int S;            // iterations in this launch (1: plain pbbi_hmc_iter semantics)
-    int wrap2;
-    int64_t slab0;    // index of the first iteration's position slab
-    int64_t slab;     // elements per slab (D * N)
-    double* q_base;   // slab 0 of the position slabs
-};
-
 // FULL: D is a multiple of 16, every dim of every part exists: no guards (as scalar branches they
 // put an s_waitcnt between consecutive loads / stores)
 // run.S > 1: the workgroup keeps its 64 chains in registers for run.S consecutive iterations -- the
@@ -71,7 +61,7 @@ struct SepRun {
 // -- and the wave stops when its longest chain has; every wave of the workgroup holds the same 64 chains, so
 // they all run the same count.
 template <bool UNIT, bool FULL, int METHOD, bool DYN = false>
-__global__ void __launch_bounds__(64 * MAXG) k_sep_hmc(SepPrm prm, SepRun run) {
+__global__ void __launch_bounds__(64 * MAXG) k_sep_hmc(SepPrm prm, ChainRun run) {
     static_assert(!DYN || METHOD == PBBI_LEAPFROG, "per-chain lengths: Leapfrog");
     __shared__ double dH[2][MAXG][64];  // by iteration parity: one barrier per iteration is enough
     const int c = threadIdx.x & 63;
@@ -220,7 +210,7 @@ __global__ void __launch_bounds__(64 * MAXG) k_sep_hmc(SepPrm prm, SepRun run) {
     for (int g = 0; g < G; ++g) dsum += dH[kf & 1][g][c];
     const double ratio = exp(dsum * pbbi_accept_beta(prm.flags, prm.kT));  // src/HMC.py:115
     const double u = prm.rng ? rng_uniform(prm.seed, iter_k, chain) : prm.u_in[n0 + cc];
-    const bool reject = (ratio == ratio) && (u > (ratio < 1.0 ? ratio : 1.0));
+    const bool reject = metropolis_reject(ratio, u);
     // back to positions: q = x + mu, or the untouched old position for a rejected chain (:175)
 #pragma unroll
     for (int j = 0; j < DL; ++j) q[j] = q[j] + mu[j];
@@ -404,7 +394,7 @@ __global__ void __launch_bounds__(64 * MAXG) k_sep_exact_hmc(SepPrm prm) {
     const double newH = hamiltonian();
     const double ratio = exp((oldH - newH) * pbbi_accept_beta(prm.flags, prm.kT));  // src/HMC.py:115
     const double u = prm.rng ? rng_uniform(prm.seed, prm.iter, chain) : prm.u_in[n0 + cc];
-    const bool reject = (ratio == ratio) && (u > (ratio < 1.0 ? ratio : 1.0));
+    const bool reject = metropolis_reject(ratio, u);
     if (reject) {
 #pragma unroll
         for (int j = 0; j < DL; ++j) q[j] = ld(bq, j);  // :175
@@ -456,8 +446,7 @@ int sepn_hmc_iter(const IterArgs& a) {
     const dim3 grid((unsigned)((a.N + 63) / 64)), block(64 * G);
     const bool full = (pot->D % DL == 0);
     const bool dyn = pbbi_dyn(a);   // (lane_hmc_iter sends PBBI_PER_CHAIN_STEPS without PBBI_UTURN_STOP only)
-    SepRun run{1, 0, 0, (int64_t)pot->D * a.N, (double*)a.q_out};
-    if (a.fuse_S > 1) run = SepRun{a.fuse_S, a.fuse_wrap2, a.fuse_slab0, (int64_t)pot->D * a.N, (double*)a.fuse_q_base};
+    const ChainRun run = chain_run(a);
 #define SEP_LAUNCH(U_, F_)                                                                              \
     {                                                                                                   \
         if (dyn)                                                                                        \

@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "pbbi_internal.h"
+#include "pbbi_chain.h"
 #include "pbbi_rng.h"
 
 // ------------------------------------------------------------------- errors
@@ -247,7 +248,7 @@ __global__ void k_gist_accept(const T* q_prev, int64_t ld_prev, const T* p_draw,
     const int tf = tau_f[n], L = Ls[n], tb = tau_b[n];
     const double ratio = (L <= tb) ? hr * ((double)tf / (double)tb) : 0.0;
     const double u = rng_uniform(seed, iter, chain0 + (uint64_t)n);
-    const bool reject = (ratio == ratio) && (u > (ratio < 1.0 ? ratio : 1.0));
+    const bool reject = metropolis_reject(ratio, u);
     const bool compat = (flags & PBBI_COMPAT_P_FROM_OLDQ) != 0;
     for (int d = 0; d < D; ++d) {
         const T qo = q_prev[(int64_t)d * ld_prev + n];
