@@ -167,6 +167,24 @@ int pbbi_potential_create_rosenbrock(int D, double a, double b, double s, int dt
  * model constants, or the data set of a Bayesian model. */
 int pbbi_potential_create_custom(const char* plugin_path, int D, const double* params, int n_params,
                                  int dtype, int device, pbbi_potential** out);
+/* Generalised linear model with a Gaussian prior -- the likelihood as two matrix products shared by all chains,
+ * on the fp64 matrix cores (csrc/kernels_glm.hip):
+ *     U(w) = sum_i [ b(x_i . w) - y_i (x_i . w) ] + 0.5 prior_precision |w|^2   over the M rows x_i of X,
+ *     logistic: b = softplus (y in {0, 1});   poisson: b = exp (y = counts, log link).
+ * X (M x D row-major) and y (M) are HOST pointers, copied at creation (X into MFMA fragment order).  fp64 and
+ * 1 <= D <= 128 only (otherwise PBBI_ERR_UNSUPPORTED); M >= 1; prior_precision >= 0.  The handle serves the
+ * evaluations, the integrators, pbbi_hmc_iter / _iter_kt and pbbi_hmc_run (Leapfrog and Stormer-Verlet, always in
+ * kick-drift-kick form); per-chain trajectory lengths and GIST return PBBI_ERR_UNSUPPORTED. */
+enum { PBBI_GLM_LOGISTIC = 0, PBBI_GLM_POISSON = 1 };
+int pbbi_potential_create_glm(int D, int64_t M, const double* X, const double* y, int family,
+                              double prior_precision, int dtype, int device, pbbi_potential** out);
+/* The fragment image pbbi_potential_create_glm uploads, on the HOST (touches no device): *len_out <- its length in
+ * doubles; with `out` non-NULL (out_len >= that length) the image itself.  Per block of 16 observations b, with
+ * DP = D padded to 16 / 32 / 64 / 128, KS = DP/4, NT = DP/16, lane = 0..63, e = 0, 1:
+ *     P1[s2][lane][e]    = X[16b + (lane & 15)][4 (2 s2 + e) + (lane >> 4)]            s2 < KS/2
+ *     P2[r2][t][lane][e] = X[16b + 4 (2 r2 + e) + (lane >> 4)][16 t + (lane & 15)]     r2 < 2, t < NT
+ * (P1 then P2, 32 DP doubles per block), zero padded; the block count is padded to a multiple of 4. */
+int pbbi_glm_pack_design(int D, int64_t M, const double* X, double* out, int64_t out_len, int64_t* len_out);
 int pbbi_potential_destroy(pbbi_potential* pot);
 int pbbi_potential_dim(const pbbi_potential* pot);
 int pbbi_potential_dtype(const pbbi_potential* pot);

@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get("PBBI_LIB") or os.path.join(_HERE, "libpbbi.so")
 OK = 0
 F64, F32 = 0, 1
 LEAPFROG, STORMER_VERLET = 0, 1
+GLM_LOGISTIC, GLM_POISSON = 0, 1
+ERR_INVALID, ERR_UNSUPPORTED, ERR_HIP = -1, -2, -3
 COMPAT_P_FROM_OLDQ = 1
 KDK_FMA = 2
 BETA_ACCEPT = 4
@@ -51,6 +53,8 @@ PROTOTYPES = {
     "pbbi_potential_create_gauss_dense": [_i, _dp, _dp, _d, _i, _i, _pp],
     "pbbi_potential_create_rosenbrock": [_i, _d, _d, _d, _i, _i, _pp],
     "pbbi_potential_create_custom": [C.c_char_p, _i, _dp, _i, _i, _i, _pp],
+    "pbbi_potential_create_glm": [_i, _i64, _dp, _dp, _i, _d, _i, _i, _pp],
+    "pbbi_glm_pack_design": [_i, _i64, _dp, _dp, _i64, C.POINTER(C.c_int64)],
     "pbbi_potential_destroy": [_vp],
     "pbbi_potential_dim": [_vp],
     "pbbi_potential_dtype": [_vp],

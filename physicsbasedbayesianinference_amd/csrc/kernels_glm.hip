@@ -1,0 +1,499 @@
+// kernels_glm.hip -- generalised linear models whose likelihood runs on the fp64 matrix cores (gfx950).
+//
+//   U(w) = sum_i [ b(x_i.w) - y_i (x_i.w) ] + 0.5 lam |w|^2,   grad U = X^T (b'(eta) - y) + lam w,   eta = X w
+// over the M rows x_i of the design matrix X (M x D).  For an ENSEMBLE of chains these are two matrix products
+// shared by all of them -- eta = X W and g = X^T R with W, R of one column per chain -- so the data set is read
+// once per 64 chains instead of once per chain (the user-source plugin path, custom.LOGISTIC_REGRESSION_SOURCE).
+//
+// Layout.  One wave owns 16 chains and keeps q, the half-step velocity vh and the gradient accumulator in
+// registers in the layout of kernels_dense_dev.h: element s of a lane is row 4s + g, g = lane >> 4, chain =
+// lane & 15.  X travels through LDS in blocks of 16 observations, pre-swizzled on the host (glm_pack) into the
+// A-fragment order of v_mfma_f64_16x16x4_f64 -- twice, once per product:
+//   P1[s2][lane][e]     = X[16b + (lane & 15)][4 (2 s2 + e) + (lane >> 4)]       eta tile   = X_b (16 x DP) . W
+//   P2[r2][t][lane][e]  = X[16b + 4 (2 r2 + e) + (lane >> 4)][16 t + (lane & 15)] g tile t += X_b^T (DP x 16) . R_b
+// (e = the two halves of one 16-byte LDS read).  The first product's B operand of K-step s is q[s] as it sits
+// (B[k = lane >> 4][j = lane & 15] = W[4s + g][chain]).  Its result has C/D map col = lane & 15, row =
+// (lane >> 4) + 4 reg: register r of the eta tile holds the observations {4r + g} of the lane's own chain --
+// exactly the B operand of the K-step of the SECOND product that sums over those four observations.  The link
+// function is applied in place on the four accumulator values and they go straight back into the matrix pipe: no
+// cross-lane movement, no LDS round trip.  The second product's C/D rows (lane >> 4) + 4 r' of tile t are rows
+// 16t + 4r' + g: the state layout again.
+//
+// Padding.  Rows of the last block past M are zeros in the image, but b(0) and b'(0) are not zero (log 2 and 1/2,
+// 1 and 1): both the residual and the energy term of an observation >= M are masked.  Columns D <= d < DP are
+// zeros in the image; the state arrays are addressed through bounded descriptors (pbbi_buf.h), so rows d >= D
+// load 0 and their stores are dropped.
+//
+// One launch is one HMC iteration (or one integrate(), or one evaluation): kick-drift-kick with fused
+// multiply-adds like the other MFMA kernels, ONE call site of the gradient inside a loop over the trajectory's
+// evaluations whose kick / drift coefficients say which update follows it.  Nothing is carried between the
+// iterations of a run, so a run of S iterations is S launches and equals S runs of one bit for bit by
+// construction.
+#include <cstring>
+
+#include "kernels_dense_dev.h"
+#include "pbbi_chain.h"
+
+namespace {
+
+struct GlmPrm {
+    const double* img;  // nbp blocks of 2 * KS * 64 doubles (P1 then P2), nbp = blocks padded to a multiple of 4
+    const double* y;    // nbp * 16, zero padded
+    const double* q_in;
+    const double* p_in;
+    const double* u_in;
+    const double* mass;
+    double* q_out;
+    double* p_out;
+    double* v_out;
+    double* ratio_out;
+    uint8_t* reject_out;
+    double* U_out;     // modes 2..4
+    double* grad_out;  // mode 2
+    double* w_out;     // mode 3
+    int64_t N, ldn_in, ldn_out, M;
+    double h, lam, kT;
+    int L, D, flags, rng, mode, method, nb;
+    uint64_t seed, iter, chain0;
+};
+enum { GLM_HMC = 0, GLM_INTEGRATE = 1, GLM_EVAL = 2, GLM_ENERGY = 3, GLM_RATIO = 4 };
+
+template <int NT>
+struct GlmCfg {
+    static constexpr int KS = 4 * NT;
+    static constexpr int CB = NT >= 4 ? 1 : 4 / NT;    // observation blocks per staged chunk
+    static constexpr int BLKV = NT * 256;              // 16-byte elements per block (P1 + P2)
+    static constexpr int CHV = CB * BLKV;              // ... per chunk
+    static constexpr int PER_THREAD = CHV / BLOCK;     // = CB * NT
+    static_assert(CHV % BLOCK == 0, "whole 16-byte elements per thread");
+};
+
+// b(eta) - y eta and b'(eta) - y of one observation
+template <int FAM>
+__device__ __forceinline__ void glm_link(double eta, double yv, bool want_u, double& resid, double& uterm) {
+    if constexpr (FAM == PBBI_GLM_LOGISTIC) {
+        const double e = exp(-fabs(eta));
+        const double inv = 1.0 / (1.0 + e);
+        resid = (eta >= 0.0 ? inv : e * inv) - yv;
+        uterm = 0.0;
+        if (want_u) uterm = ((eta > 0.0 ? eta : 0.0) + log1p(e)) - yv * eta;
+    } else {
+        const double e = exp(eta);
+        resid = e - yv;
+        uterm = e - yv * eta;
+    }
+}
+
+// gacc[t][r] (row 16t + 4r + g) = sum_i X[i][row] (b'(eta_i) - y_i) for the wave's 16 chains, usum = this lane's
+// share of sum_i b(eta_i) - y_i eta_i (observations {4r + g} of every block; chain_sum completes it).
+// Every wave of the workgroup takes part in the staging: one chunk of CB blocks is in LDS while the next waits
+// in registers (fetched before the MFMAs of the current one, written after the barrier that ends its reads).
+template <int NT, int FAM>
+__device__ __forceinline__ void glm_grad(const GlmPrm& prm, v2f64* __restrict__ lds, double* __restrict__ ylds,
+                                         int lane, int g, const double (&q)[4 * NT], v4f64 (&gacc)[NT],
+                                         double& usum, bool want_u) {
+    using C = GlmCfg<NT>;
+    constexpr int KS = C::KS;
+    const v2f64* __restrict__ src = reinterpret_cast<const v2f64*>(prm.img);
+    const int nch = (prm.nb + C::CB - 1) / C::CB;
+    v2f64 tmp[C::PER_THREAD];
+    double ytmp = 0.0;
+#pragma unroll
+    for (int j = 0; j < C::PER_THREAD; ++j) tmp[j] = src[threadIdx.x + j * BLOCK];
+    if (threadIdx.x < C::CB * 16) ytmp = prm.y[threadIdx.x];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) gacc[t] = v4f64{0.0, 0.0, 0.0, 0.0};
+    usum = 0.0;
+    for (int ch = 0; ch < nch; ++ch) {
+        __syncthreads();  // everybody has finished reading the previous chunk
+#pragma unroll
+        for (int j = 0; j < C::PER_THREAD; ++j) lds[threadIdx.x + j * BLOCK] = tmp[j];
+        if (threadIdx.x < C::CB * 16) ylds[threadIdx.x] = ytmp;
+        __syncthreads();
+        if (ch + 1 < nch) {
+            const v2f64* nsrc = src + (size_t)(ch + 1) * C::CHV;
+#pragma unroll
+            for (int j = 0; j < C::PER_THREAD; ++j) tmp[j] = nsrc[threadIdx.x + j * BLOCK];
+            if (threadIdx.x < C::CB * 16) ytmp = prm.y[(size_t)(ch + 1) * (C::CB * 16) + threadIdx.x];
+        }
+#pragma unroll
+        for (int bi = 0; bi < C::CB; ++bi) {
+            const int blk = ch * C::CB + bi;
+            if (C::CB > 1 && blk >= prm.nb) break;
+            const v2f64* __restrict__ P1 = lds + bi * C::BLKV + lane;
+            const v2f64* __restrict__ P2 = P1 + (KS / 2) * 64;
+            // eta tile: 16 observations x 16 chains, K = DP
+            v4f64 eta = v4f64{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int s2 = 0; s2 < KS / 2; ++s2) {
+                const v2f64 A = P1[s2 * 64];
+                eta = __builtin_amdgcn_mfma_f64_16x16x4f64(A.x, q[2 * s2], eta, 0, 0, 0);
+                eta = __builtin_amdgcn_mfma_f64_16x16x4f64(A.y, q[2 * s2 + 1], eta, 0, 0, 0);
+            }
+            // link function in place: register r = observations {4r + g} of this lane's chain
+            double res[4];
+            const int64_t obs0 = (int64_t)blk * 16 + g;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const bool ok = obs0 + 4 * r < prm.M;
+                double rr, ut;
+                glm_link<FAM>(eta[r], ylds[bi * 16 + 4 * r + g], want_u, rr, ut);
+                res[r] = ok ? rr : 0.0;
+                usum += ok ? ut : 0.0;
+            }
+            // g tiles += X_b^T . R_b: K-step r sums over the observations register r holds
+#pragma unroll
+            for (int r2 = 0; r2 < 2; ++r2)
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    const v2f64 A = P2[(r2 * NT + t) * 64];
+                    gacc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(A.x, res[2 * r2], gacc[t], 0, 0, 0);
+                    gacc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(A.y, res[2 * r2 + 1], gacc[t], 0, 0, 0);
+                }
+        }
+    }
+}
+
+template <int NT, int FAM>
+__global__ void __launch_bounds__(BLOCK, NT <= 2 ? 2 : 1) k_glm(GlmPrm prm) {
+    using C = GlmCfg<NT>;
+    constexpr int KS = C::KS;
+    __shared__ __attribute__((aligned(16))) v2f64 lds[C::CHV];
+    __shared__ double ylds[C::CB * 16];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int g = lane >> 4;
+    const int c = lane & 15;
+    const int D = prm.D;
+    const int mode = prm.mode;
+
+    // every wave takes part in the staging barriers: one past the end of the ensemble recomputes the last tile
+    // with its stores masked
+    int64_t n0 = ((int64_t)blockIdx.x * 4 + wave) * CHAINS_PER_WAVE;  // wave-uniform
+    bool ghost = false;
+    if (n0 >= prm.N) {
+        ghost = true;
+        n0 = (prm.N - 1) / CHAINS_PER_WAVE * CHAINS_PER_WAVE;
+    }
+    const int64_t left = prm.N - n0;
+    const bool valid = !ghost && c < left;
+    const int cc = c < left ? c : (int)left - 1;  // ragged tail: compute on a clamped chain
+    const uint32_t ld_in = 8u * (uint32_t)prm.ldn_in, ld_out = 8u * (uint32_t)prm.ldn_out;
+    const uint32_t vin = (uint32_t)g * ld_in + 8u * (uint32_t)cc, s4in = 4u * ld_in;
+    const uint32_t vout = (uint32_t)g * ld_out + 8u * (uint32_t)cc, s4out = 4u * ld_out;
+    const __amdgpu_buffer_rsrc_t qin = rows_of<false>(prm.q_in, n0, D, prm.ldn_in, prm.N);
+    const __amdgpu_buffer_rsrc_t pin = rows_of<false>(prm.p_in, n0, D, prm.ldn_in, prm.N);
+    const __amdgpu_buffer_rsrc_t qout = rows_of<false>(prm.q_out, n0, D, prm.ldn_out, prm.N);
+    const __amdgpu_buffer_rsrc_t pout = rows_of<false>(prm.p_out, n0, D, prm.ldn_out, prm.N);
+    const bool have_pout = (prm.p_out != nullptr);
+    const double m = prm.mass ? prm.mass[n0 + cc] : 1.0;
+    const double minv = prm.mass ? 1.0 / m : 1.0;
+    const bool traj = (mode == GLM_HMC || mode == GLM_INTEGRATE);
+    const bool rng = (mode == GLM_HMC) && prm.rng;
+    const uint64_t chain = prm.chain0 + (uint64_t)(n0 + cc);
+
+    double q[KS], vh[KS];
+    v4f64 gacc[NT];
+    // ---- momentum first (vh holds p until the division by the mass below)
+    double u = 0.0;
+    if (rng) {
+        const double pstd = sqrt(m * prm.kT);  // src/ensemble.py:88
+#pragma unroll
+        for (int k = 0; k < NT; ++k) {  // block k: rows 16k + 4*slot + g
+            double z[4];
+            rng_normal4d(prm.seed, PBBI_STREAM_MOMENTUM, prm.iter, chain, (uint32_t)((k << 2) | g),
+                         (prm.flags & PBBI_DRAW_F64) != 0, z);
+#pragma unroll
+            for (int sl = 0; sl < 4; ++sl) vh[4 * k + sl] = (16 * k + 4 * sl + g < D) ? z[sl] * pstd : 0.0;
+        }
+        u = rng_uniform(prm.seed, prm.iter, chain);
+        if (have_pout && !(prm.flags & PBBI_COMPAT_P_FROM_OLDQ) && valid) {
+            // non-compat: a rejected chain reports its drawn momentum; park the draw now
+#pragma unroll
+            for (int s = 0; s < KS; ++s) store_row(pout, vout, s4out, s, vh[s]);
+        }
+    } else if (mode != GLM_EVAL) {
+#pragma unroll
+        for (int s = 0; s < KS; ++s) vh[s] = load_row(pin, vin, s4in, s);
+        if (mode == GLM_HMC) u = prm.u_in[n0 + cc];
+    } else {
+#pragma unroll
+        for (int s = 0; s < KS; ++s) vh[s] = 0.0;
+    }
+#pragma unroll
+    for (int s = 0; s < KS; ++s) q[s] = load_row(qin, vin, s4in, s);
+    double pp_old = 0.0;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) pp_old = fma(vh[s], vh[s], pp_old);
+    if (traj) {
+#pragma unroll
+        for (int s = 0; s < KS; ++s) vh[s] *= minv;  // v = p/m
+    }
+
+    // ---- the trajectory as a list of gradient evaluations, each followed by a kick of ck and a drift of hd:
+    //   Leapfrog        e = 0: h/2, h    e = 1 .. L-1: h, h    e = L: h/2, 0          (L = 0: one evaluation, no update)
+    //   Stormer-Verlet  e = 0: h/2, h    e = 1 .. L:   h, h    e = L+1 (HMC only): 0, 0 -- U at the last position;
+    //                   (q_{n+1} - q_n)/h = vh is the velocity it returns (src/integrator.py:142-163)
+    const bool sv = prm.method == PBBI_STORMER_VERLET;
+    const int L = prm.L;
+    int nev = 1;
+    if (traj) nev = sv ? L + 1 + (mode == GLM_HMC ? 1 : 0) : L + 1;
+    const double lam = prm.lam;
+    const double h = prm.h;
+    double U_old = 0.0, U_new = 0.0;
+    for (int e = 0; e < nev; ++e) {
+        double ck = 0.0, hd = 0.0;
+        if (traj) {
+            if (sv) {
+                if (e <= L) { ck = e == 0 ? 0.5 * h : h; hd = h; }
+            } else if (L >= 1) {
+                ck = (e == 0 || e == L) ? 0.5 * h : h;
+                hd = e < L ? h : 0.0;
+            }
+        }
+        ck *= minv;
+        const bool want_u = (e == 0 || e == nev - 1) && mode != GLM_INTEGRATE;
+        double usum;
+        glm_grad<NT, FAM>(prm, lds, ylds, lane, g, q, gacc, usum, want_u);
+        if (want_u) {
+            double qq = 0.0;
+#pragma unroll
+            for (int s = 0; s < KS; ++s) qq = fma(q[s], q[s], qq);
+            U_new = chain_sum(usum) + (0.5 * lam) * chain_sum(qq);
+            if (e == 0) U_old = U_new;
+        }
+        if (mode == GLM_EVAL) break;  // the gradient stays in gacc
+        // an evaluation for U alone is followed by no update (a product 0 * inf would turn an overflowed
+        // gradient, whose energy rejects the proposal, into a NaN momentum)
+        if (!(traj && (sv ? e <= L : L >= 1))) continue;
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int s = 4 * t + r;
+                const double gt = fma(lam, q[s], gacc[t][r]);
+                vh[s] = fma(-gt, ck, vh[s]);
+                q[s] = fma(vh[s], hd, q[s]);
+            }
+    }
+
+    if (mode == GLM_EVAL) {
+        if (prm.grad_out && valid) {
+            const __amdgpu_buffer_rsrc_t gout = rows_of<false>(prm.grad_out, n0, D, prm.ldn_out, prm.N);
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    store_row(gout, vout, s4out, 4 * t + r, fma(lam, q[4 * t + r], gacc[t][r]));
+        }
+        if (prm.U_out && valid && g == 0) prm.U_out[n0 + c] = U_old;
+        return;
+    }
+    if (mode == GLM_ENERGY || mode == GLM_RATIO) {
+        const double H = 0.5 * chain_sum(pp_old) / m + U_old;
+        if (valid && g == 0) {
+            if (mode == GLM_ENERGY) {
+                if (prm.U_out) prm.U_out[n0 + c] = H;
+                if (prm.w_out) prm.w_out[n0 + c] = exp(-H);
+            } else {
+                prm.U_out[n0 + c] = exp(prm.U_out[n0 + c] - H);
+            }
+        }
+        return;
+    }
+    if (mode == GLM_INTEGRATE) {  // in place q, p; optional Integrator.v
+        if (valid) {
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                store_row(qout, vout, s4out, s, q[s]);
+                store_row(pout, vout, s4out, s, prm.mass ? vh[s] * m : vh[s]);
+            }
+            if (prm.v_out) {
+                const __amdgpu_buffer_rsrc_t vo = rows_of<false>(prm.v_out, n0, D, prm.ldn_out, prm.N);
+#pragma unroll
+                for (int s = 0; s < KS; ++s) store_row(vo, vout, s4out, s, vh[s]);
+            }
+        }
+        return;
+    }
+
+    // ---- energies, ratio, decision (src/HMC.py:109-115,166-173)
+    double pp_new = 0.0;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+        if (prm.mass) vh[s] *= m;  // p = v*m; vh now holds p
+        pp_new = fma(vh[s], vh[s], pp_new);
+    }
+    const double oldH = 0.5 * chain_sum(pp_old) / m + U_old;
+    const double newH = 0.5 * chain_sum(pp_new) / m + U_new;
+    const double ratio = exp((oldH - newH) * pbbi_accept_beta(prm.flags, prm.kT));
+    const bool reject = metropolis_reject(ratio, u);
+    const bool compat = (prm.flags & PBBI_COMPAT_P_FROM_OLDQ) != 0;
+    bool store_p = have_pout;
+    if (reject) {  // fetch the old point again instead of keeping it live through the trajectory
+#pragma unroll
+        for (int s = 0; s < KS; ++s) q[s] = load_row(qin, vin, s4in, s);  // :175
+        if (compat) {  // :176  p <- oldQ
+#pragma unroll
+            for (int s = 0; s < KS; ++s) vh[s] = q[s];
+        } else if (rng) {
+            store_p = false;  // the parked draw stays
+        } else if (have_pout) {
+#pragma unroll
+            for (int s = 0; s < KS; ++s) vh[s] = load_row(pin, vin, s4in, s);
+        }
+    }
+    if (valid) {
+#pragma unroll
+        for (int s = 0; s < KS; ++s) store_row(qout, vout, s4out, s, q[s]);  // :178
+        if (store_p) {
+#pragma unroll
+            for (int s = 0; s < KS; ++s) store_row(pout, vout, s4out, s, vh[s]);  // :179
+        }
+    }
+    if (valid && g == 0) {
+        if (prm.ratio_out) prm.ratio_out[n0 + c] = ratio;
+        if (prm.reject_out) prm.reject_out[n0 + c] = reject ? 1 : 0;
+    }
+}
+
+int glm_check(const pbbi_potential* pot, int64_t ld) {
+    if (pot->dtype != PBBI_F64 || pot->glm_DP == 0 || !pot->d_glm_img)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM kernels: fp64, D <= 128");
+    if ((int64_t)pot->glm_DP * ld >= ((int64_t)1 << 29))
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED,
+                         "GLM kernels address a lane's rows with 32-bit offsets: padded D * leading stride must "
+                         "be < 2^29 elements; shard the ensemble");
+    return PBBI_OK;
+}
+
+GlmPrm glm_prm(const pbbi_potential* pot) {
+    GlmPrm prm{};
+    prm.img = (const double*)pot->d_glm_img;
+    prm.y = (const double*)pot->d_glm_y;
+    prm.M = pot->glm_M;
+    prm.nb = (int)((pot->glm_M + 15) / 16);
+    prm.lam = pot->glm_lam;
+    prm.D = pot->D;
+    prm.kT = 1.0;
+    return prm;
+}
+
+int glm_launch(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t stream) {
+    const dim3 grid((unsigned)((prm.N + CHAINS_PER_WG - 1) / CHAINS_PER_WG)), block(BLOCK);
+#define GLM_CASE(NT_)                                                                                       \
+    if (pot->glm_DP == 16 * NT_) {                                                                          \
+        if (pot->glm_family == PBBI_GLM_LOGISTIC)                                                           \
+            hipLaunchKernelGGL((k_glm<NT_, PBBI_GLM_LOGISTIC>), grid, block, 0, stream, prm);               \
+        else                                                                                                \
+            hipLaunchKernelGGL((k_glm<NT_, PBBI_GLM_POISSON>), grid, block, 0, stream, prm);                \
+    }
+    GLM_CASE(1) GLM_CASE(2) GLM_CASE(4) GLM_CASE(8)
+#undef GLM_CASE
+    PBBI_HIP(hipGetLastError());
+    return PBBI_OK;
+}
+
+}  // namespace
+
+// ---- host side: the fragment image of X ------------------------------------------------------------------
+int glm_padded_dim(int D) { return D <= 16 ? 16 : D <= 32 ? 32 : D <= 64 ? 64 : 128; }
+static int64_t glm_blocks_padded(int64_t M) { return ((M + 15) / 16 + 3) / 4 * 4; }
+int64_t glm_image_len(int D, int64_t M) { return glm_blocks_padded(M) * (int64_t)glm_padded_dim(D) * 32; }
+
+// X (M x D, row-major) -> per block of 16 observations P1 [KS/2][64][2] then P2 [2][NT][64][2] (see the top of
+// the file), zero padded to DP columns and to a multiple of 4 blocks.  Host only.
+void glm_pack(int D, int64_t M, const double* X, double* out) {
+    const int DP = glm_padded_dim(D), NT = DP / 16, KS = DP / 4;
+    const int64_t nbp = glm_blocks_padded(M);
+    const int64_t blk_len = (int64_t)DP * 32;
+    std::memset(out, 0, sizeof(double) * (size_t)(nbp * blk_len));
+    auto at = [&](int64_t i, int d) -> double { return (i < M && d < D) ? X[(size_t)i * D + d] : 0.0; };
+    for (int64_t b = 0; b < (M + 15) / 16; ++b) {
+        double* P1 = out + b * blk_len;
+        double* P2 = P1 + (int64_t)KS * 64;
+        for (int l = 0; l < 64; ++l) {
+            const int lo = l & 15, hi = l >> 4;
+            for (int s2 = 0; s2 < KS / 2; ++s2)
+                for (int e = 0; e < 2; ++e)
+                    P1[((size_t)s2 * 64 + l) * 2 + e] = at(16 * b + lo, 4 * (2 * s2 + e) + hi);
+            for (int r2 = 0; r2 < 2; ++r2)
+                for (int t = 0; t < NT; ++t)
+                    for (int e = 0; e < 2; ++e)
+                        P2[(((size_t)r2 * NT + t) * 64 + l) * 2 + e] = at(16 * b + 4 * (2 * r2 + e) + hi, 16 * t + lo);
+        }
+    }
+}
+
+int glm_build(pbbi_potential* pot, int64_t M, const double* X, const double* y, int family, double lam) {
+    const int D = pot->D;
+    if (D > 128 || pot->dtype != PBBI_F64)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials run on the fp64 matrix-core kernels: float64 and "
+                                               "D <= 128 only (D = " + std::to_string(D) + ")");
+    std::vector<double> img((size_t)glm_image_len(D, M));
+    glm_pack(D, M, X, img.data());
+    std::vector<double> yp((size_t)glm_blocks_padded(M) * 16, 0.0);
+    std::memcpy(yp.data(), y, sizeof(double) * (size_t)M);
+    PBBI_HIP(hipMalloc(&pot->d_glm_img, img.size() * sizeof(double)));
+    PBBI_HIP(hipMalloc(&pot->d_glm_y, yp.size() * sizeof(double)));
+    PBBI_HIP(hipMemcpy(pot->d_glm_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
+    PBBI_HIP(hipMemcpy(pot->d_glm_y, yp.data(), yp.size() * sizeof(double), hipMemcpyHostToDevice));
+    pot->glm_DP = glm_padded_dim(D);
+    pot->glm_M = M;
+    pot->glm_family = family;
+    pot->glm_lam = lam;
+    return PBBI_OK;
+}
+
+int glm_hmc_iter(const IterArgs& a) {
+    if (int rc = glm_check(a.pot, a.ldn_in > a.ldn_out ? a.ldn_in : a.ldn_out)) return rc;
+    if (pbbi_dyn(a)) return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials: fixed trajectory lengths only");
+    if (a.fuse_S > 1) return pbbi_fail(PBBI_ERR_INVALID, "the GLM kernel takes one iteration per launch (internal)");
+    if (a.N == 0) return PBBI_OK;
+    GlmPrm prm = glm_prm(a.pot);
+    prm.q_in = (const double*)a.q_in;
+    prm.p_in = (const double*)a.p_in;
+    prm.u_in = (const double*)a.u_in;
+    prm.mass = (const double*)a.mass;
+    prm.q_out = (double*)a.q_out;
+    prm.p_out = (double*)a.p_out;
+    prm.ratio_out = (double*)a.ratio_out;
+    prm.reject_out = a.reject_out;
+    prm.N = a.N; prm.ldn_in = a.ldn_in; prm.ldn_out = a.ldn_out;
+    prm.h = a.h; prm.kT = a.kT; prm.L = a.L; prm.flags = a.flags; prm.rng = a.rng;
+    prm.mode = GLM_HMC; prm.method = a.method;
+    prm.seed = a.seed; prm.iter = a.iter; prm.chain0 = a.chain0;
+    return glm_launch(a.pot, prm, a.stream);
+}
+
+int glm_integrate(const IntegrateArgs& a) {
+    if (int rc = glm_check(a.pot, a.ldn)) return rc;
+    if (a.N == 0) return PBBI_OK;
+    GlmPrm prm = glm_prm(a.pot);
+    prm.q_in = (const double*)a.q;
+    prm.p_in = (const double*)a.p;
+    prm.mass = (const double*)a.mass;
+    prm.q_out = (double*)a.q;
+    prm.p_out = (double*)a.p;
+    prm.v_out = (double*)a.v_out;
+    prm.N = a.N; prm.ldn_in = a.ldn; prm.ldn_out = a.ldn;
+    prm.h = a.h; prm.L = a.L; prm.mode = GLM_INTEGRATE; prm.method = a.method;
+    return glm_launch(a.pot, prm, a.stream);
+}
+
+static int glm_eval_launch(const EvalArgs& a, int mode) {
+    if (int rc = glm_check(a.pot, a.ldn)) return rc;
+    if (a.N == 0) return PBBI_OK;
+    GlmPrm prm = glm_prm(a.pot);
+    prm.q_in = (const double*)a.q;
+    prm.p_in = (const double*)a.p;
+    prm.mass = (const double*)a.mass;
+    prm.U_out = (double*)a.U_out;
+    prm.grad_out = (double*)a.grad_out;
+    prm.w_out = (double*)a.w_out;
+    prm.N = a.N; prm.ldn_in = a.ldn; prm.ldn_out = a.ldn;
+    prm.mode = mode;
+    return glm_launch(a.pot, prm, a.stream);
+}
+int glm_eval(const EvalArgs& a) { return glm_eval_launch(a, GLM_EVAL); }
+int glm_energy(const EvalArgs& a) { return glm_eval_launch(a, a.ratio_finish ? GLM_RATIO : GLM_ENERGY); }

@@ -90,6 +90,8 @@ int new_handle(int kind, int D, int dtype, int device, pbbi_potential** out) {
     p->n_params = 0;
     p->plugin_hmc_iter = nullptr; p->plugin_integrate = nullptr; p->plugin_eval = nullptr;
     p->zero_mean = true;
+    p->glm_DP = 0; p->glm_family = 0; p->glm_M = 0; p->glm_lam = 0.0;
+    p->d_glm_img = p->d_glm_y = nullptr;
     *out = p;
     return PBBI_OK;
 }
@@ -139,6 +141,7 @@ int plugin_rc(int rc) {
 }
 int route_hmc(const IterArgs& a) {
     const pbbi_potential* pot = a.pot;
+    if (pot->kind == KIND_GLM) return glm_hmc_iter(a);
     if (pbbi_dyn(a) && (pot->kind == KIND_CUSTOM || (is_big(pot) && !dense_stream_applies(a))))
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, "per-chain trajectory lengths are served by the chain-per-lane "
                                                "kernels (D <= 32) and the dense kernels (fp64, D <= 256) only");
@@ -149,6 +152,7 @@ int route_hmc(const IterArgs& a) {
 // consecutive iterations of pbbi_hmc_run that ONE route_hmc call may cover (IterArgs::fuse_*)
 int route_fused_iterations(const IterArgs& a) {
     const pbbi_potential* pot = a.pot;
+    if (pot->kind == KIND_GLM) return 1;  // one iteration per launch (kernels_glm.hip)
     if (is_big(pot) && pot->kind != KIND_CUSTOM) return dense_stream_applies(a) ? dense_stream_fused_iterations(a) : 1;
     if (pot->kind == KIND_CUSTOM) {
         // plugins (PBBI_PLUGIN_ABI >= 4) take the iterations of a run several at a time: their register
@@ -161,17 +165,20 @@ int route_fused_iterations(const IterArgs& a) {
 }
 int route_integrate(const IntegrateArgs& a) {
     const pbbi_potential* pot = a.pot;
+    if (pot->kind == KIND_GLM) return glm_integrate(a);
     if (pot->kind == KIND_CUSTOM) return a.N ? plugin_rc(pot->plugin_integrate(&a)) : PBBI_OK;
     if (is_big(pot) && dense_stream_integrate_applies(a)) return dense_stream_integrate(a);
     return is_big(pot) ? big_integrate(a) : is_dense(pot) ? dense_integrate(a) : lane_integrate(a);
 }
 int route_eval(const EvalArgs& a) {
     const pbbi_potential* pot = a.pot;
+    if (pot->kind == KIND_GLM) return glm_eval(a);
     if (pot->kind == KIND_CUSTOM) return a.N ? plugin_rc(pot->plugin_eval(&a, 0)) : PBBI_OK;
     return is_big(pot) ? big_eval(a) : is_dense(pot) ? dense_eval(a) : lane_eval(a);
 }
 int route_energy(const EvalArgs& a) {
     const pbbi_potential* pot = a.pot;
+    if (pot->kind == KIND_GLM) return glm_energy(a);
     if (pot->kind == KIND_CUSTOM)
         return a.N ? plugin_rc(pot->plugin_eval(&a, a.ratio_finish ? 2 : 1)) : PBBI_OK;
     return is_big(pot) ? big_energy(a) : is_dense(pot) ? dense_energy(a) : lane_energy(a);
@@ -745,11 +752,38 @@ int pbbi_potential_create_custom(const char* plugin_path, int D, const double* p
     return finish_or_destroy(rc, out);
 }
 
+int pbbi_potential_create_glm(int D, int64_t M, const double* X, const double* y, int family,
+                              double prior_precision, int dtype, int device, pbbi_potential** out) {
+    if (!X || !y) return pbbi_fail(PBBI_ERR_INVALID, "X / y is NULL");
+    if (M < 1) return pbbi_fail(PBBI_ERR_INVALID, "M must be >= 1");
+    if (family != PBBI_GLM_LOGISTIC && family != PBBI_GLM_POISSON)
+        return pbbi_fail(PBBI_ERR_INVALID, "unknown GLM family");
+    if (!(prior_precision >= 0.0)) return pbbi_fail(PBBI_ERR_INVALID, "prior_precision must be >= 0");
+    if (out) *out = nullptr;
+    if (D > 128 || dtype == PBBI_F32)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials run on the fp64 matrix-core kernels: float64 and "
+                                               "D <= 128 only");
+    if (int rc = new_handle(KIND_GLM, D, dtype, device, out)) return rc;
+    DeviceGuard guard(device);
+    return finish_or_destroy(glm_build(*out, M, X, y, family, prior_precision), out);
+}
+
+int pbbi_glm_pack_design(int D, int64_t M, const double* X, double* out, int64_t out_len, int64_t* len_out) {
+    if (D < 1 || D > 128 || M < 1) return pbbi_fail(PBBI_ERR_INVALID, "need 1 <= D <= 128 and M >= 1");
+    const int64_t len = glm_image_len(D, M);
+    if (len_out) *len_out = len;
+    if (!out) return PBBI_OK;
+    if (!X) return pbbi_fail(PBBI_ERR_INVALID, "X is NULL");
+    if (out_len < len) return pbbi_fail(PBBI_ERR_INVALID, "out is shorter than the image");
+    glm_pack(D, M, X, out);
+    return PBBI_OK;
+}
+
 int pbbi_potential_destroy(pbbi_potential* pot) {
     if (!pot) return PBBI_OK;
     DeviceGuard guard(pot->device);
     for (void* p : {pot->d_mean, pot->d_prec, pot->d_frag, pot->d_mean_pad, pot->d_big_PT, pot->d_big_mu,
-                    pot->d_sfrag, pot->d_smean, pot->d_params})
+                    pot->d_sfrag, pot->d_smean, pot->d_params, pot->d_glm_img, pot->d_glm_y})
         if (p) (void)hipFree(p);
     if (pot->plugin) (void)dlclose(pot->plugin);
     delete pot;
@@ -851,6 +885,8 @@ int pbbi_hmc_iter_dyn(const pbbi_potential* pot, int method, const void* q_in, c
         return pbbi_fail(PBBI_ERR_INVALID, "q_in / p_in / u_in / q_out must be non-NULL");
     if (!(kT > 0.0)) return pbbi_fail(PBBI_ERR_INVALID, "kT must be > 0");
     if (method != PBBI_LEAPFROG) return pbbi_fail(PBBI_ERR_UNSUPPORTED, "per-chain trajectory lengths: Leapfrog only");
+    if (pot->kind == KIND_GLM)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials: pbbi_hmc_iter / pbbi_hmc_run (fixed trajectory lengths) only");
     DeviceGuard guard(pot->device);
     IterArgs a{};
     a.pot = pot; a.method = method; a.q_in = q_in; a.p_in = p_in; a.u_in = u_in; a.mass = mass;
@@ -901,6 +937,8 @@ int pbbi_hmc_run_dyn(const pbbi_potential* pot, int method, void* q_state, const
                      uint64_t seed, uint64_t iter0, uint64_t chain0, double kT, void* stream) {
     if (int rc = hmc_check(pot, method, N, ldn, L)) return rc;
     const bool dyn = (flags & (PBBI_PER_CHAIN_STEPS | PBBI_UTURN_STOP)) != 0;
+    if (pot->kind == KIND_GLM && (dyn || steps_out))
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials: pbbi_hmc_run (fixed trajectory lengths) only");
     if (dyn && method != PBBI_LEAPFROG)
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, "per-chain trajectory lengths: Leapfrog only");
     if (S < 0) return pbbi_fail(PBBI_ERR_INVALID, "S must be >= 0");
@@ -1033,6 +1071,7 @@ int pbbi_hmc_run_gist(const pbbi_potential* pot, void* q_state, const void* mass
                       int64_t ldn, double h, int Lmax, int S, int flags, uint64_t seed, uint64_t iter0,
                       uint64_t chain0, double kT, void* stream) {
     if (int rc = hmc_check(pot, PBBI_LEAPFROG, N, ldn, Lmax)) return rc;
+    if (pot->kind == KIND_GLM) return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials: GIST is not served");
     if (Lmax < 1) return pbbi_fail(PBBI_ERR_INVALID, "GIST: the U-turn search needs Lmax >= 1");
     if (S < 0) return pbbi_fail(PBBI_ERR_INVALID, "S must be >= 0");
     if (!(kT > 0.0)) return pbbi_fail(PBBI_ERR_INVALID, "kT must be > 0");
@@ -1092,7 +1131,11 @@ int pbbi_describe_run(const pbbi_potential* pot, int method, int64_t N, int64_t 
     a.carry = 2; a.carry_g = (void*)(uintptr_t)16; a.carry_sel = (uint8_t*)(uintptr_t)16;
     std::string d;
     int fuse = 1;
-    if (pot->kind == KIND_CUSTOM) {
+    if (pot->kind == KIND_GLM) {
+        d = "k_glm: GLM likelihood as two fp64 MFMA products per gradient (eta = X W, g = X^T r), 16 chains per wave, X "
+            "staged through LDS in blocks of 16 observations (rows padded to " + std::to_string(pot->glm_DP) + ")";
+        fuse = 1;
+    } else if (pot->kind == KIND_CUSTOM) {
         d = "user-potential plugin kernels (one chain per lane; registers up to D = 16 / 32, workspace beyond)";
         fuse = route_fused_iterations(a);
     } else if (is_big(pot) && dense_stream_applies(a)) {

@@ -7,7 +7,7 @@
 
 #include "pbbi.h"
 
-enum { KIND_HARMONIC = 0, KIND_GAUSS_DIAG = 1, KIND_GAUSS_DENSE = 2, KIND_ROSENBROCK = 3, KIND_CUSTOM = 4 };
+enum { KIND_HARMONIC = 0, KIND_GAUSS_DIAG = 1, KIND_GAUSS_DENSE = 2, KIND_ROSENBROCK = 3, KIND_CUSTOM = 4, KIND_GLM = 5 };
 
 // layout version of the structs a user-potential plugin (pbbi_custom.h) shares with libpbbi.so
 #define PBBI_PLUGIN_ABI 4  /* 4: plugins honour IterArgs::fuse_* (several iterations of a run per call) */
@@ -44,6 +44,13 @@ struct pbbi_potential {
     int DPS;           // D padded to 192 or 256 (0 = path not available)
     void* d_sfrag;     // DPS*DPS elements: precision in the order the stream consumes it
     void* d_smean;     // DPS elements, zero padded
+    // generalised linear model (KIND_GLM), kernels_glm.hip.  (Appended: plugins built against the fields above keep working.)
+    int glm_DP;        // D padded to 16, 32, 64 or 128 (0 = not a GLM handle)
+    int glm_family;    // PBBI_GLM_*
+    int64_t glm_M;     // observations
+    double glm_lam;    // prior precision
+    void* d_glm_img;   // X in MFMA A-fragment order, blocks of 16 observations (glm_pack)
+    void* d_glm_y;     // y, zero padded to the blocks of the image
 };
 
 // ---- error plumbing ---------------------------------------------------------
@@ -246,3 +253,12 @@ int big_integrate(const IntegrateArgs& a);
 int big_eval(const EvalArgs& a);
 int big_energy(const EvalArgs& a);
 int big_build(pbbi_potential* pot, const double* precision_host, const double* mean_host);
+// generalised linear models, likelihood on the fp64 matrix cores (fp64, D <= 128), kernels_glm.hip
+int glm_build(pbbi_potential* pot, int64_t M, const double* X, const double* y, int family, double lam);
+int glm_padded_dim(int D);
+int64_t glm_image_len(int D, int64_t M);                       // doubles of the fragment image of an M x D design matrix
+void glm_pack(int D, int64_t M, const double* X, double* out);  // host only
+int glm_hmc_iter(const IterArgs& a);
+int glm_integrate(const IntegrateArgs& a);
+int glm_eval(const EvalArgs& a);
+int glm_energy(const EvalArgs& a);

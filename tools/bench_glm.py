@@ -1,0 +1,119 @@
+"""GLM potentials (csrc/kernels_glm.hip) against the user-source plugin path on the same data, one GPU.
+
+Bayesian logistic regression at two shapes, pbbi_hmc_run with in-kernel single-precision draws, L = 10, K
+iterations per timed window.  GLM(X, y) and logistic_regression_posterior(X, y) are timed in ONE process,
+alternating, five repeats each after warming both.  Writes both series, the ratio and the share of the
+78.6 TFLOP/s fp64 MFMA peak (executed 4 M DP flop per chain-gradient, algorithmic 4 M D beside it) to
+profiles/glm_bench.json.
+
+usage: tools/bench_glm.py [--shape small|large|all] [--K 32] [--repeats 5] [--glm-only] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import physicsbasedbayesianinference_amd as P  # noqa: E402
+from physicsbasedbayesianinference_amd import _lib, glm  # noqa: E402
+from physicsbasedbayesianinference_amd.custom import logistic_regression_posterior  # noqa: E402
+
+PEAK_F64_MFMA = 78.6e12
+SHAPES = {"small": dict(M=256, D=16, N=65536, h=0.2), "large": dict(M=16384, D=64, N=16384, h=0.16)}
+
+
+def problem(M, D, seed=0):
+    rs = np.random.RandomState(seed)
+    X = rs.standard_normal((M, D)) / np.sqrt(D)
+    w = rs.standard_normal(D)
+    y = (rs.uniform(size=M) < 1.0 / (1.0 + np.exp(-(X @ w)))).astype(np.float64)
+    return X, y, w, rs
+
+
+class Runner:
+    def __init__(self, pot, D, N, q0, h, L, K):
+        self.pot, self.D, self.N, self.h, self.L, self.K = pot, D, N, h, L, K
+        self.q0 = torch.from_numpy(q0).to("cuda")
+        self.q = self.q0.clone()
+        self.samples = torch.empty((K, D, N), dtype=torch.float64, device="cuda")
+        self.rej = torch.empty((K, N), dtype=torch.uint8, device="cuda")
+        self.it = 0
+
+    def go(self, S):
+        st = torch.cuda.current_stream().cuda_stream
+        _lib.call("pbbi_hmc_run", self.pot.handle, _lib.LEAPFROG, self.q.data_ptr(), None, self.samples.data_ptr(),
+                  None, self.rej.data_ptr(), None, self.N, self.N, self.h, self.L, S, _lib.COMPAT_P_FROM_OLDQ, 7,
+                  self.it, 0, 1.0, st)
+        self.it += S
+
+    def timed(self):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        self.go(self.K)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+
+def bench_shape(name, M, D, N, h, L, K, repeats, warm, glm_only):
+    X, y, w, rs = problem(M, D)
+    q0 = np.ascontiguousarray(w[:, None] + 0.3 * rs.standard_normal((D, N)))
+    runners = {"glm": Runner(P.GLM(X, y), D, N, q0, h, L, K)}
+    if not glm_only:
+        runners["plugin"] = Runner(logistic_regression_posterior(X, y), D, N, q0, h, L, K)
+    for r in runners.values():
+        r.go(warm)
+    torch.cuda.synchronize()
+    series = {k: [] for k in runners}
+    for i in range(repeats):
+        for k, r in runners.items():   # alternating
+            series[k].append(r.timed())
+            print(f"# {name} repeat {i} {k}: {series[k][-1]:.4f} s", flush=True)
+    DP = glm.padded_dim(D)
+    grads = L + 1                       # per iteration and chain: g(q_0) and one per step
+    out = dict(shape=name, M=M, D=D, DP=DP, chains=N, L=L, K=K, h=h,
+               accept_rate={k: 1.0 - float(r.rej.float().mean().item()) for k, r in runners.items()})
+    for k, ts in series.items():
+        out[k + "_seconds"] = ts
+        out[k + "_step_chain_per_s"] = [K * L * N / t for t in ts]
+    tg = np.array(series["glm"])
+    out["glm_executed_tflops"] = [4.0 * M * DP * grads * N * K / t / 1e12 for t in tg]
+    out["glm_algorithmic_tflops"] = [4.0 * M * D * grads * N * K / t / 1e12 for t in tg]
+    out["glm_share_of_fp64_mfma_peak_executed"] = float(4.0 * M * DP * grads * N * K / np.median(tg) / PEAK_F64_MFMA)
+    out["glm_share_of_fp64_mfma_peak_algorithmic"] = float(4.0 * M * D * grads * N * K / np.median(tg) / PEAK_F64_MFMA)
+    if "plugin" in series:
+        tp = np.array(series["plugin"])
+        out["ratio_median"] = float(np.median(tp) / np.median(tg))
+        out["ratio_worst_case"] = float(tp.min() / tg.max())   # fastest plugin repeat over slowest GLM repeat
+        out["slowest_glm_beats_fastest_plugin"] = bool(tg.max() < tp.min())
+    return out
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shape", default="all")
+    ap.add_argument("--K", type=int, default=32)
+    ap.add_argument("--L", type=int, default=10)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--glm-only", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "glm_bench.json"))
+    a = ap.parse_args()
+    names = list(SHAPES) if a.shape == "all" else [a.shape]
+    results = []
+    if os.path.exists(a.out) and a.shape != "all":   # one shape per call: keep the other's record
+        with open(a.out) as f:
+            results = [r for r in json.load(f)["results"] if r["shape"] not in names]
+    for n in names:
+        res = bench_shape(n, L=a.L, K=a.K, repeats=a.repeats, warm=a.warmup, glm_only=a.glm_only, **SHAPES[n])
+        print(json.dumps(res))
+        results.append(res)
+        with open(a.out, "w") as f:
+            json.dump(dict(device=_lib.device_info(0)["name"], peak_fp64_mfma_flops=PEAK_F64_MFMA,
+                           results=sorted(results, key=lambda r: r["shape"], reverse=True)), f, indent=1)
+            f.write("\n")
