@@ -426,6 +426,18 @@ __global__ void __launch_bounds__(BLOCK, 1) k_dense_traj(DensePrm prm) {
 //      (~60 fp64 polynomial constants of log/sincospi/exp, all row offsets) and keeps them
 //      live for the whole kernel (~140 VGPRs); branches around array updates double the
 //      arrays through phi copies; flat addressing costs one 64-bit VGPR address per row.
+//   4. (fixed trajectory lengths, P in LDS: INPL in the kernel) The C/D layout of the MFMA is the layout of the velocity
+//      registers, so an interior full kick does not need an accumulator and an fma behind it: the state is the
+//      momentum IN GRADIENT UNITS,
+//        w = vh / (-h/m):   w_0 = g_0/2 - p/h,   q_{j+1} = q_j + w_j*(-h^2/m),   w_{j+1} = w_j + P x_{j+1},
+//      and the full kick is the mat-vec's own accumulation into w (matvec_inplace: all NT row tiles in one pass, x
+//      formed once, nothing zeroed, no vector instruction behind the last MFMA -- the MFMA stream runs through
+//      the step boundary).  P is unscaled and the drift coefficient is per lane, so masses work as before.  In place:
+//      Leapfrog's steps 1 .. L-1 and all L steps of Stormer-Verlet.  The gradients that are needed as VALUES keep
+//      the two row passes into a zeroed 32-register accumulator: the opening one (x.g for H_old, half kick; from
+//      the carried slab where there is one) and the last trip's (x.g for H_new, the carried gradient -- which
+//      thereby stays what a fresh mat-vec at that position produces -- and Leapfrog's closing half kick,
+//      p_new = -h*(w + g_L/2)).  Per-chain lengths (DYN: per-lane kick coefficients) and the streamed kernels keep vh.
 // The momentum is drawn straight into the velocity registers: one Philox block and two
 // single-precision Box-Muller transforms per four rows (pbbi_rng.h), nothing goes through memory.
 // ------------------------------------------------------------------------------------------
@@ -443,10 +455,16 @@ template <int NT>
 struct KSkip {  // smallest ks_act a kernel of NT row tiles is launched with: D > the next smaller tile size
     static constexpr int MIN = NT == 2 ? 1 : NT == 4 ? 9 : NT == 6 ? 17 : NT == 8 ? 25 : NT == 12 ? 33 : NT == 16 ? 49 : 1;
 };
-template <int NT, int NTP, int PASS, bool DRIFT, bool ZMEAN, bool KSKIP = false>
+// The velocity the drift reads is element s of the caller's state: vh[s], or -- in the units of the in-place form
+// below -- w[s / 4][s % 4] with h = the drift coefficient -h^2/m.
+template <int N>
+__device__ __forceinline__ double vel_at(const double (&v)[N], int s) { return v[s]; }
+template <int N>
+__device__ __forceinline__ double vel_at(const v4f64 (&v)[N], int s) { return v[s >> 2][s & 3]; }
+template <int NT, int NTP, int PASS, bool DRIFT, bool ZMEAN, bool KSKIP = false, class V>
 __device__ __forceinline__ void matvec_pass(const v2f64* __restrict__ fragL,
                                             const double* __restrict__ muG, double (&q)[4 * NT],
-                                            const double (&vh)[4 * NT], v4f64 (&acc)[NTP],
+                                            const V& vh, v4f64 (&acc)[NTP],
                                             double h, int ks_act = 4 * NT) {
     constexpr int KS = 4 * NT;
     constexpr int H = NT / 2;    // fragment pairs per K-step in the LDS image
@@ -457,7 +475,7 @@ __device__ __forceinline__ void matvec_pass(const v2f64* __restrict__ fragL,
     for (int t2 = 0; t2 < HP; ++t2) A[t2] = fragL[(T0 + t2) * 64];
 #pragma unroll
     for (int t = 0; t < NTP; ++t) acc[t] = v4f64{0.0, 0.0, 0.0, 0.0};
-    if constexpr (DRIFT) q[0] = fma(vh[0], h, q[0]);
+    if constexpr (DRIFT) q[0] = fma(vel_at(vh, 0), h, q[0]);
     double x = ZMEAN ? q[0] : q[0] - muG[0];
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
@@ -472,9 +490,53 @@ __device__ __forceinline__ void matvec_pass(const v2f64* __restrict__ fragL,
         }
         double xn = 0.0;
         if (s + 1 < KS) {
-            if constexpr (DRIFT) q[s + 1] = fma(vh[s + 1], h, q[s + 1]);
+            if constexpr (DRIFT) q[s + 1] = fma(vel_at(vh, s + 1), h, q[s + 1]);
             xn = ZMEAN ? q[s + 1] : q[s + 1] - muG[4 * (s + 1)];
         }
+        __builtin_amdgcn_sched_barrier(0);
+        x = xn;
+    }
+}
+
+// The IN-PLACE form (interior leapfrog steps of k_dense_hmc): the accumulator is the caller's live state w, the
+// momentum in gradient units, so that a full kick IS the mat-vec's own accumulation, w += P x.  One pass over the
+// K-steps covers all NT row tiles; nothing is zeroed and nothing follows the last MFMA, so the next step's MFMAs
+// issue straight behind this one's.  Same K order, same A-fragment reload right behind the pair that consumed
+// it, same sched_barrier shape and same KSKIP exits as matvec_pass.
+// The drift q_s += w_s * cd (cd = -h^2/m) needs w_s as the PREVIOUS step left it, and K-step 0 already
+// accumulates into every row tile.  The drift of a tile pair's eight elements therefore sits in K-step 0, directly
+// in front of the pair's first MFMAs: it reads values whose last MFMA is NT - 1 instructions old and it is done
+// before the pair is written again.  (Drifting element s next to K-step s, as matvec_pass does, would read a w_s
+// that already holds s K-steps of the new gradient.)  K-steps 1.. form x from the finished q.
+template <int NT, bool ZMEAN, bool KSKIP>
+__device__ __forceinline__ void matvec_inplace(const v2f64* __restrict__ fragL, const double* __restrict__ muG,
+                                               double (&q)[4 * NT], v4f64 (&w)[NT], double cd, int ks_act) {
+    constexpr int KS = 4 * NT;
+    constexpr int H = NT / 2;
+    v2f64 A[H];
+#pragma unroll
+    for (int t2 = 0; t2 < H; ++t2) A[t2] = fragL[t2 * 64];
+    auto drift_pair = [&](int t2) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) q[8 * t2 + e] = fma(vel_at(w, 8 * t2 + e), cd, q[8 * t2 + e]);
+    };
+    drift_pair(0);
+    double x = ZMEAN ? q[0] : q[0] - muG[0];
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+        if constexpr (KSKIP) {
+            if (s >= KSkip<NT>::MIN && s >= ks_act) break;
+        }
+#pragma unroll
+        for (int t2 = 0; t2 < H; ++t2) {
+            if (s == 0 && t2 > 0) drift_pair(t2);
+            w[2 * t2] = __builtin_amdgcn_mfma_f64_16x16x4f64(A[t2].x, x, w[2 * t2], 0, 0, 0);
+            w[2 * t2 + 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(A[t2].y, x, w[2 * t2 + 1], 0, 0, 0);
+            if (s + 1 < KS) A[t2] = fragL[((s + 1) * H + t2) * 64];
+            if (s == 0) __builtin_amdgcn_sched_barrier(0);  // (or every drift is hoisted in front of the first MFMA)
+        }
+        double xn = 0.0;
+        if (s + 1 < KS) xn = ZMEAN ? q[s + 1] : q[s + 1] - muG[4 * (s + 1)];
         __builtin_amdgcn_sched_barrier(0);
         x = xn;
     }
@@ -652,6 +714,15 @@ __device__ __forceinline__ void kick_pass(double (&vh)[4 * NT], const v4f64 (&ac
         }
 }
 
+// the half kicks of the in-place form: w_s += 0.5 * g_s (w = vh / (-h/m), see k_dense_hmc)
+template <int NT, int NTP, int PASS>
+__device__ __forceinline__ void halfkick_pass(v4f64 (&w)[NT], const v4f64 (&acc)[NTP]) {
+#pragma unroll
+    for (int t = 0; t < NTP; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) w[PASS * NTP + t][r] = fma(acc[t][r], 0.5, w[PASS * NTP + t][r]);
+}
+
 // MODE 0: one HMC iteration (src/HMC.py:154-179).  MODE 1: integrate() in place.
 // METHOD: Leapfrog, or Stormer-Verlet (src/integrator.py:142-163), which in the same state is
 //   d = q_n - q_{n-1} = vh*h:  vh_1 = v_0 + (0.5*a_0)*h;  q_{n+1} = q_n + vh*h;  vh += a_n*h
@@ -686,6 +757,7 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
     constexpr int NPASS = (NT % 4 == 0) ? 2 : 1;  // row passes per mat-vec (NT = 6, DP = 96: one pass of six row tiles)
     constexpr int NTP = NT / NPASS;         // row tiles per pass (even)
     constexpr int WPB = STREAM ? 4 : 8;     // waves per workgroup
+    constexpr bool INPL = !STREAM && !DYN;  // momentum in gradient units, interior kicks in the MFMA's C operand
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -759,6 +831,8 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
     const __amdgpu_buffer_rsrc_t pout = rows_of<FULL>(prm.p_out, n0, D, prm.ldn_out, prm.N);
     const double m = prm.mass ? prm.mass[n0 + cc] : 1.0;
     const double minv = prm.mass ? 1.0 / m : 1.0;
+    // INPL: drift coefficient -h^2/m (per lane: masses), p -> w and w -> p factors -1/h and -h
+    [[maybe_unused]] const double cd = -(h * h) * minv, nih = -1.0 / h, nh = -h;
     const bool rng = (MODE == 0) && prm.rng;
     // carried gradient: slabs [2][D][N] with the leading stride N; this lane's offset into the current one
     [[maybe_unused]] const uint32_t ld_g = 8u * (uint32_t)prm.N, s4g = 4u * ld_g;
@@ -863,7 +937,17 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
     }
 
     // ---- momentum: one Philox block per 4 rows (RNG mode) or the uploaded p_in, then q
-    double vh[KS];
+    // (INPL: the state is w, element s = 4t + r in w[t][r]; everybody else keeps vh)
+    [[maybe_unused]] double vh[KS];
+    [[maybe_unused]] v4f64 w[INPL ? NT : 1];
+    auto vget = [&](int s) -> double {
+        if constexpr (INPL) return w[s >> 2][s & 3];
+        else return vh[s];
+    };
+    auto vset = [&](int s, double val) {
+        if constexpr (INPL) w[s >> 2][s & 3] = val;
+        else vh[s] = val;
+    };
     // rows of pass PASS of the carried gradient <-> acc (element s = 4*(PASS*NTP + t) + r, like q[s])
     auto carry_load = [&](auto pass_c) {
         constexpr int PASS = decltype(pass_c)::value;
@@ -926,18 +1010,18 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
             rng_normal4d(prm.seed, PBBI_STREAM_MOMENTUM, iter_k, chain, (uint32_t)((k << 2) | g), draw64, z);
 #pragma unroll
             for (int sl = 0; sl < 4; ++sl)
-                vh[4 * k + sl] = (FULL || 16 * k + 4 * sl + g < D) ? z[sl] * pstd : 0.0;
+                vset(4 * k + sl, (FULL || 16 * k + 4 * sl + g < D) ? z[sl] * pstd : 0.0);
         }
         if (prm.p_out && !(prm.flags & PBBI_COMPAT_P_FROM_OLDQ) && valid) {
             // non-compat: a rejected chain reports its drawn momentum; park the draw in the slab
             // now (accepted chains overwrite it below) rather than regenerate it later.
 #pragma unroll
-            for (int s = 0; s < KS; ++s) store_row(pout_k, vout, s4out, s, vh[s]);
+            for (int s = 0; s < KS; ++s) store_row(pout_k, vout, s4out, s, vget(s));
         }
     } else {
         const __amdgpu_buffer_rsrc_t pin = rows_of<FULL>(prm.p_in, n0, D, prm.ldn_in, prm.N);
 #pragma unroll
-        for (int s = 0; s < KS; ++s) vh[s] = load_row(pin, vin, s4in, s);
+        for (int s = 0; s < KS; ++s) vset(s, load_row(pin, vin, s4in, s));
     }
     STAMP(2);
     if constexpr (!FUSE) {
@@ -947,8 +1031,9 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
-        pp += vh[s] * vh[s];
-        vh[s] *= minv;  // v = p/m  (:106), as p*(1/m)
+        const double pv = vget(s);
+        pp += pv * pv;
+        vset(s, pv * (INPL ? nih : minv));  // v = p/m  (:106), as p*(1/m); INPL: -p/h, the kick-free part of w_0
     }
     __builtin_amdgcn_sched_barrier(0);
     }
@@ -974,18 +1059,23 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
     } else if constexpr (!FOLD1) {
     if constexpr (CARRY == 2) {
         if constexpr (!FUSE) carry_load(P0{});
+    } else if constexpr (INPL) {
+        MATVEC(0, false, q, w, acc, h);
     } else {
         MATVEC(0, false, q, vh, acc, h);
     }
     if constexpr (CARRY == 1) carry_store(P0{}, vg_cur);
     xg = dot_pass<NT, NTP, 0, ZMEAN>(muG, q, acc);
-    kick_pass<NT, NTP, 0>(vh, acc, ck0);
+    if constexpr (INPL) halfkick_pass<NT, NTP, 0>(w, acc);  // w_0 = g_0/2 - p/h
+    else kick_pass<NT, NTP, 0>(vh, acc, ck0);
     if constexpr (NPASS == 2) {
         if constexpr (CARRY == 2) carry_load(P1{});
+        else if constexpr (INPL) MATVEC(1, false, q, w, acc, h);
         else MATVEC(1, false, q, vh, acc, h);
         if constexpr (CARRY == 1) carry_store(P1{}, vg_cur);
         xg += dot_pass<NT, NTP, 1, ZMEAN>(muG, q, acc);
-        kick_pass<NT, NTP, 1>(vh, acc, ck0);
+        if constexpr (INPL) halfkick_pass<NT, NTP, 1>(w, acc);
+        else kick_pass<NT, NTP, 1>(vh, acc, ck0);
     }
     }
     // H(q_old, p_old) now, so that only one double stays live across the trajectory
@@ -1071,6 +1161,37 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
             if (active && j == Ln - 1) alive = false;
         }
         Ln = taken;
+    } else if constexpr (INPL) {
+    // Interior trips: every full kick of the trajectory, in place (matvec_inplace).  Leapfrog has L - 1 of them
+    // (none at L = 1), Stormer-Verlet L.  The LAST trip is the only one whose gradient is needed as a value --
+    // x.g for H_new, the carried gradient, the closing half kick -- and keeps the two row passes into a zeroed
+    // acc, i.e. the instructions of a fresh mat-vec at that position.  For Leapfrog it is step L with the half
+    // kick; for Stormer-Verlet's HMC iteration the position step L + 1 (:155-159 on the last pass of the
+    // reference's loop), which has no kick; Stormer-Verlet's integrate() ends with that drift alone.
+    constexpr bool TAIL = METHOD == PBBI_LEAPFROG || MODE == 0;
+    const int n_in = METHOD == PBBI_LEAPFROG ? prm.L - 1 : prm.L;
+#pragma nounroll
+    for (int j = 0; j < n_in; ++j) {
+        STAMP(5 + 2 * j);
+        matvec_inplace<NT, ZMEAN, !FULL>(fragL, muG, q, w, cd, ks_act);  // drift + full kick
+    }
+    if constexpr (TAIL) {
+        STAMP(5 + 2 * n_in);
+        MATVEC(0, true, q, w, acc, cd);  // drift + g(q_new)
+        if constexpr (MODE == 0) xg = dot_pass<NT, NTP, 0, ZMEAN>(muG, q, acc);
+        if constexpr (CARRY != 0) carry_store(P0{}, vg_new);  // g(q_new), for the next iteration if this one accepts
+        if constexpr (METHOD == PBBI_LEAPFROG) halfkick_pass<NT, NTP, 0>(w, acc);
+        STAMP(6 + 2 * n_in);
+        if constexpr (NPASS == 2) {
+            MATVEC(1, false, q, w, acc, cd);
+            if constexpr (MODE == 0) xg += dot_pass<NT, NTP, 1, ZMEAN>(muG, q, acc);
+            if constexpr (CARRY != 0) carry_store(P1{}, vg_new);
+            if constexpr (METHOD == PBBI_LEAPFROG) halfkick_pass<NT, NTP, 1>(w, acc);
+        }
+    } else {
+#pragma unroll
+        for (int s = 0; s < KS; ++s) q[s] = fma(vget(s), cd, q[s]);
+    }
     } else {
     // Stormer-Verlet's position step L + 1 (:155-159 on the last pass of the reference's loop) is, for an HMC
     // iteration, one more trip through the same body: drift + the mat-vec that yields U(q_new) -- which is also
@@ -1116,23 +1237,23 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
         }
     }
     }
-    if constexpr (METHOD == PBBI_STORMER_VERLET && MODE == 1) {  // integrate(): position step L + 1, no evaluation
+    if constexpr (METHOD == PBBI_STORMER_VERLET && MODE == 1 && !INPL) {  // integrate(): position step L + 1, no evaluation
 #pragma unroll
         for (int s = 0; s < KS; ++s) q[s] = fma(vh[s], h, q[s]);
     }
-    // vh = final velocity, xg = x . g at the final position
+    // vh = final velocity (INPL: w = -p_new/h), xg = x . g at the final position
 
     if constexpr (MODE == 1) {  // integrate(): in place q, p; optional Integrator.v
         const __amdgpu_buffer_rsrc_t vout_p = rows_of<FULL>(prm.v_out, n0, D, prm.ldn_out, prm.N);
         if (valid) {
             if (prm.v_out) {
 #pragma unroll
-                for (int s = 0; s < KS; ++s) store_row(vout_p, vout, s4out, s, vh[s]);
+                for (int s = 0; s < KS; ++s) store_row(vout_p, vout, s4out, s, INPL ? (vget(s) * nh) * minv : vget(s));
             }
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
                 store_row(qout, vout, s4out, s, q[s]);
-                store_row(pout, vout, s4out, s, vh[s] * m);  // p = v*m (:119)
+                store_row(pout, vout, s4out, s, vget(s) * (INPL ? nh : m));  // p = v*m (:119); INPL: -h*w
             }
         }
     } else {
@@ -1140,8 +1261,9 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
         pp = 0.0;
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
-            vh[s] *= m;  // p = v*m  (:119); vh now holds p
-            pp += vh[s] * vh[s];
+            const double pv = vget(s) * (INPL ? nh : m);  // p = v*m  (:119), INPL: -h*w; the state now holds p
+            vset(s, pv);
+            pp += pv * pv;
         }
         const double newH = 0.5 * chain_sum(pp) / m + (0.5 * chain_sum(xg) + prm.cst);
         STAMP(40);
@@ -1165,13 +1287,13 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
             }
             if (compat) {  // :176  p <- oldQ
 #pragma unroll
-                for (int s = 0; s < KS; ++s) vh[s] = q[s];
+                for (int s = 0; s < KS; ++s) vset(s, q[s]);
             } else if (rng) {
                 store_p = false;  // the draw parked in the slab stays
             } else if (store_p) {
                 const __amdgpu_buffer_rsrc_t pin = rows_of<FULL>(prm.p_in, n0, D, prm.ldn_in, prm.N);
 #pragma unroll
-                for (int s = 0; s < KS; ++s) vh[s] = load_row(pin, vin, s4in, s);
+                for (int s = 0; s < KS; ++s) vset(s, load_row(pin, vin, s4in, s));
             }
         }
         if (valid) {
@@ -1179,7 +1301,7 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
             for (int s = 0; s < KS; ++s) store_row(qout_k, vout, s4out, s, q[s]);  // :178
             if (store_p) {
 #pragma unroll
-                for (int s = 0; s < KS; ++s) store_row(pout_k, vout, s4out, s, vh[s]);  // :179
+                for (int s = 0; s < KS; ++s) store_row(pout_k, vout, s4out, s, vget(s));  // :179
             }
         }
         if constexpr (CARRY != 0) csel ^= reject ? 0u : 1u;  // accepted: the other slab is current now

@@ -38,9 +38,10 @@ st = stamps.cpu().numpy().astype(np.int64)  # last iteration's stamps
 if not LIGHT:
     names = {0: "start", 1: "LDS staged", 2: "RNG done", 3: "q,p loaded", 4: "g(q0)+kick", 40: "steps done",
              41: "stored"}
+    # steps 0 .. L-2 are in place (one pass, one stamp at their start); the last one has two row passes
     for j in range(L):
         names[5 + 2 * j] = f"step{j} begin"; names[6 + 2 * j] = f"step{j} pass0+kick"
-    order = [0, 1, 2, 3, 4] + [k for j in range(L) for k in (5 + 2 * j, 6 + 2 * j)] + [40, 41]
+    order = [0, 1, 2, 3, 4] + [5 + 2 * j for j in range(L - 1)] + [5 + 2 * (L - 1), 6 + 2 * (L - 1)] + [40, 41]
     for label, rows in (("waves 0-3 (prio 1)", [b * 8 + w for b in (0, 100, 300) for w in range(4)]),
                         ("waves 4-7 (prio 0)", [b * 8 + w for b in (0, 100, 300) for w in range(4, 8)])):
         print(label)
