@@ -185,6 +185,26 @@ int pbbi_potential_create_glm(int D, int64_t M, const double* X, const double* y
  *     P2[r2][t][lane][e] = X[16b + 4 (2 r2 + e) + (lane >> 4)][16 t + (lane & 15)]     r2 < 2, t < NT
  * (P1 then P2, 32 DP doubles per block), zero padded; the block count is padded to a multiple of 4. */
 int pbbi_glm_pack_design(int D, int64_t M, const double* X, double* out, int64_t out_len, int64_t* len_out);
+/* The full model: observation weights a_i, offsets o_i, binomial trials n_i and a prior per coefficient,
+ *     U(w) = sum_i a_i [ n_i b(eta_i) - y_i eta_i ] + 0.5 sum_d lam_d (w_d - mu_d)^2,    eta_i = x_i . w + o_i,
+ *     grad U = X^T r + lam (.) (w - mu),    r_i = a_i [ n_i b'(eta_i) - y_i ].
+ * weights / offset / trials: host pointers to M doubles, NULL = all 1 / all 0 / all 1; weights finite and >= 0 (a
+ * row of weight 0 contributes exactly 0 to U and the gradient, even where b(eta_i) overflows), offset finite (for
+ * Poisson rates typically log(exposure)), trials integers >= 1 and logistic only (y_i = successes, integers in
+ * [0, n_i]; Poisson y = counts).  prior_precision: D doubles, each finite and >= 0 (0 = a flat coordinate), required;
+ * prior_mean: D doubles or NULL = 0.  Violations return PBBI_ERR_INVALID with a message before anything is
+ * allocated.  The handle runs the same kernels and serves the same calls as one of pbbi_potential_create_glm (whose
+ * model is the case weights = trials = 1, offset = 0, lam_d = prior_precision, mu = 0, on kernels of its own whose
+ * arithmetic this entry does not touch); the device keeps c_i = a_i n_i, d_i = a_i y_i and o_i. */
+int pbbi_potential_create_glm_ex(int D, int64_t M, const double* X, const double* y, int family,
+                                 const double* weights, const double* offset, const double* trials,
+                                 const double* prior_precision, const double* prior_mean, int dtype, int device,
+                                 pbbi_potential** out);
+/* The three observation streams pbbi_potential_create_glm_ex uploads, on the HOST (touches no device, checks the
+ * same rules): *len_out <- their total length in doubles, 3 * 16 * (blocks of 16 observations padded to a multiple of
+ * 4); with `out` non-NULL (out_len >= that length) c | d | o, each stream zero padded past M. */
+int pbbi_glm_pack_observations(int64_t M, int family, const double* y, const double* weights, const double* offset,
+                               const double* trials, double* out, int64_t out_len, int64_t* len_out);
 int pbbi_potential_destroy(pbbi_potential* pot);
 int pbbi_potential_dim(const pbbi_potential* pot);
 int pbbi_potential_dtype(const pbbi_potential* pot);

@@ -55,6 +55,8 @@ PROTOTYPES = {
     "pbbi_potential_create_custom": [C.c_char_p, _i, _dp, _i, _i, _i, _pp],
     "pbbi_potential_create_glm": [_i, _i64, _dp, _dp, _i, _d, _i, _i, _pp],
     "pbbi_glm_pack_design": [_i, _i64, _dp, _dp, _i64, C.POINTER(C.c_int64)],
+    "pbbi_potential_create_glm_ex": [_i, _i64, _dp, _dp, _i, _dp, _dp, _dp, _dp, _dp, _i, _i, _pp],
+    "pbbi_glm_pack_observations": [_i64, _i, _dp, _dp, _dp, _dp, _dp, _i64, C.POINTER(C.c_int64)],
     "pbbi_potential_destroy": [_vp],
     "pbbi_potential_dim": [_vp],
     "pbbi_potential_dtype": [_vp],

@@ -29,10 +29,23 @@
 // evaluations whose kick / drift coefficients say which update follows it.  Nothing is carried between the
 // iterations of a run, so a run of S iterations is S launches and equals S runs of one bit for bit by
 // construction.
+//
+// The full model (RICH = true; handles of pbbi_potential_create_glm_ex):
+//   U(w) = sum_i a_i [ n_i b(eta_i) - y_i eta_i ] + 0.5 sum_d lam_d (w_d - mu_d)^2,   eta_i = x_i.w + o_i
+// with observation weights a_i, binomial trials n_i and offsets o_i.  The device sees c_i = a_i n_i, d_i = a_i y_i
+// and o_i: three streams of one value per observation that travel through LDS beside the X chunk where the plain
+// model stages y alone (U_i = c_i b(eta_i) - d_i eta_i, r_i = c_i b'(eta_i) - d_i).  An observation with c_i = d_i
+// = 0 is SELECTED out like one past M -- its b(eta_i) may have overflowed and 0 * inf is NaN.  lam_d and mu_d sit in
+// LDS for the whole launch (2 DP doubles, loaded once): KS more values per lane in registers would push the DP =
+// 128 kernels into scratch, and they are read KS times per gradient next to M DP / 8 MFMAs.  The plain model's
+// instantiations (RICH = false) hold none of this: their code is what it was before the full model existed.
+#include <cmath>
 #include <cstring>
 
 #include "kernels_dense_dev.h"
 #include "pbbi_chain.h"
+
+static int64_t glm_blocks_padded(int64_t M);
 
 namespace {
 
@@ -56,6 +69,16 @@ struct GlmPrm {
     int L, D, flags, rng, mode, method, nb;
     uint64_t seed, iter, chain0;
 };
+// the full model's kernel arguments (the plain kernels keep theirs as they are)
+struct GlmPrmRich : GlmPrm {
+    const double* obs;    // c | d | o, each obs_stride = nbp * 16 doubles, zero padded
+    const double* prior;  // lam (DP) | mu (DP), zero padded past D
+    int64_t obs_stride;
+};
+template <bool RICH>
+struct GlmArgs { using type = GlmPrm; };
+template <>
+struct GlmArgs<true> { using type = GlmPrmRich; };
 enum { GLM_HMC = 0, GLM_INTEGRATE = 1, GLM_EVAL = 2, GLM_ENERGY = 3, GLM_RATIO = 4 };
 
 template <int NT>
@@ -66,6 +89,8 @@ struct GlmCfg {
     static constexpr int CHV = CB * BLKV;              // ... per chunk
     static constexpr int PER_THREAD = CHV / BLOCK;     // = CB * NT
     static_assert(CHV % BLOCK == 0, "whole 16-byte elements per thread");
+    static constexpr int OBS = CB * 16;                // observations per chunk
+    static_assert(3 * OBS <= BLOCK, "one thread per staged value of c | d | o");
 };
 
 // b(eta) - y eta and b'(eta) - y of one observation
@@ -84,13 +109,31 @@ __device__ __forceinline__ void glm_link(double eta, double yv, bool want_u, dou
     }
 }
 
+// the full model's c b(eta) - d eta and c b'(eta) - d
+template <int FAM>
+__device__ __forceinline__ void glm_link_rich(double eta, double cv, double dv, bool want_u, double& resid,
+                                              double& uterm) {
+    if constexpr (FAM == PBBI_GLM_LOGISTIC) {
+        const double e = exp(-fabs(eta));
+        const double inv = 1.0 / (1.0 + e);
+        resid = cv * (eta >= 0.0 ? inv : e * inv) - dv;
+        uterm = 0.0;
+        if (want_u) uterm = cv * ((eta > 0.0 ? eta : 0.0) + log1p(e)) - dv * eta;
+    } else {
+        const double e = exp(eta);
+        resid = cv * e - dv;
+        uterm = cv * e - dv * eta;
+    }
+}
+
 // gacc[t][r] (row 16t + 4r + g) = sum_i X[i][row] (b'(eta_i) - y_i) for the wave's 16 chains, usum = this lane's
 // share of sum_i b(eta_i) - y_i eta_i (observations {4r + g} of every block; chain_sum completes it).
 // Every wave of the workgroup takes part in the staging: one chunk of CB blocks is in LDS while the next waits
 // in registers (fetched before the MFMAs of the current one, written after the barrier that ends its reads).
-template <int NT, int FAM>
-__device__ __forceinline__ void glm_grad(const GlmPrm& prm, v2f64* __restrict__ lds, double* __restrict__ ylds,
-                                         int lane, int g, const double (&q)[4 * NT], v4f64 (&gacc)[NT],
+// RICH: ylds holds the chunk's c | d | o (OBS values each); thread j < 3 OBS stages value j % OBS of stream j / OBS.
+template <int NT, int FAM, bool RICH>
+__device__ __forceinline__ void glm_grad(const typename GlmArgs<RICH>::type& prm, v2f64* __restrict__ lds,
+                                         double* __restrict__ ylds, int lane, int g, const double (&q)[4 * NT], v4f64 (&gacc)[NT],
                                          double& usum, bool want_u) {
     using C = GlmCfg<NT>;
     constexpr int KS = C::KS;
@@ -98,9 +141,16 @@ __device__ __forceinline__ void glm_grad(const GlmPrm& prm, v2f64* __restrict__ 
     const int nch = (prm.nb + C::CB - 1) / C::CB;
     v2f64 tmp[C::PER_THREAD];
     double ytmp = 0.0;
+    const double* __restrict__ osrc = nullptr;  // RICH: this thread's value of chunk 0
+    if constexpr (RICH)
+        if (threadIdx.x < 3 * C::OBS) osrc = prm.obs + (threadIdx.x / C::OBS) * prm.obs_stride + threadIdx.x % C::OBS;
 #pragma unroll
     for (int j = 0; j < C::PER_THREAD; ++j) tmp[j] = src[threadIdx.x + j * BLOCK];
-    if (threadIdx.x < C::CB * 16) ytmp = prm.y[threadIdx.x];
+    if constexpr (RICH) {
+        if (osrc) ytmp = osrc[0];
+    } else {
+        if (threadIdx.x < C::CB * 16) ytmp = prm.y[threadIdx.x];
+    }
 #pragma unroll
     for (int t = 0; t < NT; ++t) gacc[t] = v4f64{0.0, 0.0, 0.0, 0.0};
     usum = 0.0;
@@ -108,13 +158,21 @@ __device__ __forceinline__ void glm_grad(const GlmPrm& prm, v2f64* __restrict__ 
         __syncthreads();  // everybody has finished reading the previous chunk
 #pragma unroll
         for (int j = 0; j < C::PER_THREAD; ++j) lds[threadIdx.x + j * BLOCK] = tmp[j];
-        if (threadIdx.x < C::CB * 16) ylds[threadIdx.x] = ytmp;
+        if constexpr (RICH) {
+            if (osrc) ylds[threadIdx.x] = ytmp;
+        } else {
+            if (threadIdx.x < C::CB * 16) ylds[threadIdx.x] = ytmp;
+        }
         __syncthreads();
         if (ch + 1 < nch) {
             const v2f64* nsrc = src + (size_t)(ch + 1) * C::CHV;
 #pragma unroll
             for (int j = 0; j < C::PER_THREAD; ++j) tmp[j] = nsrc[threadIdx.x + j * BLOCK];
-            if (threadIdx.x < C::CB * 16) ytmp = prm.y[(size_t)(ch + 1) * (C::CB * 16) + threadIdx.x];
+            if constexpr (RICH) {
+                if (osrc) ytmp = osrc[(size_t)(ch + 1) * C::OBS];
+            } else {
+                if (threadIdx.x < C::CB * 16) ytmp = prm.y[(size_t)(ch + 1) * (C::CB * 16) + threadIdx.x];
+            }
         }
 #pragma unroll
         for (int bi = 0; bi < C::CB; ++bi) {
@@ -137,9 +195,18 @@ __device__ __forceinline__ void glm_grad(const GlmPrm& prm, v2f64* __restrict__ 
             for (int r = 0; r < 4; ++r) {
                 const bool ok = obs0 + 4 * r < prm.M;
                 double rr, ut;
-                glm_link<FAM>(eta[r], ylds[bi * 16 + 4 * r + g], want_u, rr, ut);
-                res[r] = ok ? rr : 0.0;
-                usum += ok ? ut : 0.0;
+                if constexpr (RICH) {
+                    const int i = bi * 16 + 4 * r + g;
+                    const double cv = ylds[i], dv = ylds[C::OBS + i], ov = ylds[2 * C::OBS + i];
+                    glm_link_rich<FAM>(eta[r] + ov, cv, dv, want_u, rr, ut);
+                    const bool on = ok && !(cv == 0.0 && dv == 0.0);  // weight 0: exactly nothing, whatever b() gave
+                    res[r] = on ? rr : 0.0;
+                    usum += on ? ut : 0.0;
+                } else {
+                    glm_link<FAM>(eta[r], ylds[bi * 16 + 4 * r + g], want_u, rr, ut);
+                    res[r] = ok ? rr : 0.0;
+                    usum += ok ? ut : 0.0;
+                }
             }
             // g tiles += X_b^T . R_b: K-step r sums over the observations register r holds
 #pragma unroll
@@ -154,12 +221,18 @@ __device__ __forceinline__ void glm_grad(const GlmPrm& prm, v2f64* __restrict__ 
     }
 }
 
-template <int NT, int FAM>
-__global__ void __launch_bounds__(BLOCK, NT <= 2 ? 2 : 1) k_glm(GlmPrm prm) {
+template <int NT, int FAM, bool RICH>
+__global__ void __launch_bounds__(BLOCK, NT <= 2 ? 2 : 1) k_glm(typename GlmArgs<RICH>::type prm) {
     using C = GlmCfg<NT>;
     constexpr int KS = C::KS;
+    constexpr int DP = 16 * NT;
     __shared__ __attribute__((aligned(16))) v2f64 lds[C::CHV];
-    __shared__ double ylds[C::CB * 16];
+    __shared__ double ylds[(RICH ? 3 : 1) * C::CB * 16];
+    __shared__ __attribute__((aligned(16))) v2f64 plds[RICH ? DP : 1];  // RICH: {lam, mu} of each row (else unused)
+    if constexpr (RICH) {
+        for (int i = threadIdx.x; i < DP; i += BLOCK) plds[i] = v2f64{prm.prior[i], prm.prior[DP + i]};
+        __syncthreads();
+    }
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane >> 4;
@@ -254,12 +327,22 @@ __global__ void __launch_bounds__(BLOCK, NT <= 2 ? 2 : 1) k_glm(GlmPrm prm) {
         ck *= minv;
         const bool want_u = (e == 0 || e == nev - 1) && mode != GLM_INTEGRATE;
         double usum;
-        glm_grad<NT, FAM>(prm, lds, ylds, lane, g, q, gacc, usum, want_u);
+        glm_grad<NT, FAM, RICH>(prm, lds, ylds, lane, g, q, gacc, usum, want_u);
         if (want_u) {
             double qq = 0.0;
+            if constexpr (RICH) {
 #pragma unroll
-            for (int s = 0; s < KS; ++s) qq = fma(q[s], q[s], qq);
-            U_new = chain_sum(usum) + (0.5 * lam) * chain_sum(qq);
+                for (int s = 0; s < KS; ++s) {
+                    const v2f64 pm = plds[4 * s + g];
+                    const double dq = q[s] - pm.y;
+                    qq = fma(pm.x * dq, dq, qq);
+                }
+                U_new = chain_sum(usum) + 0.5 * chain_sum(qq);
+            } else {
+#pragma unroll
+                for (int s = 0; s < KS; ++s) qq = fma(q[s], q[s], qq);
+                U_new = chain_sum(usum) + (0.5 * lam) * chain_sum(qq);
+            }
             if (e == 0) U_old = U_new;
         }
         if (mode == GLM_EVAL) break;  // the gradient stays in gacc
@@ -271,7 +354,13 @@ __global__ void __launch_bounds__(BLOCK, NT <= 2 ? 2 : 1) k_glm(GlmPrm prm) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int s = 4 * t + r;
-                const double gt = fma(lam, q[s], gacc[t][r]);
+                double gt;
+                if constexpr (RICH) {
+                    const v2f64 pm = plds[4 * s + g];
+                    gt = fma(pm.x, q[s] - pm.y, gacc[t][r]);
+                } else {
+                    gt = fma(lam, q[s], gacc[t][r]);
+                }
                 vh[s] = fma(-gt, ck, vh[s]);
                 q[s] = fma(vh[s], hd, q[s]);
             }
@@ -283,8 +372,17 @@ __global__ void __launch_bounds__(BLOCK, NT <= 2 ? 2 : 1) k_glm(GlmPrm prm) {
 #pragma unroll
             for (int t = 0; t < NT; ++t)
 #pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    store_row(gout, vout, s4out, 4 * t + r, fma(lam, q[4 * t + r], gacc[t][r]));
+                for (int r = 0; r < 4; ++r) {
+                    const int s = 4 * t + r;
+                    double gt;
+                    if constexpr (RICH) {
+                        const v2f64 pm = plds[4 * s + g];
+                        gt = fma(pm.x, q[s] - pm.y, gacc[t][r]);
+                    } else {
+                        gt = fma(lam, q[s], gacc[t][r]);
+                    }
+                    store_row(gout, vout, s4out, s, gt);
+                }
         }
         if (prm.U_out && valid && g == 0) prm.U_out[n0 + c] = U_old;
         return;
@@ -381,14 +479,21 @@ GlmPrm glm_prm(const pbbi_potential* pot) {
 
 int glm_launch(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t stream) {
     const dim3 grid((unsigned)((prm.N + CHAINS_PER_WG - 1) / CHAINS_PER_WG)), block(BLOCK);
-#define GLM_CASE(NT_)                                                                                       \
-    if (pot->glm_DP == 16 * NT_) {                                                                          \
+    const bool rich = pot->d_glm_obs != nullptr;  // handle of pbbi_potential_create_glm_ex
+    GlmPrmRich rprm{};
+    static_cast<GlmPrm&>(rprm) = prm;
+    rprm.obs = (const double*)pot->d_glm_obs;
+    rprm.prior = (const double*)pot->d_glm_prior;
+    rprm.obs_stride = glm_blocks_padded(pot->glm_M) * 16;
+#define GLM_CASE(NT_, RICH_, PRM_)                                                                          \
+    if (pot->glm_DP == 16 * NT_ && rich == RICH_) {                                                         \
         if (pot->glm_family == PBBI_GLM_LOGISTIC)                                                           \
-            hipLaunchKernelGGL((k_glm<NT_, PBBI_GLM_LOGISTIC>), grid, block, 0, stream, prm);               \
+            hipLaunchKernelGGL((k_glm<NT_, PBBI_GLM_LOGISTIC, RICH_>), grid, block, 0, stream, PRM_);       \
         else                                                                                                \
-            hipLaunchKernelGGL((k_glm<NT_, PBBI_GLM_POISSON>), grid, block, 0, stream, prm);                \
+            hipLaunchKernelGGL((k_glm<NT_, PBBI_GLM_POISSON, RICH_>), grid, block, 0, stream, PRM_);        \
     }
-    GLM_CASE(1) GLM_CASE(2) GLM_CASE(4) GLM_CASE(8)
+    GLM_CASE(1, false, prm) GLM_CASE(2, false, prm) GLM_CASE(4, false, prm) GLM_CASE(8, false, prm)
+    GLM_CASE(1, true, rprm) GLM_CASE(2, true, rprm) GLM_CASE(4, true, rprm) GLM_CASE(8, true, rprm)
 #undef GLM_CASE
     PBBI_HIP(hipGetLastError());
     return PBBI_OK;
@@ -442,6 +547,95 @@ int glm_build(pbbi_potential* pot, int64_t M, const double* X, const double* y, 
     pot->glm_M = M;
     pot->glm_family = family;
     pot->glm_lam = lam;
+    return PBBI_OK;
+}
+
+// ---- host side: the full model's observation streams and prior vectors ------------------------------------
+int64_t glm_obs_len(int64_t M) { return 3 * glm_blocks_padded(M) * 16; }
+
+// Every rule of the full model's per-observation arguments (NULL = the default: weights 1, offset 0, trials 1).
+int glm_check_obs(int64_t M, int family, const double* y, const double* weights, const double* offset,
+                  const double* trials) {
+    if (M < 1) return pbbi_fail(PBBI_ERR_INVALID, "M must be >= 1");
+    if (family != PBBI_GLM_LOGISTIC && family != PBBI_GLM_POISSON)
+        return pbbi_fail(PBBI_ERR_INVALID, "unknown GLM family");
+    if (!y) return pbbi_fail(PBBI_ERR_INVALID, "y is NULL");
+    if (trials && family != PBBI_GLM_LOGISTIC)
+        return pbbi_fail(PBBI_ERR_INVALID, "trials belong to the logistic (binomial) family only");
+    for (int64_t i = 0; i < M; ++i) {
+        auto at = [i] { return " (observation " + std::to_string(i) + ")"; };
+        const double n = trials ? trials[i] : 1.0;
+        if (!std::isfinite(n) || n < 1.0 || n != std::floor(n))
+            return pbbi_fail(PBBI_ERR_INVALID, "trials must be integers >= 1" + at());
+        if (!std::isfinite(y[i]) || y[i] < 0.0 || y[i] != std::floor(y[i]))
+            return pbbi_fail(PBBI_ERR_INVALID, "y must hold non-negative integers" + at());
+        if (family == PBBI_GLM_LOGISTIC && y[i] > n)
+            return pbbi_fail(PBBI_ERR_INVALID, "logistic: y must not exceed the trials" + at());
+        if (weights && !(std::isfinite(weights[i]) && weights[i] >= 0.0))
+            return pbbi_fail(PBBI_ERR_INVALID, "weights must be finite and >= 0" + at());
+        if (offset && !std::isfinite(offset[i]))
+            return pbbi_fail(PBBI_ERR_INVALID, "offset must be finite" + at());
+    }
+    return PBBI_OK;
+}
+
+// c = a n | d = a y | o, each zero padded to the image's block count (glm_obs_len(M) doubles).  Host only.
+void glm_pack_obs(int64_t M, const double* y, const double* weights, const double* offset, const double* trials,
+                  double* out) {
+    const int64_t len = glm_blocks_padded(M) * 16;
+    std::memset(out, 0, sizeof(double) * (size_t)(3 * len));
+    for (int64_t i = 0; i < M; ++i) {
+        const double a = weights ? weights[i] : 1.0;
+        out[i] = a * (trials ? trials[i] : 1.0);
+        out[len + i] = a * y[i];
+        out[2 * len + i] = offset ? offset[i] : 0.0;
+    }
+}
+
+int glm_check_prior(int D, const double* lam, const double* mu) {
+    if (!lam) return pbbi_fail(PBBI_ERR_INVALID, "prior_precision is NULL");
+    for (int d = 0; d < D; ++d) {
+        if (!(std::isfinite(lam[d]) && lam[d] >= 0.0))
+            return pbbi_fail(PBBI_ERR_INVALID, "prior_precision must be finite and >= 0 (coefficient " + std::to_string(d) + ")");
+        if (mu && !std::isfinite(mu[d]))
+            return pbbi_fail(PBBI_ERR_INVALID, "prior_mean must be finite (coefficient " + std::to_string(d) + ")");
+    }
+    return PBBI_OK;
+}
+
+// the caller has run glm_check_obs and glm_check_prior
+int glm_build_ex(pbbi_potential* pot, int64_t M, const double* X, const double* y, int family, const double* weights,
+                 const double* offset, const double* trials, const double* lam, const double* mu) {
+    const int D = pot->D;
+    if (D > 128 || pot->dtype != PBBI_F64)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials run on the fp64 matrix-core kernels: float64 and "
+                                               "D <= 128 only (D = " + std::to_string(D) + ")");
+    const int DP = glm_padded_dim(D);
+    std::vector<double> img((size_t)glm_image_len(D, M));
+    glm_pack(D, M, X, img.data());
+    std::vector<double> obs((size_t)glm_obs_len(M));
+    glm_pack_obs(M, y, weights, offset, trials, obs.data());
+    std::vector<double> prior((size_t)2 * DP, 0.0);  // lam | mu, zeros past D
+    bool flat = true, centred = true, one = true;
+    for (int d = 0; d < D; ++d) {
+        prior[d] = lam[d];
+        prior[DP + d] = mu ? mu[d] : 0.0;
+        flat = flat && lam[d] == 0.0;
+        one = one && lam[d] == lam[0];
+        centred = centred && prior[DP + d] == 0.0;
+    }
+    PBBI_HIP(hipMalloc(&pot->d_glm_img, img.size() * sizeof(double)));
+    PBBI_HIP(hipMalloc(&pot->d_glm_obs, obs.size() * sizeof(double)));
+    PBBI_HIP(hipMalloc(&pot->d_glm_prior, prior.size() * sizeof(double)));
+    PBBI_HIP(hipMemcpy(pot->d_glm_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
+    PBBI_HIP(hipMemcpy(pot->d_glm_obs, obs.data(), obs.size() * sizeof(double), hipMemcpyHostToDevice));
+    PBBI_HIP(hipMemcpy(pot->d_glm_prior, prior.data(), prior.size() * sizeof(double), hipMemcpyHostToDevice));
+    pot->glm_DP = DP;
+    pot->glm_M = M;
+    pot->glm_family = family;
+    pot->glm_lam = one ? lam[0] : 0.0;  // (the full model's kernels read d_glm_prior)
+    pot->glm_terms = (weights ? GLM_TERM_WEIGHTS : 0) | (offset ? GLM_TERM_OFFSET : 0) | (trials ? GLM_TERM_TRIALS : 0) |
+                     (one ? 0 : GLM_TERM_PRIOR_VECTOR) | (centred ? 0 : GLM_TERM_PRIOR_MEAN) | (flat ? GLM_TERM_PRIOR_FLAT : 0);
     return PBBI_OK;
 }
 

@@ -92,6 +92,8 @@ int new_handle(int kind, int D, int dtype, int device, pbbi_potential** out) {
     p->zero_mean = true;
     p->glm_DP = 0; p->glm_family = 0; p->glm_M = 0; p->glm_lam = 0.0;
     p->d_glm_img = p->d_glm_y = nullptr;
+    p->d_glm_obs = p->d_glm_prior = nullptr;
+    p->glm_terms = 0;
     *out = p;
     return PBBI_OK;
 }
@@ -768,6 +770,35 @@ int pbbi_potential_create_glm(int D, int64_t M, const double* X, const double* y
     return finish_or_destroy(glm_build(*out, M, X, y, family, prior_precision), out);
 }
 
+int pbbi_potential_create_glm_ex(int D, int64_t M, const double* X, const double* y, int family,
+                                 const double* weights, const double* offset, const double* trials,
+                                 const double* prior_precision, const double* prior_mean, int dtype, int device,
+                                 pbbi_potential** out) {
+    if (out) *out = nullptr;
+    if (!X || !y) return pbbi_fail(PBBI_ERR_INVALID, "X / y is NULL");
+    if (D < 1) return pbbi_fail(PBBI_ERR_INVALID, "D must be >= 1");
+    if (int rc = glm_check_obs(M, family, y, weights, offset, trials)) return rc;
+    if (D > 128 || dtype == PBBI_F32)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials run on the fp64 matrix-core kernels: float64 and "
+                                               "D <= 128 only");
+    if (int rc = glm_check_prior(D, prior_precision, prior_mean)) return rc;
+    if (int rc = new_handle(KIND_GLM, D, dtype, device, out)) return rc;
+    DeviceGuard guard(device);
+    return finish_or_destroy(glm_build_ex(*out, M, X, y, family, weights, offset, trials, prior_precision, prior_mean), out);
+}
+
+int pbbi_glm_pack_observations(int64_t M, int family, const double* y, const double* weights, const double* offset,
+                               const double* trials, double* out, int64_t out_len, int64_t* len_out) {
+    if (M < 1) return pbbi_fail(PBBI_ERR_INVALID, "M must be >= 1");
+    const int64_t len = glm_obs_len(M);
+    if (len_out) *len_out = len;
+    if (!out) return PBBI_OK;
+    if (int rc = glm_check_obs(M, family, y, weights, offset, trials)) return rc;
+    if (out_len < len) return pbbi_fail(PBBI_ERR_INVALID, "out is shorter than the three streams");
+    glm_pack_obs(M, y, weights, offset, trials, out);
+    return PBBI_OK;
+}
+
 int pbbi_glm_pack_design(int D, int64_t M, const double* X, double* out, int64_t out_len, int64_t* len_out) {
     if (D < 1 || D > 128 || M < 1) return pbbi_fail(PBBI_ERR_INVALID, "need 1 <= D <= 128 and M >= 1");
     const int64_t len = glm_image_len(D, M);
@@ -783,7 +814,7 @@ int pbbi_potential_destroy(pbbi_potential* pot) {
     if (!pot) return PBBI_OK;
     DeviceGuard guard(pot->device);
     for (void* p : {pot->d_mean, pot->d_prec, pot->d_frag, pot->d_mean_pad, pot->d_big_PT, pot->d_big_mu,
-                    pot->d_sfrag, pot->d_smean, pot->d_params, pot->d_glm_img, pot->d_glm_y})
+                    pot->d_sfrag, pot->d_smean, pot->d_params, pot->d_glm_img, pot->d_glm_y, pot->d_glm_obs, pot->d_glm_prior})
         if (p) (void)hipFree(p);
     if (pot->plugin) (void)dlclose(pot->plugin);
     delete pot;
@@ -1134,6 +1165,17 @@ int pbbi_describe_run(const pbbi_potential* pot, int method, int64_t N, int64_t 
     if (pot->kind == KIND_GLM) {
         d = "k_glm: GLM likelihood as two fp64 MFMA products per gradient (eta = X W, g = X^T r), 16 chains per wave, X "
             "staged through LDS in blocks of 16 observations (rows padded to " + std::to_string(pot->glm_DP) + ")";
+        if (pot->d_glm_obs) {
+            const int t = pot->glm_terms;
+            d += "; full model (c | d | o streams beside X, prior vectors in LDS):";
+            d += (t & GLM_TERM_WEIGHTS) ? " weights," : "";
+            d += (t & GLM_TERM_OFFSET) ? " offset," : "";
+            d += (t & GLM_TERM_TRIALS) ? " binomial trials," : "";
+            d += (t & GLM_TERM_PRIOR_FLAT) ? " flat prior" : (t & GLM_TERM_PRIOR_VECTOR) ? " per-coefficient prior precision" : " scalar prior precision";
+            d += (t & GLM_TERM_PRIOR_MEAN) ? ", prior mean" : "";
+        } else {
+            d += "; plain model (every observation once, one prior precision)";
+        }
         fuse = 1;
     } else if (pot->kind == KIND_CUSTOM) {
         d = "user-potential plugin kernels (one chain per lane; registers up to D = 16 / 32, workspace beyond)";

@@ -51,6 +51,10 @@ struct pbbi_potential {
     double glm_lam;    // prior precision
     void* d_glm_img;   // X in MFMA A-fragment order, blocks of 16 observations (glm_pack)
     void* d_glm_y;     // y, zero padded to the blocks of the image
+    // the full model (pbbi_potential_create_glm_ex); all zero / NULL on a handle of pbbi_potential_create_glm.  (Appended.)
+    void* d_glm_obs;   // c = a n | d = a y | o, each zero padded to the blocks of the image (glm_pack_obs)
+    void* d_glm_prior; // lam (glm_DP) | mu (glm_DP), zeros past D
+    int glm_terms;     // GLM_TERM_*: what pbbi_describe_run names
 };
 
 // ---- error plumbing ---------------------------------------------------------
@@ -255,6 +259,16 @@ int big_energy(const EvalArgs& a);
 int big_build(pbbi_potential* pot, const double* precision_host, const double* mean_host);
 // generalised linear models, likelihood on the fp64 matrix cores (fp64, D <= 128), kernels_glm.hip
 int glm_build(pbbi_potential* pot, int64_t M, const double* X, const double* y, int family, double lam);
+enum { GLM_TERM_WEIGHTS = 1, GLM_TERM_OFFSET = 2, GLM_TERM_TRIALS = 4, GLM_TERM_PRIOR_VECTOR = 8, GLM_TERM_PRIOR_MEAN = 16,
+       GLM_TERM_PRIOR_FLAT = 32 };
+int glm_build_ex(pbbi_potential* pot, int64_t M, const double* X, const double* y, int family, const double* weights,
+                 const double* offset, const double* trials, const double* lam, const double* mu);
+int glm_check_obs(int64_t M, int family, const double* y, const double* weights, const double* offset,
+                  const double* trials);                       // host only: PBBI_ERR_INVALID with a message
+int glm_check_prior(int D, const double* lam, const double* mu);
+int64_t glm_obs_len(int64_t M);                                // doubles of the three observation streams
+void glm_pack_obs(int64_t M, const double* y, const double* weights, const double* offset, const double* trials,
+                  double* out);                                // host only
 int glm_padded_dim(int D);
 int64_t glm_image_len(int D, int64_t M);                       // doubles of the fragment image of an M x D design matrix
 void glm_pack(int D, int64_t M, const double* X, double* out);  // host only

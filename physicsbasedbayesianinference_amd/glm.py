@@ -6,6 +6,15 @@ over the M rows x_i of the design matrix X: -log posterior of the weights of a G
 and a N(0, I / prior_precision) prior.  `family="logistic"`: b = softplus, y in {0, 1} (the model of
 custom.logistic_regression_posterior); `family="poisson"`: b = exp, y counts.
 
+With any of `weights`, `offset`, `trials`, `prior_mean` or a `(D,)` vector of prior precisions the model is
+
+    U(w) = sum_i a_i [ n_i b(eta_i) - y_i eta_i ] + 0.5 sum_d lam_d (w_d - mu_d)^2,   eta_i = x_i . w + o_i
+
+a_i observation weights (>= 0; a row of weight 0 is held out exactly), o_i offsets (Poisson: log exposure),
+n_i binomial trials (logistic only; y_i successes out of n_i), lam_d >= 0 a precision per coefficient (0 = flat)
+around the prior mean mu_d.  It runs on kernels of its own (the `RICH` instantiations of k_glm); the plain
+model above keeps its kernels and its arithmetic.
+
 For an ensemble the model is two matrix products shared by all chains (eta = X W, g = X^T (b'(eta) - y)
 + prior_precision W with W the (D, N) state), which csrc/kernels_glm.hip runs on the MFMA units with X
 staged through LDS -- the data set is read once per 64 chains, not once per chain.  float64, D <= 128.
@@ -17,7 +26,7 @@ import numpy as np
 from . import _lib
 from .potential import Potential, _dptr
 
-__all__ = ["GLM", "FAMILIES", "pack_design", "padded_dim"]
+__all__ = ["GLM", "FAMILIES", "pack_design", "pack_observations", "padded_dim"]
 
 FAMILIES = {"logistic": _lib.GLM_LOGISTIC, "poisson": _lib.GLM_POISSON}
 MAX_DIM = 128
@@ -48,7 +57,39 @@ def pack_design(X):
     return out.reshape(-1, 2, DP * 16)
 
 
-def _validate(X, y, family, prior_precision, dtype):
+def pack_observations(y, family="logistic", weights=None, offset=None, trials=None):
+    """The three per-observation streams the handle of the full model keeps on the device, computed (and
+    checked) on the host by libpbbi.so: array (3, L) -- c = weights * trials, d = weights * y and the
+    offset, each zero padded to L = 16 * (blocks of 16 observations, padded to a multiple of 4)."""
+    if family not in FAMILIES:
+        raise ValueError("family must be one of %s (got %r)" % (sorted(FAMILIES), family))
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if y.ndim != 1 or y.size < 1:
+        raise ValueError("y must be 1-D with at least one entry")
+    M = y.size
+    vec = [None if v is None else _vector(v, M, name, "M") for v, name in
+           ((weights, "weights"), (offset, "offset"), (trials, "trials"))]
+    n = C.c_int64()
+    _lib.call("pbbi_glm_pack_observations", M, FAMILIES[family], None, None, None, None, None, 0, C.byref(n))
+    out = np.empty(n.value, dtype=np.float64)
+    try:
+        _lib.call("pbbi_glm_pack_observations", M, FAMILIES[family], _dptr(y), _dptr(vec[0]), _dptr(vec[1]),
+                  _dptr(vec[2]), _dptr(out), out.size, C.byref(n))
+    except RuntimeError as e:
+        raise ValueError(str(e)) from None
+    return out.reshape(3, -1)
+
+
+def _vector(v, n, name, letter):
+    v = np.asarray(v, dtype=np.float64)
+    if v.ndim != 1 or v.size != n:
+        raise ValueError("%s must be 1-D with %s = %d entries (shape %s)" % (name, letter, n, v.shape))
+    if not np.all(np.isfinite(v)):
+        raise ValueError("%s must be finite" % name)
+    return np.ascontiguousarray(v)
+
+
+def _validate(X, y, family, prior_precision, dtype, prior_mean=None, weights=None, offset=None, trials=None):
     X = np.asarray(X, dtype=np.float64)
     if X.ndim != 2:
         raise ValueError("X must be 2-D: (M, D)")
@@ -62,34 +103,71 @@ def _validate(X, y, family, prior_precision, dtype):
         raise ValueError("family must be one of %s (got %r)" % (sorted(FAMILIES), family))
     if not np.all(np.isfinite(X)) or not np.all(np.isfinite(y)):
         raise ValueError("X and y must be finite")
-    if family == "logistic" and not np.all((y == 0) | (y == 1)):
-        raise ValueError("logistic: y must be 0 or 1")
+    if weights is not None:
+        weights = _vector(weights, M, "weights", "M")
+        if not np.all(weights >= 0):
+            raise ValueError("weights must be >= 0")
+    if offset is not None:
+        offset = _vector(offset, M, "offset", "M")
+    if trials is not None:
+        if family != "logistic":
+            raise ValueError("trials belong to the logistic (binomial) family only")
+        trials = _vector(trials, M, "trials", "M")
+        if not (np.all(trials >= 1) and np.all(trials == np.floor(trials))):
+            raise ValueError("trials must hold integers >= 1")
+    if family == "logistic":
+        if trials is None and not np.all((y == 0) | (y == 1)):
+            raise ValueError("logistic: y must be 0 or 1 (or successes out of `trials`)")
+        if trials is not None and not (np.all(y >= 0) and np.all(y <= trials) and np.all(y == np.floor(y))):
+            raise ValueError("logistic: y must hold integers with 0 <= y <= trials")
     if family == "poisson" and not (np.all(y >= 0) and np.all(y == np.floor(y))):
         raise ValueError("poisson: y must hold non-negative integers")
-    lam = float(prior_precision)
-    if not (np.isfinite(lam) and lam >= 0):
-        raise ValueError("prior_precision must be a finite scalar >= 0")
+    lam = np.asarray(prior_precision, dtype=np.float64)
+    if lam.ndim == 0:
+        lam = float(lam)
+        if not (np.isfinite(lam) and lam >= 0):
+            raise ValueError("prior_precision must be a finite scalar >= 0 (or a (D,) vector of such)")
+    else:
+        lam = _vector(lam, D, "prior_precision", "D")
+        if not np.all(lam >= 0):
+            raise ValueError("every prior_precision must be >= 0")
+    if prior_mean is not None:
+        prior_mean = _vector(prior_mean, D, "prior_mean", "D")
     if D > MAX_DIM:
         raise ValueError(f"GLM potentials serve D <= {MAX_DIM} (D = {D})")
     if np.dtype(dtype) != np.dtype("float64"):
         raise ValueError("GLM potentials are float64 only")
-    return np.ascontiguousarray(X), np.ascontiguousarray(y), lam
+    return np.ascontiguousarray(X), np.ascontiguousarray(y), lam, prior_mean, weights, offset, trials
 
 
 class GLM(Potential):
     """-log posterior of the weights of a generalised linear model (see the module text).
 
         pot = GLM(X, y, family="logistic", prior_precision=1.0)
+        pot = GLM(X, counts, family="poisson", offset=np.log(exposure), weights=w,
+                  prior_precision=np.r_[0.0, np.full(D - 1, 4.0)])          # flat intercept, tight slopes
         HMC(Ensemble(D, N), 1.0, 0.1, None, potential=pot, rng="philox").getSamples(...)
+
+    `prior_precision` is a scalar or a (D,) vector, `prior_mean` a (D,) vector (default 0); `weights`, `offset` and
+    `trials` are (M,) vectors (defaults 1, 0, 1; `trials` with family="logistic" only).  With none of them and a
+    scalar precision the potential is the plain model on its own kernels.
 
     Works wherever a Potential does (HMC in both rng modes, Leapfrog / StormerVerlet, TemperedSMC,
     TemperingLadder).  Arguments are checked on the host before anything touches the GPU."""
 
     kind = "glm"
 
-    def __init__(self, X, y, family="logistic", prior_precision=1.0, dtype="float64", device=None):
-        X, y, lam = _validate(X, y, family, prior_precision, dtype)
+    def __init__(self, X, y, family="logistic", prior_precision=1.0, prior_mean=None, weights=None, offset=None,
+                 trials=None, dtype="float64", device=None):
+        X, y, lam, mu, a, o, n = _validate(X, y, family, prior_precision, dtype, prior_mean, weights, offset, trials)
         super().__init__(X.shape[1], dtype, device)
         self.X, self.y, self.family, self.prior_precision = X, y, family, lam
-        _lib.call("pbbi_potential_create_glm", X.shape[1], X.shape[0], _dptr(X), _dptr(y),
-                  FAMILIES[family], lam, self._dt, self.device, C.byref(self._handle))
+        self.prior_mean, self.weights, self.offset, self.trials = mu, a, o, n
+        M, D = X.shape
+        if all(v is None for v in (mu, a, o, n)) and isinstance(lam, float):
+            _lib.call("pbbi_potential_create_glm", D, M, _dptr(X), _dptr(y),
+                      FAMILIES[family], lam, self._dt, self.device, C.byref(self._handle))
+        else:
+            lam_d = np.full(D, lam) if isinstance(lam, float) else lam
+            _lib.call("pbbi_potential_create_glm_ex", D, M, _dptr(X), _dptr(y), FAMILIES[family], _dptr(a), _dptr(o),
+                      _dptr(n), _dptr(lam_d), _dptr(mu), self._dt, self.device, C.byref(self._handle))

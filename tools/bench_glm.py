@@ -6,7 +6,13 @@ alternating, five repeats each after warming both.  Writes both series, the rati
 78.6 TFLOP/s fp64 MFMA peak (executed 4 M DP flop per chain-gradient, algorithmic 4 M D beside it) to
 profiles/glm_bench.json.
 
+--model rich benchmarks the full model (observation weights, offsets, binomial trials, a prior per coefficient:
+the RICH instantiations of k_glm) against the plain model on the same X, alternating in one process; with
+--custom also the full model as a CustomPotential (what its users had before).  That record goes to
+profiles/glm_model_bench.json under the key given by --label.
+
 usage: tools/bench_glm.py [--shape small|large|all] [--K 32] [--repeats 5] [--glm-only] [--out FILE]
+       tools/bench_glm.py --model rich [--custom] [--label NAME] [--shape ...]
 """
 import argparse
 import json
@@ -34,6 +40,86 @@ def problem(M, D, seed=0):
     w = rs.standard_normal(D)
     y = (rs.uniform(size=M) < 1.0 / (1.0 + np.exp(-(X @ w)))).astype(np.float64)
     return X, y, w, rs
+
+
+# the full model as user source: prm = [M, X, c, d, o, lam(D), mu(D)], c = a n, d = a y
+RICH_LOGISTIC_SOURCE = """
+template <class Q>
+PBBI_FN T potential(const Q& q, int D, const T* prm) {
+    const int M = (int)prm[0];
+    const T *X = prm + 1, *c = X + (long)M * D, *d = c + M, *o = d + M, *lam = o + M, *mu = lam + D;
+    T s = 0;
+    for (int i = 0; i < M; ++i) {
+        if (c[i] == 0 && d[i] == 0) continue;
+        T z = o[i];
+        for (int j = 0; j < D; ++j) z += X[i * D + j] * q[j];
+        s += c[i] * ((z > 0 ? z : T(0)) + log1p(exp(-fabs(z)))) - d[i] * z;
+    }
+    T r = 0;
+    for (int j = 0; j < D; ++j) r += lam[j] * (q[j] - mu[j]) * (q[j] - mu[j]);
+    return s + T(0.5) * r;
+}
+template <class Q, class G>
+PBBI_FN void gradient(const Q& q, G& g, int D, const T* prm) {
+    const int M = (int)prm[0];
+    const T *X = prm + 1, *c = X + (long)M * D, *d = c + M, *o = d + M, *lam = o + M, *mu = lam + D;
+    for (int j = 0; j < D; ++j) g[j] = lam[j] * (q[j] - mu[j]);
+    for (int i = 0; i < M; ++i) {
+        if (c[i] == 0 && d[i] == 0) continue;
+        T z = o[i];
+        for (int j = 0; j < D; ++j) z += X[i * D + j] * q[j];
+        const T w = c[i] / (T(1) + exp(-z)) - d[i];
+        for (int j = 0; j < D; ++j) g[j] += w * X[i * D + j];
+    }
+}
+"""
+
+
+def rich_problem(M, D, seed=0):
+    """problem()'s X with weights from {0, 0.5, 1, 3}, offsets ~ N(0, 0.3), trials in 1..20, a flat intercept and
+    precisions from {0.5, 4} on the slopes around a prior mean ~ N(0, 0.5)."""
+    X, _, w, rs = problem(M, D, seed)
+    a = rs.choice([0.0, 0.5, 1.0, 3.0], size=M)
+    o = 0.3 * rs.standard_normal(M)
+    n = rs.randint(1, 21, size=M).astype(np.float64)
+    y = rs.binomial(n.astype(int), 1.0 / (1.0 + np.exp(-(X @ w + o)))).astype(np.float64)
+    lam = np.r_[0.0, rs.choice([0.5, 4.0], size=D - 1)]
+    mu = 0.5 * rs.standard_normal(D)
+    return dict(X=X, y=y, weights=a, offset=o, trials=n, prior_precision=lam, prior_mean=mu), w, rs
+
+
+def bench_rich(name, M, D, N, h, L, K, repeats, warm, custom):
+    """Plain and full model (and the full model through CustomPotential) alternating in one process.  The full
+    model's posterior is ~sqrt(mean a n) narrower than the plain one's: its step size is scaled by that, so both
+    run L steps per iteration at comparable accept rates (the cost per step does not depend on h)."""
+    kw, w, rs = rich_problem(M, D)
+    hr = h / np.sqrt(np.mean(kw["weights"] * kw["trials"]))
+    q0 = np.ascontiguousarray(w[:, None] + 0.1 * rs.standard_normal((D, N)))
+    yp = (kw["y"] > 0.5 * kw["trials"]).astype(np.float64)
+    runners = {"plain": Runner(P.GLM(kw["X"], yp), D, N, q0, h, L, K), "rich": Runner(P.GLM(**kw), D, N, q0, hr, L, K)}
+    if custom:
+        from physicsbasedbayesianinference_amd.custom import CustomPotential
+        prm = np.concatenate([[float(M)], kw["X"].ravel(), kw["weights"] * kw["trials"], kw["weights"] * kw["y"],
+                              kw["offset"], kw["prior_precision"], kw["prior_mean"]])
+        runners["custom"] = Runner(CustomPotential(D, RICH_LOGISTIC_SOURCE, prm), D, N, q0, hr, L, K)
+    for r in runners.values():
+        r.go(warm)
+    torch.cuda.synchronize()
+    series = {k: [] for k in runners}
+    for i in range(repeats):
+        for k, r in runners.items():   # alternating
+            series[k].append(r.timed())
+            print(f"# {name} repeat {i} {k}: {series[k][-1]:.4f} s", flush=True)
+    out = dict(shape=name, M=M, D=D, DP=glm.padded_dim(D), chains=N, L=L, K=K, h=dict(plain=h, rich=hr),
+               accept_rate={k: 1.0 - float(r.rej.float().mean().item()) for k, r in runners.items()})
+    for k, ts in series.items():
+        out[k + "_seconds"] = ts
+        out[k + "_step_chain_per_s"] = [K * L * N / t for t in ts]
+    med = {k: float(np.median(ts)) for k, ts in series.items()}
+    out["rich_over_plain_time_median"] = med["rich"] / med["plain"]
+    if custom:
+        out["custom_over_rich_time_median"] = med["custom"] / med["rich"]
+    return out
 
 
 class Runner:
@@ -102,9 +188,30 @@ if __name__ == "__main__":
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--glm-only", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "glm_bench.json"))
+    ap.add_argument("--model", default="plain", choices=["plain", "rich"])
+    ap.add_argument("--custom", action="store_true", help="--model rich: also the full model as a CustomPotential")
+    ap.add_argument("--label", default="rich_vs_plain", help="--model rich: key of the record in the output file")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     names = list(SHAPES) if a.shape == "all" else [a.shape]
+    if a.model == "rich":
+        a.out = a.out or os.path.join(ROOT, "profiles", "glm_model_bench.json")
+        doc = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                doc = json.load(f)
+        doc["device"] = _lib.device_info(0)["name"]
+        rec = {r["shape"]: r for r in doc.get(a.label, [])}
+        for n in names:
+            res = bench_rich(n, L=a.L, K=a.K, repeats=a.repeats, warm=a.warmup, custom=a.custom, **SHAPES[n])
+            print(json.dumps(res))
+            rec[n] = res
+            doc[a.label] = [rec[k] for k in sorted(rec, reverse=True)]
+            with open(a.out, "w") as f:
+                json.dump(doc, f, indent=1)
+                f.write("\n")
+        sys.exit(0)
+    a.out = a.out or os.path.join(ROOT, "profiles", "glm_bench.json")
     results = []
     if os.path.exists(a.out) and a.shape != "all":   # one shape per call: keep the other's record
         with open(a.out) as f:
