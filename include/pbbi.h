@@ -401,6 +401,43 @@ int pbbi_chain_autocov(const void* samples_sdn, const void* chain_mean, int S, i
 int pbbi_sample_covariance(const void* samples_sdn, int S, int D, int64_t N, int dtype, int device,
                            const double* mean, double* cov_out, void* stream);
 
+/* ---- running statistics: the same quantities merged across chunks on the device -------------
+ * A long run yields its draws chunk by chunk ((c, D, N) slabs, HMC.sampleChunks); the four calls above need every
+ * draw resident.  Here a device-resident state of DOUBLES is updated by one pass over each chunk and can be
+ * finalised at any time; only one chunk is ever resident.  T = the largest lag kept, 0 <= T <= PBBI_MAX_LAG.
+ *
+ * State, per (dim, chain) (arrays of D*N, chain axis fastest): the shift c = the chain's first draw (y_s = x_s - c),
+ * s1 = sum y_s, A_t = sum_{s>=t} y_s y_{s-t} (t = 0..T), the last T and the first T values of y; per ensemble: a
+ * shift vector (D; the first slab's mean over the chains), e = sum (x - shift) (D) and the D x D sum of
+ * (x - shift)(x - shift)^T.  pbbi_stats_state_len: *doubles_out = (3T + 3) D N + 2 D + D^2 (host only, no device
+ * needed): a lag that is not asked for costs no state and no traffic.
+ *
+ * pbbi_stats_accumulate: adds the c draws of slabs_sdn ((c, D, N), fp64 or fp32 by `dtype`) to `state`, in draw
+ *   order.  S_before = the draws the state already holds, given by the CALLER (nothing is read back);
+ *   S_before == 0 starts the state (no reset call: whatever the buffer held is overwritten or never read).  Each
+ *   draw goes through ONE update (explicit fma for the lagged products), so the per-chain state after S draws is
+ *   bit-identical however the S draws were cut into chunks; the D x D sum is accumulated in 16 x 16 tiles over
+ *   slices of the chunk and added in a fixed order (deterministic for a given cut; cuts agree to rounding).
+ * pbbi_stats_finalize: from a state of S_total draws, with m_n the mean of chain n and delta = s1 / S_total,
+ *     sum_{s=t}^{S-1} (x_s - m)(x_{s-t} - m) = A_t - delta (2 s1 - head_t - tail_t) + (S - t) delta^2      (t < S)
+ *   (head_t / tail_t = the sum of the first / last t values of y; lags t >= S are exactly 0), reduced over the
+ *   chains in two fixed-order stages without atomics.  Outputs are device DOUBLES, any of them may be NULL:
+ *     mean_out, var_out (D): as pbbi_sample_moments (var biased, over all S*N draws);
+ *     cov_out (D x D): as pbbi_sample_covariance about the mean;
+ *     acov_out ((T+1) x D): pbbi_chain_autocov's definition, the 1/S included;
+ *     w_out (D): the mean over chains of the unbiased chain variances;  bvar_out (D): the biased variance over
+ *     chains of the chain means;  chain_mean_out, chain_var_out (D x N): as pbbi_chain_moments.
+ *   mean, var, W, bvar, acov and the per-chain outputs come from the per-chain state alone (bit-stable under
+ *   re-chunking); only cov uses the tile sums.  The state is left unchanged: finalise, continue, finalise again.
+ * PBBI_ERR_INVALID before any launch: T out of range, c < 1, S_before < 0, a NULL state or slab pointer, an unknown
+ * dtype, S_total < 1, S_total < 2 with w_out or chain_var_out given. */
+int pbbi_stats_state_len(int D, int64_t N, int T, int64_t* doubles_out);
+int pbbi_stats_accumulate(double* state, int D, int64_t N, int T, int64_t S_before, const void* slabs_sdn, int c,
+                          int dtype, int device, void* stream);
+int pbbi_stats_finalize(const double* state, int D, int64_t N, int T, int64_t S_total, int device, double* mean_out,
+                        double* var_out, double* cov_out, double* acov_out, double* w_out, double* bvar_out,
+                        double* chain_mean_out, double* chain_var_out, void* stream);
+
 /* ---- ensemble weights ----------------------------------------------
  * Normalised canonical weights of an ensemble from its per-chain Hamiltonians (pbbi_energy),
  *     w_n = exp(-beta (H_n - H_min)) / sum_m exp(-beta (H_m - H_min)),

@@ -35,6 +35,7 @@ from . import _hoststream, _lib
 from ._device import as_device, empty, stream_ptr, synchronize, to_numpy
 from .integrator import Leapfrog, StormerVerlet, mass_or_none, resolve_potential
 from .potential import Potential
+from .stats import RunningStats, ess_from_autocov, rhat_from_moments
 
 __all__ = ["HMC"]
 
@@ -576,7 +577,7 @@ class HMC:
         return self._to_dns(samples), self._to_dns(momenta)
 
     def sampleChunks(self, numSamples, chunk, temperature, qStd, seed=None, chain0=0, iter0=0,
-                     spill_dir=None, momenta=False):
+                     spill_dir=None, momenta=False, stats=None):
         """Generator over a long in-kernel-draw run in chunks of `chunk` iterations (SURVEY 8f row 4:
         at C2 scale 1000 draws are 64 GB, more than one wants resident or returned at once).  The
         chain state stays on the GPU between chunks and the Philox iteration counter continues,
@@ -584,7 +585,9 @@ class HMC:
         call.  Yields (samples, momenta_or_None) per chunk as (D, N, c) device views that are
         OVERWRITTEN by the next chunk -- reduce them (sampleMoments) or copy them before
         advancing.  With spill_dir every chunk is also written as samples_00000.npy, ... in the
-        reference's (D, N, c) layout (momenta_XXXXX.npy when momenta=True)."""
+        reference's (D, N, c) layout (momenta_XXXXX.npy when momenta=True).  stats (a stats.RunningStats of
+        this ensemble's D and N) is fed every chunk before it is yielded: the run's mean, covariance, R-hat and
+        ESS without more than one chunk resident."""
         import os
         pot, ens = self._pot, self.ensemble
         D, N = ens.numDimensions, ens.numParticles
@@ -615,6 +618,8 @@ class HMC:
             n_rej += float(reject[:c].float().sum().item()) if N else 0.0
             s_view = samples[:c].permute(1, 2, 0)
             m_view = mom[:c].permute(1, 2, 0) if momenta else None
+            if stats is not None:
+                stats.update(samples[:c])
             if spill_dir is not None:
                 np.save(os.path.join(spill_dir, f"samples_{k:05d}.npy"), self._to_dns(samples[:c]))
                 if momenta:
@@ -623,6 +628,53 @@ class HMC:
             k += 1
             self.acceptRate = 1.0 - n_rej / (done * N) if N else None
             yield s_view, m_view
+
+    def sampleStats(self, numSamples, chunk, temperature, qStd, burn_in=0, max_lag=32, seed=None, chain0=0, iter0=0):
+        """A long in-kernel-draw run reduced on the device as it goes: numSamples iterations in chunks of `chunk`
+        into ONE reused (chunk, D, N) slab, every chunk accumulated into a stats.RunningStats (max_lag: the largest
+        autocovariance lag kept), which is returned -- moments(), covariance(), rhat(), ess() of the whole run
+        with one chunk resident.  The draws are those of getSamples(numSamples, rng="philox", burn_in=burn_in) for the
+        same seed and counters (burn_in unrecorded iterations first, draw indices iter0 .. iter0+burn_in-1, run
+        without a sample slab).  Nothing is read back between chunks: the launches of all chunks are queued one
+        after the other, the reject count is summed on the device and read once at the end into acceptRate."""
+        import torch
+        pot, ens = self._pot, self.ensemble
+        D, N = ens.numDimensions, ens.numParticles
+        S, chunk = int(numSamples), max(1, int(chunk))
+        if D != pot.numDimensions:
+            raise ValueError(f"potential has D={pot.numDimensions}, ensemble has D={D}")
+        seed = self.seed if seed is None else int(seed)
+        dev, dt = pot.device, pot.dtype
+        stats = RunningStats(D, N, max_lag=max_lag, device=dev)
+        stream = stream_ptr(dev)
+        kT = float(boltzmannConst * temperature)
+        flags, L, h = self._flags(), self.integrator.numSteps, float(self.stepSize)
+        md = self._mass()
+        mptr = md.data_ptr() if md is not None else None
+        q_state = empty((D, N), dt, dev)
+        _lib.call("pbbi_philox_normal", seed, self._position_stream(), int(iter0), int(chain0), D, N, N,
+                  float(qStd), None, pot._dt, dev, q_state.data_ptr(), stream)
+        it = int(iter0)
+        if burn_in:
+            _lib.call("pbbi_hmc_run", pot.handle, self.integrator.method_id, q_state.data_ptr(), mptr, None, None,
+                      None, None, N, N, h, L, int(burn_in), flags, seed, it, int(chain0), kT, stream)
+            it += int(burn_in)
+        c_alloc = min(chunk, max(S, 1))
+        samples = empty((c_alloc, D, N), dt, dev)
+        reject = empty((c_alloc, N), np.uint8, dev)
+        n_rej = None                                         # a device scalar
+        done = 0
+        while done < S:
+            c = min(chunk, S - done)
+            _lib.call("pbbi_hmc_run", pot.handle, self.integrator.method_id, q_state.data_ptr(), mptr,
+                      samples.data_ptr(), None, reject.data_ptr(), None, N, N, h, L, c, flags, seed, it + done,
+                      int(chain0), kT, stream)
+            stats.update(samples[:c])
+            r = reject[:c].sum(dtype=torch.int64)
+            n_rej = r if n_rej is None else n_rej + r
+            done += c
+        self.acceptRate = 1.0 - float(n_rej.item()) / (S * N) if S > 0 and N > 0 else None   # the one read-back
+        return stats
 
     def sampleChunksGathered(self, numSamples, chunk, temperature, qStd, n_total=None, seed=None, chain0=0, iter0=0,
                              host_stream=None, momenta=False, group=None, rng=None):
@@ -821,9 +873,7 @@ class HMC:
                   stream)                                     # W = mean over chains of the chain variances
         _lib.call("pbbi_sample_moments", cm.data_ptr(), 1, D, N, pot._dt, pot.device, None,
                   bvar.data_ptr(), stream)                    # biased variance over chains of the chain means
-        W = to_numpy(w).astype(np.float64)
-        B_over_S = to_numpy(bvar).astype(np.float64) * N / (N - 1.0)
-        return np.sqrt(((S - 1.0) / S * W + B_over_S) / W)
+        return rhat_from_moments(to_numpy(w).astype(np.float64), to_numpy(bvar).astype(np.float64), S, N)
 
     def sampleCovariance(self, samples_dns):
         """(mean (D,), covariance (D, D)) over every draw of every chain, computed on the GPU from the
@@ -875,24 +925,7 @@ class HMC:
         _lib.call("pbbi_sample_moments", cm.data_ptr(), 1, D, N, code, pot.device, None, bvar.data_ptr(),
                   stream)                                      # biased variance over chains of the chain means
         g = to_numpy(acov)                                     # (T+1, D): mean_n gamma_t,n
-        W = g[0] * S / (S - 1.0)
-        var_plus = W * (S - 1.0) / S + to_numpy(bvar).astype(np.float64) * N / (N - 1.0)
-        rho = 1.0 - (W[None, :] - g) / var_plus[None, :]
-        rho[0] = 1.0
-        ess = np.empty(D)
-        self.ess_truncated = np.zeros(D, dtype=bool)
-        for d in range(D):
-            tau, prev, cut = -1.0, np.inf, False
-            for t in range(0, T, 2):
-                pair = rho[t, d] + rho[t + 1, d]
-                if pair < 0.0:
-                    cut = True
-                    break
-                pair = min(pair, prev)                         # Geyer's initial monotone sequence
-                tau += 2.0 * pair
-                prev = pair
-            self.ess_truncated[d] = not cut
-            ess[d] = N * S / max(tau, 1.0 / np.log10(max(N * S, 10)))
+        ess, self.ess_truncated = ess_from_autocov(g, to_numpy(bvar).astype(np.float64), S, N, T)
         return ess
 
     @staticmethod
