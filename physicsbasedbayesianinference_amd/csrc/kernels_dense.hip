@@ -330,7 +330,7 @@ int dense_hmc_iter(const IterArgs& a) {
         prm.carry_slab_bytes = (uint32_t)((uint64_t)a.pot->DP * (uint64_t)a.N * 8u);  // slabs hold the padded rows too
     }
     if (a.fuse_S > 1) {
-        if (carry == 0 || a.ldn_in != a.ldn_out || !a.rng)
+        if (carry == 0 || a.ldn_in != a.ldn_out || !a.rng)  // (!a.rng: the fused kernels draw unconditionally, k_dense_hmc)
             return pbbi_fail(PBBI_ERR_INVALID, "fused dense iterations belong to a carried run (internal)");
         prm.fuse_first = (carry == 1);  // the launch starts the run: its iteration 0 forms g(q_0)
         carry = 2;

@@ -451,6 +451,41 @@ constexpr int CHAINS_PER_WG2 = 128;
 // ZMEAN: mu == 0, x_s is q_s itself (no LDS read, no subtraction).  The drift is one fma.
 // KSKIP (D < DP): the K-steps past the last column of P multiply zeros -- the pass ends at ks_act = ceil(D / 4)
 // (wave-uniform; the exit points that can occur for this tile size are the only ones compiled in).
+// LDS addressing of the A fragments.  Fragment pair i of the image (1 KiB: 64 lanes x 16 B) is read by lane l at
+// byte 1024 i + 16 l, and a ds_read carries a 16-bit immediate offset: from ONE base register a pass reaches the
+// pairs below the 64 KiB line only (FRAG_LINE; the image is 128 KiB at DP = 128, 72 KiB at DP = 96).  A pass
+// therefore RE-BASES its pointer where its reads cross the line and takes the 64 KiB off again behind its last
+// read, on every way out -- two vector adds per pass, where a base + constant add per read beyond the line cost
+// 64 in every step (a second live base register does not fit: the kernel sits at 256).  The empty asm keeps the
+// re-based value opaque, or the compiler folds the constants back into one add per read.  `hi` is a constant of
+// the unrolled code at every read.  The pointer is in the LDS address space: one 32-bit register.
+typedef const __attribute__((address_space(3))) v2f64* lds_frag_p;
+constexpr int FRAG_LINE = 64;
+__device__ __forceinline__ void frag_shift(lds_frag_p& p, int pairs) {
+    p += pairs * 64;
+    asm volatile("" : "+v"(p));
+}
+// (FP = lds_frag_p.  The per-chain-length kernels pass a plain pointer, which is read with a base + constant add per
+//  read beyond the line as before and never re-based: re-based, their padded-D instantiation spilled 64 registers
+//  where it spills 52.)
+template <class FP>
+__device__ __forceinline__ v2f64 frag_read(FP& p, bool& hi, int i) {
+    if constexpr (std::is_same<FP, lds_frag_p>::value) {
+        if (i >= FRAG_LINE && !hi) {
+            frag_shift(p, FRAG_LINE);
+            hi = true;
+        }
+    }
+    return p[(hi ? i - FRAG_LINE : i) * 64];
+}
+template <class FP>
+__device__ __forceinline__ void frag_home(FP& p, bool& hi) {
+    if constexpr (std::is_same<FP, lds_frag_p>::value) {
+        if (hi) frag_shift(p, -FRAG_LINE);
+    }
+    hi = false;
+}
+
 template <int NT>
 struct KSkip {  // smallest ks_act a kernel of NT row tiles is launched with: D > the next smaller tile size
     static constexpr int MIN = NT == 2 ? 1 : NT == 4 ? 9 : NT == 6 ? 17 : NT == 8 ? 25 : NT == 12 ? 33 : NT == 16 ? 49 : 1;
@@ -461,8 +496,8 @@ template <int N>
 __device__ __forceinline__ double vel_at(const double (&v)[N], int s) { return v[s]; }
 template <int N>
 __device__ __forceinline__ double vel_at(const v4f64 (&v)[N], int s) { return v[s >> 2][s & 3]; }
-template <int NT, int NTP, int PASS, bool DRIFT, bool ZMEAN, bool KSKIP = false, class V>
-__device__ __forceinline__ void matvec_pass(const v2f64* __restrict__ fragL,
+template <int NT, int NTP, int PASS, bool DRIFT, bool ZMEAN, bool KSKIP = false, class FP, class V>
+__device__ __forceinline__ void matvec_pass(FP& fragL,
                                             const double* __restrict__ muG, double (&q)[4 * NT],
                                             const V& vh, v4f64 (&acc)[NTP],
                                             double h, int ks_act = 4 * NT) {
@@ -471,8 +506,9 @@ __device__ __forceinline__ void matvec_pass(const v2f64* __restrict__ fragL,
     constexpr int HP = NTP / 2;  // pairs this pass consumes
     constexpr int T0 = PASS * HP;
     v2f64 A[HP];
+    bool hi = false;  // fragL is past the 64 KiB line (frag_read)
 #pragma unroll
-    for (int t2 = 0; t2 < HP; ++t2) A[t2] = fragL[(T0 + t2) * 64];
+    for (int t2 = 0; t2 < HP; ++t2) A[t2] = frag_read(fragL, hi, T0 + t2);
 #pragma unroll
     for (int t = 0; t < NTP; ++t) acc[t] = v4f64{0.0, 0.0, 0.0, 0.0};
     if constexpr (DRIFT) q[0] = fma(vel_at(vh, 0), h, q[0]);
@@ -480,14 +516,18 @@ __device__ __forceinline__ void matvec_pass(const v2f64* __restrict__ fragL,
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
         if constexpr (KSKIP) {
-            if (s >= KSkip<NT>::MIN && s >= ks_act) break;
+            if (s >= KSkip<NT>::MIN && s >= ks_act) {
+                frag_home(fragL, hi);
+                break;
+            }
         }
 #pragma unroll
         for (int t2 = 0; t2 < HP; ++t2) {
             acc[2 * t2] = __builtin_amdgcn_mfma_f64_16x16x4f64(A[t2].x, x, acc[2 * t2], 0, 0, 0);
             acc[2 * t2 + 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(A[t2].y, x, acc[2 * t2 + 1], 0, 0, 0);
-            if (s + 1 < KS) A[t2] = fragL[((s + 1) * H + T0 + t2) * 64];
+            if (s + 1 < KS) A[t2] = frag_read(fragL, hi, (s + 1) * H + T0 + t2);
         }
+        if (s + 2 == KS) frag_home(fragL, hi);  // behind the pass's last read
         double xn = 0.0;
         if (s + 1 < KS) {
             if constexpr (DRIFT) q[s + 1] = fma(vel_at(vh, s + 1), h, q[s + 1]);
@@ -509,13 +549,14 @@ __device__ __forceinline__ void matvec_pass(const v2f64* __restrict__ fragL,
 // before the pair is written again.  (Drifting element s next to K-step s, as matvec_pass does, would read a w_s
 // that already holds s K-steps of the new gradient.)  K-steps 1.. form x from the finished q.
 template <int NT, bool ZMEAN, bool KSKIP>
-__device__ __forceinline__ void matvec_inplace(const v2f64* __restrict__ fragL, const double* __restrict__ muG,
+__device__ __forceinline__ void matvec_inplace(lds_frag_p& fragL, const double* __restrict__ muG,
                                                double (&q)[4 * NT], v4f64 (&w)[NT], double cd, int ks_act) {
     constexpr int KS = 4 * NT;
     constexpr int H = NT / 2;
     v2f64 A[H];
+    bool hi = false;  // fragL is past the 64 KiB line (frag_read)
 #pragma unroll
-    for (int t2 = 0; t2 < H; ++t2) A[t2] = fragL[t2 * 64];
+    for (int t2 = 0; t2 < H; ++t2) A[t2] = frag_read(fragL, hi, t2);
     auto drift_pair = [&](int t2) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) q[8 * t2 + e] = fma(vel_at(w, 8 * t2 + e), cd, q[8 * t2 + e]);
@@ -525,16 +566,20 @@ __device__ __forceinline__ void matvec_inplace(const v2f64* __restrict__ fragL, 
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
         if constexpr (KSKIP) {
-            if (s >= KSkip<NT>::MIN && s >= ks_act) break;
+            if (s >= KSkip<NT>::MIN && s >= ks_act) {
+                frag_home(fragL, hi);
+                break;
+            }
         }
 #pragma unroll
         for (int t2 = 0; t2 < H; ++t2) {
             if (s == 0 && t2 > 0) drift_pair(t2);
             w[2 * t2] = __builtin_amdgcn_mfma_f64_16x16x4f64(A[t2].x, x, w[2 * t2], 0, 0, 0);
             w[2 * t2 + 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(A[t2].y, x, w[2 * t2 + 1], 0, 0, 0);
-            if (s + 1 < KS) A[t2] = fragL[((s + 1) * H + t2) * 64];
+            if (s + 1 < KS) A[t2] = frag_read(fragL, hi, (s + 1) * H + t2);
             if (s == 0) __builtin_amdgcn_sched_barrier(0);  // (or every drift is hoisted in front of the first MFMA)
         }
+        if (s + 2 == KS) frag_home(fragL, hi);  // behind the pass's last read
         double xn = 0.0;
         if (s + 1 < KS) xn = ZMEAN ? q[s + 1] : q[s + 1] - muG[4 * (s + 1)];
         __builtin_amdgcn_sched_barrier(0);
@@ -752,6 +797,11 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
     static_assert(CARRY == 0 || (MODE == 0 && !DYN), "carry: HMC iterations of fixed trajectory length");
     static_assert(!FUSE || CARRY == 2, "a fused launch reads the carried gradient (its first iteration may form it)");
     static_assert(!STREAM || NT % 4 == 0, "streamed P: two row passes");
+    // args() below re-reads prm through the kernarg pointer (pbbi_buf.h::kernarg_fresh): the block must be the kernel's
+    // ONLY parameter (it then starts the kernarg segment) and must never be written in the kernel.
+    static_assert(std::is_same<decltype(&k_dense_hmc<NT, FULL, MODE, ZMEAN, METHOD, DYN, CARRY, FUSE, DRAW, STREAM>),
+                               void (*)(DensePrm)>::value,
+                  "kernarg_fresh<DensePrm>() reads the argument block at offset 0 of the kernarg segment");
     constexpr int DP = 16 * NT;
     constexpr int KS = 4 * NT;
     constexpr int NPASS = (NT % 4 == 0) ? 2 : 1;  // row passes per mat-vec (NT = 6, DP = 96: one pass of six row tiles)
@@ -800,7 +850,8 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
     STAMP(1);
     const int g = lane >> 4;
     const int c = lane & 15;
-    const v2f64* fragL = frag2 + lane;
+    [[maybe_unused]] const v2f64* fragL = frag2 + lane;         // STREAM: the ring; DYN: the image, plain addressing
+    [[maybe_unused]] lds_frag_p fragA = (lds_frag_p)(frag2 + lane);  // the resident image; re-based inside a pass (frag_read)
     const double* muG = mu + g;
     const int D = prm.D;
     const double h = prm.h;
@@ -809,7 +860,8 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
 #define MATVEC(PASS_, DRIFT_, Q_, V_, ACC_, H_)                                                        \
     do {                                                                                              \
         if constexpr (STREAM) matvec_pass_stream<NT, PASS_, DRIFT_, ZMEAN, !FULL>(ring, fragL, muG, Q_, V_, ACC_, H_, ks_act); \
-        else matvec_pass<NT, NTP, PASS_, DRIFT_, ZMEAN, !FULL>(fragL, muG, Q_, V_, ACC_, H_, ks_act); \
+        else if constexpr (DYN) matvec_pass<NT, NTP, PASS_, DRIFT_, ZMEAN, !FULL>(fragL, muG, Q_, V_, ACC_, H_, ks_act); \
+        else matvec_pass<NT, NTP, PASS_, DRIFT_, ZMEAN, !FULL>(fragA, muG, Q_, V_, ACC_, H_, ks_act); \
     } while (0)
 
     int64_t n0 = ((int64_t)blockIdx.x * WPB + wave) * CHAINS_PER_WAVE;  // wave-uniform
@@ -833,7 +885,11 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
     const double minv = prm.mass ? 1.0 / m : 1.0;
     // INPL: drift coefficient -h^2/m (per lane: masses), p -> w and w -> p factors -1/h and -h
     [[maybe_unused]] const double cd = -(h * h) * minv, nih = -1.0 / h, nh = -h;
-    const bool rng = (MODE == 0) && prm.rng;
+    // A fused launch with P in LDS ALWAYS draws in the kernel; prm.rng is not consulted there, which takes the
+    // uploaded-momentum path (32 row offsets of p_in, held across the loop) out of those kernels.  The host guarantees
+    // it: kernels_dense.hip::dense_hmc_iter refuses fuse_S > 1, and a carried Stormer-Verlet iteration (a fused
+    // launch of one), without a.rng.  A fused caller with uploaded momenta would have to lift this first.
+    const bool rng = (FUSE && !STREAM) || ((MODE == 0) && prm.rng);
     // carried gradient: slabs [2][D][N] with the leading stride N; this lane's offset into the current one
     [[maybe_unused]] const uint32_t ld_g = 8u * (uint32_t)prm.N, s4g = 4u * ld_g;
     [[maybe_unused]] uint32_t vg_cur = 0, vg_new = 0;
@@ -916,20 +972,63 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
             xg_keep += dot_pass<NT, NTP, 1, ZMEAN>(muG, q, acc);
         }
     }
+    // Scalars inside the iteration loop (P in LDS).  Every row offset, descriptor, flag test and key schedule below
+    // is a loop invariant, and hoisted in front of the loop they are twice the scalar registers there are: the
+    // overflow was parked in VGPR lanes and came back through the vector unit, 160 v_readlane_b32 and their hazard
+    // nops per iteration.  Each group of accesses therefore forms its scalars itself, from a fresh copy of the
+    // stride or counter (here(): pbbi_buf.h::sgpr_fresh) and of the kernel arguments (args(): kernarg_fresh) -- scalar
+    // multiplies and loads next to the use, which cost the vector unit nothing.  The streamed kernels and the
+    // per-chain-length ones (which have no loop over iterations) keep the plain values, formed at the top of the
+    // iteration as before; the kernels with a mean re-read no arguments (their fused forms, which spill around
+    // x = q - mu, went from 47 to 54 spilled registers with the reloads and stay at 47 without).
+    constexpr bool LOCAL = !STREAM && !DYN;
+    auto here = [](auto x) {
+        if constexpr (LOCAL) return sgpr_fresh(x);
+        else return x;
+    };
+    auto args = [&]() -> decltype(auto) {
+        // (ZMEAN only: with the reloads the fused kernels with a mean spill 54 registers, without them 47 as before)
+        if constexpr (LOCAL && ZMEAN) return kernarg_fresh<DensePrm>();
+        else return (prm);
+    };
 #pragma nounroll
     for (int kf = 0; kf < nfuse; ++kf) {
     STAMP(42);
     const uint64_t iter_k = prm.iter + (uint64_t)kf;
-    double* const ratio_k = (FUSE && prm.ratio_out) ? prm.ratio_out + (int64_t)kf * prm.N : prm.ratio_out;
-    uint8_t* const reject_k = (FUSE && prm.reject_out) ? prm.reject_out + (int64_t)kf * prm.N : prm.reject_out;
-    __amdgpu_buffer_rsrc_t qin_k = qin, qout_k = qout, pout_k = pout;
-    if constexpr (FUSE) {
+    // The slabs and rows of iteration kf: the launch's own without FUSE.  !LOCAL: formed here; LOCAL: by the
+    // lambdas below, where they are used (a: the user's copy of the arguments, k: its copy of kf).
+    [[maybe_unused]] double* const ratio_top = (FUSE && prm.ratio_out) ? prm.ratio_out + (int64_t)kf * prm.N : prm.ratio_out;
+    [[maybe_unused]] uint8_t* const reject_top = (FUSE && prm.reject_out) ? prm.reject_out + (int64_t)kf * prm.N : prm.reject_out;
+    [[maybe_unused]] __amdgpu_buffer_rsrc_t qin_top = qin, qout_top = qout, pout_top = pout;
+    if constexpr (!LOCAL && FUSE) {
         const int64_t s_out = prm.fuse_wrap2 ? ((prm.fuse_slab0 + kf) & 1) : prm.fuse_slab0 + kf;
         const int64_t s_prev = prm.fuse_wrap2 ? ((prm.fuse_slab0 + kf - 1) & 1) : prm.fuse_slab0 + kf - 1;
-        if (kf > 0) qin_k = rows_of<FULL>(prm.fuse_q_base + s_prev * prm.fuse_slab, n0, D, prm.ldn_out, prm.N);
-        qout_k = rows_of<FULL>(prm.fuse_q_base + s_out * prm.fuse_slab, n0, D, prm.ldn_out, prm.N);
-        pout_k = rows_of<FULL>(prm.p_out + (prm.p_out ? (int64_t)kf * prm.fuse_slab : 0), n0, D, prm.ldn_out, prm.N);
+        if (kf > 0) qin_top = rows_of<FULL>(prm.fuse_q_base + s_prev * prm.fuse_slab, n0, D, prm.ldn_out, prm.N);
+        qout_top = rows_of<FULL>(prm.fuse_q_base + s_out * prm.fuse_slab, n0, D, prm.ldn_out, prm.N);
+        pout_top = rows_of<FULL>(prm.p_out + (prm.p_out ? (int64_t)kf * prm.fuse_slab : 0), n0, D, prm.ldn_out, prm.N);
     }
+    auto qslab_of = [&](const auto& a, int k) {  // position slab of iteration k (kf - 1: where this iteration started)
+        const int64_t sl = a.fuse_wrap2 ? ((a.fuse_slab0 + k) & 1) : a.fuse_slab0 + k;
+        return rows_of<FULL>(a.fuse_q_base + sl * a.fuse_slab, n0, D, a.ldn_out, a.N);
+    };
+    auto qin_of = [&](const auto& a, int k) {
+        if constexpr (!LOCAL) return qin_top;
+        else if constexpr (FUSE) {
+            if (k > 0) return qslab_of(a, k - 1);
+            return rows_of<FULL>(a.q_in, n0, D, a.ldn_in, a.N);  // (qin, not held across the loop)
+        } else return qin;
+    };
+    auto qout_of = [&](const auto& a, int k) {
+        if constexpr (!LOCAL) return qout_top;
+        else if constexpr (FUSE) return qslab_of(a, k);
+        else return qout;
+    };
+    auto pout_of = [&](const auto& a, int k) {
+        if constexpr (!LOCAL) return pout_top;
+        else if constexpr (FUSE)
+            return rows_of<FULL>(a.p_out + (a.p_out ? (int64_t)k * a.fuse_slab : 0), n0, D, a.ldn_out, a.N);
+        else return pout;
+    };
     if constexpr (CARRY != 0) {
         const uint32_t vg0 = (uint32_t)g * ld_g + 8u * (uint32_t)cc;
         vg_cur = vg0 + (csel ? prm.carry_slab_bytes : 0u);
@@ -951,20 +1050,22 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
     // rows of pass PASS of the carried gradient <-> acc (element s = 4*(PASS*NTP + t) + r, like q[s])
     auto carry_load = [&](auto pass_c) {
         constexpr int PASS = decltype(pass_c)::value;
+        const uint32_t st = here(s4g);
 #pragma unroll
         for (int t = 0; t < NTP; ++t)
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                acc[t][r] = load_row(gbuf, vg_cur, s4g, 4 * (PASS * NTP + t) + r);
+                acc[t][r] = load_row(gbuf, vg_cur, st, 4 * (PASS * NTP + t) + r);
     };
     auto carry_store = [&](auto pass_c, uint32_t voff) {
         constexpr int PASS = decltype(pass_c)::value;
         if (valid) {
+            const uint32_t st = here(s4g);
 #pragma unroll
             for (int t = 0; t < NTP; ++t)
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    store_row(gbuf, voff, s4g, 4 * (PASS * NTP + t) + r, acc[t][r]);
+                    store_row(gbuf, voff, st, 4 * (PASS * NTP + t) + r, acc[t][r]);
         }
     };
     using P0 = std::integral_constant<int, 0>;
@@ -983,6 +1084,7 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
         const double ck0k = 0.5 * (h * minv);
         const bool park = prm.p_out && !(prm.flags & PBBI_COMPAT_P_FROM_OLDQ) && valid;
         const bool draw64 = DRAW == 2 ? (prm.flags & PBBI_DRAW_F64) != 0 : DRAW == 1;  // wave-uniform
+        const __amdgpu_buffer_rsrc_t pout_k = pout_of(prm, kf);
 #pragma unroll
         for (int k = 0; k < KS / 4; ++k) {
             double z[4];
@@ -1003,20 +1105,24 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
     if (rng) {
         const uint64_t chain = prm.chain0 + (uint64_t)(n0 + cc);
         const double pstd = sqrt(m * prm.kT);  // src/ensemble.py:88
-        const bool draw64 = DRAW == 2 ? (prm.flags & PBBI_DRAW_F64) != 0 : DRAW == 1;  // wave-uniform
+        const auto& ad = args();
+        const bool draw64 = DRAW == 2 ? (ad.flags & PBBI_DRAW_F64) != 0 : DRAW == 1;  // wave-uniform
+        const uint64_t seed_k = ad.seed;
 #pragma unroll
         for (int k = 0; k < KS / 4; ++k) {  // block k: rows 16k + 4*slot + g, slot = 0..3
             double z[4];
-            rng_normal4d(prm.seed, PBBI_STREAM_MOMENTUM, iter_k, chain, (uint32_t)((k << 2) | g), draw64, z);
+            rng_normal4d(seed_k, PBBI_STREAM_MOMENTUM, iter_k, chain, (uint32_t)((k << 2) | g), draw64, z);
 #pragma unroll
             for (int sl = 0; sl < 4; ++sl)
                 vset(4 * k + sl, (FULL || 16 * k + 4 * sl + g < D) ? z[sl] * pstd : 0.0);
         }
-        if (prm.p_out && !(prm.flags & PBBI_COMPAT_P_FROM_OLDQ) && valid) {
+        if (ad.p_out && !(ad.flags & PBBI_COMPAT_P_FROM_OLDQ) && valid) {
             // non-compat: a rejected chain reports its drawn momentum; park the draw in the slab
             // now (accepted chains overwrite it below) rather than regenerate it later.
+            const uint32_t st = here(s4out);
+            const __amdgpu_buffer_rsrc_t pout_k = pout_of(ad, here(kf));
 #pragma unroll
-            for (int s = 0; s < KS; ++s) store_row(pout_k, vout, s4out, s, vget(s));
+            for (int s = 0; s < KS; ++s) store_row(pout_k, vout, st, s, vget(s));
         }
     } else {
         const __amdgpu_buffer_rsrc_t pin = rows_of<FULL>(prm.p_in, n0, D, prm.ldn_in, prm.N);
@@ -1079,7 +1185,7 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
     }
     }
     // H(q_old, p_old) now, so that only one double stays live across the trajectory
-    double oldH = 0.5 * chain_sum(pp) / m + (0.5 * chain_sum(xg) + prm.cst);   // (FOLD1: set in trip -1 below)
+    double oldH = 0.5 * chain_sum(pp) / m + (0.5 * chain_sum(xg) + args().cst);   // (FOLD1: set in trip -1 below)
     STAMP(4);
     [[maybe_unused]] const double xg_old_keep = xg;
     if constexpr (!DYN) xg = 0.0;  // (DYN keeps x.g(q_0): a wave none of whose chains steps ends where it started)
@@ -1103,7 +1209,7 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
             constexpr int PASS = decltype(pass_c)::value;
             double q0r[4 * NTP];
 #pragma unroll
-            for (int t = 0; t < 4 * NTP; ++t) q0r[t] = load_row(qin_k, vin, s4in, 4 * PASS * NTP + t);
+            for (int t = 0; t < 4 * NTP; ++t) q0r[t] = load_row(qin, vin, s4in, 4 * PASS * NTP + t);
             double sum = 0.0;
 #pragma unroll
             for (int t = 0; t < NTP; ++t)
@@ -1169,11 +1275,11 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
     // kick; for Stormer-Verlet's HMC iteration the position step L + 1 (:155-159 on the last pass of the
     // reference's loop), which has no kick; Stormer-Verlet's integrate() ends with that drift alone.
     constexpr bool TAIL = METHOD == PBBI_LEAPFROG || MODE == 0;
-    const int n_in = METHOD == PBBI_LEAPFROG ? prm.L - 1 : prm.L;
+    const int n_in = METHOD == PBBI_LEAPFROG ? here(prm.L) - 1 : here(prm.L);
 #pragma nounroll
     for (int j = 0; j < n_in; ++j) {
         STAMP(5 + 2 * j);
-        matvec_inplace<NT, ZMEAN, !FULL>(fragL, muG, q, w, cd, ks_act);  // drift + full kick
+        matvec_inplace<NT, ZMEAN, !FULL>(fragA, muG, q, w, cd, ks_act);  // drift + full kick
     }
     if constexpr (TAIL) {
         STAMP(5 + 2 * n_in);
@@ -1265,17 +1371,21 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
             vset(s, pv);
             pp += pv * pv;
         }
-        const double newH = 0.5 * chain_sum(pp) / m + (0.5 * chain_sum(xg) + prm.cst);
+        const auto& ae = args();     // the epilogue's own copies: its descriptors and row pointers are formed here
+        const int kf_e = here(kf);
+        const double newH = 0.5 * chain_sum(pp) / m + (0.5 * chain_sum(xg) + ae.cst);
         STAMP(40);
-        const double ratio = exp((oldH - newH) * pbbi_accept_beta(prm.flags, prm.kT));
-        const double u = rng ? rng_uniform(prm.seed, iter_k, prm.chain0 + (uint64_t)(n0 + cc))
+        const double ratio = exp((oldH - newH) * pbbi_accept_beta(ae.flags, ae.kT));
+        const double u = rng ? rng_uniform(ae.seed, iter_k, ae.chain0 + (uint64_t)(n0 + cc))
                              : prm.u_in[n0 + cc];
         const bool reject = (ratio == ratio) && (u > (ratio < 1.0 ? ratio : 1.0));
-        const bool compat = (prm.flags & PBBI_COMPAT_P_FROM_OLDQ) != 0;
-        bool store_p = (prm.p_out != nullptr);
+        const bool compat = (ae.flags & PBBI_COMPAT_P_FROM_OLDQ) != 0;
+        bool store_p = (ae.p_out != nullptr);
         if (reject) {  // rare: fetch the old point again instead of keeping it in registers
+            const uint32_t st = here(s4in);
+            const __amdgpu_buffer_rsrc_t qin_k = qin_of(ae, kf_e);
 #pragma unroll
-            for (int s = 0; s < KS; ++s) q[s] = load_row(qin_k, vin, s4in, s);  // :175
+            for (int s = 0; s < KS; ++s) q[s] = load_row(qin_k, vin, st, s);  // :175
             if constexpr (KEEPG) {  // ... and its gradient, from the slab of the position the chain started from
 #pragma unroll
                 for (int t = 0; t < NTP; ++t)
@@ -1297,22 +1407,29 @@ __global__ void __launch_bounds__(STREAM ? BLOCK : BLOCK2, STREAM ? 1 : 2) k_den
             }
         }
         if (valid) {
+            const uint32_t st = here(s4out);
+            const __amdgpu_buffer_rsrc_t qout_k = qout_of(ae, kf_e);
 #pragma unroll
-            for (int s = 0; s < KS; ++s) store_row(qout_k, vout, s4out, s, q[s]);  // :178
+            for (int s = 0; s < KS; ++s) store_row(qout_k, vout, st, s, q[s]);  // :178
             if (store_p) {
+                const uint32_t stp = here(s4out);
+                const __amdgpu_buffer_rsrc_t pout_k = pout_of(ae, kf_e);
 #pragma unroll
-                for (int s = 0; s < KS; ++s) store_row(pout_k, vout, s4out, s, vget(s));  // :179
+                for (int s = 0; s < KS; ++s) store_row(pout_k, vout, stp, s, vget(s));  // :179
             }
         }
         if constexpr (CARRY != 0) csel ^= reject ? 0u : 1u;  // accepted: the other slab is current now
         if constexpr (KEEPG) xg_keep = reject ? xg_old_keep : xg;
-        if (valid && g == 0) {
-            if (ratio_k) ratio_k[n0 + c] = ratio;
-            if (reject_k) reject_k[n0 + c] = reject ? 1 : 0;
+        if (valid && (LOCAL ? vgpr_fresh(g) : g) == 0) {
+            const int64_t n0_e = here(n0);  // (the row addresses from this copy: not a pointer per array across the loop)
+            double* const ratio_k = !LOCAL ? ratio_top : (FUSE && ae.ratio_out) ? ae.ratio_out + (int64_t)kf_e * ae.N : ae.ratio_out;
+            uint8_t* const reject_k = !LOCAL ? reject_top : (FUSE && ae.reject_out) ? ae.reject_out + (int64_t)kf_e * ae.N : ae.reject_out;
+            if (ratio_k) ratio_k[n0_e + c] = ratio;
+            if (reject_k) reject_k[n0_e + c] = reject ? 1 : 0;
             if constexpr (DYN) {
-                if (prm.steps_out) prm.steps_out[n0 + c] = Ln;
+                if (prm.steps_out) prm.steps_out[n0_e + c] = Ln;
             }
-            if constexpr (CARRY != 0 && !FUSE) prm.carry_sel[n0 + c] = (uint8_t)csel;
+            if constexpr (CARRY != 0 && !FUSE) prm.carry_sel[n0_e + c] = (uint8_t)csel;
         }
         STAMP(41);
     }

@@ -57,3 +57,31 @@ __device__ __forceinline__ void buf_store(__amdgpu_buffer_rsrc_t r, uint32_t vof
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, x), r, voff_bytes,
                                           soff_bytes, 0);
 }
+
+// A wave-uniform value made opaque at the place it is used.  Row offsets (row * stride) and descriptors are loop
+// invariants: inside a loop over iterations the compiler forms all of them in front of the loop, they outnumber the
+// scalar registers, and the overflow is parked in the lanes of a VGPR -- fetched back through the VECTOR unit
+// (v_readlane_b32 and its hazard nops) at every use.  Built from a fresh copy of the stride, the offsets of one
+// group of accesses are scalar multiplies next to that group and are dead behind it.  The same holds for flags,
+// counters and pointers among the kernel arguments: tested or offset through a fresh copy, the condition is a scalar
+// compare at the branch, not a lane mask held (two registers each) from the top of the kernel.
+template <typename T>
+__device__ __forceinline__ T sgpr_fresh(T x) {
+    asm volatile("" : "+s"(x));
+    return x;
+}
+// (the per-lane counterpart: a compare on the copy is made where it stands, not kept as a lane mask)
+template <typename T>
+__device__ __forceinline__ T vgpr_fresh(T x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+
+// The kernel's argument block, read again.  A kernel argument is loaded once at the top and then holds its scalar
+// registers to the end; through a fresh copy of the kernarg pointer the same field is an s_load next to its use and
+// is dead behind it.  For kernels whose ONLY parameter is the block (it then starts the kernarg segment).
+template <typename PRM>
+__device__ __forceinline__ const __attribute__((address_space(4))) PRM& kernarg_fresh() {
+    typedef const __attribute__((address_space(4))) PRM* ptr_t;
+    return *sgpr_fresh((ptr_t)__builtin_amdgcn_kernarg_segment_ptr());
+}

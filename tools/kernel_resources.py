@@ -12,18 +12,14 @@ import subprocess
 import sys
 import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from hipcc_asm import device_asm_command  # noqa: E402
+
 src = sys.argv[1]
 stem = os.path.splitext(os.path.basename(src))[0]
-made = subprocess.run(["make", "-s", "-C", os.path.dirname(os.path.abspath(src)), "print-flags-" + stem],
-                      capture_output=True, text=True)
-if made.returncode != 0:
-    sys.exit("csrc/Makefile has no print-flags-%% target: %s" % made.stderr.strip())
 with tempfile.TemporaryDirectory() as tmp:
     asm = os.path.join(tmp, stem + ".s")
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
-           "-ffp-contract=off", "-I" + os.path.join(ROOT, "include")] + made.stdout.split() + \
-          ["--cuda-device-only", "-S", src, "-o", asm, "-Rpass-analysis=kernel-resource-usage"] + sys.argv[2:]
+    cmd = device_asm_command(src, asm, ["-Rpass-analysis=kernel-resource-usage"] + sys.argv[2:])
     out = subprocess.run(cmd, capture_output=True, text=True).stderr
     text = open(asm).read() if os.path.exists(asm) else ""
 rows, cur = [], None
