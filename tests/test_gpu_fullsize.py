@@ -21,7 +21,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
-from test_gpu_parity import device_normal, device_uniform, scaled_err
+from test_gpu_parity import device_normal, device_uniform, route_of, scaled_err
 
 pytestmark = pytest.mark.gpu
 
@@ -389,14 +389,22 @@ def test_dense_stream_strided_state_and_small_ensembles(P, lib, D, N):
     assert np.array_equal(qf, samples[S - 1])
 
 
+# (D, dtype) -> the family the row's run takes (route_of's text): fp64 at 128 < D <= 256 went to the streamed-P
+# kernel, which carries its gradient in its own format; fp64 at D > 256 and every fp32 shape stay on the GEMM path
+CARRY_ROUTES = {(512, "float32"): "kernels_big", (200, "float64"): "streamed P", (384, "float32"): "kernels_big",
+                (300, "float64"): "kernels_big"}
+
+
 @pytest.mark.parametrize("D,N,dtype,zero_mean,mass", [(512, 768, "float32", True, False),
                                                       (200, 150, "float64", False, True),
-                                                      (384, 300, "float32", False, True)])
+                                                      (384, 300, "float32", False, True),
+                                                      (300, 150, "float64", False, True)])
 def test_gemm_path_run_carries_the_gradient_bit_identically(P, lib, D, N, dtype, zero_mean, mass):
-    """The same on the GEMM path (kernels_big.hip, D > 128 / fp32): inside pbbi_hmc_run the first of the
+    """The same on the GEMM path (kernels_big.hip, D > 256 / fp32): inside pbbi_hmc_run the first of the
     L + 1 GEMMs of an iteration is replaced by one elementwise pass over the gradient the previous iteration
     kept (its last GEMM's for accepted chains, the older one for rejected chains), and H_old by the kept x.g
-    partial sums.  One run of S iterations == S runs of one, bit for bit, rejections included."""
+    partial sums.  One run of S iterations == S runs of one, bit for bit, rejections included.  The fp64 row at
+    D = 200 holds the streamed-P kernel's carried run to the same identity; CARRY_ROUTES says which is which."""
     import torch
     from physicsbasedbayesianinference_amd._device import as_device, empty, stream_ptr, to_numpy
     h, L, S, seed, chain0, iter0 = 0.35, 3, 5, 4, 9, 1
@@ -423,6 +431,9 @@ def test_gemm_path_run_carries_the_gradient_bit_identically(P, lib, D, N, dtype,
         torch.cuda.synchronize()
         return to_numpy(samples), to_numpy(momenta), to_numpy(reject), to_numpy(ratio), to_numpy(qd)
 
+    for s_per_call in (S, 1):
+        d = route_of(lib, pot, N, L, s_per_call, lib.COMPAT_P_FROM_OLDQ, 0)
+        assert CARRY_ROUTES[(D, dtype)] in d and ("carried between iterations: yes" in d) == (s_per_call > 1), d
     one, each = run(S), run(1)
     for a, b in zip(one, each):
         assert np.array_equal(a, b)

@@ -51,6 +51,18 @@ def scaled_err(a, b):
     return float(np.max(np.abs(a[ok] - b[ok]))) / max(1.0, float(np.max(np.abs(b[ok]))))
 
 
+def route_of(lib, pot, N, L, S, flags, method, ldn=None):
+    """The route witness: pbbi_describe_run's text for these arguments (the kernel family first), without
+    launching anything.  It describes pbbi_hmc_run's route and pbbi_hmc_iter's alike: route_hmc, lane_hmc_iter
+    and every *_applies predicate they ask read the potential, the method, L, the flags, N and the strides,
+    never IterArgs::rng.  (What does differ between the two entry points is only whether the gradient is carried
+    and how many iterations one launch covers, which the text reports for a run of S.)"""
+    buf = C.create_string_buffer(1024)
+    lib.call("pbbi_describe_run", pot.handle, orc.METHODS.get(method, method), N, N if ldn is None else ldn, L, S,
+             flags, buf, len(buf))
+    return buf.value.decode()
+
+
 def make_pot(P, g, kind):
     if kind == "dense":
         return P.GaussianDense(g["mean"], precision=g["precision"], const=float(g["const"]))
@@ -567,11 +579,14 @@ def test_big_dense_integrate_vs_oracle(P, D, mass, method, L):
 
 @pytest.mark.parametrize("method,L", [("Stormer-Verlet", 6), ("Stormer-Verlet", 0), ("Leapfrog", 0)])
 def test_big_dense_hmc_iter_methods_vs_oracle(P, lib, method, L):
-    """D > 128: Stormer-Verlet and the zero-step trajectory on the GEMM path (padded input stride
-    is covered by gpu_hmc_iter's contiguous arrays; masks equal, state within the dense tolerance)."""
+    """D = 200: Stormer-Verlet on the streamed-P kernel (128 < D <= 256 with L >= 1 is kernels_dstream.hip's) and
+    the zero-step trajectory, which that kernel does not take, on the GEMM path (kernels_big.hip); masks equal,
+    state within the dense tolerance.  The GEMM path's fp64 trajectories with L >= 1 are held to the oracle at
+    D > 256 in test_route_coverage.py."""
     D, N, h = 200, 150, 0.3
     Pm, mu = _dense_problem(D, 8)
     pot, op = P.GaussianDense(mu, precision=Pm, const=0.0), orc.pot_gauss_dense(mu, Pm)
+    assert ("streamed P" if L else "kernels_big") in route_of(lib, pot, N, L, 1, lib.COMPAT_P_FROM_OLDQ, method)
     rs = np.random.RandomState(9)
     q, p, u = rs.standard_normal((D, N)), rs.standard_normal((D, N)), rs.uniform(size=N)
     m = 1.0 + (np.arange(N) % 3) * 0.5
@@ -588,9 +603,12 @@ def test_big_dense_hmc_iter_methods_vs_oracle(P, lib, method, L):
 
 @pytest.mark.parametrize("rng", ["numpy", "philox"])
 def test_big_dense_getsamples_vs_oracle(P, lib, rng):
+    """getSamples at D = 256, the largest size of the streamed-P kernel (kernels_dstream.hip; the GEMM path served
+    this shape before that kernel took 128 < D <= 256), in both RNG modes against the oracle."""
     D, N, S, L, h = 256, 140, 3, 10, 0.1
     Pm, mu = _dense_problem(D, 5)
     pot, op = P.GaussianDense(mu, precision=Pm, const=0.0), orc.pot_gauss_dense(mu, Pm)
+    assert "streamed P" in route_of(lib, pot, N, L, S, lib.COMPAT_P_FROM_OLDQ, "Leapfrog")
     m = 1.0 + (np.arange(N) % 2) * 0.5
     ens = P.Ensemble(D, N)
     ens.mass = m.copy()
@@ -717,7 +735,7 @@ def test_rosenbrock_two_lane_kernel_bitexact(P, lib, D, N, mass, compat):
 @pytest.mark.parametrize("D", [1, 3, 128, 130])
 @pytest.mark.parametrize("N", [0, 1, 17])
 def test_dense_tiny_shapes(P, D, N):
-    """Dense Gaussian at degenerate sizes (D = 1 pads to a 32-wide tile; D = 130 takes the GEMM path)."""
+    """Dense Gaussian at degenerate sizes (D = 1 pads to a 32-wide tile; D = 130 takes the streamed-P kernel)."""
     rs = np.random.RandomState(D + N)
     A = rs.standard_normal((D, D))
     Pm = np.linalg.inv(A @ A.T / D + np.eye(D))
@@ -809,13 +827,31 @@ def _stream_case(P, kind, D, rs, dtype="float64"):
     return P.Rosenbrock(D, dtype=dtype), orc.pot_rosenbrock(D)
 
 
+# (kind, D, method) -> the family that serves the row's accept/reject step (route_of's text).  The separable rows
+# with 16 < D <= 256 and Rosenbrock 70 with Leapfrog were written for the workspace kernel and moved to the
+# multi-lane reference-order kernels when those took their range; D > 256 and Rosenbrock with Stormer-Verlet stream.
+STREAM_ROUTES = {
+    ("harmonic", 65, "Leapfrog"): "k_sep_exact_hmc", ("diag", 100, "Stormer-Verlet"): "k_sep_exact_hmc",
+    ("diag", 72, "Leapfrog"): "k_sep_exact_hmc", ("rosenbrock", 70, "Leapfrog"): "k_rosg_exact_hmc",
+    ("rosenbrock", 128, "Stormer-Verlet"): "k_stream_hmc", ("rosenbrock", 257, "Leapfrog"): "k_stream_hmc",
+    ("harmonic", 257, "Stormer-Verlet"): "k_stream_hmc", ("diag", 300, "Leapfrog"): "k_stream_hmc",
+    ("diag", 257, "Leapfrog"): "k_stream_hmc",
+}
+
+
 @pytest.mark.parametrize("kind,D,N,method,mass", [
     ("harmonic", 65, 100, "Leapfrog", False), ("diag", 100, 130, "Stormer-Verlet", True),
     ("diag", 72, 64, "Leapfrog", True), ("rosenbrock", 70, 200, "Leapfrog", False),
-    ("rosenbrock", 128, 65, "Stormer-Verlet", False), ("rosenbrock", 257, 70, "Leapfrog", True)])
+    ("rosenbrock", 128, 65, "Stormer-Verlet", False), ("rosenbrock", 257, 70, "Leapfrog", True),
+    # separable shapes that still stream (D > 256): the separable branch of k_stream_hmc's accept/reject step
+    ("harmonic", 257, 70, "Stormer-Verlet", True), ("diag", 300, 130, "Leapfrog", False),
+    ("diag", 257, 64, "Leapfrog", True)])
 def test_streaming_lane_path_bit_exact(P, lib, kind, D, N, method, mass):
-    """D > 64: the chain's q, v, a live in a device workspace (kernels_stream.hip); same
-    arithmetic in the same order as the oracle => bit-identical q, p, masks, energies."""
+    """D > 64, one chain per lane or per group of lanes, in the reference's operation order: the same arithmetic
+    in the same order as the oracle => bit-identical q, p, masks, energies.  The HMC step runs on the family
+    STREAM_ROUTES names (asserted): the workspace kernel k_stream_hmc (kernels_stream.hip) for D > 256 and for
+    Rosenbrock with Stormer-Verlet, k_sep_exact_hmc / k_rosg_exact_hmc below that; potential, gradient and
+    integrate() run on the workspace kernels at every D > 64."""
     from physicsbasedbayesianinference_amd._device import as_device, empty, stream_ptr, to_numpy
     rs = np.random.RandomState(D)
     pot, op = _stream_case(P, kind, D, rs)
@@ -828,6 +864,8 @@ def test_streaming_lane_path_bit_exact(P, lib, kind, D, N, method, mass):
     if mass:
         p *= np.sqrt(m)
     for compat in (True, False):
+        assert STREAM_ROUTES[(kind, D, method)] in route_of(lib, pot, N, L, 1, lib.COMPAT_P_FROM_OLDQ if compat else 0,
+                                                            method)
         qo, po, ratio, rej = gpu_hmc_iter(lib, pot, method, q, p, u, m, h, L, compat=compat)
         q_or, p_or = q.copy(), p.copy()
         r_or, rej_or = orc.hmc_iter(op, method, q_or, p_or, u, m, h, L,
@@ -2343,33 +2381,36 @@ def test_f64_draw_distribution(lib):
 
 
 F64_RUNS = [
-    # name, kind, D, N, flags (beyond compat | DRAW_F64), dtype, tolerance (None = bit-exact), mass
-    ("lane_diag8", "diag", 8, 300, 0, "float64", None, True),
-    ("lane2_ros32_exact", "ros", 32, 200, 0, "float64", None, False),
-    ("lane2_ros32_kdk", "ros", 32, 200, "kdk", "float64", 1e-12, False),
-    ("lane2_ros24_kdk_mass", "ros", 24, 130, "kdk", "float64", 1e-12, True),
-    ("sepx_diag64_exact", "diag", 64, 200, 0, "float64", None, True),
-    ("sepn_diag64_kdk", "diag", 64, 200, "kdk", "float64", 1e-12, False),
-    ("rosgx_ros64_exact", "ros", 64, 130, 0, "float64", None, False),
-    ("rosg_ros64_kdk", "ros", 64, 130, "kdk", "float64", 1e-12, True),
-    ("rosn_ros200_kdk", "ros", 200, 70, "kdk", "float64", 1e-12, False),
-    ("stream_ros300", "ros", 300, 70, 0, "float64", None, True),
-    ("stream_diag12_f32", "diag", 12, 200, 0, "float32", 3e-5, False),
-    ("dense128_fused", "dense", 128, 300, 0, "float64", 1e-11, False),
-    ("dense128_mass", "dense", 128, 150, 0, "float64", 1e-11, True),
-    ("dense100", "dense", 100, 150, 0, "float64", 1e-11, False),
-    ("dense96", "dense", 96, 150, 0, "float64", 1e-11, False),
-    ("dense80_mass", "dense", 80, 150, 0, "float64", 1e-11, True),
-    ("dense24", "dense", 24, 70, 0, "float64", 1e-11, True),
-    ("gemm_dense200", "dense", 200, 150, 0, "float64", 1e-10, False),
-    ("gemm_dense256_f32", "dense", 256, 128, 0, "float32", 2e-4, False),
-    ("custom_quartic9", "quartic", 9, 300, 0, "float64", None, True),
-    ("custom_quartic48", "quartic", 48, 100, 0, "float64", None, False),
+    # name, kind, D, N, flags (beyond compat | DRAW_F64), dtype, tolerance (None = bit-exact), mass, the kernel
+    # family the row is there for: a substring of pbbi_describe_run's text, asserted before the launch
+    # ("k_sep_hmc:" with its colon, so that k_sep_hmc<DYN> or another name that begins alike is no match)
+    ("lane_diag8", "diag", 8, 300, 0, "float64", None, True, "k_lane_hmc"),
+    ("lane2_ros32_exact", "ros", 32, 200, 0, "float64", None, False, "k_ros2_hmc"),
+    ("lane2_ros32_kdk", "ros", 32, 200, "kdk", "float64", 1e-12, False, "k_ros2_hmc"),
+    ("lane2_ros24_kdk_mass", "ros", 24, 130, "kdk", "float64", 1e-12, True, "k_ros2_hmc"),
+    ("sepx_diag64_exact", "diag", 64, 200, 0, "float64", None, True, "k_sep_exact_hmc"),
+    ("sepn_diag64_kdk", "diag", 64, 200, "kdk", "float64", 1e-12, False, "k_sep_hmc:"),
+    ("rosgx_ros64_exact", "ros", 64, 130, 0, "float64", None, False, "k_rosg_exact_hmc"),
+    ("rosg_ros64_kdk", "ros", 64, 130, "kdk", "float64", 1e-12, True, "k_rosg_hmc:"),
+    ("rosn_ros200_kdk", "ros", 200, 70, "kdk", "float64", 1e-12, False, "k_rosn_hmc"),
+    ("stream_ros300", "ros", 300, 70, 0, "float64", None, True, "k_stream_hmc"),
+    ("stream_diag300", "diag", 300, 150, 0, "float64", None, True, "k_stream_hmc"),
+    ("stream_diag12_f32", "diag", 12, 200, 0, "float32", 3e-5, False, "k_stream_hmc"),
+    ("dense128_fused", "dense", 128, 300, 0, "float64", 1e-11, False, "k_dense_hmc:"),
+    ("dense128_mass", "dense", 128, 150, 0, "float64", 1e-11, True, "k_dense_hmc:"),
+    ("dense100", "dense", 100, 150, 0, "float64", 1e-11, False, "k_dense_hmc:"),
+    ("dense96", "dense", 96, 150, 0, "float64", 1e-11, False, "k_dense_hmc:"),
+    ("dense80_mass", "dense", 80, 150, 0, "float64", 1e-11, True, "k_dense_hmc:"),
+    ("dense24", "dense", 24, 70, 0, "float64", 1e-11, True, "k_dense_hmc:"),
+    ("dstream_dense200", "dense", 200, 150, 0, "float64", 1e-10, False, "streamed P"),
+    ("gemm_dense256_f32", "dense", 256, 128, 0, "float32", 2e-4, False, "kernels_big"),
+    ("custom_quartic9", "quartic", 9, 300, 0, "float64", None, True, "plugin"),
+    ("custom_quartic48", "quartic", 48, 100, 0, "float64", None, False, "plugin"),
 ]
 
 
-@pytest.mark.parametrize("name,kind,D,N,extra,dtype,tol,mass", F64_RUNS, ids=[r[0] for r in F64_RUNS])
-def test_hmc_run_with_f64_draws_vs_host_only_oracle(P, lib, name, kind, D, N, extra, dtype, tol, mass):
+@pytest.mark.parametrize("name,kind,D,N,extra,dtype,tol,mass,route", F64_RUNS, ids=[r[0] for r in F64_RUNS])
+def test_hmc_run_with_f64_draws_vs_host_only_oracle(P, lib, name, kind, D, N, extra, dtype, tol, mass, route):
     """pbbi_hmc_run with PBBI_DRAW_F64 in every kernel family against oracle_hmc_run_philox with the same flag,
     which draws ITS OWN momenta (the oracle's C restatement of the draw): decisions equal, states bit-exact
     where the kernel keeps the reference's operation order, within the family's tolerance elsewhere."""
@@ -2403,6 +2444,7 @@ def test_hmc_run_with_f64_draws_vs_host_only_oracle(P, lib, name, kind, D, N, ex
     qd = as_device(q0, 0, npdt)
     samples, momenta = empty((S, D, N), npdt, 0), empty((S, D, N), npdt, 0)
     reject = empty((S, N), np.uint8, 0)
+    assert route in route_of(lib, pot, N, L, S, flags, lib.LEAPFROG), name
     lib.call("pbbi_hmc_run", pot.handle, lib.LEAPFROG, qd.data_ptr(), md.data_ptr() if mass else None,
              samples.data_ptr(), momenta.data_ptr(), reject.data_ptr(), None, N, N, h, L, S, flags, seed, iter0,
              chain0, kT, stream_ptr(0))
@@ -2486,13 +2528,10 @@ def test_sample_chunks_gathered_equal_one_run(P, rng):
 def test_describe_run_names_the_route_and_the_carry_cliff(P, lib):
     """pbbi_describe_run: the kernel family, the carried-gradient state (with the N = 2^31 / (16 D) cliff of the
     dense path spelled out) and the iterations per launch, without launching anything."""
-    import ctypes
     Pm = np.eye(128) + 0.01
 
     def describe(pot, N, L=10, S=100, flags=1, method=0):
-        buf = ctypes.create_string_buffer(1024)
-        lib.call("pbbi_describe_run", pot.handle, method, N, N, L, S, flags, buf, len(buf))
-        return buf.value.decode()
+        return route_of(lib, pot, N, L, S, flags, method)
     dense = P.GaussianDense(None, precision=Pm, const=0.0)
     d = describe(dense, 65536)
     assert "k_dense_hmc" in d and "carried between iterations: yes" in d and "up to 64" in d
