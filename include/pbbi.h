@@ -205,6 +205,23 @@ int pbbi_potential_create_glm_ex(int D, int64_t M, const double* X, const double
  * 4); with `out` non-NULL (out_len >= that length) c | d | o, each stream zero padded past M. */
 int pbbi_glm_pack_observations(int64_t M, int family, const double* y, const double* weights, const double* offset,
                                const double* trials, double* out, int64_t out_len, int64_t* len_out);
+/* K-class (multinomial logistic / softmax) regression, every class with coefficients and a Gaussian prior shared by
+ * the classes (csrc/kernels_glm_softmax.hip):
+ *     U(W) = sum_i [ logsumexp_k(eta_ik) - eta_{i,y_i} ] + 0.5 sum_k sum_d lam_d W_kd^2,    eta_ik = x_i . W_k.
+ * The handle's dimension is K*D: one chain is the K coefficient vectors class-major, w[k*D + d].  X (M x D row-major),
+ * y (M labels as doubles, integers in [0, K)) and prior_precision (D values, finite and >= 0) are HOST pointers,
+ * checked (PBBI_ERR_INVALID) and copied at creation.  fp64 only; each class is padded to Dc = 16, 32 or 64 rows and
+ * 2 <= K <= 8, K * Dc <= 128 (D <= 16 for K <= 8, D <= 32 for K <= 4, D <= 64 for K = 2), otherwise
+ * PBBI_ERR_UNSUPPORTED.  The handle is a GLM handle of family PBBI_GLM_SOFTMAX: it serves what those serve and
+ * refuses what they refuse (per-chain trajectory lengths, GIST).  pbbi_potential_create_glm / _glm_ex do not accept
+ * this family. */
+enum { PBBI_GLM_SOFTMAX = 2 };
+int pbbi_potential_create_glm_softmax(int D, int K, int64_t M, const double* X, const double* y,
+                                      const double* prior_precision /* D values */, int dtype, int device,
+                                      pbbi_potential** out);
+/* host only, no GPU: the padded class size, the tile count and (row_map != NULL) the external row of each of the
+   NT*16 internal rows, -1 for padding */
+int pbbi_glm_softmax_layout(int D, int K, int* Dc_out, int* NT_out, int32_t* row_map);
 int pbbi_potential_destroy(pbbi_potential* pot);
 int pbbi_potential_dim(const pbbi_potential* pot);
 int pbbi_potential_dtype(const pbbi_potential* pot);

@@ -16,13 +16,13 @@ from .potential import (GaussianDense, GaussianDiag, Harmonic, Potential, Rosenb
 from .integrator import Integrator, Leapfrog, StormerVerlet
 from .HMC import HMC
 from .custom import CustomPotential
-from .glm import GLM
+from .glm import GLM, SoftmaxGLM
 from .stats import RunningStats
 from . import trace
 from .trace import grad, trace_potential
 
 __all__ = ["Ensemble", "HMC", "Integrator", "Leapfrog", "StormerVerlet", "Potential",
            "Harmonic", "GaussianDiag", "StandardGaussian", "GaussianDense", "Rosenbrock",
-           "harmonicPotentialND", "linear_regression_posterior", "CustomPotential", "GLM", "RunningStats",
+           "harmonicPotentialND", "linear_regression_posterior", "CustomPotential", "GLM", "SoftmaxGLM", "RunningStats",
            "trace", "grad", "trace_potential"]
 __version__ = "0.1.0"

@@ -221,6 +221,8 @@ __device__ __forceinline__ void glm_grad(const typename GlmArgs<RICH>::type& prm
     }
 }
 
+// TWIN: k_glm_softmax of kernels_glm_softmax.hip restates this frame (ghost waves and ragged tail, momentum first, the
+// kick / drift schedule of the evaluation loop, the five modes, the accept epilogue).  A fix to either belongs in both.
 template <int NT, int FAM, bool RICH>
 __global__ void __launch_bounds__(BLOCK, NT <= 2 ? 2 : 1) k_glm(typename GlmArgs<RICH>::type prm) {
     using C = GlmCfg<NT>;

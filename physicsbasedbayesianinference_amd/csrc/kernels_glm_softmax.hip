@@ -1,0 +1,573 @@
+// kernels_glm_softmax.hip -- K-class (multinomial logistic / softmax) regression on the fp64 matrix cores (gfx950).
+//
+//   U(W) = sum_i [ logsumexp_k(eta_ik) - eta_{i,y_i} ] + 0.5 sum_k sum_d lam_d W_kd^2,   eta_ik = x_i . W_k,
+//   dU/dW_k = sum_i (softmax_k(eta_i) - [y_i == k]) x_i + lam (.) W_k,                    y_i in {0 .. K-1}
+// The sampler sees one vector of K D numbers per chain, class-major (w[k D + d]).  The chain frame is that of
+// kernels_glm.hip (k_glm): 16 chains per wave, 4 waves per workgroup, ghost waves and a clamped ragged tail, q, the
+// half-step velocity and the gradient accumulator in registers (element s of a lane is INTERNAL row 4s + g), X staged
+// through LDS in the image glm_pack makes of an M x D matrix at DP = Dc, kick-drift-kick with one call site of the
+// gradient, five modes, the accept test of pbbi_chain.h.  What is new:
+//
+// Internal layout.  Every class is padded to Dc = 16, 32 or 64 rows and owns the NTc = Dc / 16 tiles k NTc ..
+// k NTc + NTc - 1 of the chain's state; NT = K NTc <= 8.  Internal row k Dc + d is external row k D + d for d < D.
+// The K linear predictors of an observation are K eta tiles X_b . W_k: the SAME A fragments of X (each read from
+// LDS once, s2 outer, k inner) against class k's rows, and under the MFMA's C/D map they land in the SAME lane.  The
+// softmax over the classes is therefore in-lane arithmetic on K accumulator values, and each class's residual is
+// already the B operand of X_b^T . R_k, which goes into class k's gradient tiles.  The K eta chains are independent
+// of each other and interleave in the matrix pipe.
+//
+// Padding.  Rows d >= D of a class load 0 and are never stored.  A bounded descriptor alone cannot do that: the
+// natural address of a padded row of class k is a real row of class k + 1.  The accessors below therefore decide per
+// lane: a lane whose row is padding READS a row that certainly exists (the first row of its group of four, or row 0
+// when the whole group is padding) and discards the value, and its store is not issued at all.  The descriptor is
+// bounded over the K D external rows on top of that.
+//
+// Draws.  The in-kernel momentum must be the draw of a (K D, N) state: the normal of external row r is slot
+// (r % 16) / 4 of block rng_block_of_dim(r).  The four elements of a tile are the rows r0 + 4e, r0 = k D + 16 tc + g:
+// they lie in the block of r0 and, when k D is no multiple of 16, in the next block of the same r % 4 -- two Philox
+// blocks per tile there instead of one, the same numbers.
+//
+// An observation >= M is masked out of the residual and of the energy (softmax(0) = 1 / K, log K).
+#include <cmath>
+#include <cstring>
+
+#include "kernels_dense_dev.h"
+#include "pbbi_chain.h"
+
+namespace {
+
+struct SmxPrm {
+    const double* img;    // nbp blocks of 32 Dc doubles (P1 then P2), nbp = blocks padded to a multiple of 4
+    const double* y;      // labels as doubles, nbp * 16, zero padded
+    const double* prior;  // lam, Dc values, zero padded past D
+    const double* q_in;
+    const double* p_in;
+    const double* u_in;
+    const double* mass;
+    double* q_out;
+    double* p_out;
+    double* v_out;
+    double* ratio_out;
+    uint8_t* reject_out;
+    double* U_out;     // modes 2..4
+    double* grad_out;  // mode 2
+    double* w_out;     // mode 3
+    int64_t N, ldn_in, ldn_out, M;
+    double h, kT;
+    int L, D, flags, rng, mode, method, nb;  // D: coefficients per class
+    uint64_t seed, iter, chain0;
+};
+enum { SMX_HMC = 0, SMX_INTEGRATE = 1, SMX_EVAL = 2, SMX_ENERGY = 3, SMX_RATIO = 4 };
+
+template <int NTc>
+struct SmxCfg {
+    static constexpr int KSc = 4 * NTc;                  // K-steps (elements of a lane) per class
+    static constexpr int CB = NTc >= 4 ? 1 : 4 / NTc;    // observation blocks per staged chunk
+    static constexpr int BLKV = NTc * 256;               // 16-byte elements per block (P1 + P2)
+    static constexpr int CHV = CB * BLKV;                // ... per chunk
+    static constexpr int PER_THREAD = CHV / BLOCK;       // = CB * NTc
+    static_assert(CHV % BLOCK == 0, "whole 16-byte elements per thread");
+};
+
+// Element s of a lane: class s / KSc, row d = 4 (s % KSc) + g of that class, external row k D + d.
+// voff = this lane's offset (8 (g ld + cc)), v0 = the offset of row 0 of its group (8 cc), ld8 = 8 ld.
+template <int NTc>
+__device__ __forceinline__ double smx_load(__amdgpu_buffer_rsrc_t base, uint32_t voff, uint32_t v0, uint32_t ld8, int s,
+                                           int g, int D) {
+    constexpr int KSc = 4 * NTc;
+    const int k = s / KSc, d0 = 4 * (s % KSc);
+    D = sgpr_fresh(D);  // (the row offset is formed next to its access, not held in a scalar register from the top)
+    const bool ok = d0 + g < D;  // d0 >= D: no lane is
+    const uint32_t soff = d0 < D ? (uint32_t)(k * D + d0) * sgpr_fresh(ld8) : 0u;
+    const double t = buf_load<double>(base, ok ? voff : v0, soff);
+    return ok ? t : 0.0;
+}
+template <int NTc>
+__device__ __forceinline__ void smx_store(__amdgpu_buffer_rsrc_t base, uint32_t voff, uint32_t ld8, int s, int g, int D,
+                                          double val) {
+    constexpr int KSc = 4 * NTc;
+    const int k = s / KSc, d0 = 4 * (s % KSc);
+    D = sgpr_fresh(D);
+    if (d0 + g < D) buf_store(base, voff, (uint32_t)(k * D + d0) * sgpr_fresh(ld8), val);
+}
+
+// gacc[k NTc + t][r] (class k, row 16t + 4r + g) = sum_i X[i][row] (softmax_k(eta_i) - [y_i == k]) for the wave's 16
+// chains, usum = this lane's share of sum_i logsumexp(eta_i) - eta_{i, y_i}.  Staging as in kernels_glm.hip: one chunk of
+// CB blocks is in LDS while the next waits in registers.
+template <int NTc, int K>
+__device__ __forceinline__ void smx_grad(const SmxPrm& prm, v2f64* __restrict__ lds, double* __restrict__ ylds, int lane,
+                                         int g, const double (&q)[4 * NTc * K], v4f64 (&gacc)[NTc * K], double& usum,
+                                         bool want_u) {
+    using C = SmxCfg<NTc>;
+    constexpr int KSc = C::KSc;
+    const v2f64* __restrict__ src = reinterpret_cast<const v2f64*>(prm.img);
+    const int nch = (prm.nb + C::CB - 1) / C::CB;
+    v2f64 tmp[C::PER_THREAD];
+    double ytmp = 0.0;
+#pragma unroll
+    for (int j = 0; j < C::PER_THREAD; ++j) tmp[j] = src[threadIdx.x + j * BLOCK];
+    if (threadIdx.x < C::CB * 16) ytmp = prm.y[threadIdx.x];
+#pragma unroll
+    for (int t = 0; t < NTc * K; ++t) gacc[t] = v4f64{0.0, 0.0, 0.0, 0.0};
+    usum = 0.0;
+    for (int ch = 0; ch < nch; ++ch) {
+        __syncthreads();  // everybody has finished reading the previous chunk
+#pragma unroll
+        for (int j = 0; j < C::PER_THREAD; ++j) lds[threadIdx.x + j * BLOCK] = tmp[j];
+        if (threadIdx.x < C::CB * 16) ylds[threadIdx.x] = ytmp;
+        __syncthreads();
+        if (ch + 1 < nch) {
+            const v2f64* nsrc = src + (size_t)(ch + 1) * C::CHV;
+#pragma unroll
+            for (int j = 0; j < C::PER_THREAD; ++j) tmp[j] = nsrc[threadIdx.x + j * BLOCK];
+            if (threadIdx.x < C::CB * 16) ytmp = prm.y[(size_t)(ch + 1) * (C::CB * 16) + threadIdx.x];
+        }
+#pragma unroll
+        for (int bi = 0; bi < C::CB; ++bi) {
+            const int blk = ch * C::CB + bi;
+            if (C::CB > 1 && blk >= prm.nb) break;
+            const v2f64* __restrict__ P1 = lds + bi * C::BLKV + lane;
+            const v2f64* __restrict__ P2 = P1 + (KSc / 2) * 64;
+            // K eta tiles, each 16 observations x 16 chains: every fragment of X read once, used by all classes
+            v4f64 eta[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) eta[k] = v4f64{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int s2 = 0; s2 < KSc / 2; ++s2) {
+                const v2f64 A = P1[s2 * 64];
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    eta[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(A.x, q[k * KSc + 2 * s2], eta[k], 0, 0, 0);
+                    eta[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(A.y, q[k * KSc + 2 * s2 + 1], eta[k], 0, 0, 0);
+                }
+            }
+            // softmax in place: register r of every class = observations {4r + g} of this lane's chain
+            const int64_t obs0 = (int64_t)blk * 16 + g;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const bool ok = obs0 + 4 * r < prm.M;
+                const double yv = ylds[bi * 16 + 4 * r + g];
+                double m = eta[0][r];
+#pragma unroll
+                for (int k = 1; k < K; ++k) m = eta[k][r] > m ? eta[k][r] : m;
+                double eta_y = 0.0, Z = 0.0;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    eta_y = yv == (double)k ? eta[k][r] : eta_y;
+                    const double e = exp(eta[k][r] - m);
+                    eta[k][r] = e;
+                    Z += e;
+                }
+                const double inv = 1.0 / Z;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const double rr = eta[k][r] * inv - (yv == (double)k ? 1.0 : 0.0);
+                    eta[k][r] = ok ? rr : 0.0;
+                }
+                if (want_u) usum += ok ? (m + log(Z)) - eta_y : 0.0;
+            }
+            // class k's g tiles += X_b^T . R_k: K-step r sums over the observations register r holds
+#pragma unroll
+            for (int r2 = 0; r2 < 2; ++r2)
+#pragma unroll
+                for (int t = 0; t < NTc; ++t) {
+                    const v2f64 A = P2[(r2 * NTc + t) * 64];
+#pragma unroll
+                    for (int k = 0; k < K; ++k) {
+                        gacc[k * NTc + t] = __builtin_amdgcn_mfma_f64_16x16x4f64(A.x, eta[k][2 * r2], gacc[k * NTc + t], 0, 0, 0);
+                        gacc[k * NTc + t] = __builtin_amdgcn_mfma_f64_16x16x4f64(A.y, eta[k][2 * r2 + 1], gacc[k * NTc + t], 0, 0, 0);
+                    }
+                }
+        }
+    }
+}
+
+// TWIN: the frame below (ghost waves and ragged tail, momentum first, the kick / drift schedule of the evaluation loop,
+// the five modes, the accept epilogue) restates k_glm of kernels_glm.hip, which must keep compiling to what it compiles
+// to.  A fix to either frame belongs in both.
+template <int NTc, int K>
+__global__ void __launch_bounds__(BLOCK, NTc * K <= 2 ? 2 : 1) k_glm_softmax(SmxPrm prm) {
+    using C = SmxCfg<NTc>;
+    constexpr int NT = NTc * K;
+    constexpr int KS = 4 * NT;
+    constexpr int KSc = C::KSc;
+    constexpr int Dc = 16 * NTc;
+    static_assert(K >= 2 && K <= 8 && NT <= 8, "2 <= K <= 8 classes of Dc = 16, 32 or 64 rows, K * Dc <= 128");
+    __shared__ __attribute__((aligned(16))) v2f64 lds[C::CHV];
+    __shared__ double ylds[C::CB * 16];
+    __shared__ double plds[Dc];  // lam of each row of a class, zero past D
+    for (int i = threadIdx.x; i < Dc; i += BLOCK) plds[i] = prm.prior[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int g = lane >> 4;
+    const int c = lane & 15;
+    const int D = prm.D;
+    const int mode = prm.mode;
+
+    // every wave takes part in the staging barriers: one past the end of the ensemble recomputes the last tile
+    // with its stores masked
+    int64_t n0 = ((int64_t)blockIdx.x * 4 + wave) * CHAINS_PER_WAVE;  // wave-uniform
+    bool ghost = false;
+    if (n0 >= prm.N) {
+        ghost = true;
+        n0 = (prm.N - 1) / CHAINS_PER_WAVE * CHAINS_PER_WAVE;
+    }
+    const int64_t left = prm.N - n0;
+    const bool valid = !ghost && c < left;
+    const int cc = c < left ? c : (int)left - 1;  // ragged tail: compute on a clamped chain
+    const uint32_t ld_in = 8u * (uint32_t)prm.ldn_in, ld_out = 8u * (uint32_t)prm.ldn_out;
+    const uint32_t v0 = 8u * (uint32_t)cc;
+    const uint32_t vin = (uint32_t)g * ld_in + v0, vout = (uint32_t)g * ld_out + v0;
+    const __amdgpu_buffer_rsrc_t qin = rows_of<false>(prm.q_in, n0, K * D, prm.ldn_in, prm.N);
+    const __amdgpu_buffer_rsrc_t pin = rows_of<false>(prm.p_in, n0, K * D, prm.ldn_in, prm.N);
+    const __amdgpu_buffer_rsrc_t qout = rows_of<false>(prm.q_out, n0, K * D, prm.ldn_out, prm.N);
+    const __amdgpu_buffer_rsrc_t pout = rows_of<false>(prm.p_out, n0, K * D, prm.ldn_out, prm.N);
+    const bool have_pout = (prm.p_out != nullptr);
+    const double m = prm.mass ? prm.mass[n0 + cc] : 1.0;
+    const double minv = prm.mass ? 1.0 / m : 1.0;
+    const bool traj = (mode == SMX_HMC || mode == SMX_INTEGRATE);
+    const bool rng = (mode == SMX_HMC) && prm.rng;
+    const uint64_t chain = prm.chain0 + (uint64_t)(n0 + cc);
+
+    double q[KS], vh[KS];
+    v4f64 gacc[NT];
+    // ---- momentum first (vh holds p until the division by the mass below)
+    double u = 0.0;
+    if (rng) {
+        const double pstd = sqrt(m * prm.kT);  // src/ensemble.py:88
+        const bool f64 = (prm.flags & PBBI_DRAW_F64) != 0;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {  // element e of the tile: external row r0 + 4e
+            const int k = t / NTc, tc = t % NTc;
+            const int r0 = k * D + 16 * tc + g;
+            const uint32_t blk = rng_block_of_dim(r0);
+            const int j = (r0 >> 2) & 3;  // slot of element 0; elements past slot 3 are in the next block of r0 % 4
+            double z[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            {
+                double za[4];
+                rng_normal4d(prm.seed, PBBI_STREAM_MOMENTUM, prm.iter, chain, blk, f64, za);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) z[i] = za[i];
+            }
+            // wave-uniform: no lane needs the next block when the class starts on a block boundary (j == 0 everywhere),
+            // nor when the tile's last live element (emax, lane group 0's) stays within slot 3 for the largest j
+            const int off = (k * D) & 15;
+            const int jmax = off + 3 >= 12 ? 3 : (off + 3) >> 2;
+            const int live = D - 16 * tc;  // live rows of this tile (<= 0: all padding)
+            const int emax = live >= 16 ? 3 : (live + 3) / 4 - 1;
+            if (off != 0 && live > 0 && jmax + emax >= 4) {
+                double zb[4];
+                rng_normal4d(prm.seed, PBBI_STREAM_MOMENTUM, prm.iter, chain, blk + 4u, f64, zb);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) z[4 + i] = zb[i];
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const double ze = j == 0 ? z[e] : j == 1 ? z[e + 1] : j == 2 ? z[e + 2] : z[e + 3];
+                vh[4 * t + e] = (16 * tc + 4 * e + g < D) ? ze * pstd : 0.0;
+            }
+        }
+        u = rng_uniform(prm.seed, prm.iter, chain);
+        if (have_pout && !(prm.flags & PBBI_COMPAT_P_FROM_OLDQ) && valid) {
+            // non-compat: a rejected chain reports its drawn momentum; park the draw now
+#pragma unroll
+            for (int s = 0; s < KS; ++s) smx_store<NTc>(pout, vout, ld_out, s, g, D, vh[s]);
+        }
+    } else if (mode != SMX_EVAL) {
+#pragma unroll
+        for (int s = 0; s < KS; ++s) vh[s] = smx_load<NTc>(pin, vin, v0, ld_in, s, g, D);
+        if (mode == SMX_HMC) u = prm.u_in[n0 + cc];
+    } else {
+#pragma unroll
+        for (int s = 0; s < KS; ++s) vh[s] = 0.0;
+    }
+#pragma unroll
+    for (int s = 0; s < KS; ++s) q[s] = smx_load<NTc>(qin, vin, v0, ld_in, s, g, D);
+    double pp_old = 0.0;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) pp_old = fma(vh[s], vh[s], pp_old);
+    if (traj) {
+#pragma unroll
+        for (int s = 0; s < KS; ++s) vh[s] *= minv;  // v = p/m
+    }
+
+    // ---- the trajectory as a list of gradient evaluations, each followed by a kick of ck and a drift of hd:
+    //   Leapfrog        e = 0: h/2, h    e = 1 .. L-1: h, h    e = L: h/2, 0          (L = 0: one evaluation, no update)
+    //   Stormer-Verlet  e = 0: h/2, h    e = 1 .. L:   h, h    e = L+1 (HMC only): 0, 0 -- U at the last position;
+    //                   (q_{n+1} - q_n)/h = vh is the velocity it returns (src/integrator.py:142-163)
+    const bool sv = prm.method == PBBI_STORMER_VERLET;
+    const int L = prm.L;
+    int nev = 1;
+    if (traj) nev = sv ? L + 1 + (mode == SMX_HMC ? 1 : 0) : L + 1;
+    const double h = prm.h;
+    double U_old = 0.0, U_new = 0.0;
+    for (int e = 0; e < nev; ++e) {
+        double ck = 0.0, hd = 0.0;
+        if (traj) {
+            if (sv) {
+                if (e <= L) { ck = e == 0 ? 0.5 * h : h; hd = h; }
+            } else if (L >= 1) {
+                ck = (e == 0 || e == L) ? 0.5 * h : h;
+                hd = e < L ? h : 0.0;
+            }
+        }
+        ck *= minv;
+        const bool want_u = (e == 0 || e == nev - 1) && mode != SMX_INTEGRATE;
+        double usum;
+        smx_grad<NTc, K>(prm, lds, ylds, lane, g, q, gacc, usum, want_u);
+        if (want_u) {
+            double qq = 0.0;
+#pragma unroll
+            for (int s = 0; s < KS; ++s) qq = fma(plds[4 * (s % KSc) + g] * q[s], q[s], qq);
+            U_new = chain_sum(usum) + 0.5 * chain_sum(qq);
+            if (e == 0) U_old = U_new;
+        }
+        if (mode == SMX_EVAL) break;  // the gradient stays in gacc
+        // an evaluation for U alone is followed by no update (a product 0 * inf would turn an overflowed
+        // gradient, whose energy rejects the proposal, into a NaN momentum)
+        if (!(traj && (sv ? e <= L : L >= 1))) continue;
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int s = 4 * t + r;
+                const double gt = fma(plds[4 * (s % KSc) + g], q[s], gacc[t][r]);
+                vh[s] = fma(-gt, ck, vh[s]);
+                q[s] = fma(vh[s], hd, q[s]);
+            }
+    }
+
+    if (mode == SMX_EVAL) {
+        if (prm.grad_out && valid) {
+            const __amdgpu_buffer_rsrc_t gout = rows_of<false>(prm.grad_out, n0, K * D, prm.ldn_out, prm.N);
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int s = 4 * t + r;
+                    smx_store<NTc>(gout, vout, ld_out, s, g, D, fma(plds[4 * (s % KSc) + g], q[s], gacc[t][r]));
+                }
+        }
+        if (prm.U_out && valid && g == 0) prm.U_out[n0 + c] = U_old;
+        return;
+    }
+    if (mode == SMX_ENERGY || mode == SMX_RATIO) {
+        const double H = 0.5 * chain_sum(pp_old) / m + U_old;
+        if (valid && g == 0) {
+            if (mode == SMX_ENERGY) {
+                if (prm.U_out) prm.U_out[n0 + c] = H;
+                if (prm.w_out) prm.w_out[n0 + c] = exp(-H);
+            } else {
+                prm.U_out[n0 + c] = exp(prm.U_out[n0 + c] - H);
+            }
+        }
+        return;
+    }
+    if (mode == SMX_INTEGRATE) {  // in place q, p; optional Integrator.v
+        if (valid) {
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                smx_store<NTc>(qout, vout, ld_out, s, g, D, q[s]);
+                smx_store<NTc>(pout, vout, ld_out, s, g, D, prm.mass ? vh[s] * m : vh[s]);
+            }
+            if (prm.v_out) {
+                const __amdgpu_buffer_rsrc_t vo = rows_of<false>(prm.v_out, n0, K * D, prm.ldn_out, prm.N);
+#pragma unroll
+                for (int s = 0; s < KS; ++s) smx_store<NTc>(vo, vout, ld_out, s, g, D, vh[s]);
+            }
+        }
+        return;
+    }
+
+    // ---- energies, ratio, decision (src/HMC.py:109-115,166-173)
+    double pp_new = 0.0;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+        if (prm.mass) vh[s] *= m;  // p = v*m; vh now holds p
+        pp_new = fma(vh[s], vh[s], pp_new);
+    }
+    const double oldH = 0.5 * chain_sum(pp_old) / m + U_old;
+    const double newH = 0.5 * chain_sum(pp_new) / m + U_new;
+    const double ratio = exp((oldH - newH) * pbbi_accept_beta(prm.flags, prm.kT));
+    const bool reject = metropolis_reject(ratio, u);
+    const bool compat = (prm.flags & PBBI_COMPAT_P_FROM_OLDQ) != 0;
+    bool store_p = have_pout;
+    if (reject) {  // fetch the old point again instead of keeping it live through the trajectory
+#pragma unroll
+        for (int s = 0; s < KS; ++s) q[s] = smx_load<NTc>(qin, vin, v0, ld_in, s, g, D);  // :175
+        if (compat) {  // :176  p <- oldQ
+#pragma unroll
+            for (int s = 0; s < KS; ++s) vh[s] = q[s];
+        } else if (rng) {
+            store_p = false;  // the parked draw stays
+        } else if (have_pout) {
+#pragma unroll
+            for (int s = 0; s < KS; ++s) vh[s] = smx_load<NTc>(pin, vin, v0, ld_in, s, g, D);
+        }
+    }
+    if (valid) {
+#pragma unroll
+        for (int s = 0; s < KS; ++s) smx_store<NTc>(qout, vout, ld_out, s, g, D, q[s]);  // :178
+        if (store_p) {
+#pragma unroll
+            for (int s = 0; s < KS; ++s) smx_store<NTc>(pout, vout, ld_out, s, g, D, vh[s]);  // :179
+        }
+    }
+    if (valid && g == 0) {
+        if (prm.ratio_out) prm.ratio_out[n0 + c] = ratio;
+        if (prm.reject_out) prm.reject_out[n0 + c] = reject ? 1 : 0;
+    }
+}
+
+const char* const SMX_RULE = "softmax GLM: float64, 2 <= K <= 8 classes, each padded to Dc = 16, 32 or 64 rows with "
+                             "K * Dc <= 128 (D <= 16 for K <= 8, D <= 32 for K <= 4, D <= 64 for K = 2)";
+
+int smx_check(const pbbi_potential* pot, int64_t ld) {
+    if (pot->dtype != PBBI_F64 || pot->glm_K < 2 || !pot->d_glm_img || !pot->d_glm_prior)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, SMX_RULE);
+    if ((int64_t)(pot->D + 4) * ld >= ((int64_t)1 << 29))
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED,
+                         "GLM kernels address a lane's rows with 32-bit offsets: rows * leading stride must "
+                         "be < 2^29 elements; shard the ensemble");
+    return PBBI_OK;
+}
+
+SmxPrm smx_prm(const pbbi_potential* pot) {
+    SmxPrm prm{};
+    prm.img = (const double*)pot->d_glm_img;
+    prm.y = (const double*)pot->d_glm_y;
+    prm.prior = (const double*)pot->d_glm_prior;
+    prm.M = pot->glm_M;
+    prm.nb = (int)((pot->glm_M + 15) / 16);
+    prm.D = pot->D / pot->glm_K;
+    prm.kT = 1.0;
+    return prm;
+}
+
+int smx_launch(const pbbi_potential* pot, const SmxPrm& prm, hipStream_t stream) {
+    const dim3 grid((unsigned)((prm.N + CHAINS_PER_WG - 1) / CHAINS_PER_WG)), block(BLOCK);
+    const int NTc = pot->glm_DP / 16, K = pot->glm_K;
+    bool done = false;
+#define SMX_CASE(NTC_, K_)                                                                 \
+    if (NTc == NTC_ && K == K_) {                                                          \
+        hipLaunchKernelGGL((k_glm_softmax<NTC_, K_>), grid, block, 0, stream, prm);        \
+        done = true;                                                                       \
+    }
+    SMX_CASE(1, 2) SMX_CASE(1, 3) SMX_CASE(1, 4) SMX_CASE(1, 5) SMX_CASE(1, 6) SMX_CASE(1, 7) SMX_CASE(1, 8)
+    SMX_CASE(2, 2) SMX_CASE(2, 3) SMX_CASE(2, 4)
+    SMX_CASE(4, 2)
+#undef SMX_CASE
+    if (!done) return pbbi_fail(PBBI_ERR_UNSUPPORTED, SMX_RULE);
+    PBBI_HIP(hipGetLastError());
+    return PBBI_OK;
+}
+
+}  // namespace
+
+// ---- host side ---------------------------------------------------------------------------------------------
+// The padded class size and the tile count of a (D, K) model, and the external row of each of the NT * 16 internal
+// rows (-1 = padding).  Touches no device.
+int glm_softmax_layout(int D, int K, int* Dc_out, int* NT_out, int32_t* row_map) {
+    if (D < 1 || K < 2 || K > 8 || D > 64) return pbbi_fail(PBBI_ERR_UNSUPPORTED, SMX_RULE);
+    const int Dc = glm_padded_dim(D);
+    if (K * Dc > 128) return pbbi_fail(PBBI_ERR_UNSUPPORTED, SMX_RULE);
+    if (Dc_out) *Dc_out = Dc;
+    if (NT_out) *NT_out = K * Dc / 16;
+    if (row_map)
+        for (int k = 0; k < K; ++k)
+            for (int d = 0; d < Dc; ++d) row_map[k * Dc + d] = d < D ? k * D + d : -1;
+    return PBBI_OK;
+}
+
+int glm_softmax_check(int D, int K, int64_t M, const double* X, const double* y, const double* lam) {
+    if (!X || !y) return pbbi_fail(PBBI_ERR_INVALID, "X / y is NULL");
+    if (!lam) return pbbi_fail(PBBI_ERR_INVALID, "prior_precision is NULL");
+    if (M < 1) return pbbi_fail(PBBI_ERR_INVALID, "M must be >= 1");
+    if (D < 1) return pbbi_fail(PBBI_ERR_INVALID, "D must be >= 1");
+    if (K < 2) return pbbi_fail(PBBI_ERR_INVALID, "softmax GLM: at least two classes");
+    for (int64_t i = 0; i < M; ++i)
+        if (!(std::isfinite(y[i]) && y[i] >= 0.0 && y[i] < (double)K && y[i] == std::floor(y[i])))
+            return pbbi_fail(PBBI_ERR_INVALID, "labels must be integers in [0, K) (observation " + std::to_string(i) + ")");
+    for (int64_t i = 0; i < M * D; ++i)
+        if (!std::isfinite(X[i])) return pbbi_fail(PBBI_ERR_INVALID, "X must be finite (row " + std::to_string(i / D) + ")");
+    return glm_check_prior(D, lam, nullptr);
+}
+
+// the caller has run glm_softmax_check and glm_softmax_layout; pot->D = K * D
+int glm_softmax_build(pbbi_potential* pot, int D, int K, int64_t M, const double* X, const double* y, const double* lam) {
+    int Dc = 0;
+    if (int rc = glm_softmax_layout(D, K, &Dc, nullptr, nullptr)) return rc;
+    if (pot->dtype != PBBI_F64) return pbbi_fail(PBBI_ERR_UNSUPPORTED, SMX_RULE);
+    std::vector<double> img((size_t)glm_image_len(D, M));  // the image of an M x D matrix at DP = Dc
+    glm_pack(D, M, X, img.data());
+    const int64_t nbp = glm_image_len(D, M) / ((int64_t)Dc * 32);
+    std::vector<double> yp((size_t)nbp * 16, 0.0);
+    std::memcpy(yp.data(), y, sizeof(double) * (size_t)M);
+    std::vector<double> prior((size_t)Dc, 0.0);
+    std::memcpy(prior.data(), lam, sizeof(double) * (size_t)D);
+    PBBI_HIP(hipMalloc(&pot->d_glm_img, img.size() * sizeof(double)));
+    PBBI_HIP(hipMalloc(&pot->d_glm_y, yp.size() * sizeof(double)));
+    PBBI_HIP(hipMalloc(&pot->d_glm_prior, prior.size() * sizeof(double)));
+    PBBI_HIP(hipMemcpy(pot->d_glm_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
+    PBBI_HIP(hipMemcpy(pot->d_glm_y, yp.data(), yp.size() * sizeof(double), hipMemcpyHostToDevice));
+    PBBI_HIP(hipMemcpy(pot->d_glm_prior, prior.data(), prior.size() * sizeof(double), hipMemcpyHostToDevice));
+    pot->glm_DP = Dc;
+    pot->glm_K = K;
+    pot->glm_M = M;
+    pot->glm_family = PBBI_GLM_SOFTMAX;
+    return PBBI_OK;
+}
+
+int glm_softmax_hmc_iter(const IterArgs& a) {
+    if (int rc = smx_check(a.pot, a.ldn_in > a.ldn_out ? a.ldn_in : a.ldn_out)) return rc;
+    if (pbbi_dyn(a)) return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials: fixed trajectory lengths only");
+    if (a.fuse_S > 1) return pbbi_fail(PBBI_ERR_INVALID, "the GLM kernel takes one iteration per launch (internal)");
+    if (a.N == 0) return PBBI_OK;
+    SmxPrm prm = smx_prm(a.pot);
+    prm.q_in = (const double*)a.q_in;
+    prm.p_in = (const double*)a.p_in;
+    prm.u_in = (const double*)a.u_in;
+    prm.mass = (const double*)a.mass;
+    prm.q_out = (double*)a.q_out;
+    prm.p_out = (double*)a.p_out;
+    prm.ratio_out = (double*)a.ratio_out;
+    prm.reject_out = a.reject_out;
+    prm.N = a.N; prm.ldn_in = a.ldn_in; prm.ldn_out = a.ldn_out;
+    prm.h = a.h; prm.kT = a.kT; prm.L = a.L; prm.flags = a.flags; prm.rng = a.rng;
+    prm.mode = SMX_HMC; prm.method = a.method;
+    prm.seed = a.seed; prm.iter = a.iter; prm.chain0 = a.chain0;
+    return smx_launch(a.pot, prm, a.stream);
+}
+
+int glm_softmax_integrate(const IntegrateArgs& a) {
+    if (int rc = smx_check(a.pot, a.ldn)) return rc;
+    if (a.N == 0) return PBBI_OK;
+    SmxPrm prm = smx_prm(a.pot);
+    prm.q_in = (const double*)a.q;
+    prm.p_in = (const double*)a.p;
+    prm.mass = (const double*)a.mass;
+    prm.q_out = (double*)a.q;
+    prm.p_out = (double*)a.p;
+    prm.v_out = (double*)a.v_out;
+    prm.N = a.N; prm.ldn_in = a.ldn; prm.ldn_out = a.ldn;
+    prm.h = a.h; prm.L = a.L; prm.mode = SMX_INTEGRATE; prm.method = a.method;
+    return smx_launch(a.pot, prm, a.stream);
+}
+
+static int smx_eval_launch(const EvalArgs& a, int mode) {
+    if (int rc = smx_check(a.pot, a.ldn)) return rc;
+    if (a.N == 0) return PBBI_OK;
+    SmxPrm prm = smx_prm(a.pot);
+    prm.q_in = (const double*)a.q;
+    prm.p_in = (const double*)a.p;
+    prm.mass = (const double*)a.mass;
+    prm.U_out = (double*)a.U_out;
+    prm.grad_out = (double*)a.grad_out;
+    prm.w_out = (double*)a.w_out;
+    prm.N = a.N; prm.ldn_in = a.ldn; prm.ldn_out = a.ldn;
+    prm.mode = mode;
+    return smx_launch(a.pot, prm, a.stream);
+}
+int glm_softmax_eval(const EvalArgs& a) { return smx_eval_launch(a, SMX_EVAL); }
+int glm_softmax_energy(const EvalArgs& a) { return smx_eval_launch(a, a.ratio_finish ? SMX_RATIO : SMX_ENERGY); }

@@ -94,6 +94,7 @@ int new_handle(int kind, int D, int dtype, int device, pbbi_potential** out) {
     p->d_glm_img = p->d_glm_y = nullptr;
     p->d_glm_obs = p->d_glm_prior = nullptr;
     p->glm_terms = 0;
+    p->glm_K = 0;
     *out = p;
     return PBBI_OK;
 }
@@ -143,7 +144,7 @@ int plugin_rc(int rc) {
 }
 int route_hmc(const IterArgs& a) {
     const pbbi_potential* pot = a.pot;
-    if (pot->kind == KIND_GLM) return glm_hmc_iter(a);
+    if (pot->kind == KIND_GLM) return pot->glm_K ? glm_softmax_hmc_iter(a) : glm_hmc_iter(a);
     if (pbbi_dyn(a) && (pot->kind == KIND_CUSTOM || (is_big(pot) && !dense_stream_applies(a))))
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, "per-chain trajectory lengths are served by the chain-per-lane "
                                                "kernels (D <= 32) and the dense kernels (fp64, D <= 256) only");
@@ -167,20 +168,20 @@ int route_fused_iterations(const IterArgs& a) {
 }
 int route_integrate(const IntegrateArgs& a) {
     const pbbi_potential* pot = a.pot;
-    if (pot->kind == KIND_GLM) return glm_integrate(a);
+    if (pot->kind == KIND_GLM) return pot->glm_K ? glm_softmax_integrate(a) : glm_integrate(a);
     if (pot->kind == KIND_CUSTOM) return a.N ? plugin_rc(pot->plugin_integrate(&a)) : PBBI_OK;
     if (is_big(pot) && dense_stream_integrate_applies(a)) return dense_stream_integrate(a);
     return is_big(pot) ? big_integrate(a) : is_dense(pot) ? dense_integrate(a) : lane_integrate(a);
 }
 int route_eval(const EvalArgs& a) {
     const pbbi_potential* pot = a.pot;
-    if (pot->kind == KIND_GLM) return glm_eval(a);
+    if (pot->kind == KIND_GLM) return pot->glm_K ? glm_softmax_eval(a) : glm_eval(a);
     if (pot->kind == KIND_CUSTOM) return a.N ? plugin_rc(pot->plugin_eval(&a, 0)) : PBBI_OK;
     return is_big(pot) ? big_eval(a) : is_dense(pot) ? dense_eval(a) : lane_eval(a);
 }
 int route_energy(const EvalArgs& a) {
     const pbbi_potential* pot = a.pot;
-    if (pot->kind == KIND_GLM) return glm_energy(a);
+    if (pot->kind == KIND_GLM) return pot->glm_K ? glm_softmax_energy(a) : glm_energy(a);
     if (pot->kind == KIND_CUSTOM)
         return a.N ? plugin_rc(pot->plugin_eval(&a, a.ratio_finish ? 2 : 1)) : PBBI_OK;
     return is_big(pot) ? big_energy(a) : is_dense(pot) ? dense_energy(a) : lane_energy(a);
@@ -787,6 +788,21 @@ int pbbi_potential_create_glm_ex(int D, int64_t M, const double* X, const double
     return finish_or_destroy(glm_build_ex(*out, M, X, y, family, weights, offset, trials, prior_precision, prior_mean), out);
 }
 
+int pbbi_potential_create_glm_softmax(int D, int K, int64_t M, const double* X, const double* y,
+                                      const double* prior_precision, int dtype, int device, pbbi_potential** out) {
+    if (out) *out = nullptr;
+    if (int rc = glm_softmax_check(D, K, M, X, y, prior_precision)) return rc;
+    if (dtype != PBBI_F64) return pbbi_fail(PBBI_ERR_UNSUPPORTED, "softmax GLM potentials are float64 only");
+    if (int rc = glm_softmax_layout(D, K, nullptr, nullptr, nullptr)) return rc;
+    if (int rc = new_handle(KIND_GLM, K * D, dtype, device, out)) return rc;
+    DeviceGuard guard(device);
+    return finish_or_destroy(glm_softmax_build(*out, D, K, M, X, y, prior_precision), out);
+}
+
+int pbbi_glm_softmax_layout(int D, int K, int* Dc_out, int* NT_out, int32_t* row_map) {
+    return glm_softmax_layout(D, K, Dc_out, NT_out, row_map);
+}
+
 int pbbi_glm_pack_observations(int64_t M, int family, const double* y, const double* weights, const double* offset,
                                const double* trials, double* out, int64_t out_len, int64_t* len_out) {
     if (M < 1) return pbbi_fail(PBBI_ERR_INVALID, "M must be >= 1");
@@ -1162,7 +1178,13 @@ int pbbi_describe_run(const pbbi_potential* pot, int method, int64_t N, int64_t 
     a.carry = 2; a.carry_g = (void*)(uintptr_t)16; a.carry_sel = (uint8_t*)(uintptr_t)16;
     std::string d;
     int fuse = 1;
-    if (pot->kind == KIND_GLM) {
+    if (pot->kind == KIND_GLM && pot->glm_K) {
+        d = "k_glm_softmax: K = " + std::to_string(pot->glm_K) + " class softmax regression, per block of 16 observations K eta "
+            "tiles from the same fp64 MFMA A fragments (eta_k = X W_k), the softmax in lane, g_k = X^T r_k; 16 chains per "
+            "wave, X staged through LDS, " + std::to_string(pot->D / pot->glm_K) + " coefficients per class padded to " +
+            std::to_string(pot->glm_DP) + " rows (" + std::to_string(pot->glm_K * pot->glm_DP / 16) + " tiles)";
+        fuse = 1;
+    } else if (pot->kind == KIND_GLM) {
         d = "k_glm: GLM likelihood as two fp64 MFMA products per gradient (eta = X W, g = X^T r), 16 chains per wave, X "
             "staged through LDS in blocks of 16 observations (rows padded to " + std::to_string(pot->glm_DP) + ")";
         if (pot->d_glm_obs) {

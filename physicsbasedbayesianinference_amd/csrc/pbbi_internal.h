@@ -55,6 +55,9 @@ struct pbbi_potential {
     void* d_glm_obs;   // c = a n | d = a y | o, each zero padded to the blocks of the image (glm_pack_obs)
     void* d_glm_prior; // lam (glm_DP) | mu (glm_DP), zeros past D
     int glm_terms;     // GLM_TERM_*: what pbbi_describe_run names
+    // softmax regression (pbbi_potential_create_glm_softmax), kernels_glm_softmax.hip.  (Appended.)  D = glm_K * (coefficients
+    // per class), glm_DP = the padded class size Dc, d_glm_y the labels, d_glm_prior lam (Dc values, zeros past D)
+    int glm_K;         // classes (0 = not a softmax handle)
 };
 
 // ---- error plumbing ---------------------------------------------------------
@@ -276,3 +279,11 @@ int glm_hmc_iter(const IterArgs& a);
 int glm_integrate(const IntegrateArgs& a);
 int glm_eval(const EvalArgs& a);
 int glm_energy(const EvalArgs& a);
+// K-class softmax regression on the same frame (fp64, K * Dc <= 128), kernels_glm_softmax.hip
+int glm_softmax_layout(int D, int K, int* Dc_out, int* NT_out, int32_t* row_map);  // host only
+int glm_softmax_check(int D, int K, int64_t M, const double* X, const double* y, const double* lam);
+int glm_softmax_build(pbbi_potential* pot, int D, int K, int64_t M, const double* X, const double* y, const double* lam);
+int glm_softmax_hmc_iter(const IterArgs& a);
+int glm_softmax_integrate(const IntegrateArgs& a);
+int glm_softmax_eval(const EvalArgs& a);
+int glm_softmax_energy(const EvalArgs& a);

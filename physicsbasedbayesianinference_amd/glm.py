@@ -18,6 +18,9 @@ model above keeps its kernels and its arithmetic.
 For an ensemble the model is two matrix products shared by all chains (eta = X W, g = X^T (b'(eta) - y)
 + prior_precision W with W the (D, N) state), which csrc/kernels_glm.hip runs on the MFMA units with X
 staged through LDS -- the data set is read once per 64 chains, not once per chain.  float64, D <= 128.
+
+`SoftmaxGLM` is the categorical family on the same frame (csrc/kernels_glm_softmax.hip): K-class softmax regression,
+every class with its own coefficient vector, the chain's state the K vectors class-major.
 """
 import ctypes as C
 
@@ -26,7 +29,7 @@ import numpy as np
 from . import _lib
 from .potential import Potential, _dptr
 
-__all__ = ["GLM", "FAMILIES", "pack_design", "pack_observations", "padded_dim"]
+__all__ = ["GLM", "SoftmaxGLM", "FAMILIES", "pack_design", "pack_observations", "padded_dim", "softmax_layout"]
 
 FAMILIES = {"logistic": _lib.GLM_LOGISTIC, "poisson": _lib.GLM_POISSON}
 MAX_DIM = 128
@@ -171,3 +174,86 @@ class GLM(Potential):
             lam_d = np.full(D, lam) if isinstance(lam, float) else lam
             _lib.call("pbbi_potential_create_glm_ex", D, M, _dptr(X), _dptr(y), FAMILIES[family], _dptr(a), _dptr(o),
                       _dptr(n), _dptr(lam_d), _dptr(mu), self._dt, self.device, C.byref(self._handle))
+
+
+def softmax_layout(D, K):
+    """(Dc, NT, row_map) of a K-class model with D coefficients per class, from libpbbi.so (host only, no GPU):
+    the padded class size, the number of 16-row tiles of a chain's state in the kernel, and for each of the NT * 16
+    internal rows the row of the (K * D, N) state it holds (-1: padding, loads 0 and is never stored).  Class k owns
+    internal rows k * Dc .. k * Dc + Dc - 1.  Raises ValueError outside the supported shapes."""
+    D, K = int(D), int(K)
+    Dc, NT = C.c_int(), C.c_int()
+    try:
+        _lib.call("pbbi_glm_softmax_layout", D, K, C.byref(Dc), C.byref(NT), None)
+        row_map = np.empty(NT.value * 16, dtype=np.int32)
+        _lib.call("pbbi_glm_softmax_layout", D, K, C.byref(Dc), C.byref(NT), row_map.ctypes.data_as(C.POINTER(C.c_int32)))
+    except RuntimeError as e:
+        raise ValueError(str(e)) from None
+    return Dc.value, NT.value, row_map
+
+
+class SoftmaxGLM(Potential):
+    """-log posterior of the coefficients of K-class (multinomial logistic / softmax) regression:
+
+        U(W) = sum_i [ logsumexp_k(x_i . W_k) - x_i . W_{y_i} ] + 0.5 sum_k sum_d lam_d W_kd^2,   y_i in {0 .. K-1}
+
+        pot = SoftmaxGLM(X, y, classes=None, prior_precision=1.0)      # classes default: int(max(y)) + 1
+        hmc = HMC(Ensemble(pot.numDimensions, N), 1.0, 0.1, None, potential=pot, rng="philox")
+        W = pot.coefficients(samples)                                  # (K * D, ...) -> (K, D, ...), a view
+
+    All K classes carry coefficients; the Gaussian prior identifies them.  The sampler sees one vector of
+    `classes * D` numbers per chain, class-major: w[k * D + d].  `prior_precision` is a scalar or a (D,) vector of
+    finite values >= 0, shared by the classes.  A precision of ZERO on a column leaves the posterior improper along
+    the direction that shifts that column's coefficient in every class together: the softmax does not see that
+    direction, so only the prior can hold it.
+
+    Supported shapes: 2 <= classes <= 8, each class padded to Dc = 16, 32 or 64 rows, classes * Dc <= 128 (D <= 16
+    for classes <= 8, D <= 32 for classes <= 4, D <= 64 for classes = 2); float64 only.  Not served: observation
+    weights, offsets, multinomial counts, a prior mean, a pinned reference class, classes > 8, per-chain trajectory
+    lengths and GIST (they raise as for `GLM`); nothing (U, gradient) is carried between iterations.
+
+    Works wherever `GLM` does (HMC in both rng modes, Leapfrog / StormerVerlet, TemperedSMC, TemperingLadder,
+    sampleStats).  Arguments are checked on the host before anything touches the GPU."""
+
+    kind = "glm"
+
+    def __init__(self, X, y, classes=None, prior_precision=1.0, dtype="float64", device=None):
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError("X must be 2-D: (M, D) with at least one row and one column")
+        M, D = X.shape
+        y = np.asarray(y, dtype=np.float64)
+        if y.ndim != 1 or y.size != M:
+            raise ValueError("X has %d rows, y must be 1-D with as many entries (shape %s)" % (M, y.shape))
+        if not np.all(np.isfinite(X)) or not np.all(np.isfinite(y)):
+            raise ValueError("X and y must be finite")
+        if not (np.all(y >= 0) and np.all(y == np.floor(y))):
+            raise ValueError("labels must be integers >= 0")
+        K = int(y.max()) + 1 if classes is None else int(classes)
+        if classes is not None and K != classes:
+            raise ValueError("classes must be an integer")
+        if K < 2:
+            raise ValueError("softmax regression needs classes >= 2 (classes = %d)" % K)
+        if not np.all(y < K):
+            raise ValueError("labels must be < classes = %d" % K)
+        lam = np.asarray(prior_precision, dtype=np.float64)
+        if lam.ndim == 0 and not np.isfinite(lam):
+            raise ValueError("prior_precision must be finite and >= 0")
+        lam = np.full(D, float(lam)) if lam.ndim == 0 else _vector(lam, D, "prior_precision", "D")
+        if not np.all(lam >= 0):
+            raise ValueError("every prior_precision must be >= 0")
+        softmax_layout(D, K)   # the shape rule, stated once: in libpbbi.so (host only); raises ValueError
+        if np.dtype(dtype) != np.dtype("float64"):
+            raise ValueError("GLM potentials are float64 only")
+        X, y, lam = np.ascontiguousarray(X), np.ascontiguousarray(y), np.ascontiguousarray(lam)
+        super().__init__(K * D, dtype, device)
+        self.X, self.y, self.classes, self.prior_precision = X, y, K, lam
+        self.family = "softmax"
+        _lib.call("pbbi_potential_create_glm_softmax", D, K, M, _dptr(X), _dptr(y), _dptr(lam), self._dt, self.device,
+                  C.byref(self._handle))
+
+    def coefficients(self, samples):
+        """(K * D, ...) -> (K, D, ...): the leading axis of a state, sample or gradient array split by class (a view
+        wherever the array allows one)."""
+        D = self.numDimensions // self.classes
+        return samples.reshape((self.classes, D) + tuple(samples.shape[1:]))

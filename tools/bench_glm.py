@@ -11,8 +11,17 @@ the RICH instantiations of k_glm) against the plain model on the same X, alterna
 --custom also the full model as a CustomPotential (what its users had before).  That record goes to
 profiles/glm_model_bench.json under the key given by --label.
 
+--model softmax times SoftmaxGLM (csrc/kernels_glm_softmax.hip) against the same model as a CustomPotential, alternating
+in one process, at (M = 256, D = 5, K = 3, N = 65 536), (M = 256, D = 16, K = 8, N = 65 536) and (M = 16 384, D = 16,
+K = 8, N = 16 384), and writes profiles/glm_softmax_bench.json (executed 4 M K Dc flop per chain-gradient).  The plugin
+at K D = 128 is two orders of magnitude slower, so each side has its own window length: SOFTMAX_SHAPES gives per shape
+the iterations per pbbi_hmc_run call (the slabs of the sample buffer), the iterations per timed window of each side
+(about a second of the softmax path), the repeats and the warm-up; --K / --repeats / --warmup override them.  All
+figures are host-clock rates over whole windows of pbbi_hmc_run calls, not kernel times.
+
 usage: tools/bench_glm.py [--shape small|large|all] [--K 32] [--repeats 5] [--glm-only] [--out FILE]
        tools/bench_glm.py --model rich [--custom] [--label NAME] [--shape ...]
+       tools/bench_glm.py --model softmax [--shape k3|k8|k8large|all]
 """
 import argparse
 import json
@@ -122,9 +131,119 @@ def bench_rich(name, M, D, N, h, L, K, repeats, warm, custom):
     return out
 
 
+# K-class softmax regression as user source: prm = [M, K, X, y, lam(D)]; the state is the K coefficient vectors class-major
+SOFTMAX_SOURCE = """
+template <class Q>
+PBBI_FN T potential(const Q& q, int DT, const T* prm) {
+    const int M = (int)prm[0], K = (int)prm[1];
+    const int D = DT / K;
+    const T* X = prm + 2;
+    const T* y = X + (long)M * D;
+    const T* lam = y + M;
+    T s = 0;
+    for (int i = 0; i < M; ++i) {
+        T z[16]; T m = 0;
+        for (int k = 0; k < K; ++k) {
+            T a = 0;
+            for (int j = 0; j < D; ++j) a += X[i * D + j] * q[k * D + j];
+            z[k] = a; if (k == 0 || a > m) m = a;
+        }
+        T Z = 0;
+        for (int k = 0; k < K; ++k) Z += exp(z[k] - m);
+        s += (m + log(Z)) - z[(int)y[i]];
+    }
+    T r = 0;
+    for (int k = 0; k < K; ++k) for (int j = 0; j < D; ++j) r += lam[j] * q[k * D + j] * q[k * D + j];
+    return s + T(0.5) * r;
+}
+template <class Q, class G>
+PBBI_FN void gradient(const Q& q, G& g, int DT, const T* prm) {
+    const int M = (int)prm[0], K = (int)prm[1];
+    const int D = DT / K;
+    const T* X = prm + 2;
+    const T* y = X + (long)M * D;
+    const T* lam = y + M;
+    for (int k = 0; k < K; ++k) for (int j = 0; j < D; ++j) g[k * D + j] = lam[j] * q[k * D + j];
+    for (int i = 0; i < M; ++i) {
+        T z[16]; T m = 0;
+        for (int k = 0; k < K; ++k) {
+            T a = 0;
+            for (int j = 0; j < D; ++j) a += X[i * D + j] * q[k * D + j];
+            z[k] = a; if (k == 0 || a > m) m = a;
+        }
+        T Z = 0;
+        for (int k = 0; k < K; ++k) { z[k] = exp(z[k] - m); Z += z[k]; }
+        for (int k = 0; k < K; ++k) {
+            const T w = z[k] / Z - (k == (int)y[i] ? T(1) : T(0));
+            for (int j = 0; j < D; ++j) g[k * D + j] += w * X[i * D + j];
+        }
+    }
+}
+"""
+# per_call: iterations per pbbi_hmc_run call; window: iterations per timed window of each side; warm: unrecorded iterations
+SOFTMAX_SHAPES = {
+    "k3": dict(M=256, D=5, classes=3, N=65536, h=0.2, per_call=32, window=dict(softmax=640, plugin=64), repeats=5, warm=4),
+    "k8": dict(M=256, D=16, classes=8, N=65536, h=0.2, per_call=8, window=dict(softmax=256, plugin=8), repeats=5, warm=4),
+    "k8large": dict(M=16384, D=16, classes=8, N=16384, h=0.02, per_call=2, window=dict(softmax=20, plugin=2), repeats=3,
+                    warm=2),
+}
+
+
+def softmax_problem(M, D, K, seed=0):
+    rs = np.random.RandomState(seed)
+    X = rs.standard_normal((M, D)) / np.sqrt(D)
+    X[:, 0] = 1.0
+    W = rs.standard_normal((K, D))
+    eta = X @ W.T
+    g = -np.log(-np.log(rs.uniform(size=eta.shape)))     # Gumbel-max: y ~ softmax(eta)
+    y = np.argmax(eta + g, axis=1).astype(np.float64)
+    return X, y, W.ravel(), rs
+
+
+def bench_softmax(name, M, D, classes, N, h, L, per_call, window, repeats, warm):
+    """SoftmaxGLM and the same model through CustomPotential alternating in one process.  A window is window[side]
+    iterations in pbbi_hmc_run calls of per_call (Runner.go never asks for more slabs than its buffers hold)."""
+    from physicsbasedbayesianinference_amd.custom import CustomPotential
+    X, y, w, rs = softmax_problem(M, D, classes)
+    DT = classes * D
+    q0 = np.ascontiguousarray(w[:, None] + 0.1 * rs.standard_normal((DT, N)))
+    prm = np.concatenate([[float(M), float(classes)], X.ravel(), y, np.ones(D)])
+    runners = {"softmax": Runner(P.SoftmaxGLM(X, y, classes=classes), DT, N, q0, h, L, per_call, window["softmax"]),
+               "plugin": Runner(CustomPotential(DT, SOFTMAX_SOURCE, prm), DT, N, q0, h, L, per_call, window["plugin"])}
+    for r in runners.values():
+        r.go(warm)
+    torch.cuda.synchronize()
+    series = {k: [] for k in runners}
+    for i in range(repeats):
+        for k, r in runners.items():   # alternating
+            series[k].append(r.timed())
+            print(f"# {name} repeat {i} {k}: {series[k][-1]:.4f} s", flush=True)
+    Dc, NT, _ = glm.softmax_layout(D, classes)
+    grads = L + 1
+    out = dict(shape=name, M=M, D=D, classes=classes, Dc=Dc, NT=NT, chains=N, L=L, h=h, iterations_per_call=per_call,
+               iterations_per_window=dict(window), repeats=repeats, warmup_iterations=warm,
+               timing="host clock over whole windows of pbbi_hmc_run calls (synchronised before and after)",
+               accept_rate={k: 1.0 - float(r.rej.float().mean().item()) for k, r in runners.items()})
+    per_it = {}
+    for k, ts in series.items():
+        out[k + "_seconds"] = ts
+        out[k + "_step_chain_per_s"] = [window[k] * L * N / t for t in ts]
+        per_it[k] = np.array(ts) / window[k]          # seconds per iteration
+    flop_it = 4.0 * M * classes * Dc * grads * N
+    out["softmax_executed_tflops"] = [flop_it / t / 1e12 for t in per_it["softmax"]]
+    out["softmax_share_of_fp64_mfma_peak_executed"] = float(flop_it / np.median(per_it["softmax"]) / PEAK_F64_MFMA)
+    out["ratio_median"] = float(np.median(per_it["plugin"]) / np.median(per_it["softmax"]))
+    out["ratio_worst_case"] = float(per_it["plugin"].min() / per_it["softmax"].max())
+    out["softmax_faster_by_the_medians"] = bool(np.median(per_it["softmax"]) < np.median(per_it["plugin"]))
+    return out
+
+
 class Runner:
-    def __init__(self, pot, D, N, q0, h, L, K):
+    def __init__(self, pot, D, N, q0, h, L, K, window=None):
+        # K: slabs of the sample / reject buffers = the most iterations one pbbi_hmc_run call may record;
+        # window: iterations per timed window (default K: one call)
         self.pot, self.D, self.N, self.h, self.L, self.K = pot, D, N, h, L, K
+        self.window = K if window is None else window
         self.q0 = torch.from_numpy(q0).to("cuda")
         self.q = self.q0.clone()
         self.samples = torch.empty((K, D, N), dtype=torch.float64, device="cuda")
@@ -132,16 +251,20 @@ class Runner:
         self.it = 0
 
     def go(self, S):
+        """S iterations, in calls of at most K: iteration i of a call is written to slab i of the K-slab buffers."""
         st = torch.cuda.current_stream().cuda_stream
-        _lib.call("pbbi_hmc_run", self.pot.handle, _lib.LEAPFROG, self.q.data_ptr(), None, self.samples.data_ptr(),
-                  None, self.rej.data_ptr(), None, self.N, self.N, self.h, self.L, S, _lib.COMPAT_P_FROM_OLDQ, 7,
-                  self.it, 0, 1.0, st)
-        self.it += S
+        while S > 0:
+            n = min(S, self.K)
+            _lib.call("pbbi_hmc_run", self.pot.handle, _lib.LEAPFROG, self.q.data_ptr(), None, self.samples.data_ptr(),
+                      None, self.rej.data_ptr(), None, self.N, self.N, self.h, self.L, n, _lib.COMPAT_P_FROM_OLDQ, 7,
+                      self.it, 0, 1.0, st)
+            self.it += n
+            S -= n
 
     def timed(self):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        self.go(self.K)
+        self.go(self.window)
         torch.cuda.synchronize()
         return time.perf_counter() - t0
 
@@ -183,16 +306,42 @@ def bench_shape(name, M, D, N, h, L, K, repeats, warm, glm_only):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", default="all")
-    ap.add_argument("--K", type=int, default=32)
+    ap.add_argument("--K", type=int, default=None, help="iterations per window (default 32; --model softmax: per shape)")
     ap.add_argument("--L", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--repeats", type=int, default=None, help="default 5 (--model softmax: per shape)")
+    ap.add_argument("--warmup", type=int, default=None, help="default 4 (--model softmax: per shape)")
     ap.add_argument("--glm-only", action="store_true")
-    ap.add_argument("--model", default="plain", choices=["plain", "rich"])
+    ap.add_argument("--model", default="plain", choices=["plain", "rich", "softmax"])
     ap.add_argument("--custom", action="store_true", help="--model rich: also the full model as a CustomPotential")
     ap.add_argument("--label", default="rich_vs_plain", help="--model rich: key of the record in the output file")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.model == "softmax":
+        a.out = a.out or os.path.join(ROOT, "profiles", "glm_softmax_bench.json")
+        names = list(SOFTMAX_SHAPES) if a.shape == "all" else [a.shape]
+        results = []
+        if os.path.exists(a.out) and a.shape != "all":   # one shape per call: keep the others' records
+            with open(a.out) as f:
+                results = [r for r in json.load(f)["results"] if r["shape"] not in names]
+        for n in names:
+            cfg = dict(SOFTMAX_SHAPES[n])
+            if a.K is not None:        # one window length for both sides, one call per window
+                cfg["per_call"], cfg["window"] = a.K, dict(softmax=a.K, plugin=a.K)
+            if a.repeats is not None:
+                cfg["repeats"] = a.repeats
+            if a.warmup is not None:
+                cfg["warm"] = a.warmup
+            res = bench_softmax(n, L=a.L, **cfg)
+            print(json.dumps(res))
+            results.append(res)
+            with open(a.out, "w") as f:
+                json.dump(dict(device=_lib.device_info(0)["name"], peak_fp64_mfma_flops=PEAK_F64_MFMA,
+                               results=sorted(results, key=lambda r: r["shape"])), f, indent=1)
+                f.write("\n")
+        sys.exit(0)
+    a.K = 32 if a.K is None else a.K
+    a.repeats = 5 if a.repeats is None else a.repeats
+    a.warmup = 4 if a.warmup is None else a.warmup
     names = list(SHAPES) if a.shape == "all" else [a.shape]
     if a.model == "rich":
         a.out = a.out or os.path.join(ROOT, "profiles", "glm_model_bench.json")
