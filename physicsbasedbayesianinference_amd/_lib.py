@@ -15,6 +15,7 @@ F64, F32 = 0, 1
 LEAPFROG, STORMER_VERLET = 0, 1
 GLM_LOGISTIC, GLM_POISSON = 0, 1
 GLM_SOFTMAX = 2         # pbbi_potential_create_glm_softmax only
+GLM_GAUSSIAN, GLM_NEGBINOMIAL = 3, 4   # pbbi_potential_create_glm_dispersion only
 ERR_INVALID, ERR_UNSUPPORTED, ERR_HIP = -1, -2, -3
 COMPAT_P_FROM_OLDQ = 1
 KDK_FMA = 2
@@ -60,6 +61,8 @@ PROTOTYPES = {
     "pbbi_glm_pack_observations": [_i64, _i, _dp, _dp, _dp, _dp, _dp, _i64, C.POINTER(C.c_int64)],
     "pbbi_potential_create_glm_softmax": [_i, _i, _i64, _dp, _dp, _dp, _i, _i, _pp],
     "pbbi_glm_softmax_layout": [_i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int32)],
+    "pbbi_potential_create_glm_dispersion": [_i, _i64, _dp, _dp, _i, _dp, _dp, _dp, _dp, _i, _d, _i, _i, _pp],
+    "pbbi_glm_pack_observations_dispersion": [_i64, _i, _dp, _dp, _dp, _dp, _i64, C.POINTER(C.c_int64)],
     "pbbi_potential_destroy": [_vp],
     "pbbi_potential_dim": [_vp],
     "pbbi_potential_dtype": [_vp],

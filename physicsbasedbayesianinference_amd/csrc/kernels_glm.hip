@@ -39,8 +39,21 @@
 // LDS for the whole launch (2 DP doubles, loaded once): KS more values per lane in registers would push the DP =
 // 128 kernels into scratch, and they are read KS times per gradient next to M DP / 8 MFMAs.  The plain model's
 // instantiations (RICH = false) hold none of this: their code is what it was before the full model existed.
+//
+// The dispersion families (FAM = PBBI_GLM_GAUSSIAN, PBBI_GLM_NEGBINOMIAL of k_glm<NT, FAM, true>; handles of
+// pbbi_potential_create_glm_dispersion) add a parameter that is no coefficient of X: theta, the log-dispersion, which
+// enters every observation's link and whose gradient is a sum over observations per chain (include/pbbi.h has the model).
+// Sampled, theta is row D of the state (D = the coefficient count): the image is that of [X | 0], so eta does not see the
+// row, while the momentum draw, kick, drift, stores and the {lam, mu} prior in plds treat it like any other.  Once per
+// gradient evaluation the lane that owns row D (s = D >> 2, g = D & 3) contributes its q[s] to a chain_sum, the other
+// three lane groups contribute 0 (adding zeros is exact), and every lane of the chain has theta; the per-chain
+// quantities (tau; phi, psi(phi), lgamma(phi)) are formed there, once.  Each lane accumulates dU_i/dtheta of its
+// observations next to usum, and chain_sum of that goes into the gradient accumulator at (s, g) before the kick and the
+// evaluation's store.  Held, theta comes from the kernel arguments (a wave-uniform switch, no further instantiations)
+// and the state is w alone.  The streams are c = a, d = y (raw), o; a row with c = 0 is selected out.
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "kernels_dense_dev.h"
 #include "pbbi_chain.h"
@@ -75,10 +88,16 @@ struct GlmPrmRich : GlmPrm {
     const double* prior;  // lam (DP) | mu (DP), zero padded past D
     int64_t obs_stride;
 };
-template <bool RICH>
+// the dispersion families' kernel arguments (the full model's kernels keep theirs as they are)
+struct GlmPrmDisp : GlmPrmRich {
+    double theta;  // the held log-dispersion (trow < 0)
+    int trow;      // the state row of theta when it is sampled, -1 when it is held
+};
+constexpr bool glm_disp(int fam) { return fam == PBBI_GLM_GAUSSIAN || fam == PBBI_GLM_NEGBINOMIAL; }
+template <int FAM, bool RICH>
 struct GlmArgs { using type = GlmPrm; };
-template <>
-struct GlmArgs<true> { using type = GlmPrmRich; };
+template <int FAM>
+struct GlmArgs<FAM, true> { using type = std::conditional_t<glm_disp(FAM), GlmPrmDisp, GlmPrmRich>; };
 enum { GLM_HMC = 0, GLM_INTEGRATE = 1, GLM_EVAL = 2, GLM_ENERGY = 3, GLM_RATIO = 4 };
 
 template <int NT>
@@ -126,15 +145,91 @@ __device__ __forceinline__ void glm_link_rich(double eta, double cv, double dv, 
     }
 }
 
+// psi and log Gamma for x > 0: the recurrences psi(x) = psi(x + 1) - 1/x and lgamma(x) = lgamma(x + 1) - log x, two steps
+// at a time (one division per pair, at most three pairs), up to an argument >= 6, then the asymptotic series: psi
+// through x^-14 (the first term left out is 3617 / (8160 x^16): 1.6e-13 at 6), Stirling's through x^-13 (3617 / (122400
+// x^15): 6e-14 at 6).  The library's lgamma, inlined once per accumulator register, costs these kernels their registers.
+__device__ __forceinline__ double glm_psi(double x) {
+    double acc = 0.0;
+    while (x < 6.0) {
+        acc -= (2.0 * x + 1.0) / (x * (x + 1.0));  // 1/x + 1/(x + 1)
+        x += 2.0;
+    }
+    const double r = 1.0 / x, r2 = r * r;
+    const double tail = r2 * (1.0 / 12 - r2 * (1.0 / 120 - r2 * (1.0 / 252 - r2 * (1.0 / 240 - r2 * (1.0 / 132 -
+                        r2 * (691.0 / 32760 - r2 * (1.0 / 12)))))));
+    return acc + ((log(x) - 0.5 * r) - tail);
+}
+__device__ __forceinline__ double glm_lgamma(double x) {
+    double prod = 1.0;
+    while (x < 6.0) {
+        prod *= x * (x + 1.0);
+        x += 2.0;
+    }
+    const double r = 1.0 / x, r2 = r * r;
+    const double tail = r * (1.0 / 12 - r2 * (1.0 / 360 - r2 * (1.0 / 1260 - r2 * (1.0 / 1680 - r2 * (1.0 / 1188 -
+                        r2 * (691.0 / 360360 - r2 * (1.0 / 156)))))));
+    return ((((x - 0.5) * log(x) - x) + 0.91893853320467274178) + tail) - log(prod);
+}
+
+// what a dispersion family forms once per chain and gradient evaluation
+//   gaussian:     a = tau = exp(-2 theta)
+//   negbinomial:  a = phi = exp(theta), b = psi(phi), c = lgamma(phi) (an evaluation that wants U only)
+struct GlmDispChain { double theta, a, b, c; };
+
+template <int FAM>
+__device__ __forceinline__ GlmDispChain glm_disp_chain(double theta, bool want_u) {
+    GlmDispChain k{theta, 0.0, 0.0, 0.0};
+    if constexpr (FAM == PBBI_GLM_GAUSSIAN) {
+        k.a = exp(-2.0 * theta);
+    } else {
+        k.a = exp(theta);
+        k.b = glm_psi(k.a);
+        if (want_u) k.c = glm_lgamma(k.a);
+    }
+    return k;
+}
+
+// the dispersion families' U_i, dU_i/deta and dU_i/dtheta (cv = a_i, yv = y_i)
+template <int FAM>
+__device__ __forceinline__ void glm_link_disp(double eta, double cv, double yv, const GlmDispChain& k, bool want_u,
+                                              double& resid, double& uterm, double& tterm) {
+    if constexpr (FAM == PBBI_GLM_GAUSSIAN) {
+        const double r = yv - eta;
+        const double tr = k.a * r;
+        const double trr = tr * r;  // tau (y - eta)^2
+        resid = -(cv * tr);
+        tterm = cv * (1.0 - trr);
+        uterm = cv * (0.5 * trr + k.theta);
+    } else {
+        // z = eta - theta: s = sigmoid(z), sp = softplus(z); logaddexp(eta, theta) = theta + sp, so
+        // -phi theta - y eta + (y + phi) logaddexp = (y + phi) sp - y z
+        const double z = eta - k.theta;
+        const double e = exp(-fabs(z));
+        const double ope = 1.0 + e;  // in [1, 2]: log(ope) is log1p(e) to 1.2e-16 ABSOLUTE, which is what sp needs, and
+        const double inv = 1.0 / ope;  // keeps these kernels to one logarithm's constants
+        const double s = z >= 0.0 ? inv : e * inv;
+        const double s1 = z >= 0.0 ? e * inv : inv;  // 1 - s
+        const double sp = (z > 0.0 ? z : 0.0) + log(ope);
+        const double yp = yv + k.a;
+        resid = cv * (yp * s - yv);
+        tterm = cv * (k.a * (((k.b - glm_psi(yp)) + sp) - s) + yv * s1);
+        uterm = 0.0;
+        if (want_u) uterm = cv * (((k.c - glm_lgamma(yp)) + yp * sp) - yv * z);
+    }
+}
+
 // gacc[t][r] (row 16t + 4r + g) = sum_i X[i][row] (b'(eta_i) - y_i) for the wave's 16 chains, usum = this lane's
 // share of sum_i b(eta_i) - y_i eta_i (observations {4r + g} of every block; chain_sum completes it).
 // Every wave of the workgroup takes part in the staging: one chunk of CB blocks is in LDS while the next waits
 // in registers (fetched before the MFMAs of the current one, written after the barrier that ends its reads).
 // RICH: ylds holds the chunk's c | d | o (OBS values each); thread j < 3 OBS stages value j % OBS of stream j / OBS.
+// Dispersion families: dk = the chain's theta-derived values, tsum = this lane's share of sum_i dU_i/dtheta.
 template <int NT, int FAM, bool RICH>
-__device__ __forceinline__ void glm_grad(const typename GlmArgs<RICH>::type& prm, v2f64* __restrict__ lds,
+__device__ __forceinline__ void glm_grad(const typename GlmArgs<FAM, RICH>::type& prm, v2f64* __restrict__ lds,
                                          double* __restrict__ ylds, int lane, int g, const double (&q)[4 * NT], v4f64 (&gacc)[NT],
-                                         double& usum, bool want_u) {
+                                         double& usum, bool want_u, [[maybe_unused]] const GlmDispChain& dk,
+                                         [[maybe_unused]] double& tsum) {
     using C = GlmCfg<NT>;
     constexpr int KS = C::KS;
     const v2f64* __restrict__ src = reinterpret_cast<const v2f64*>(prm.img);
@@ -154,6 +249,7 @@ __device__ __forceinline__ void glm_grad(const typename GlmArgs<RICH>::type& prm
 #pragma unroll
     for (int t = 0; t < NT; ++t) gacc[t] = v4f64{0.0, 0.0, 0.0, 0.0};
     usum = 0.0;
+    if constexpr (glm_disp(FAM)) tsum = 0.0;
     for (int ch = 0; ch < nch; ++ch) {
         __syncthreads();  // everybody has finished reading the previous chunk
 #pragma unroll
@@ -195,7 +291,16 @@ __device__ __forceinline__ void glm_grad(const typename GlmArgs<RICH>::type& prm
             for (int r = 0; r < 4; ++r) {
                 const bool ok = obs0 + 4 * r < prm.M;
                 double rr, ut;
-                if constexpr (RICH) {
+                if constexpr (glm_disp(FAM)) {
+                    const int i = bi * 16 + 4 * r + g;
+                    const double cv = ylds[i], yv = ylds[C::OBS + i], ov = ylds[2 * C::OBS + i];
+                    double tt;
+                    glm_link_disp<FAM>(eta[r] + ov, cv, yv, dk, want_u, rr, ut, tt);
+                    const bool on = ok && cv != 0.0;  // weight 0: exactly nothing
+                    res[r] = on ? rr : 0.0;
+                    usum += on ? ut : 0.0;
+                    tsum += on ? tt : 0.0;
+                } else if constexpr (RICH) {
                     const int i = bi * 16 + 4 * r + g;
                     const double cv = ylds[i], dv = ylds[C::OBS + i], ov = ylds[2 * C::OBS + i];
                     glm_link_rich<FAM>(eta[r] + ov, cv, dv, want_u, rr, ut);
@@ -221,10 +326,14 @@ __device__ __forceinline__ void glm_grad(const typename GlmArgs<RICH>::type& prm
     }
 }
 
+// Waves per SIMD: two up to DP = 32, except the negative binomial at DP = 32 -- the constants of its exp, log and two
+// series sit in vector registers beside the state (the scalar file is full), and held to 256 registers it spills; at DP
+// = 128 it spills even with all 512 and is not instantiated (glm_build_disp refuses that shape).
 // TWIN: k_glm_softmax of kernels_glm_softmax.hip restates this frame (ghost waves and ragged tail, momentum first, the
 // kick / drift schedule of the evaluation loop, the five modes, the accept epilogue).  A fix to either belongs in both.
 template <int NT, int FAM, bool RICH>
-__global__ void __launch_bounds__(BLOCK, NT <= 2 ? 2 : 1) k_glm(typename GlmArgs<RICH>::type prm) {
+__global__ void __launch_bounds__(BLOCK, (NT <= 2 && !(NT == 2 && FAM == PBBI_GLM_NEGBINOMIAL)) ? 2 : 1) k_glm(typename GlmArgs<FAM, RICH>::type prm) {
+    static_assert(RICH || !glm_disp(FAM), "the dispersion families live on the full model's frame");
     using C = GlmCfg<NT>;
     constexpr int KS = C::KS;
     constexpr int DP = 16 * NT;
@@ -329,7 +438,28 @@ __global__ void __launch_bounds__(BLOCK, NT <= 2 ? 2 : 1) k_glm(typename GlmArgs
         ck *= minv;
         const bool want_u = (e == 0 || e == nev - 1) && mode != GLM_INTEGRATE;
         double usum;
-        glm_grad<NT, FAM, RICH>(prm, lds, ylds, lane, g, q, gacc, usum, want_u);
+        if constexpr (glm_disp(FAM)) {
+            // theta: the owner of its row contributes q[s], everybody else 0 (exact); held: from the arguments
+            const int ts = prm.trow >> 2, tg = prm.trow & 3;  // trow = -1: no s matches
+            double th = 0.0;
+#pragma unroll
+            for (int s = 0; s < KS; ++s) th = (s == ts) ? q[s] : th;
+            th = chain_sum(g == tg ? th : 0.0);
+            if (prm.trow < 0) th = prm.theta;
+            const GlmDispChain dk = glm_disp_chain<FAM>(th, want_u);
+            double tsum;
+            glm_grad<NT, FAM, RICH>(prm, lds, ylds, lane, g, q, gacc, usum, want_u, dk, tsum);
+            tsum = chain_sum(tsum);
+            tsum = (g == tg) ? tsum : 0.0;
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) gacc[t][r] += (4 * t + r == ts) ? tsum : 0.0;
+        } else {
+            const GlmDispChain none{};
+            double tnone;
+            glm_grad<NT, FAM, RICH>(prm, lds, ylds, lane, g, q, gacc, usum, want_u, none, tnone);
+        }
         if (want_u) {
             double qq = 0.0;
             if constexpr (RICH) {
@@ -487,8 +617,22 @@ int glm_launch(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t stream)
     rprm.obs = (const double*)pot->d_glm_obs;
     rprm.prior = (const double*)pot->d_glm_prior;
     rprm.obs_stride = glm_blocks_padded(pot->glm_M) * 16;
+    const bool disp = glm_disp(pot->glm_family);  // handle of pbbi_potential_create_glm_dispersion
+    GlmPrmDisp dprm{};
+    static_cast<GlmPrmRich&>(dprm) = rprm;
+    dprm.theta = pot->glm_theta;
+    dprm.trow = pot->glm_trow;
+    if (disp && pot->glm_family == PBBI_GLM_NEGBINOMIAL && pot->glm_DP > 64)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "negbinomial: no kernel at a padded state dimension of 128 (internal)");
+#define GLM_DISP_CASE(NT_, FAM_)                                                                            \
+    if (disp && pot->glm_DP == 16 * NT_ && pot->glm_family == FAM_)                                         \
+        hipLaunchKernelGGL((k_glm<NT_, FAM_, true>), grid, block, 0, stream, dprm);
+    GLM_DISP_CASE(1, PBBI_GLM_GAUSSIAN) GLM_DISP_CASE(2, PBBI_GLM_GAUSSIAN) GLM_DISP_CASE(4, PBBI_GLM_GAUSSIAN)
+    GLM_DISP_CASE(8, PBBI_GLM_GAUSSIAN)
+    GLM_DISP_CASE(1, PBBI_GLM_NEGBINOMIAL) GLM_DISP_CASE(2, PBBI_GLM_NEGBINOMIAL) GLM_DISP_CASE(4, PBBI_GLM_NEGBINOMIAL)
+#undef GLM_DISP_CASE
 #define GLM_CASE(NT_, RICH_, PRM_)                                                                          \
-    if (pot->glm_DP == 16 * NT_ && rich == RICH_) {                                                         \
+    if (!disp && pot->glm_DP == 16 * NT_ && rich == RICH_) {                                               \
         if (pot->glm_family == PBBI_GLM_LOGISTIC)                                                           \
             hipLaunchKernelGGL((k_glm<NT_, PBBI_GLM_LOGISTIC, RICH_>), grid, block, 0, stream, PRM_);       \
         else                                                                                                \
@@ -510,8 +654,11 @@ int64_t glm_image_len(int D, int64_t M) { return glm_blocks_padded(M) * (int64_t
 
 // X (M x D, row-major) -> per block of 16 observations P1 [KS/2][64][2] then P2 [2][NT][64][2] (see the top of
 // the file), zero padded to DP columns and to a multiple of 4 blocks.  Host only.
-void glm_pack(int D, int64_t M, const double* X, double* out) {
-    const int DP = glm_padded_dim(D), NT = DP / 16, KS = DP / 4;
+static void glm_pack_dp(int D, int DP, int64_t M, const double* X, double* out);
+void glm_pack(int D, int64_t M, const double* X, double* out) { glm_pack_dp(D, glm_padded_dim(D), M, X, out); }
+// ... at a padded dimension DP >= D of the caller's: the image of [X | 0]
+static void glm_pack_dp(int D, int DP, int64_t M, const double* X, double* out) {
+    const int NT = DP / 16, KS = DP / 4;
     const int64_t nbp = glm_blocks_padded(M);
     const int64_t blk_len = (int64_t)DP * 32;
     std::memset(out, 0, sizeof(double) * (size_t)(nbp * blk_len));
@@ -638,6 +785,76 @@ int glm_build_ex(pbbi_potential* pot, int64_t M, const double* X, const double* 
     pot->glm_lam = one ? lam[0] : 0.0;  // (the full model's kernels read d_glm_prior)
     pot->glm_terms = (weights ? GLM_TERM_WEIGHTS : 0) | (offset ? GLM_TERM_OFFSET : 0) | (trials ? GLM_TERM_TRIALS : 0) |
                      (one ? 0 : GLM_TERM_PRIOR_VECTOR) | (centred ? 0 : GLM_TERM_PRIOR_MEAN) | (flat ? GLM_TERM_PRIOR_FLAT : 0);
+    return PBBI_OK;
+}
+
+// ---- host side: the dispersion families ------------------------------------------------------------------------
+int glm_check_obs_disp(int64_t M, int family, const double* y, const double* weights, const double* offset) {
+    if (M < 1) return pbbi_fail(PBBI_ERR_INVALID, "M must be >= 1");
+    if (!glm_disp(family)) return pbbi_fail(PBBI_ERR_INVALID, "unknown dispersion family (gaussian = 3, negbinomial = 4)");
+    if (!y) return pbbi_fail(PBBI_ERR_INVALID, "y is NULL");
+    for (int64_t i = 0; i < M; ++i) {
+        auto at = [i] { return " (observation " + std::to_string(i) + ")"; };
+        if (!std::isfinite(y[i])) return pbbi_fail(PBBI_ERR_INVALID, "y must be finite" + at());
+        if (family == PBBI_GLM_NEGBINOMIAL && (y[i] < 0.0 || y[i] != std::floor(y[i])))
+            return pbbi_fail(PBBI_ERR_INVALID, "negbinomial: y must hold non-negative integers" + at());
+        if (weights && !(std::isfinite(weights[i]) && weights[i] >= 0.0))
+            return pbbi_fail(PBBI_ERR_INVALID, "weights must be finite and >= 0" + at());
+        if (offset && !std::isfinite(offset[i]))
+            return pbbi_fail(PBBI_ERR_INVALID, "offset must be finite" + at());
+    }
+    return PBBI_OK;
+}
+
+// c = a | d = y (raw) | o, each zero padded to the image's block count (glm_obs_len(M) doubles).  Host only.
+void glm_pack_obs_disp(int64_t M, const double* y, const double* weights, const double* offset, double* out) {
+    const int64_t len = glm_blocks_padded(M) * 16;
+    std::memset(out, 0, sizeof(double) * (size_t)(3 * len));
+    for (int64_t i = 0; i < M; ++i) {
+        out[i] = weights ? weights[i] : 1.0;
+        out[len + i] = y[i];
+        out[2 * len + i] = offset ? offset[i] : 0.0;
+    }
+}
+
+// the caller has run glm_check_obs_disp and glm_check_prior (over pot->D entries); pot->D = Dx + (sample ? 1 : 0)
+int glm_build_disp(pbbi_potential* pot, int Dx, int64_t M, const double* X, const double* y, int family,
+                   const double* weights, const double* offset, const double* lam, const double* mu, int sample,
+                   double theta) {
+    const int Dt = pot->D;
+    if (Dt > 128 || pot->dtype != PBBI_F64)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials run on the fp64 matrix-core kernels: float64 and a state "
+                                               "dimension <= 128 only (" + std::to_string(Dt) + ")");
+    // k_glm<8, PBBI_GLM_NEGBINOMIAL, true> cannot be built without scratch (the full model's DP = 128 kernel already
+    // fills all 512 registers) and is not shipped
+    if (family == PBBI_GLM_NEGBINOMIAL && Dt > 64)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "negbinomial: the state dimension (coefficients + 1 for a sampled dispersion) "
+                                               "must be <= 64: its kernel at 65 .. 128 does not fit the register file (" +
+                                                   std::to_string(Dt) + ")");
+    const int DP = glm_padded_dim(Dt);
+    const int64_t nbp = glm_blocks_padded(M);
+    std::vector<double> img((size_t)(nbp * DP * 32));
+    glm_pack_dp(Dx, DP, M, X, img.data());  // [X | 0]: the theta row meets a zero column
+    std::vector<double> obs((size_t)glm_obs_len(M));
+    glm_pack_obs_disp(M, y, weights, offset, obs.data());
+    std::vector<double> prior((size_t)2 * DP, 0.0);  // lam | mu over the Dt state rows, zeros past them
+    for (int d = 0; d < Dt; ++d) {
+        prior[d] = lam[d];
+        prior[DP + d] = mu ? mu[d] : 0.0;
+    }
+    PBBI_HIP(hipMalloc(&pot->d_glm_img, img.size() * sizeof(double)));
+    PBBI_HIP(hipMalloc(&pot->d_glm_obs, obs.size() * sizeof(double)));
+    PBBI_HIP(hipMalloc(&pot->d_glm_prior, prior.size() * sizeof(double)));
+    PBBI_HIP(hipMemcpy(pot->d_glm_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
+    PBBI_HIP(hipMemcpy(pot->d_glm_obs, obs.data(), obs.size() * sizeof(double), hipMemcpyHostToDevice));
+    PBBI_HIP(hipMemcpy(pot->d_glm_prior, prior.data(), prior.size() * sizeof(double), hipMemcpyHostToDevice));
+    pot->glm_DP = DP;
+    pot->glm_M = M;
+    pot->glm_family = family;
+    pot->glm_lam = 0.0;  // (these kernels read d_glm_prior)
+    pot->glm_terms = (weights ? GLM_TERM_WEIGHTS : 0) | (offset ? GLM_TERM_OFFSET : 0);
+    pot->glm_trow = sample ? Dx : -1;
+    pot->glm_theta = sample ? 0.0 : theta;
     return PBBI_OK;
 }
 

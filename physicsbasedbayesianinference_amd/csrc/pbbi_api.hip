@@ -95,6 +95,7 @@ int new_handle(int kind, int D, int dtype, int device, pbbi_potential** out) {
     p->d_glm_obs = p->d_glm_prior = nullptr;
     p->glm_terms = 0;
     p->glm_K = 0;
+    p->glm_trow = -1; p->glm_theta = 0.0;
     *out = p;
     return PBBI_OK;
 }
@@ -799,6 +800,43 @@ int pbbi_potential_create_glm_softmax(int D, int K, int64_t M, const double* X, 
     return finish_or_destroy(glm_softmax_build(*out, D, K, M, X, y, prior_precision), out);
 }
 
+int pbbi_potential_create_glm_dispersion(int D, int64_t M, const double* X, const double* y, int family,
+                                         const double* weights, const double* offset, const double* lam,
+                                         const double* mu, int sample, double theta, int dtype, int device,
+                                         pbbi_potential** out) {
+    if (out) *out = nullptr;
+    if (!X || !y) return pbbi_fail(PBBI_ERR_INVALID, "X / y is NULL");
+    if (D < 1) return pbbi_fail(PBBI_ERR_INVALID, "D must be >= 1");
+    if (int rc = glm_check_obs_disp(M, family, y, weights, offset)) return rc;
+    for (int64_t i = 0; i < M * D; ++i)
+        if (!std::isfinite(X[i])) return pbbi_fail(PBBI_ERR_INVALID, "X must be finite");
+    if (!sample && !std::isfinite(theta))
+        return pbbi_fail(PBBI_ERR_INVALID, "a held dispersion must be finite and > 0 (theta = its logarithm)");
+    const int Dt = D + (sample ? 1 : 0);
+    if (Dt > 128 || dtype == PBBI_F32)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials run on the fp64 matrix-core kernels: float64 and a state "
+                                               "dimension (coefficients + 1 for a sampled dispersion) <= 128 only");
+    if (family == PBBI_GLM_NEGBINOMIAL && Dt > 64)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "negbinomial: the state dimension (coefficients + 1 for a sampled dispersion) "
+                                               "must be <= 64: its kernel at 65 .. 128 does not fit the register file");
+    if (int rc = glm_check_prior(Dt, lam, mu)) return rc;
+    if (int rc = new_handle(KIND_GLM, Dt, dtype, device, out)) return rc;
+    DeviceGuard guard(device);
+    return finish_or_destroy(glm_build_disp(*out, D, M, X, y, family, weights, offset, lam, mu, sample, theta), out);
+}
+
+int pbbi_glm_pack_observations_dispersion(int64_t M, int family, const double* y, const double* weights,
+                                          const double* offset, double* out, int64_t out_len, int64_t* len_out) {
+    if (M < 1) return pbbi_fail(PBBI_ERR_INVALID, "M must be >= 1");
+    const int64_t len = glm_obs_len(M);
+    if (len_out) *len_out = len;
+    if (!out) return PBBI_OK;
+    if (int rc = glm_check_obs_disp(M, family, y, weights, offset)) return rc;
+    if (out_len < len) return pbbi_fail(PBBI_ERR_INVALID, "out is shorter than the three streams");
+    glm_pack_obs_disp(M, y, weights, offset, out);
+    return PBBI_OK;
+}
+
 int pbbi_glm_softmax_layout(int D, int K, int* Dc_out, int* NT_out, int32_t* row_map) {
     return glm_softmax_layout(D, K, Dc_out, NT_out, row_map);
 }
@@ -1187,7 +1225,15 @@ int pbbi_describe_run(const pbbi_potential* pot, int method, int64_t N, int64_t 
     } else if (pot->kind == KIND_GLM) {
         d = "k_glm: GLM likelihood as two fp64 MFMA products per gradient (eta = X W, g = X^T r), 16 chains per wave, X "
             "staged through LDS in blocks of 16 observations (rows padded to " + std::to_string(pot->glm_DP) + ")";
-        if (pot->d_glm_obs) {
+        if (pot->glm_family == PBBI_GLM_GAUSSIAN || pot->glm_family == PBBI_GLM_NEGBINOMIAL) {
+            const int t = pot->glm_terms;
+            d += std::string("; dispersion family ") + (pot->glm_family == PBBI_GLM_GAUSSIAN ? "gaussian" : "negbinomial");
+            d += pot->glm_trow >= 0 ? " (log-dispersion sampled: state row " + std::to_string(pot->glm_trow) +
+                                          ", read by one chain sum per gradient, its gradient reduced per chain)"
+                                    : " (log-dispersion held at " + std::to_string(pot->glm_theta) + ")";
+            d += (t & GLM_TERM_WEIGHTS) ? ", weights" : "";
+            d += (t & GLM_TERM_OFFSET) ? ", offset" : "";
+        } else if (pot->d_glm_obs) {
             const int t = pot->glm_terms;
             d += "; full model (c | d | o streams beside X, prior vectors in LDS):";
             d += (t & GLM_TERM_WEIGHTS) ? " weights," : "";

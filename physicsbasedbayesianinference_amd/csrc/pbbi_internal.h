@@ -58,6 +58,10 @@ struct pbbi_potential {
     // softmax regression (pbbi_potential_create_glm_softmax), kernels_glm_softmax.hip.  (Appended.)  D = glm_K * (coefficients
     // per class), glm_DP = the padded class size Dc, d_glm_y the labels, d_glm_prior lam (Dc values, zeros past D)
     int glm_K;         // classes (0 = not a softmax handle)
+    // the dispersion families (pbbi_potential_create_glm_dispersion), FAM = 3, 4 of k_glm<NT, FAM, true>.  (Appended.)  D =
+    // the state dimension (coefficients + the theta row when sampled), d_glm_obs = a | y | o, d_glm_prior covers the theta row
+    int glm_trow;      // the state row of theta (= the coefficient count) when it is sampled, -1 when it is held
+    double glm_theta;  // the held log-dispersion
 };
 
 // ---- error plumbing ---------------------------------------------------------
@@ -272,6 +276,10 @@ int glm_check_prior(int D, const double* lam, const double* mu);
 int64_t glm_obs_len(int64_t M);                                // doubles of the three observation streams
 void glm_pack_obs(int64_t M, const double* y, const double* weights, const double* offset, const double* trials,
                   double* out);                                // host only
+int glm_check_obs_disp(int64_t M, int family, const double* y, const double* weights, const double* offset);
+void glm_pack_obs_disp(int64_t M, const double* y, const double* weights, const double* offset, double* out);
+int glm_build_disp(pbbi_potential* pot, int Dx, int64_t M, const double* X, const double* y, int family,
+                   const double* weights, const double* offset, const double* lam, const double* mu, int sample, double theta);
 int glm_padded_dim(int D);
 int64_t glm_image_len(int D, int64_t M);                       // doubles of the fragment image of an M x D design matrix
 void glm_pack(int D, int64_t M, const double* X, double* out);  // host only

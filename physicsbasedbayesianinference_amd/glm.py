@@ -21,6 +21,10 @@ staged through LDS -- the data set is read once per 64 chains, not once per chai
 
 `SoftmaxGLM` is the categorical family on the same frame (csrc/kernels_glm_softmax.hip): K-class softmax regression,
 every class with its own coefficient vector, the chain's state the K vectors class-major.
+
+`DispersionGLM` serves the two families with a free dispersion on the full model's frame: Gaussian regression with
+unknown noise and negative-binomial (NB2) counts, the log-dispersion either sampled as the last component of the
+chain's state or held at a given value.
 """
 import ctypes as C
 
@@ -29,10 +33,15 @@ import numpy as np
 from . import _lib
 from .potential import Potential, _dptr
 
-__all__ = ["GLM", "SoftmaxGLM", "FAMILIES", "pack_design", "pack_observations", "padded_dim", "softmax_layout"]
+__all__ = ["GLM", "SoftmaxGLM", "DispersionGLM", "FAMILIES", "DISPERSION_FAMILIES", "pack_design", "pack_observations",
+           "pack_observations_dispersion", "padded_dim", "softmax_layout"]
 
 FAMILIES = {"logistic": _lib.GLM_LOGISTIC, "poisson": _lib.GLM_POISSON}
+DISPERSION_FAMILIES = {"gaussian": _lib.GLM_GAUSSIAN, "negbinomial": _lib.GLM_NEGBINOMIAL}   # DispersionGLM only
 MAX_DIM = 128
+# the largest state dimension (coefficients + 1 for a sampled dispersion) of each dispersion family: the negative
+# binomial's kernel at a padded dimension of 128 does not fit the register file and is not shipped
+DISPERSION_MAX_DIM = {"gaussian": 128, "negbinomial": 64}
 
 
 def padded_dim(D):
@@ -78,6 +87,29 @@ def pack_observations(y, family="logistic", weights=None, offset=None, trials=No
     try:
         _lib.call("pbbi_glm_pack_observations", M, FAMILIES[family], _dptr(y), _dptr(vec[0]), _dptr(vec[1]),
                   _dptr(vec[2]), _dptr(out), out.size, C.byref(n))
+    except RuntimeError as e:
+        raise ValueError(str(e)) from None
+    return out.reshape(3, -1)
+
+
+def pack_observations_dispersion(y, family="negbinomial", weights=None, offset=None):
+    """The three per-observation streams a DispersionGLM handle keeps on the device, computed (and checked) on the host
+    by libpbbi.so: array (3, L) -- c = weights, d = y (raw, not weights * y) and the offset, each zero padded to L as
+    for `pack_observations`."""
+    if family not in DISPERSION_FAMILIES:
+        raise ValueError("family must be one of %s (got %r)" % (sorted(DISPERSION_FAMILIES), family))
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if y.ndim != 1 or y.size < 1:
+        raise ValueError("y must be 1-D with at least one entry")
+    M = y.size
+    vec = [None if v is None else _vector(v, M, name, "M") for v, name in ((weights, "weights"), (offset, "offset"))]
+    fam = DISPERSION_FAMILIES[family]
+    n = C.c_int64()
+    _lib.call("pbbi_glm_pack_observations_dispersion", M, fam, None, None, None, None, 0, C.byref(n))
+    out = np.empty(n.value, dtype=np.float64)
+    try:
+        _lib.call("pbbi_glm_pack_observations_dispersion", M, fam, _dptr(y), _dptr(vec[0]), _dptr(vec[1]), _dptr(out),
+                  out.size, C.byref(n))
     except RuntimeError as e:
         raise ValueError(str(e)) from None
     return out.reshape(3, -1)
@@ -257,3 +289,121 @@ class SoftmaxGLM(Potential):
         wherever the array allows one)."""
         D = self.numDimensions // self.classes
         return samples.reshape((self.classes, D) + tuple(samples.shape[1:]))
+
+
+class DispersionGLM(Potential):
+    """-log posterior of a GLM whose family has a free dispersion, with theta = log(dispersion):
+
+        gaussian     y_i ~ N(eta_i, sigma^2 / a_i), sigma = exp(theta):
+                     U_i = a_i [ 0.5 exp(-2 theta) (y_i - eta_i)^2 + theta ]
+        negbinomial  y_i ~ NB2(mu_i = exp(eta_i), phi = exp(theta)), Var = mu + mu^2 / phi, y non-negative integers:
+                     U_i = a_i [ lgamma(phi) - lgamma(y_i + phi) - phi theta - y_i eta_i + (y_i + phi) logaddexp(eta_i, theta) ]
+        U = sum_i U_i + 0.5 sum_d lam_d (w_d - mu_d)^2 + 0.5 lam_theta (theta - m_theta)^2,    eta_i = x_i . w + o_i
+
+    (constants that depend on neither w nor theta dropped; the theta prior only when theta is sampled).
+
+        pot = DispersionGLM(X, counts, family="negbinomial", dispersion="sample", log_dispersion_prior=(0.0, 0.25))
+        hmc = HMC(Ensemble(pot.numDimensions, N), 1.0, 0.05, None, potential=pot, rng="philox")
+        w, phi = pot.split(samples)             # (D, ...) coefficients and exp(theta): sigma resp. phi
+        pot = DispersionGLM(X, y, family="gaussian", dispersion=0.7)      # sigma held at 0.7: the state is w alone
+
+    `dispersion="sample"`: theta is the LAST component of the chain's state, numDimensions == D + 1, and
+    `log_dispersion_prior=(mean, precision >= 0)` is theta's Gaussian prior (default (0, 0.25); precision 0 = flat in
+    theta, p(sigma) proportional to 1 / sigma).  `dispersion=` a float > 0: sigma resp. phi is held there, numDimensions
+    == D, and `log_dispersion_prior` must not be given.  `prior_precision` is a scalar or a (D,) vector, `prior_mean` a
+    (D,) vector (default 0), `weights` (>= 0; a row of weight 0 is held out exactly) and `offset` (M,) vectors.
+
+    Shapes: float64; the state dimension is at most 128 for "gaussian" and at most 64 for "negbinomial" (the negative
+    binomial's kernel for 65 .. 128 rows cannot be built without register spills to memory and is not shipped).
+
+    Works wherever `GLM` does (HMC in both rng modes, Leapfrog / StormerVerlet, TemperedSMC, TemperingLadder,
+    sampleStats); per-chain trajectory lengths and GIST raise as for `GLM`.  Arguments are checked on the host before
+    anything touches the GPU.  It runs on csrc/kernels_glm.hip (FAM = 3, 4 of k_glm<NT, FAM, true>)."""
+
+    kind = "glm"
+
+    def __init__(self, X, y, family="negbinomial", dispersion="sample", log_dispersion_prior=None, prior_precision=1.0,
+                 prior_mean=None, weights=None, offset=None, dtype="float64", device=None):
+        if family not in DISPERSION_FAMILIES:
+            raise ValueError("family must be one of %s (got %r)" % (sorted(DISPERSION_FAMILIES), family))
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError("X must be 2-D: (M, D) with at least one row and one column")
+        M, D = X.shape
+        y = np.asarray(y, dtype=np.float64)
+        if y.ndim != 1 or y.size != M:
+            raise ValueError("X has %d rows, y must be 1-D with as many entries (shape %s)" % (M, y.shape))
+        if not np.all(np.isfinite(X)) or not np.all(np.isfinite(y)):
+            raise ValueError("X and y must be finite")
+        if family == "negbinomial" and not (np.all(y >= 0) and np.all(y == np.floor(y))):
+            raise ValueError("negbinomial: y must hold non-negative integers")
+        if weights is not None:
+            weights = _vector(weights, M, "weights", "M")
+            if not np.all(weights >= 0):
+                raise ValueError("weights must be >= 0")
+        if offset is not None:
+            offset = _vector(offset, M, "offset", "M")
+        sample = isinstance(dispersion, str)
+        if sample:
+            if dispersion != "sample":
+                raise ValueError('dispersion must be "sample" or a float > 0 (got %r)' % (dispersion,))
+            m_t, l_t = (0.0, 0.25) if log_dispersion_prior is None else _pair(log_dispersion_prior)
+            if not (np.isfinite(m_t) and np.isfinite(l_t) and l_t >= 0):
+                raise ValueError("log_dispersion_prior must be (mean, precision) with a finite mean and a finite precision >= 0")
+            theta = 0.0
+        else:
+            if log_dispersion_prior is not None:
+                raise ValueError("log_dispersion_prior belongs to dispersion=\"sample\" only: a held dispersion has no prior")
+            try:
+                disp = float(dispersion)
+            except (TypeError, ValueError):
+                raise ValueError('dispersion must be "sample" or a float > 0 (got %r)' % (dispersion,)) from None
+            if not (np.isfinite(disp) and disp > 0):
+                raise ValueError("a held dispersion must be finite and > 0 (got %r)" % (dispersion,))
+            theta = float(np.log(disp))
+        lam = np.asarray(prior_precision, dtype=np.float64)
+        if lam.ndim == 0:
+            if not np.isfinite(lam):
+                raise ValueError("prior_precision must be finite and >= 0")
+            lam = np.full(D, float(lam))
+        else:
+            lam = _vector(lam, D, "prior_precision", "D")
+        if not np.all(lam >= 0):
+            raise ValueError("every prior_precision must be >= 0")
+        mu = np.zeros(D) if prior_mean is None else _vector(prior_mean, D, "prior_mean", "D")
+        Dt = D + 1 if sample else D
+        if Dt > DISPERSION_MAX_DIM[family]:
+            raise ValueError("DispersionGLM(family=%r) serves a state dimension (coefficients%s) <= %d (got %d)"
+                             % (family, " + 1 for the sampled dispersion" if sample else "", DISPERSION_MAX_DIM[family], Dt))
+        if np.dtype(dtype) != np.dtype("float64"):
+            raise ValueError("GLM potentials are float64 only")
+        X, y = np.ascontiguousarray(X), np.ascontiguousarray(y)
+        super().__init__(Dt, dtype, device)
+        self.X, self.y, self.family, self.weights, self.offset = X, y, family, weights, offset
+        self.prior_precision, self.prior_mean = lam, mu
+        self.sampled = sample
+        self.dispersion = "sample" if sample else disp
+        self.log_dispersion_prior = (m_t, l_t) if sample else None
+        self.numCoefficients = D
+        lam_t = np.ascontiguousarray(np.r_[lam, l_t] if sample else lam)
+        mu_t = np.ascontiguousarray(np.r_[mu, m_t] if sample else mu)
+        _lib.call("pbbi_potential_create_glm_dispersion", D, M, _dptr(X), _dptr(y), DISPERSION_FAMILIES[family],
+                  _dptr(weights), _dptr(offset), _dptr(lam_t), _dptr(mu_t), int(sample), theta, self._dt, self.device,
+                  C.byref(self._handle))
+
+    def split(self, samples):
+        """(numDimensions, ...) -> (w, dispersion): the (D, ...) coefficients (a view wherever the array allows one) and
+        exp(theta) -- sigma for "gaussian", phi for "negbinomial" -- of shape (...); held: the constant itself."""
+        D = self.numCoefficients
+        if not self.sampled:
+            return samples, self.dispersion
+        theta = samples[D]
+        return samples[:D], (theta.exp() if hasattr(theta, "exp") and not isinstance(theta, np.ndarray) else np.exp(theta))
+
+
+def _pair(v):
+    try:
+        a, b = v
+        return float(a), float(b)
+    except (TypeError, ValueError):
+        raise ValueError("log_dispersion_prior must be a pair (mean, precision)") from None

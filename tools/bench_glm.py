@@ -19,9 +19,15 @@ the iterations per pbbi_hmc_run call (the slabs of the sample buffer), the itera
 (about a second of the softmax path), the repeats and the warm-up; --K / --repeats / --warmup override them.  All
 figures are host-clock rates over whole windows of pbbi_hmc_run calls, not kernel times.
 
+--model dispersion times DispersionGLM(family="negbinomial", dispersion="sample") (FAM = 4 of k_glm<NT, FAM, true>) against
+the same model as a CustomPotential, alternating in one process, at (M = 256, D = 15, N = 65 536) and (M = 16 384, D = 63,
+N = 16 384) -- state dimensions 16 and 64 -- and writes profiles/glm_dispersion_bench.json (executed 4 M DP flop per
+chain-gradient).  Window lengths per side as for --model softmax (DISPERSION_SHAPES).
+
 usage: tools/bench_glm.py [--shape small|large|all] [--K 32] [--repeats 5] [--glm-only] [--out FILE]
        tools/bench_glm.py --model rich [--custom] [--label NAME] [--shape ...]
        tools/bench_glm.py --model softmax [--shape k3|k8|k8large|all]
+       tools/bench_glm.py --model dispersion [--shape small|large|all]
 """
 import argparse
 import json
@@ -238,6 +244,114 @@ def bench_softmax(name, M, D, classes, N, h, L, per_call, window, repeats, warm)
     return out
 
 
+# negative-binomial regression with a sampled log-dispersion as user source: prm = [M, X, a, y, o, lam(D + 1), mu(D + 1)];
+# the state is (w, theta)
+NEGBINOMIAL_SOURCE = """
+PBBI_FN T nb_psi(T x) {
+    T a = 0;
+    while (x < T(6)) { a -= T(1) / x; x += T(1); }
+    const T r = T(1) / x, r2 = r * r;
+    return a + log(x) - T(0.5) * r - r2 * (T(1) / 12 - r2 * (T(1) / 120 - r2 * (T(1) / 252 - r2 * (T(1) / 240
+           - r2 * (T(1) / 132 - r2 * (T(691) / 32760 - r2 * (T(1) / 12)))))));
+}
+template <class Q>
+PBBI_FN T potential(const Q& q, int DT, const T* prm) {
+    const int M = (int)prm[0], D = DT - 1;
+    const T *X = prm + 1, *a = X + (long)M * D, *y = a + M, *o = y + M, *lam = o + M, *mu = lam + DT;
+    const T th = q[D], phi = exp(th), lgphi = lgamma(phi);
+    T s = 0;
+    for (int i = 0; i < M; ++i) {
+        if (a[i] == 0) continue;
+        T z = o[i];
+        for (int j = 0; j < D; ++j) z += X[i * D + j] * q[j];
+        const T d = z - th, sp = (d > 0 ? d : T(0)) + log1p(exp(-fabs(d)));
+        s += a[i] * (lgphi - lgamma(y[i] + phi) + (y[i] + phi) * sp - y[i] * d);
+    }
+    T r = 0;
+    for (int j = 0; j < DT; ++j) r += lam[j] * (q[j] - mu[j]) * (q[j] - mu[j]);
+    return s + T(0.5) * r;
+}
+template <class Q, class G>
+PBBI_FN void gradient(const Q& q, G& g, int DT, const T* prm) {
+    const int M = (int)prm[0], D = DT - 1;
+    const T *X = prm + 1, *a = X + (long)M * D, *y = a + M, *o = y + M, *lam = o + M, *mu = lam + DT;
+    const T th = q[D], phi = exp(th), psi_phi = nb_psi(phi);
+    for (int j = 0; j < DT; ++j) g[j] = lam[j] * (q[j] - mu[j]);
+    T gt = 0;
+    for (int i = 0; i < M; ++i) {
+        if (a[i] == 0) continue;
+        T z = o[i];
+        for (int j = 0; j < D; ++j) z += X[i * D + j] * q[j];
+        const T d = z - th, e = exp(-fabs(d)), inv = T(1) / (T(1) + e);
+        const T sg = d >= 0 ? inv : e * inv, sg1 = d >= 0 ? e * inv : inv, sp = (d > 0 ? d : T(0)) + log1p(e);
+        const T w = a[i] * ((y[i] + phi) * sg - y[i]);
+        gt += a[i] * (phi * (psi_phi - nb_psi(y[i] + phi) + sp - sg) + y[i] * sg1);
+        for (int j = 0; j < D; ++j) g[j] += w * X[i * D + j];
+    }
+    g[D] += gt;
+}
+"""
+# as SOFTMAX_SHAPES; D + 1 = 16 and 64: the last row of the DP = 16 and DP = 64 kernels is theta's
+DISPERSION_SHAPES = {
+    "small": dict(M=256, D=15, N=65536, h=0.05, per_call=32, window=dict(dispersion=256, plugin=32), repeats=5, warm=4),
+    "large": dict(M=16384, D=63, N=16384, h=0.006, per_call=4, window=dict(dispersion=16, plugin=4), repeats=3, warm=2),
+}
+
+
+def dispersion_problem(M, D, seed=0):
+    """Over-dispersed counts: X with an intercept column, offsets ~ N(0, 0.3), weights from {0.5, 1, 3}, phi = 2."""
+    rs = np.random.RandomState(seed)
+    X = rs.standard_normal((M, D)) / np.sqrt(D)
+    X[:, 0] = 1.0
+    w = 0.7 * rs.standard_normal(D)
+    a = rs.choice([0.5, 1.0, 3.0], size=M)
+    o = 0.3 * rs.standard_normal(M)
+    phi = 2.0
+    y = rs.poisson(rs.gamma(phi, np.exp(X @ w + o) / phi)).astype(np.float64)
+    return dict(X=X, y=y, weights=a, offset=o), np.r_[w, np.log(phi)], rs
+
+
+def bench_dispersion(name, M, D, N, h, L, per_call, window, repeats, warm):
+    """DispersionGLM and the same model through CustomPotential alternating in one process, same data, starts, step size
+    and draws."""
+    from physicsbasedbayesianinference_amd.custom import CustomPotential
+    kw, wt, rs = dispersion_problem(M, D)
+    DT = D + 1
+    q0 = np.ascontiguousarray(wt[:, None] + 0.05 * rs.standard_normal((DT, N)))
+    prior = (0.0, 0.25)
+    prm = np.concatenate([[float(M)], kw["X"].ravel(), kw["weights"], kw["y"], kw["offset"], np.r_[np.ones(D), prior[1]],
+                          np.r_[np.zeros(D), prior[0]]])
+    pot = P.DispersionGLM(family="negbinomial", dispersion="sample", log_dispersion_prior=prior, **kw)
+    runners = {"dispersion": Runner(pot, DT, N, q0, h, L, per_call, window["dispersion"]),
+               "plugin": Runner(CustomPotential(DT, NEGBINOMIAL_SOURCE, prm), DT, N, q0, h, L, per_call, window["plugin"])}
+    for r in runners.values():
+        r.go(warm)
+    torch.cuda.synchronize()
+    series = {k: [] for k in runners}
+    for i in range(repeats):
+        for k, r in runners.items():   # alternating
+            series[k].append(r.timed())
+            print(f"# {name} repeat {i} {k}: {series[k][-1]:.4f} s", flush=True)
+    DP = glm.padded_dim(DT)
+    grads = L + 1
+    out = dict(shape=name, M=M, D=D, state_dimension=DT, DP=DP, chains=N, L=L, h=h, iterations_per_call=per_call,
+               iterations_per_window=dict(window), repeats=repeats, warmup_iterations=warm,
+               timing="host clock over whole windows of pbbi_hmc_run calls (synchronised before and after)",
+               accept_rate={k: 1.0 - float(r.rej.float().mean().item()) for k, r in runners.items()})
+    per_it = {}
+    for k, ts in series.items():
+        out[k + "_seconds"] = ts
+        out[k + "_step_chain_per_s"] = [window[k] * L * N / t for t in ts]
+        per_it[k] = np.array(ts) / window[k]          # seconds per iteration
+    flop_it = 4.0 * M * DP * grads * N
+    out["dispersion_executed_tflops"] = [flop_it / t / 1e12 for t in per_it["dispersion"]]
+    out["dispersion_share_of_fp64_mfma_peak_executed"] = float(flop_it / np.median(per_it["dispersion"]) / PEAK_F64_MFMA)
+    out["ratio_median"] = float(np.median(per_it["plugin"]) / np.median(per_it["dispersion"]))
+    out["ratio_worst_case"] = float(per_it["plugin"].min() / per_it["dispersion"].max())  # fastest plugin over slowest kernel
+    out["slowest_dispersion_beats_fastest_plugin"] = bool(per_it["dispersion"].max() < per_it["plugin"].min())
+    return out
+
+
 class Runner:
     def __init__(self, pot, D, N, q0, h, L, K, window=None):
         # K: slabs of the sample / reject buffers = the most iterations one pbbi_hmc_run call may record;
@@ -311,27 +425,29 @@ if __name__ == "__main__":
     ap.add_argument("--repeats", type=int, default=None, help="default 5 (--model softmax: per shape)")
     ap.add_argument("--warmup", type=int, default=None, help="default 4 (--model softmax: per shape)")
     ap.add_argument("--glm-only", action="store_true")
-    ap.add_argument("--model", default="plain", choices=["plain", "rich", "softmax"])
+    ap.add_argument("--model", default="plain", choices=["plain", "rich", "softmax", "dispersion"])
     ap.add_argument("--custom", action="store_true", help="--model rich: also the full model as a CustomPotential")
     ap.add_argument("--label", default="rich_vs_plain", help="--model rich: key of the record in the output file")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.model == "softmax":
-        a.out = a.out or os.path.join(ROOT, "profiles", "glm_softmax_bench.json")
-        names = list(SOFTMAX_SHAPES) if a.shape == "all" else [a.shape]
+    if a.model in ("softmax", "dispersion"):
+        table, fn, side = ((SOFTMAX_SHAPES, bench_softmax, "softmax") if a.model == "softmax" else
+                           (DISPERSION_SHAPES, bench_dispersion, "dispersion"))
+        a.out = a.out or os.path.join(ROOT, "profiles", "glm_%s_bench.json" % a.model)
+        names = list(table) if a.shape == "all" else [a.shape]
         results = []
         if os.path.exists(a.out) and a.shape != "all":   # one shape per call: keep the others' records
             with open(a.out) as f:
                 results = [r for r in json.load(f)["results"] if r["shape"] not in names]
         for n in names:
-            cfg = dict(SOFTMAX_SHAPES[n])
+            cfg = dict(table[n])
             if a.K is not None:        # one window length for both sides, one call per window
-                cfg["per_call"], cfg["window"] = a.K, dict(softmax=a.K, plugin=a.K)
+                cfg["per_call"], cfg["window"] = a.K, {side: a.K, "plugin": a.K}
             if a.repeats is not None:
                 cfg["repeats"] = a.repeats
             if a.warmup is not None:
                 cfg["warm"] = a.warmup
-            res = bench_softmax(n, L=a.L, **cfg)
+            res = fn(n, L=a.L, **cfg)
             print(json.dumps(res))
             results.append(res)
             with open(a.out, "w") as f:
