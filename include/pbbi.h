@@ -251,6 +251,34 @@ int pbbi_potential_create_glm_dispersion(int D, int64_t M, const double* X, cons
  * each stream zero padded past M. */
 int pbbi_glm_pack_observations_dispersion(int64_t M, int family, const double* y, const double* weights,
                                           const double* offset, double* out, int64_t out_len, int64_t* len_out);
+/* Hierarchical priors with sampled group scales (random effects, a learned ridge penalty) on the full model's kernel frame
+ * (csrc/kernels_glm.hip, k_glm<NT, FAM, true, true>); families logistic and poisson, weights a_i, trials n_i, offsets o_i
+ * and eta_i = x_i . w + o_i as for pbbi_potential_create_glm_ex.  groups[d] is -1 (coefficient d keeps the fixed prior
+ * {prior[d], prior_mean[d]}) or a group index j in 0 .. J-1; the members of group j share the unknown scale sigma_j =
+ * exp(t_j), w_d | t_j ~ N(mu_d, sigma_j^2), t_j ~ N(m_tj, 1 / lam_tj) (the centred parametrisation, sampled on the log scale):
+ *     U(w, t) = sum_i a_i [ n_i b(eta_i) - y_i eta_i ]
+ *             + 0.5 sum_{d: groups_d < 0} lam_d (w_d - mu_d)^2
+ *             + sum_j [ 0.5 exp(-2 t_j) S_j + n_j t_j + 0.5 lam_tj (t_j - m_tj)^2 ]
+ *     S_j = sum_{d: groups_d = j} (w_d - mu_d)^2,   n_j = #{d: groups_d = j}
+ *     dU/dw_d = (likelihood) + exp(-2 t_j) (w_d - mu_d)   for groups_d = j
+ *     dU/dt_j = n_j - exp(-2 t_j) S_j + lam_tj (t_j - m_tj)
+ * State: rows 0 .. D-1 the coefficients, rows D .. D+J-1 t_0 .. t_{J-1}; the handle's dimension is D + J.  The design image
+ * on the device is that of [X | 0] at the padded dimension of D + J, so eta does not see the t rows.  prior: D doubles (the
+ * entries of grouped coefficients are ignored), prior_mean: D doubles or NULL = 0, log_scale_prior: J pairs (m_tj, lam_tj),
+ * lam_tj >= 0.  1 <= J <= 4 (else PBBI_ERR_UNSUPPORTED) and every index 0 .. J-1 must be used; fp64 only; D + J <= 64 for
+ * both families: their kernels for 65 .. 128 rows cannot be built without register spills to memory and are not shipped
+ * (PBBI_ERR_UNSUPPORTED).  Violations of the value rules return PBBI_ERR_INVALID before anything is
+ * allocated.  The handle is a GLM handle (same calls served and refused: no per-chain trajectory lengths, no GIST). */
+int pbbi_potential_create_glm_hier(int D, int64_t M, const double* X, const double* y, int family, const double* weights,
+                                   const double* offset, const double* trials, const double* prior,
+                                   const double* prior_mean, const int32_t* groups, int J, const double* log_scale_prior,
+                                   int dtype, int device, pbbi_potential** out);
+/* The prior table pbbi_potential_create_glm_hier uploads and the kernel keeps in LDS, on the HOST (touches no device, checks
+ * the same rules): out <- lam (DP) | mu (DP) with DP = D + J padded to 16, 32, 64 or 128 -- a fixed row {lam_d, mu_d}, a
+ * member of group j {-(j + 1), mu_d} (a negative lam slot names the group whose exp(-2 t_j) is the row's precision), row
+ * D + j {lam_tj, m_tj}, zeros past D + J; n_out <- n_0 .. n_{J-1}. */
+int pbbi_glm_pack_prior_groups(int D, int J, const double* prior, const double* prior_mean, const int32_t* groups,
+                               const double* log_scale_prior, double* out, double* n_out);
 int pbbi_potential_destroy(pbbi_potential* pot);
 int pbbi_potential_dim(const pbbi_potential* pot);
 int pbbi_potential_dtype(const pbbi_potential* pot);

@@ -63,6 +63,9 @@ PROTOTYPES = {
     "pbbi_glm_softmax_layout": [_i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int32)],
     "pbbi_potential_create_glm_dispersion": [_i, _i64, _dp, _dp, _i, _dp, _dp, _dp, _dp, _i, _d, _i, _i, _pp],
     "pbbi_glm_pack_observations_dispersion": [_i64, _i, _dp, _dp, _dp, _dp, _i64, C.POINTER(C.c_int64)],
+    "pbbi_potential_create_glm_hier": [_i, _i64, _dp, _dp, _i, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32), _i, _dp,
+                                       _i, _i, _pp],
+    "pbbi_glm_pack_prior_groups": [_i, _i, _dp, _dp, C.POINTER(C.c_int32), _dp, _dp, _dp],
     "pbbi_potential_destroy": [_vp],
     "pbbi_potential_dim": [_vp],
     "pbbi_potential_dtype": [_vp],

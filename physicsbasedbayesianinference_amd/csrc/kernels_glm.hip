@@ -51,6 +51,16 @@
 // observations next to usum, and chain_sum of that goes into the gradient accumulator at (s, g) before the kick and the
 // evaluation's store.  Held, theta comes from the kernel arguments (a wave-uniform switch, no further instantiations)
 // and the state is w alone.  The streams are c = a, d = y (raw), o; a row with c = 0 is selected out.
+//
+// Hierarchical priors (HIER = true of k_glm<NT, FAM, true, HIER>, FAM logistic / poisson; handles of
+// pbbi_potential_create_glm_hier; include/pbbi.h has the model): a block of coefficients shares the prior scale exp(t_j),
+// and t_0 .. t_{J-1} (J <= 4) are rows D .. D+J-1 of the state, behind zero columns of the image like theta above.  The
+// likelihood walk is the full model's.  The {lam, mu} table in plds carries the grouping -- a member of group j has
+// -(j + 1) in its lam slot (lam >= 0 otherwise), row D + j the Gaussian prior of t_j -- followed by four entries {n_j, 0}.
+// Once per gradient evaluation, after glm_grad: each lane sums (q - mu)^2 of its rows per group; a lane owns at most one
+// t row (they are consecutive, a lane's rows 4 apart) and contributes its q to that t_j's chain_sum, 0 to the others';
+// tau_j = exp(-2 t_j) is formed once; n_j - tau_j S_j goes into the gradient accumulator at the owner's register.  Kick,
+// evaluation store and energy use tau_j where a fixed row uses its lam (glm_hier_lam: four selects on the value read).
 #include <cmath>
 #include <cstring>
 #include <type_traits>
@@ -93,11 +103,18 @@ struct GlmPrmDisp : GlmPrmRich {
     double theta;  // the held log-dispersion (trow < 0)
     int trow;      // the state row of theta when it is sampled, -1 when it is held
 };
+// the hierarchical prior's kernel arguments (the full model's kernels keep theirs as they are)
+struct GlmPrmHier : GlmPrmRich {  // prior: lam (DP) | mu (DP) | n_j (4, the members of each group, 0 past J)
+    int trow0;     // the state row of t_0 (= the coefficient count); t_j is row trow0 + j
+    int J;         // groups, 1 .. 4
+};
 constexpr bool glm_disp(int fam) { return fam == PBBI_GLM_GAUSSIAN || fam == PBBI_GLM_NEGBINOMIAL; }
-template <int FAM, bool RICH>
+template <int FAM, bool RICH, bool HIER = false>
 struct GlmArgs { using type = GlmPrm; };
 template <int FAM>
-struct GlmArgs<FAM, true> { using type = std::conditional_t<glm_disp(FAM), GlmPrmDisp, GlmPrmRich>; };
+struct GlmArgs<FAM, true, false> { using type = std::conditional_t<glm_disp(FAM), GlmPrmDisp, GlmPrmRich>; };
+template <int FAM>
+struct GlmArgs<FAM, true, true> { using type = GlmPrmHier; };
 enum { GLM_HMC = 0, GLM_INTEGRATE = 1, GLM_EVAL = 2, GLM_ENERGY = 3, GLM_RATIO = 4 };
 
 template <int NT>
@@ -219,14 +236,25 @@ __device__ __forceinline__ void glm_link_disp(double eta, double cv, double yv, 
     }
 }
 
+// hierarchical prior: the precision of a row from the lam slot of its plds entry -- lam >= 0 is a fixed row's own,
+// -(j + 1) marks a member of group j, whose precision is tau_j = exp(-2 t_j) of this chain
+__device__ __forceinline__ double glm_hier_lam(double x, const double (&tau)[4]) {
+    double r = x;
+    r = (x == -1.0) ? tau[0] : r;
+    r = (x == -2.0) ? tau[1] : r;
+    r = (x == -3.0) ? tau[2] : r;
+    r = (x == -4.0) ? tau[3] : r;
+    return r;
+}
+
 // gacc[t][r] (row 16t + 4r + g) = sum_i X[i][row] (b'(eta_i) - y_i) for the wave's 16 chains, usum = this lane's
 // share of sum_i b(eta_i) - y_i eta_i (observations {4r + g} of every block; chain_sum completes it).
 // Every wave of the workgroup takes part in the staging: one chunk of CB blocks is in LDS while the next waits
 // in registers (fetched before the MFMAs of the current one, written after the barrier that ends its reads).
 // RICH: ylds holds the chunk's c | d | o (OBS values each); thread j < 3 OBS stages value j % OBS of stream j / OBS.
 // Dispersion families: dk = the chain's theta-derived values, tsum = this lane's share of sum_i dU_i/dtheta.
-template <int NT, int FAM, bool RICH>
-__device__ __forceinline__ void glm_grad(const typename GlmArgs<FAM, RICH>::type& prm, v2f64* __restrict__ lds,
+template <int NT, int FAM, bool RICH, bool HIER = false>
+__device__ __forceinline__ void glm_grad(const typename GlmArgs<FAM, RICH, HIER>::type& prm, v2f64* __restrict__ lds,
                                          double* __restrict__ ylds, int lane, int g, const double (&q)[4 * NT], v4f64 (&gacc)[NT],
                                          double& usum, bool want_u, [[maybe_unused]] const GlmDispChain& dk,
                                          [[maybe_unused]] double& tsum) {
@@ -331,17 +359,20 @@ __device__ __forceinline__ void glm_grad(const typename GlmArgs<FAM, RICH>::type
 // = 128 it spills even with all 512 and is not instantiated (glm_build_disp refuses that shape).
 // TWIN: k_glm_softmax of kernels_glm_softmax.hip restates this frame (ghost waves and ragged tail, momentum first, the
 // kick / drift schedule of the evaluation loop, the five modes, the accept epilogue).  A fix to either belongs in both.
-template <int NT, int FAM, bool RICH>
-__global__ void __launch_bounds__(BLOCK, (NT <= 2 && !(NT == 2 && FAM == PBBI_GLM_NEGBINOMIAL)) ? 2 : 1) k_glm(typename GlmArgs<FAM, RICH>::type prm) {
+template <int NT, int FAM, bool RICH, bool HIER = false>
+__global__ void __launch_bounds__(BLOCK, (NT <= 2 && !(NT == 2 && FAM == PBBI_GLM_NEGBINOMIAL)) ? 2 : 1) k_glm(typename GlmArgs<FAM, RICH, HIER>::type prm) {
     static_assert(RICH || !glm_disp(FAM), "the dispersion families live on the full model's frame");
+    static_assert(!HIER || (RICH && !glm_disp(FAM)), "the hierarchical prior lives on the full model's frame");
     using C = GlmCfg<NT>;
     constexpr int KS = C::KS;
     constexpr int DP = 16 * NT;
     __shared__ __attribute__((aligned(16))) v2f64 lds[C::CHV];
     __shared__ double ylds[(RICH ? 3 : 1) * C::CB * 16];
-    __shared__ __attribute__((aligned(16))) v2f64 plds[RICH ? DP : 1];  // RICH: {lam, mu} of each row (else unused)
+    __shared__ __attribute__((aligned(16))) v2f64 plds[RICH ? DP + (HIER ? 4 : 0) : 1];  // RICH: {lam, mu} of each row (else unused); HIER: then {n_j, 0}
     if constexpr (RICH) {
         for (int i = threadIdx.x; i < DP; i += BLOCK) plds[i] = v2f64{prm.prior[i], prm.prior[DP + i]};
+        if constexpr (HIER)
+            if (threadIdx.x < 4) plds[DP + threadIdx.x] = v2f64{prm.prior[2 * DP + threadIdx.x], 0.0};
         __syncthreads();
     }
     const int lane = threadIdx.x & 63;
@@ -425,6 +456,7 @@ __global__ void __launch_bounds__(BLOCK, (NT <= 2 && !(NT == 2 && FAM == PBBI_GL
     const double lam = prm.lam;
     const double h = prm.h;
     double U_old = 0.0, U_new = 0.0;
+    [[maybe_unused]] double htau[4];  // HIER: tau_j = exp(-2 t_j) of the evaluation in hand (its store follows the loop)
     for (int e = 0; e < nev; ++e) {
         double ck = 0.0, hd = 0.0;
         if (traj) {
@@ -458,11 +490,58 @@ __global__ void __launch_bounds__(BLOCK, (NT <= 2 && !(NT == 2 && FAM == PBBI_GL
         } else {
             const GlmDispChain none{};
             double tnone;
-            glm_grad<NT, FAM, RICH>(prm, lds, ylds, lane, g, q, gacc, usum, want_u, none, tnone);
+            glm_grad<NT, FAM, RICH, HIER>(prm, lds, ylds, lane, g, q, gacc, usum, want_u, none, tnone);
+        }
+        [[maybe_unused]] double hnt = 0.0;  // HIER: sum_j n_j t_j
+        if constexpr (HIER) {
+            // The t rows are J <= 4 consecutive rows, so a lane (rows 4s + g) owns at most one: row trow0 + jo, register
+            // so.  It contributes that q to the chain sum of t_jo and 0 to the others' (exact); every lane of the chain
+            // then has t_j and forms tau_j.  Groups past J stay at t = 0, S = 0 and meet no row.
+            const int jo = (g - prm.trow0) & 3;
+            const int so = (prm.trow0 + jo) >> 2;
+            // S_j = sum over the members of group j of (w - mu)^2: this lane's rows here, the chain's below
+            double S[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                const v2f64 pm = plds[4 * s + g];
+                const double dq = q[s] - pm.y;
+                const double dq2 = dq * dq;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) S[j] += (pm.x == -(double)(j + 1)) ? dq2 : 0.0;
+            }
+            double th = 0.0;
+#pragma unroll
+            for (int s = 0; s < KS; ++s) th = (s == so) ? q[s] : th;
+            // dU/dt_j = n_j - tau_j S_j (the t prior's part comes with the row's {lam, mu} like any fixed row's)
+            double gown = 0.0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                htau[j] = 1.0;
+                if (j < prm.J) {
+                    const double tj = chain_sum(jo == j ? th : 0.0);
+                    const double nj = plds[DP + j].x;
+                    htau[j] = exp(-2.0 * tj);
+                    const double gt = nj - htau[j] * chain_sum(S[j]);
+                    gown = (jo == j) ? gt : gown;
+                    hnt = fma(nj, tj, hnt);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) gacc[t][r] += (4 * t + r == so) ? gown : 0.0;
         }
         if (want_u) {
             double qq = 0.0;
-            if constexpr (RICH) {
+            if constexpr (HIER) {
+#pragma unroll
+                for (int s = 0; s < KS; ++s) {
+                    const v2f64 pm = plds[4 * s + g];
+                    const double dq = q[s] - pm.y;
+                    qq = fma(glm_hier_lam(pm.x, htau) * dq, dq, qq);
+                }
+                U_new = (chain_sum(usum) + 0.5 * chain_sum(qq)) + hnt;
+            } else if constexpr (RICH) {
 #pragma unroll
                 for (int s = 0; s < KS; ++s) {
                     const v2f64 pm = plds[4 * s + g];
@@ -487,7 +566,10 @@ __global__ void __launch_bounds__(BLOCK, (NT <= 2 && !(NT == 2 && FAM == PBBI_GL
             for (int r = 0; r < 4; ++r) {
                 const int s = 4 * t + r;
                 double gt;
-                if constexpr (RICH) {
+                if constexpr (HIER) {
+                    const v2f64 pm = plds[4 * s + g];
+                    gt = fma(glm_hier_lam(pm.x, htau), q[s] - pm.y, gacc[t][r]);
+                } else if constexpr (RICH) {
                     const v2f64 pm = plds[4 * s + g];
                     gt = fma(pm.x, q[s] - pm.y, gacc[t][r]);
                 } else {
@@ -507,7 +589,10 @@ __global__ void __launch_bounds__(BLOCK, (NT <= 2 && !(NT == 2 && FAM == PBBI_GL
                 for (int r = 0; r < 4; ++r) {
                     const int s = 4 * t + r;
                     double gt;
-                    if constexpr (RICH) {
+                    if constexpr (HIER) {
+                        const v2f64 pm = plds[4 * s + g];
+                        gt = fma(glm_hier_lam(pm.x, htau), q[s] - pm.y, gacc[t][r]);
+                    } else if constexpr (RICH) {
                         const v2f64 pm = plds[4 * s + g];
                         gt = fma(pm.x, q[s] - pm.y, gacc[t][r]);
                     } else {
@@ -631,8 +716,21 @@ int glm_launch(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t stream)
     GLM_DISP_CASE(8, PBBI_GLM_GAUSSIAN)
     GLM_DISP_CASE(1, PBBI_GLM_NEGBINOMIAL) GLM_DISP_CASE(2, PBBI_GLM_NEGBINOMIAL) GLM_DISP_CASE(4, PBBI_GLM_NEGBINOMIAL)
 #undef GLM_DISP_CASE
+    const bool hier = pot->glm_hier_J > 0;  // handle of pbbi_potential_create_glm_hier
+    GlmPrmHier hprm{};
+    static_cast<GlmPrmRich&>(hprm) = rprm;
+    hprm.trow0 = pot->D - pot->glm_hier_J;
+    hprm.J = pot->glm_hier_J;
+    if (hier && pot->glm_DP > glm_hier_max_dim(pot->glm_family))
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "hierarchical prior: no kernel at this padded state dimension (internal)");
+#define GLM_HIER_CASE(NT_, FAM_)                                                                            \
+    if (hier && pot->glm_DP == 16 * NT_ && pot->glm_family == FAM_)                                         \
+        hipLaunchKernelGGL((k_glm<NT_, FAM_, true, true>), grid, block, 0, stream, hprm);
+    GLM_HIER_CASE(1, PBBI_GLM_LOGISTIC) GLM_HIER_CASE(2, PBBI_GLM_LOGISTIC) GLM_HIER_CASE(4, PBBI_GLM_LOGISTIC)
+    GLM_HIER_CASE(1, PBBI_GLM_POISSON) GLM_HIER_CASE(2, PBBI_GLM_POISSON) GLM_HIER_CASE(4, PBBI_GLM_POISSON)
+#undef GLM_HIER_CASE
 #define GLM_CASE(NT_, RICH_, PRM_)                                                                          \
-    if (!disp && pot->glm_DP == 16 * NT_ && rich == RICH_) {                                               \
+    if (!disp && !hier && pot->glm_DP == 16 * NT_ && rich == RICH_) {                                       \
         if (pot->glm_family == PBBI_GLM_LOGISTIC)                                                           \
             hipLaunchKernelGGL((k_glm<NT_, PBBI_GLM_LOGISTIC, RICH_>), grid, block, 0, stream, PRM_);       \
         else                                                                                                \
@@ -855,6 +953,99 @@ int glm_build_disp(pbbi_potential* pot, int Dx, int64_t M, const double* X, cons
     pot->glm_terms = (weights ? GLM_TERM_WEIGHTS : 0) | (offset ? GLM_TERM_OFFSET : 0);
     pot->glm_trow = sample ? Dx : -1;
     pot->glm_theta = sample ? 0.0 : theta;
+    return PBBI_OK;
+}
+
+// ---- host side: the hierarchical prior -------------------------------------------------------------------------
+// the largest state dimension (coefficients + groups) each family's hierarchical kernels serve: k_glm<8, FAM, true, true>
+// cannot be built without scratch for either family (the full model's DP = 128 kernels already fill the register file;
+// 172 and 180 bytes per lane) and is not shipped
+int glm_hier_max_dim(int family) { return (family == PBBI_GLM_LOGISTIC || family == PBBI_GLM_POISSON) ? 64 : 0; }
+
+// Every rule of the hierarchical prior's arguments: groups (D entries, -1 or 0 .. J-1, every index used), the fixed rows'
+// {lam, mu}, the J pairs (mean, precision) of the log-scales.
+int glm_check_hier(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior) {
+    if (D < 1) return pbbi_fail(PBBI_ERR_INVALID, "D must be >= 1");
+    if (J < 1 || J > 4)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "hierarchical prior: the number of groups J must be 1 .. 4 (J = " +
+                                                   std::to_string(J) + ")");
+    if (!groups) return pbbi_fail(PBBI_ERR_INVALID, "groups is NULL");
+    if (!lam) return pbbi_fail(PBBI_ERR_INVALID, "prior_precision is NULL");
+    if (!tprior) return pbbi_fail(PBBI_ERR_INVALID, "log_scale_prior is NULL");
+    int count[4] = {0, 0, 0, 0};
+    for (int d = 0; d < D; ++d) {
+        if (groups[d] < -1 || groups[d] >= J)
+            return pbbi_fail(PBBI_ERR_INVALID, "groups must hold -1 (fixed prior) or a group index 0 .. J-1 (coefficient " +
+                                                   std::to_string(d) + ": " + std::to_string(groups[d]) + ", J = " +
+                                                   std::to_string(J) + ")");
+        if (groups[d] >= 0) ++count[groups[d]];
+        // a grouped coefficient's fixed precision is not used
+        if (groups[d] < 0 && !(std::isfinite(lam[d]) && lam[d] >= 0.0))
+            return pbbi_fail(PBBI_ERR_INVALID, "prior_precision must be finite and >= 0 (coefficient " + std::to_string(d) + ")");
+        if (mu && !std::isfinite(mu[d]))
+            return pbbi_fail(PBBI_ERR_INVALID, "prior_mean must be finite (coefficient " + std::to_string(d) + ")");
+    }
+    for (int j = 0; j < J; ++j) {
+        if (count[j] == 0)
+            return pbbi_fail(PBBI_ERR_INVALID, "every group index 0 .. J-1 must be used (group " + std::to_string(j) +
+                                                   " has no coefficient)");
+        if (!std::isfinite(tprior[2 * j]) || !(std::isfinite(tprior[2 * j + 1]) && tprior[2 * j + 1] >= 0.0))
+            return pbbi_fail(PBBI_ERR_INVALID, "log_scale_prior must hold J pairs (finite mean, finite precision >= 0) "
+                                               "(group " + std::to_string(j) + ")");
+    }
+    return PBBI_OK;
+}
+
+// The table the hierarchical kernels stage into plds, lam (DP) | mu (DP) with DP = glm_padded_dim(D + J): a fixed row its
+// {lam_d, mu_d}, a member of group j {-(j + 1), mu_d}, row D + j {lam_tj, m_tj}, zeros past D + J; n_out[j] = the members
+// of group j.  The caller has run glm_check_hier.  Host only.
+void glm_pack_prior_groups(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior,
+                           double* out, double* n_out) {
+    const int DP = glm_padded_dim(D + J);
+    std::memset(out, 0, sizeof(double) * (size_t)(2 * DP));
+    for (int j = 0; j < J; ++j) n_out[j] = 0.0;
+    for (int d = 0; d < D; ++d) {
+        out[d] = groups[d] < 0 ? lam[d] : -(double)(groups[d] + 1);
+        out[DP + d] = mu ? mu[d] : 0.0;
+        if (groups[d] >= 0) n_out[groups[d]] += 1.0;
+    }
+    for (int j = 0; j < J; ++j) {
+        out[D + j] = tprior[2 * j + 1];
+        out[DP + D + j] = tprior[2 * j];
+    }
+}
+
+// the caller has run glm_check_obs and glm_check_hier; pot->D = Dx + J
+int glm_build_hier(pbbi_potential* pot, int Dx, int64_t M, const double* X, const double* y, int family,
+                   const double* weights, const double* offset, const double* trials, const double* lam, const double* mu,
+                   const int32_t* groups, int J, const double* tprior) {
+    const int Dt = pot->D;
+    if (pot->dtype != PBBI_F64 || Dt > glm_hier_max_dim(family))
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "hierarchical GLM potentials: float64 and a state dimension (coefficients + "
+                                               "groups) <= " + std::to_string(glm_hier_max_dim(family)) + " only (" +
+                                                   std::to_string(Dt) + ")");
+    const int DP = glm_padded_dim(Dt);
+    const int64_t nbp = glm_blocks_padded(M);
+    std::vector<double> img((size_t)(nbp * DP * 32));
+    glm_pack_dp(Dx, DP, M, X, img.data());  // [X | 0]: the t rows meet zero columns
+    std::vector<double> obs((size_t)glm_obs_len(M));
+    glm_pack_obs(M, y, weights, offset, trials, obs.data());
+    std::vector<double> prior((size_t)2 * DP + 4, 0.0);  // lam | mu | n_j
+    double* nj = prior.data() + 2 * DP;
+    glm_pack_prior_groups(Dx, J, lam, mu, groups, tprior, prior.data(), nj);
+    PBBI_HIP(hipMalloc(&pot->d_glm_img, img.size() * sizeof(double)));
+    PBBI_HIP(hipMalloc(&pot->d_glm_obs, obs.size() * sizeof(double)));
+    PBBI_HIP(hipMalloc(&pot->d_glm_prior, prior.size() * sizeof(double)));
+    PBBI_HIP(hipMemcpy(pot->d_glm_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
+    PBBI_HIP(hipMemcpy(pot->d_glm_obs, obs.data(), obs.size() * sizeof(double), hipMemcpyHostToDevice));
+    PBBI_HIP(hipMemcpy(pot->d_glm_prior, prior.data(), prior.size() * sizeof(double), hipMemcpyHostToDevice));
+    pot->glm_DP = DP;
+    pot->glm_M = M;
+    pot->glm_family = family;
+    pot->glm_lam = 0.0;  // (these kernels read d_glm_prior)
+    pot->glm_terms = (weights ? GLM_TERM_WEIGHTS : 0) | (offset ? GLM_TERM_OFFSET : 0) | (trials ? GLM_TERM_TRIALS : 0);
+    pot->glm_hier_J = J;
+    for (int j = 0; j < 4; ++j) pot->glm_hier_n[j] = nj[j];
     return PBBI_OK;
 }
 

@@ -25,6 +25,9 @@ every class with its own coefficient vector, the chain's state the K vectors cla
 `DispersionGLM` serves the two families with a free dispersion on the full model's frame: Gaussian regression with
 unknown noise and negative-binomial (NB2) counts, the log-dispersion either sampled as the last component of the
 chain's state or held at a given value.
+
+`HierarchicalGLM` is the full model with hierarchical priors: blocks of coefficients (random intercepts, random slopes,
+a ridge penalty of unknown strength) share a prior scale that is sampled, on the log scale, as a further row of the state.
 """
 import ctypes as C
 
@@ -33,8 +36,9 @@ import numpy as np
 from . import _lib
 from .potential import Potential, _dptr
 
-__all__ = ["GLM", "SoftmaxGLM", "DispersionGLM", "FAMILIES", "DISPERSION_FAMILIES", "pack_design", "pack_observations",
-           "pack_observations_dispersion", "padded_dim", "softmax_layout"]
+__all__ = ["GLM", "SoftmaxGLM", "DispersionGLM", "HierarchicalGLM", "FAMILIES", "DISPERSION_FAMILIES", "HIER_MAX_DIM",
+           "HIER_MAX_GROUPS", "pack_design", "pack_observations", "pack_observations_dispersion", "pack_prior_groups",
+           "padded_dim", "softmax_layout"]
 
 FAMILIES = {"logistic": _lib.GLM_LOGISTIC, "poisson": _lib.GLM_POISSON}
 DISPERSION_FAMILIES = {"gaussian": _lib.GLM_GAUSSIAN, "negbinomial": _lib.GLM_NEGBINOMIAL}   # DispersionGLM only
@@ -42,6 +46,10 @@ MAX_DIM = 128
 # the largest state dimension (coefficients + 1 for a sampled dispersion) of each dispersion family: the negative
 # binomial's kernel at a padded dimension of 128 does not fit the register file and is not shipped
 DISPERSION_MAX_DIM = {"gaussian": 128, "negbinomial": 64}
+# the largest state dimension (coefficients + groups) of HierarchicalGLM: neither family's kernel at a padded dimension
+# of 128 can be built without register spills to memory, and neither is shipped
+HIER_MAX_DIM = {"logistic": 64, "poisson": 64}
+HIER_MAX_GROUPS = 4
 
 
 def padded_dim(D):
@@ -407,3 +415,180 @@ def _pair(v):
         return float(a), float(b)
     except (TypeError, ValueError):
         raise ValueError("log_dispersion_prior must be a pair (mean, precision)") from None
+
+
+def _groups_vector(groups, D):
+    g = np.asarray(groups)
+    if g.ndim != 1 or g.size != D:
+        raise ValueError("groups must be 1-D with D = %d entries (shape %s)" % (D, g.shape))
+    if g.dtype.kind not in "iu":
+        gf = np.asarray(g, dtype=np.float64)
+        if not (np.all(np.isfinite(gf)) and np.all(gf == np.floor(gf))):
+            raise ValueError("groups must hold integers: -1 (fixed prior) or a group index")
+        g = gf
+    g = g.astype(np.int64)
+    if np.any(g < -1):
+        raise ValueError("groups must hold -1 (fixed prior) or a group index >= 0 (got %d)" % g.min())
+    J = int(g.max()) + 1
+    if J < 1:
+        raise ValueError("groups names no group (all -1): that model is GLM")
+    if J > HIER_MAX_GROUPS:
+        raise ValueError("at most %d groups are served (group index %d)" % (HIER_MAX_GROUPS, J - 1))
+    missing = [j for j in range(J) if not np.any(g == j)]
+    if missing:
+        raise ValueError("every group index 0 .. %d must be used (unused: %s)" % (J - 1, missing))
+    return np.ascontiguousarray(g, dtype=np.int32), J
+
+
+def _log_scale_prior(v, J):
+    a = np.asarray(v, dtype=np.float64)
+    if a.shape == (2,):
+        a = np.tile(a, (J, 1))
+    if a.shape != (J, 2):
+        raise ValueError("log_scale_prior must be one pair (mean, precision) or J = %d pairs (shape %s)" % (J, a.shape))
+    if not (np.all(np.isfinite(a)) and np.all(a[:, 1] >= 0)):
+        raise ValueError("log_scale_prior: finite means and finite precisions >= 0")
+    return np.ascontiguousarray(a)
+
+
+def _hier_prior(D, groups, log_scale_prior, prior_precision, prior_mean):
+    """groups (int32), J, the (J, 2) log-scale priors, lam (D,) with 0 at the grouped coefficients, mu (D,)."""
+    groups, J = _groups_vector(groups, D)
+    try:
+        tp = _log_scale_prior(log_scale_prior, J)
+    except (TypeError, ValueError) as e:
+        raise ValueError(str(e) if "log_scale_prior" in str(e) else
+                         "log_scale_prior must be one pair (mean, precision) or J pairs") from None
+    lam = np.asarray(prior_precision, dtype=np.float64)
+    if lam.ndim == 0:
+        lam = np.full(D, float(lam))
+    elif lam.ndim != 1 or lam.size != D:
+        raise ValueError("prior_precision must be a scalar or 1-D with D = %d entries (shape %s)" % (D, lam.shape))
+    lam = np.where(groups >= 0, 0.0, lam)          # the entries of grouped coefficients are ignored
+    if not (np.all(np.isfinite(lam)) and np.all(lam >= 0)):
+        raise ValueError("every prior_precision of an ungrouped coefficient must be finite and >= 0")
+    mu = np.zeros(D) if prior_mean is None else _vector(prior_mean, D, "prior_mean", "D")
+    return groups, J, tp, np.ascontiguousarray(lam), mu
+
+
+def pack_prior_groups(groups, log_scale_prior=(0.0, 1.0), prior_precision=1.0, prior_mean=None):
+    """The prior table a HierarchicalGLM handle keeps on the device and its kernel in LDS, computed (and checked) on the
+    host by libpbbi.so: (table, n) -- table (2, DP) with DP = padded_dim(D + J): row 0 the `lam` slots (a fixed
+    coefficient's precision, -(j + 1) for a member of group j, the precision of t_j's prior at D + j), row 1 the means
+    (mu_d, the mean of t_j's prior at D + j), zeros past D + J; n (J,) the members of each group."""
+    D = np.asarray(groups).size
+    groups, J, tp, lam, mu = _hier_prior(D, groups, log_scale_prior, prior_precision, prior_mean)
+    DP = padded_dim(D + J)
+    out, n = np.empty(2 * DP, dtype=np.float64), np.empty(J, dtype=np.float64)
+    try:
+        _lib.call("pbbi_glm_pack_prior_groups", D, J, _dptr(lam), _dptr(mu), groups.ctypes.data_as(C.POINTER(C.c_int32)),
+                  _dptr(tp), _dptr(out), _dptr(n))
+    except RuntimeError as e:
+        raise ValueError(str(e)) from None
+    return out.reshape(2, DP), n
+
+
+class HierarchicalGLM(Potential):
+    """-log posterior of a GLM (family "logistic" or "poisson", the full model of `GLM`: weights a_i, trials n_i,
+    offsets o_i, eta_i = x_i . w + o_i) in which blocks of coefficients share a prior scale that is sampled:
+
+        U(w, t) = sum_i a_i [ n_i b(eta_i) - y_i eta_i ]
+                + 0.5 sum_{d: groups_d < 0} lam_d (w_d - mu_d)^2
+                + sum_j [ 0.5 exp(-2 t_j) S_j + n_j t_j + 0.5 lam_tj (t_j - m_tj)^2 ]
+        S_j = sum_{d: groups_d = j} (w_d - mu_d)^2,    n_j = #{d: groups_d = j}
+
+    i.e. w_d | t_j ~ N(mu_d, sigma_j^2) with sigma_j = exp(t_j) and t_j ~ N(m_tj, 1 / lam_tj): random intercepts per
+    school or batch (one-hot columns of X in one group), random slopes, a ridge penalty of unknown strength.
+
+        groups = np.r_[-1, -1, np.zeros(12, int)]                    # two fixed coefficients, twelve random intercepts
+        pot = HierarchicalGLM(X, y, family="logistic", groups=groups, log_scale_prior=(0.0, 1.0))
+        hmc = HMC(Ensemble(pot.numDimensions, N), 1.0, 0.05, None, potential=pot, rng="philox")
+        w, scales = pot.split(samples)                               # (D, ...) coefficients, (J, ...) sigma_j = exp(t_j)
+        pot = HierarchicalGLM.with_random_intercepts(X, y, labels)   # appends the one-hot columns itself
+
+    `groups` is a (D,) vector of -1 (the coefficient keeps its fixed prior `prior_precision` / `prior_mean`, as in
+    `GLM`) or a group index 0 .. J-1; every index must be used, 1 <= J <= 4.  The chain's state has D + J rows: the
+    coefficients, then t_0 .. t_{J-1}; numDimensions == D + J.  `log_scale_prior` is one pair (mean, precision >= 0)
+    for all groups or J pairs.  The `prior_precision` entries of grouped coefficients are IGNORED (their precision is
+    exp(-2 t_j)); their `prior_mean` entries are used.  `weights`, `offset`, `trials` as for `GLM`.
+
+    This is the CENTRED parametrisation, sampled on the log scale.  Where the data say little about a group's
+    coefficients (few observations per level, a weak likelihood) the posterior is a funnel: small t_j with all members
+    near their means is a narrow neck no single step size serves, and the chains under-sample it.  Check the accept rate
+    and the spread of t_j; a tighter `log_scale_prior` or more data per level help, the non-centred form would cure it.
+
+    Not served: the non-centred parametrisation, sampled group scales on `DispersionGLM` and `SoftmaxGLM`, more than 4
+    groups, group means as parameters, per-chain trajectory lengths and GIST (they raise as for `GLM`).  Shapes:
+    float64; D + J <= 64 for both families (`HIER_MAX_DIM`: the kernels for 65 .. 128 rows cannot be built without
+    register spills to memory and are not shipped).
+
+    Works wherever `GLM` does (HMC in both rng modes, Leapfrog / StormerVerlet, TemperedSMC, TemperingLadder,
+    sampleStats).  Arguments are checked on the host before anything touches the GPU.  It runs on csrc/kernels_glm.hip
+    (k_glm<NT, FAM, true, true>)."""
+
+    kind = "glm"
+
+    def __init__(self, X, y, family="logistic", groups=None, log_scale_prior=(0.0, 1.0), prior_precision=1.0,
+                 prior_mean=None, weights=None, offset=None, trials=None, dtype="float64", device=None):
+        if groups is None:
+            raise ValueError("groups is required: a (D,) vector of -1 (fixed prior) or group indices 0 .. J-1")
+        # X, y and the per-observation vectors: GLM's rules (the prior is checked below, with the groups)
+        X, y, _, _, a, o, n = _validate(X, y, family, 0.0, dtype, None, weights, offset, trials)
+        M, D = X.shape
+        groups, J, tp, lam, mu = _hier_prior(D, groups, log_scale_prior, prior_precision, prior_mean)
+        if D + J > HIER_MAX_DIM[family]:
+            raise ValueError("HierarchicalGLM(family=%r) serves a state dimension (coefficients + groups) <= %d (got %d + %d)"
+                             % (family, HIER_MAX_DIM[family], D, J))
+        super().__init__(D + J, dtype, device)
+        self.X, self.y, self.family = X, y, family
+        self.weights, self.offset, self.trials = a, o, n
+        self.prior_precision, self.prior_mean = lam, mu
+        self.groups, self.log_scale_prior = groups, tp
+        self.numCoefficients, self.numGroups = D, J
+        self.levels = None
+        _lib.call("pbbi_potential_create_glm_hier", D, M, _dptr(X), _dptr(y), FAMILIES[family], _dptr(a), _dptr(o),
+                  _dptr(n), _dptr(lam), _dptr(mu), groups.ctypes.data_as(C.POINTER(C.c_int32)), J, _dptr(tp), self._dt,
+                  self.device, C.byref(self._handle))
+
+    def split(self, samples):
+        """(numDimensions, ...) -> (w, scales): the (D, ...) coefficients (a view wherever the array allows one) and the
+        (J, ...) group scales sigma_j = exp(t_j); NumPy arrays and device tensors alike."""
+        D = self.numCoefficients
+        t = samples[D:D + self.numGroups]
+        return samples[:D], (t.exp() if hasattr(t, "exp") and not isinstance(t, np.ndarray) else np.exp(t))
+
+    @staticmethod
+    def random_intercept_design(X, labels, groups=None):
+        """([X | onehot(labels)], groups, levels) on the host: one column per distinct label (sorted), all in one new
+        group after those of `groups` (default: every column of X fixed)."""
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim != 2:
+            raise ValueError("X must be 2-D: (M, D)")
+        M, D = X.shape
+        labels = np.asarray(labels)
+        if labels.ndim != 1 or labels.size != M:
+            raise ValueError("labels must be 1-D with M = %d entries (shape %s)" % (M, labels.shape))
+        levels, idx = np.unique(labels, return_inverse=True)
+        base = np.full(D, -1, dtype=np.int64) if groups is None else np.asarray(groups).astype(np.int64)
+        if base.ndim != 1 or base.size != D:
+            raise ValueError("groups must be 1-D with D = %d entries (shape %s)" % (D, base.shape))
+        new = int(base.max()) + 1 if base.size and base.max() >= 0 else 0
+        onehot = np.zeros((M, levels.size))
+        onehot[np.arange(M), idx] = 1.0
+        return np.hstack([X, onehot]), np.r_[base, np.full(levels.size, new, dtype=np.int64)], levels
+
+    @classmethod
+    def with_random_intercepts(cls, X, y, labels, **kw):
+        """The model with one random intercept per distinct value of `labels` (M,): a one-hot column per level is
+        appended to X and those columns form one new group, after any groups given in `kw` (whose `groups`,
+        `prior_precision` and `prior_mean` vectors cover the columns of X; the new columns get mean 0).  Built on the
+        host; `pot.levels` keeps the sorted label values, in the order of the appended columns."""
+        Xh, groups, levels = cls.random_intercept_design(X, labels, kw.pop("groups", None))
+        D, K = np.asarray(X).shape[1], levels.size
+        for name, fill in (("prior_precision", 0.0), ("prior_mean", 0.0)):
+            v = kw.get(name)
+            if v is not None and np.ndim(v) == 1:
+                kw[name] = np.r_[_vector(v, D, name, "D"), np.full(K, fill)]
+        pot = cls(Xh, y, groups=groups, **kw)
+        pot.levels = levels
+        return pot

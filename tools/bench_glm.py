@@ -24,10 +24,17 @@ the same model as a CustomPotential, alternating in one process, at (M = 256, D 
 N = 16 384) -- state dimensions 16 and 64 -- and writes profiles/glm_dispersion_bench.json (executed 4 M DP flop per
 chain-gradient).  Window lengths per side as for --model softmax (DISPERSION_SHAPES).
 
+--model hier times HierarchicalGLM (k_glm<NT, FAM, true, true>: logistic, sampled group scales) against the same model as a
+CustomPotential (how it ran before) and against a fixed-prior GLM of the same X and state dimension ([X | 0], the group
+precisions held at their true values), all three alternating in one process with the same data, starts and step size, at
+(M = 256, D = 14 + J = 2, N = 65 536) and (M = 16 384, D = 60 + J = 4, N = 16 384), and writes profiles/glm_hier_bench.json
+with the accept rates of all sides.  Window lengths per side as for --model softmax (HIER_SHAPES).
+
 usage: tools/bench_glm.py [--shape small|large|all] [--K 32] [--repeats 5] [--glm-only] [--out FILE]
        tools/bench_glm.py --model rich [--custom] [--label NAME] [--shape ...]
        tools/bench_glm.py --model softmax [--shape k3|k8|k8large|all]
        tools/bench_glm.py --model dispersion [--shape small|large|all]
+       tools/bench_glm.py --model hier [--shape small|large|all]
 """
 import argparse
 import json
@@ -351,6 +358,118 @@ def bench_dispersion(name, M, D, N, h, L, per_call, window, repeats, warm):
     out["slowest_dispersion_beats_fastest_plugin"] = bool(per_it["dispersion"].max() < per_it["plugin"].min())
     return out
 
+# the hierarchical model as user source: prm = [M, D, X, c, d, o, lam(D + J), mu(D + J), groups(D)], c = a n, d = a y
+HIER_LOGISTIC_SOURCE = """
+template <class Q>
+PBBI_FN T potential(const Q& q, int DT, const T* prm) {
+    const int M = (int)prm[0], D = (int)prm[1];
+    const T *X = prm + 2, *c = X + (long)M * D, *d = c + M, *o = d + M, *lam = o + M, *mu = lam + DT, *grp = mu + DT;
+    T s = 0;
+    for (int i = 0; i < M; ++i) {
+        if (c[i] == 0 && d[i] == 0) continue;
+        T z = o[i];
+        for (int j = 0; j < D; ++j) z += X[i * D + j] * q[j];
+        s += c[i] * ((z > 0 ? z : T(0)) + log1p(exp(-fabs(z)))) - d[i] * z;
+    }
+    T r = 0;
+    for (int j = 0; j < D; ++j) {
+        const int k = (int)grp[j];
+        const T e = q[j] - mu[j];
+        if (k < 0) { r += lam[j] * e * e; } else { r += exp(-2 * q[D + k]) * e * e; s += q[D + k]; }
+    }
+    for (int j = D; j < DT; ++j) r += lam[j] * (q[j] - mu[j]) * (q[j] - mu[j]);
+    return s + T(0.5) * r;
+}
+template <class Q, class G>
+PBBI_FN void gradient(const Q& q, G& g, int DT, const T* prm) {
+    const int M = (int)prm[0], D = (int)prm[1];
+    const T *X = prm + 2, *c = X + (long)M * D, *d = c + M, *o = d + M, *lam = o + M, *mu = lam + DT, *grp = mu + DT;
+    for (int j = D; j < DT; ++j) g[j] = lam[j] * (q[j] - mu[j]);
+    for (int j = 0; j < D; ++j) {
+        const int k = (int)grp[j];
+        const T e = q[j] - mu[j];
+        if (k < 0) { g[j] = lam[j] * e; } else { const T tau = exp(-2 * q[D + k]); g[j] = tau * e; g[D + k] += T(1) - tau * e * e; }
+    }
+    for (int i = 0; i < M; ++i) {
+        if (c[i] == 0 && d[i] == 0) continue;
+        T z = o[i];
+        for (int j = 0; j < D; ++j) z += X[i * D + j] * q[j];
+        const T w = c[i] / (T(1) + exp(-z)) - d[i];
+        for (int j = 0; j < D; ++j) g[j] += w * X[i * D + j];
+    }
+}
+"""
+# as SOFTMAX_SHAPES; D + J = 16 and 64: the t rows are the last rows of the DP = 16 and DP = 64 kernels
+HIER_SHAPES = {
+    "small": dict(M=256, D=14, J=2, N=65536, h=0.12, per_call=32, window=dict(hier=256, plugin=32, fixed=256), repeats=5, warm=4),
+    "large": dict(M=16384, D=60, J=4, N=16384, h=0.04, per_call=4, window=dict(hier=16, plugin=4, fixed=16), repeats=3, warm=2),
+}
+
+
+def hier_problem(M, D, J, seed=0):
+    """rich_problem()'s recipe (weights, offsets, binomial trials) with the first D % J + 2 coefficients under a fixed
+    prior of precision 1 and the others in J equal groups of scale exp(t_j), t_j in [-1, 0]."""
+    rs = np.random.RandomState(seed)
+    X = rs.standard_normal((M, D)) / np.sqrt(D)
+    nfix = (D - 2) % J + 2
+    groups = np.r_[np.full(nfix, -1), np.arange(D - nfix) % J]
+    t = rs.uniform(-1.0, 0.0, size=J)
+    w = np.where(groups < 0, 1.0, np.exp(t)[np.maximum(groups, 0)]) * rs.standard_normal(D)
+    a = rs.choice([0.0, 0.5, 1.0, 3.0], size=M)
+    o = 0.3 * rs.standard_normal(M)
+    n = rs.randint(1, 21, size=M).astype(np.float64)
+    y = rs.binomial(n.astype(int), 1.0 / (1.0 + np.exp(-(X @ w + o)))).astype(np.float64)
+    return dict(X=X, y=y, weights=a, offset=o, trials=n, groups=groups), w, t, rs
+
+
+def bench_hier(name, M, D, J, N, h, L, per_call, window, repeats, warm):
+    """HierarchicalGLM, the same model through CustomPotential and a fixed-prior GLM of [X | 0] alternating in one process:
+    same data, starts, step size and draws."""
+    from physicsbasedbayesianinference_amd.custom import CustomPotential
+    kw, w, t, rs = hier_problem(M, D, J)
+    DT = D + J
+    tprior = (-0.5, 1.0)
+    q0 = np.ascontiguousarray(np.r_[w, t][:, None] + 0.05 * rs.standard_normal((DT, N)))
+    groups = kw["groups"]
+    prm = np.concatenate([[float(M), float(D)], kw["X"].ravel(), kw["weights"] * kw["trials"], kw["weights"] * kw["y"],
+                          kw["offset"], np.r_[np.ones(D), np.full(J, tprior[1])], np.r_[np.zeros(D), np.full(J, tprior[0])],
+                          groups.astype(float)])
+    lam_fixed = np.r_[np.where(groups < 0, 1.0, np.exp(-2.0 * t)[np.maximum(groups, 0)]), np.full(J, tprior[1])]
+    fixed = P.GLM(np.hstack([kw["X"], np.zeros((M, J))]), kw["y"], prior_precision=lam_fixed,
+                  prior_mean=np.r_[np.zeros(D), np.full(J, tprior[0])], weights=kw["weights"], offset=kw["offset"],
+                  trials=kw["trials"])
+    pot = P.HierarchicalGLM(log_scale_prior=tprior, prior_precision=1.0, **kw)
+    runners = {"hier": Runner(pot, DT, N, q0, h, L, per_call, window["hier"]),
+               "plugin": Runner(CustomPotential(DT, HIER_LOGISTIC_SOURCE, prm), DT, N, q0, h, L, per_call, window["plugin"]),
+               "fixed": Runner(fixed, DT, N, q0, h, L, per_call, window["fixed"])}
+    for r in runners.values():
+        r.go(warm)
+    torch.cuda.synchronize()
+    series = {k: [] for k in runners}
+    for i in range(repeats):
+        for k, r in runners.items():   # alternating
+            series[k].append(r.timed())
+            print(f"# {name} repeat {i} {k}: {series[k][-1]:.4f} s", flush=True)
+    DP = glm.padded_dim(DT)
+    grads = L + 1
+    out = dict(shape=name, M=M, D=D, J=J, state_dimension=DT, DP=DP, chains=N, L=L, h=h, iterations_per_call=per_call,
+               iterations_per_window=dict(window), repeats=repeats, warmup_iterations=warm,
+               timing="host clock over whole windows of pbbi_hmc_run calls (synchronised before and after)",
+               accept_rate={k: 1.0 - float(r.rej.float().mean().item()) for k, r in runners.items()})
+    per_it = {}
+    for k, ts in series.items():
+        out[k + "_seconds"] = ts
+        out[k + "_step_chain_per_s"] = [window[k] * L * N / t_ for t_ in ts]
+        per_it[k] = np.array(ts) / window[k]          # seconds per iteration
+    flop_it = 4.0 * M * DP * grads * N
+    out["hier_executed_tflops"] = [flop_it / t_ / 1e12 for t_ in per_it["hier"]]
+    out["hier_share_of_fp64_mfma_peak_executed"] = float(flop_it / np.median(per_it["hier"]) / PEAK_F64_MFMA)
+    out["ratio_median"] = float(np.median(per_it["plugin"]) / np.median(per_it["hier"]))
+    out["ratio_worst_case"] = float(per_it["plugin"].min() / per_it["hier"].max())  # fastest plugin over slowest kernel
+    out["slowest_hier_beats_fastest_plugin"] = bool(per_it["hier"].max() < per_it["plugin"].min())
+    out["hier_over_fixed_median"] = float(np.median(per_it["hier"]) / np.median(per_it["fixed"]))   # recorded, not gated
+    return out
+
 
 class Runner:
     def __init__(self, pot, D, N, q0, h, L, K, window=None):
@@ -425,14 +544,15 @@ if __name__ == "__main__":
     ap.add_argument("--repeats", type=int, default=None, help="default 5 (--model softmax: per shape)")
     ap.add_argument("--warmup", type=int, default=None, help="default 4 (--model softmax: per shape)")
     ap.add_argument("--glm-only", action="store_true")
-    ap.add_argument("--model", default="plain", choices=["plain", "rich", "softmax", "dispersion"])
+    ap.add_argument("--model", default="plain", choices=["plain", "rich", "softmax", "dispersion", "hier"])
     ap.add_argument("--custom", action="store_true", help="--model rich: also the full model as a CustomPotential")
     ap.add_argument("--label", default="rich_vs_plain", help="--model rich: key of the record in the output file")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.model in ("softmax", "dispersion"):
-        table, fn, side = ((SOFTMAX_SHAPES, bench_softmax, "softmax") if a.model == "softmax" else
-                           (DISPERSION_SHAPES, bench_dispersion, "dispersion"))
+    if a.model in ("softmax", "dispersion", "hier"):
+        table, fn, side = {"softmax": (SOFTMAX_SHAPES, bench_softmax, "softmax"),
+                           "dispersion": (DISPERSION_SHAPES, bench_dispersion, "dispersion"),
+                           "hier": (HIER_SHAPES, bench_hier, "hier")}[a.model]
         a.out = a.out or os.path.join(ROOT, "profiles", "glm_%s_bench.json" % a.model)
         names = list(table) if a.shape == "all" else [a.shape]
         results = []
@@ -442,7 +562,7 @@ if __name__ == "__main__":
         for n in names:
             cfg = dict(table[n])
             if a.K is not None:        # one window length for both sides, one call per window
-                cfg["per_call"], cfg["window"] = a.K, {side: a.K, "plugin": a.K}
+                cfg["per_call"], cfg["window"] = a.K, {k: a.K for k in cfg["window"]}
             if a.repeats is not None:
                 cfg["repeats"] = a.repeats
             if a.warmup is not None:
