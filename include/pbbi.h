@@ -252,7 +252,7 @@ int pbbi_potential_create_glm_dispersion(int D, int64_t M, const double* X, cons
 int pbbi_glm_pack_observations_dispersion(int64_t M, int family, const double* y, const double* weights,
                                           const double* offset, double* out, int64_t out_len, int64_t* len_out);
 /* Hierarchical priors with sampled group scales (random effects, a learned ridge penalty) on the full model's kernel frame
- * (csrc/kernels_glm.hip, k_glm<NT, FAM, true, true>); families logistic and poisson, weights a_i, trials n_i, offsets o_i
+ * (csrc/kernels_glm.hip, k_glm<NT, FAM, true, GLM_HIER_CENTRED>); families logistic and poisson, weights a_i, trials n_i, offsets o_i
  * and eta_i = x_i . w + o_i as for pbbi_potential_create_glm_ex.  groups[d] is -1 (coefficient d keeps the fixed prior
  * {prior[d], prior_mean[d]}) or a group index j in 0 .. J-1; the members of group j share the unknown scale sigma_j =
  * exp(t_j), w_d | t_j ~ N(mu_d, sigma_j^2), t_j ~ N(m_tj, 1 / lam_tj) (the centred parametrisation, sampled on the log scale):
@@ -273,6 +273,26 @@ int pbbi_potential_create_glm_hier(int D, int64_t M, const double* X, const doub
                                    const double* offset, const double* trials, const double* prior,
                                    const double* prior_mean, const int32_t* groups, int J, const double* log_scale_prior,
                                    int dtype, int device, pbbi_potential** out);
+/* ... with a choice of parametrisation.  PBBI_HIER_CENTRED is pbbi_potential_create_glm_hier exactly (same kernel, same
+ * bits).  PBBI_HIER_NONCENTRED (k_glm<NT, FAM, true, GLM_HIER_NC>) samples z_d in place of w_d on the grouped rows:
+ *     rows 0 .. D-1: groups_d < 0 holds w_d as above; groups_d = j holds z_d, w_d = mu_d + exp(t_j) z_d, z_d ~ N(0, 1)
+ *     rows D .. D+J-1: t_j as above
+ *     U(z, t)  = L(w(z, t)) + 0.5 sum_{fixed} lam_d (w_d - mu_d)^2 + 0.5 sum_{grouped} z_d^2 + sum_j 0.5 lam_tj (t_j - m_tj)^2
+ *     dU/dz_d  = exp(t_j) gL_d + z_d,   gL = X^T r at w(z, t)       (grouped rows)
+ *     dU/dw_d  = gL_d + lam_d (w_d - mu_d)                          (fixed rows)
+ *     dU/dt_j  = exp(t_j) sum_{d in j} gL_d z_d + lam_tj (t_j - m_tj)
+ * with L the likelihood sum above.  It is the same posterior in other coordinates: U_nc(z, t) = U_c(w(z, t), t) - sum_j n_j
+ * t_j, the n_j t_j being the Jacobian of (w, t) -> (z, t).  Choose it when a level has few observations (the centred
+ * posterior is then a funnel in (w, t) whose neck no single step size serves); with many observations per level the
+ * centred form mixes better.  States, samples and running statistics of such a handle are in sampler coordinates (z on
+ * the grouped rows).  The scaling runs inside the kernel on a copy of the state; the table of pbbi_glm_pack_prior_groups
+ * is the same.  All rules above apply; D + J <= 64 for both families; any other `parametrisation` is PBBI_ERR_INVALID. */
+#define PBBI_HIER_CENTRED 0
+#define PBBI_HIER_NONCENTRED 1
+int pbbi_potential_create_glm_hier_ex(int D, int64_t M, const double* X, const double* y, int family, const double* weights,
+                                      const double* offset, const double* trials, const double* prior,
+                                      const double* prior_mean, const int32_t* groups, int J, const double* log_scale_prior,
+                                      int parametrisation, int dtype, int device, pbbi_potential** out);
 /* The prior table pbbi_potential_create_glm_hier uploads and the kernel keeps in LDS, on the HOST (touches no device, checks
  * the same rules): out <- lam (DP) | mu (DP) with DP = D + J padded to 16, 32, 64 or 128 -- a fixed row {lam_d, mu_d}, a
  * member of group j {-(j + 1), mu_d} (a negative lam slot names the group whose exp(-2 t_j) is the row's precision), row

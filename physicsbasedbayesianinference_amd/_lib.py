@@ -16,6 +16,7 @@ LEAPFROG, STORMER_VERLET = 0, 1
 GLM_LOGISTIC, GLM_POISSON = 0, 1
 GLM_SOFTMAX = 2         # pbbi_potential_create_glm_softmax only
 GLM_GAUSSIAN, GLM_NEGBINOMIAL = 3, 4   # pbbi_potential_create_glm_dispersion only
+HIER_CENTRED, HIER_NONCENTRED = 0, 1    # pbbi_potential_create_glm_hier_ex
 ERR_INVALID, ERR_UNSUPPORTED, ERR_HIP = -1, -2, -3
 COMPAT_P_FROM_OLDQ = 1
 KDK_FMA = 2
@@ -65,6 +66,8 @@ PROTOTYPES = {
     "pbbi_glm_pack_observations_dispersion": [_i64, _i, _dp, _dp, _dp, _dp, _i64, C.POINTER(C.c_int64)],
     "pbbi_potential_create_glm_hier": [_i, _i64, _dp, _dp, _i, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32), _i, _dp,
                                        _i, _i, _pp],
+    "pbbi_potential_create_glm_hier_ex": [_i, _i64, _dp, _dp, _i, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32), _i, _dp,
+                                          _i, _i, _i, _pp],
     "pbbi_glm_pack_prior_groups": [_i, _i, _dp, _dp, C.POINTER(C.c_int32), _dp, _dp, _dp],
     "pbbi_potential_destroy": [_vp],
     "pbbi_potential_dim": [_vp],

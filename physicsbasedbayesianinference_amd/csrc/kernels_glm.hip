@@ -52,7 +52,7 @@
 // evaluation's store.  Held, theta comes from the kernel arguments (a wave-uniform switch, no further instantiations)
 // and the state is w alone.  The streams are c = a, d = y (raw), o; a row with c = 0 is selected out.
 //
-// Hierarchical priors (HIER = true of k_glm<NT, FAM, true, HIER>, FAM logistic / poisson; handles of
+// Hierarchical priors (HIER = GLM_HIER_CENTRED of k_glm<NT, FAM, true, HIER>, FAM logistic / poisson; handles of
 // pbbi_potential_create_glm_hier; include/pbbi.h has the model): a block of coefficients shares the prior scale exp(t_j),
 // and t_0 .. t_{J-1} (J <= 4) are rows D .. D+J-1 of the state, behind zero columns of the image like theta above.  The
 // likelihood walk is the full model's.  The {lam, mu} table in plds carries the grouping -- a member of group j has
@@ -61,6 +61,16 @@
 // t row (they are consecutive, a lane's rows 4 apart) and contributes its q to that t_j's chain_sum, 0 to the others';
 // tau_j = exp(-2 t_j) is formed once; n_j - tau_j S_j goes into the gradient accumulator at the owner's register.  Kick,
 // evaluation store and energy use tau_j where a fixed row uses its lam (glm_hier_lam: four selects on the value read).
+//
+// The non-centred parametrisation (HIER = GLM_HIER_NC; handles of pbbi_potential_create_glm_hier_ex): a grouped row of the
+// state holds z_d with w_d = mu_d + sig_j z_d, sig_j = exp(t_j), and z_d ~ N(0, 1) a priori; fixed rows and t rows are as
+// above, and so is the table in plds (its {n_j, 0} tail is not staged).  Before glm_grad: the t_j are broadcast as above,
+// sig_j is formed once, and the first product's B operand is a scaled copy weff of the state (grouped ? fma(sig_j, q, mu) :
+// q -- compile-time-indexed selects on the sign-coded lam slot); q is not touched.  After it, gL = X^T r at w(z, t) sits in
+// gacc: each lane sums gL_d z_d of its rows per group, sig_j chain_sum(...) = dU/dt_j's likelihood part goes to the owner's
+// register, and grouped rows of gacc are multiplied by sig_j (dU/dz_d = sig_j gL_d + z_d).  Kick, evaluation store and
+// energy give a grouped row precision 1 and mean 0 (glm_nc_prior: its mu slot is the mean of w and must not enter the prior
+// of z).  No n_j t_j in U: U_nc(z, t) = U_c(w(z, t), t) - sum_j n_j t_j, the Jacobian of the change of variables.
 #include <cmath>
 #include <cstring>
 #include <type_traits>
@@ -109,12 +119,12 @@ struct GlmPrmHier : GlmPrmRich {  // prior: lam (DP) | mu (DP) | n_j (4, the mem
     int J;         // groups, 1 .. 4
 };
 constexpr bool glm_disp(int fam) { return fam == PBBI_GLM_GAUSSIAN || fam == PBBI_GLM_NEGBINOMIAL; }
-template <int FAM, bool RICH, bool HIER = false>
-struct GlmArgs { using type = GlmPrm; };
+// HIER of k_glm: no hierarchical prior, the centred parametrisation (the chain holds w_d), the non-centred one (z_d)
+enum { GLM_HIER_NONE = 0, GLM_HIER_CENTRED = 1, GLM_HIER_NC = 2 };
+template <int FAM, bool RICH, int HIER = GLM_HIER_NONE>
+struct GlmArgs { using type = std::conditional_t<HIER != GLM_HIER_NONE, GlmPrmHier, GlmPrm>; };
 template <int FAM>
-struct GlmArgs<FAM, true, false> { using type = std::conditional_t<glm_disp(FAM), GlmPrmDisp, GlmPrmRich>; };
-template <int FAM>
-struct GlmArgs<FAM, true, true> { using type = GlmPrmHier; };
+struct GlmArgs<FAM, true, GLM_HIER_NONE> { using type = std::conditional_t<glm_disp(FAM), GlmPrmDisp, GlmPrmRich>; };
 enum { GLM_HMC = 0, GLM_INTEGRATE = 1, GLM_EVAL = 2, GLM_ENERGY = 3, GLM_RATIO = 4 };
 
 template <int NT>
@@ -247,13 +257,20 @@ __device__ __forceinline__ double glm_hier_lam(double x, const double (&tau)[4])
     return r;
 }
 
+// non-centred hierarchical prior: the {precision, mean} of a row's prior in the SAMPLED coordinate.  A grouped row (lam
+// slot < 0) holds z_d ~ N(0, 1): its mu slot is the mean of w_d, which enters weff and not this prior.
+__device__ __forceinline__ v2f64 glm_nc_prior(v2f64 pm) {
+    const bool grouped = pm.x < 0.0;
+    return v2f64{grouped ? 1.0 : pm.x, grouped ? 0.0 : pm.y};
+}
+
 // gacc[t][r] (row 16t + 4r + g) = sum_i X[i][row] (b'(eta_i) - y_i) for the wave's 16 chains, usum = this lane's
 // share of sum_i b(eta_i) - y_i eta_i (observations {4r + g} of every block; chain_sum completes it).
 // Every wave of the workgroup takes part in the staging: one chunk of CB blocks is in LDS while the next waits
 // in registers (fetched before the MFMAs of the current one, written after the barrier that ends its reads).
 // RICH: ylds holds the chunk's c | d | o (OBS values each); thread j < 3 OBS stages value j % OBS of stream j / OBS.
 // Dispersion families: dk = the chain's theta-derived values, tsum = this lane's share of sum_i dU_i/dtheta.
-template <int NT, int FAM, bool RICH, bool HIER = false>
+template <int NT, int FAM, bool RICH, int HIER = GLM_HIER_NONE>
 __device__ __forceinline__ void glm_grad(const typename GlmArgs<FAM, RICH, HIER>::type& prm, v2f64* __restrict__ lds,
                                          double* __restrict__ ylds, int lane, int g, const double (&q)[4 * NT], v4f64 (&gacc)[NT],
                                          double& usum, bool want_u, [[maybe_unused]] const GlmDispChain& dk,
@@ -357,21 +374,26 @@ __device__ __forceinline__ void glm_grad(const typename GlmArgs<FAM, RICH, HIER>
 // Waves per SIMD: two up to DP = 32, except the negative binomial at DP = 32 -- the constants of its exp, log and two
 // series sit in vector registers beside the state (the scalar file is full), and held to 256 registers it spills; at DP
 // = 128 it spills even with all 512 and is not instantiated (glm_build_disp refuses that shape).
+// Likewise the non-centred logistic kernel at DP = 32: q, its scaled copy and the link's constants need 12 bytes of scratch
+// at 256 registers.
+constexpr int glm_waves_per_simd(int NT, int fam, int hier) {
+    return (NT <= 2 && !(NT == 2 && (fam == PBBI_GLM_NEGBINOMIAL || (hier == GLM_HIER_NC && fam == PBBI_GLM_LOGISTIC)))) ? 2 : 1;
+}
 // TWIN: k_glm_softmax of kernels_glm_softmax.hip restates this frame (ghost waves and ragged tail, momentum first, the
 // kick / drift schedule of the evaluation loop, the five modes, the accept epilogue).  A fix to either belongs in both.
-template <int NT, int FAM, bool RICH, bool HIER = false>
-__global__ void __launch_bounds__(BLOCK, (NT <= 2 && !(NT == 2 && FAM == PBBI_GLM_NEGBINOMIAL)) ? 2 : 1) k_glm(typename GlmArgs<FAM, RICH, HIER>::type prm) {
+template <int NT, int FAM, bool RICH, int HIER = GLM_HIER_NONE>
+__global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_glm(typename GlmArgs<FAM, RICH, HIER>::type prm) {
     static_assert(RICH || !glm_disp(FAM), "the dispersion families live on the full model's frame");
-    static_assert(!HIER || (RICH && !glm_disp(FAM)), "the hierarchical prior lives on the full model's frame");
+    static_assert(HIER == GLM_HIER_NONE || (RICH && !glm_disp(FAM)), "the hierarchical prior lives on the full model's frame");
     using C = GlmCfg<NT>;
     constexpr int KS = C::KS;
     constexpr int DP = 16 * NT;
     __shared__ __attribute__((aligned(16))) v2f64 lds[C::CHV];
     __shared__ double ylds[(RICH ? 3 : 1) * C::CB * 16];
-    __shared__ __attribute__((aligned(16))) v2f64 plds[RICH ? DP + (HIER ? 4 : 0) : 1];  // RICH: {lam, mu} of each row (else unused); HIER: then {n_j, 0}
+    __shared__ __attribute__((aligned(16))) v2f64 plds[RICH ? DP + (HIER == GLM_HIER_CENTRED ? 4 : 0) : 1];  // RICH: {lam, mu} of each row (else unused); centred HIER: then {n_j, 0}
     if constexpr (RICH) {
         for (int i = threadIdx.x; i < DP; i += BLOCK) plds[i] = v2f64{prm.prior[i], prm.prior[DP + i]};
-        if constexpr (HIER)
+        if constexpr (HIER == GLM_HIER_CENTRED)
             if (threadIdx.x < 4) plds[DP + threadIdx.x] = v2f64{prm.prior[2 * DP + threadIdx.x], 0.0};
         __syncthreads();
     }
@@ -456,7 +478,7 @@ __global__ void __launch_bounds__(BLOCK, (NT <= 2 && !(NT == 2 && FAM == PBBI_GL
     const double lam = prm.lam;
     const double h = prm.h;
     double U_old = 0.0, U_new = 0.0;
-    [[maybe_unused]] double htau[4];  // HIER: tau_j = exp(-2 t_j) of the evaluation in hand (its store follows the loop)
+    [[maybe_unused]] double htau[4];  // centred HIER: tau_j = exp(-2 t_j) of the evaluation in hand (its store follows the loop)
     for (int e = 0; e < nev; ++e) {
         double ck = 0.0, hd = 0.0;
         if (traj) {
@@ -490,10 +512,60 @@ __global__ void __launch_bounds__(BLOCK, (NT <= 2 && !(NT == 2 && FAM == PBBI_GL
         } else {
             const GlmDispChain none{};
             double tnone;
-            glm_grad<NT, FAM, RICH, HIER>(prm, lds, ylds, lane, g, q, gacc, usum, want_u, none, tnone);
+            if constexpr (HIER == GLM_HIER_NC) {
+                // The chain holds z_d on a grouped row: w_d = mu_d + sig_j z_d is what the likelihood sees.  The t_j reach
+                // every lane of the chain as below (the owner contributes, the others add exact zeros); weff, the B operand
+                // of the first product, is a scaled COPY of the state -- q itself is what the drift, the stores and the prior
+                // work on, and scaling in place and back is not exact.
+                const int jo = (g - prm.trow0) & 3;
+                const int so = (prm.trow0 + jo) >> 2;
+                double th = 0.0;
+#pragma unroll
+                for (int s = 0; s < KS; ++s) th = (s == so) ? q[s] : th;
+                double sig[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    sig[j] = 1.0;
+                    if (j < prm.J) sig[j] = exp(chain_sum(jo == j ? th : 0.0));
+                }
+                double weff[KS];
+#pragma unroll
+                for (int s = 0; s < KS; ++s) {
+                    const v2f64 pm = plds[4 * s + g];
+                    weff[s] = (pm.x < 0.0) ? fma(glm_hier_lam(pm.x, sig), q[s], pm.y) : q[s];
+                }
+                glm_grad<NT, FAM, RICH, HIER>(prm, lds, ylds, lane, g, weff, gacc, usum, want_u, none, tnone);
+                // dU/dt_j = sig_j sum_{d in j} gL_d z_d (this lane's rows here, the chain's below) goes to the owner's
+                // register; dU/dz_d = sig_j gL_d (the priors' parts come with the rows below)
+                double G[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int s = 0; s < KS; ++s) {
+                    const v2f64 pm = plds[4 * s + g];
+                    const double gz = gacc[s >> 2][s & 3] * q[s];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) G[j] += (pm.x == -(double)(j + 1)) ? gz : 0.0;
+                }
+                double gown = 0.0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < prm.J) {
+                        const double gt = chain_sum(G[j]) * sig[j];
+                        gown = (jo == j) ? gt : gown;
+                    }
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const double lx = plds[4 * (4 * t + r) + g].x;
+                        const double gs = (lx < 0.0) ? gacc[t][r] * glm_hier_lam(lx, sig) : gacc[t][r];
+                        gacc[t][r] = gs + ((4 * t + r == so) ? gown : 0.0);
+                    }
+            } else {
+                glm_grad<NT, FAM, RICH, HIER>(prm, lds, ylds, lane, g, q, gacc, usum, want_u, none, tnone);
+            }
         }
-        [[maybe_unused]] double hnt = 0.0;  // HIER: sum_j n_j t_j
-        if constexpr (HIER) {
+        [[maybe_unused]] double hnt = 0.0;  // centred HIER: sum_j n_j t_j
+        if constexpr (HIER == GLM_HIER_CENTRED) {
             // The t rows are J <= 4 consecutive rows, so a lane (rows 4s + g) owns at most one: row trow0 + jo, register
             // so.  It contributes that q to the chain sum of t_jo and 0 to the others' (exact); every lane of the chain
             // then has t_j and forms tau_j.  Groups past J stay at t = 0, S = 0 and meet no row.
@@ -533,7 +605,15 @@ __global__ void __launch_bounds__(BLOCK, (NT <= 2 && !(NT == 2 && FAM == PBBI_GL
         }
         if (want_u) {
             double qq = 0.0;
-            if constexpr (HIER) {
+            if constexpr (HIER == GLM_HIER_NC) {
+#pragma unroll
+                for (int s = 0; s < KS; ++s) {
+                    const v2f64 pm = glm_nc_prior(plds[4 * s + g]);
+                    const double dq = q[s] - pm.y;
+                    qq = fma(pm.x * dq, dq, qq);
+                }
+                U_new = chain_sum(usum) + 0.5 * chain_sum(qq);  // no n_j t_j: the Jacobian of w -> z took it
+            } else if constexpr (HIER == GLM_HIER_CENTRED) {
 #pragma unroll
                 for (int s = 0; s < KS; ++s) {
                     const v2f64 pm = plds[4 * s + g];
@@ -566,7 +646,10 @@ __global__ void __launch_bounds__(BLOCK, (NT <= 2 && !(NT == 2 && FAM == PBBI_GL
             for (int r = 0; r < 4; ++r) {
                 const int s = 4 * t + r;
                 double gt;
-                if constexpr (HIER) {
+                if constexpr (HIER == GLM_HIER_NC) {
+                    const v2f64 pm = glm_nc_prior(plds[4 * s + g]);
+                    gt = fma(pm.x, q[s] - pm.y, gacc[t][r]);
+                } else if constexpr (HIER == GLM_HIER_CENTRED) {
                     const v2f64 pm = plds[4 * s + g];
                     gt = fma(glm_hier_lam(pm.x, htau), q[s] - pm.y, gacc[t][r]);
                 } else if constexpr (RICH) {
@@ -589,7 +672,10 @@ __global__ void __launch_bounds__(BLOCK, (NT <= 2 && !(NT == 2 && FAM == PBBI_GL
                 for (int r = 0; r < 4; ++r) {
                     const int s = 4 * t + r;
                     double gt;
-                    if constexpr (HIER) {
+                    if constexpr (HIER == GLM_HIER_NC) {
+                        const v2f64 pm = glm_nc_prior(plds[4 * s + g]);
+                        gt = fma(pm.x, q[s] - pm.y, gacc[t][r]);
+                    } else if constexpr (HIER == GLM_HIER_CENTRED) {
                         const v2f64 pm = plds[4 * s + g];
                         gt = fma(glm_hier_lam(pm.x, htau), q[s] - pm.y, gacc[t][r]);
                     } else if constexpr (RICH) {
@@ -716,7 +802,8 @@ int glm_launch(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t stream)
     GLM_DISP_CASE(8, PBBI_GLM_GAUSSIAN)
     GLM_DISP_CASE(1, PBBI_GLM_NEGBINOMIAL) GLM_DISP_CASE(2, PBBI_GLM_NEGBINOMIAL) GLM_DISP_CASE(4, PBBI_GLM_NEGBINOMIAL)
 #undef GLM_DISP_CASE
-    const bool hier = pot->glm_hier_J > 0;  // handle of pbbi_potential_create_glm_hier
+    const bool nc = pot->glm_hier_J > 0 && pot->glm_hier_nc;  // handle of pbbi_potential_create_glm_hier_ex, non-centred
+    const bool hier = pot->glm_hier_J > 0 && !nc;             // handle of pbbi_potential_create_glm_hier
     GlmPrmHier hprm{};
     static_cast<GlmPrmRich&>(hprm) = rprm;
     hprm.trow0 = pot->D - pot->glm_hier_J;
@@ -725,12 +812,20 @@ int glm_launch(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t stream)
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, "hierarchical prior: no kernel at this padded state dimension (internal)");
 #define GLM_HIER_CASE(NT_, FAM_)                                                                            \
     if (hier && pot->glm_DP == 16 * NT_ && pot->glm_family == FAM_)                                         \
-        hipLaunchKernelGGL((k_glm<NT_, FAM_, true, true>), grid, block, 0, stream, hprm);
+        hipLaunchKernelGGL((k_glm<NT_, FAM_, true, GLM_HIER_CENTRED>), grid, block, 0, stream, hprm);
     GLM_HIER_CASE(1, PBBI_GLM_LOGISTIC) GLM_HIER_CASE(2, PBBI_GLM_LOGISTIC) GLM_HIER_CASE(4, PBBI_GLM_LOGISTIC)
     GLM_HIER_CASE(1, PBBI_GLM_POISSON) GLM_HIER_CASE(2, PBBI_GLM_POISSON) GLM_HIER_CASE(4, PBBI_GLM_POISSON)
 #undef GLM_HIER_CASE
+    if (nc && pot->glm_DP > glm_hier_nc_max_dim(pot->glm_family))
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "non-centred hierarchical prior: no kernel at this padded state dimension (internal)");
+#define GLM_NC_CASE(NT_, FAM_)                                                                              \
+    if (nc && pot->glm_DP == 16 * NT_ && pot->glm_family == FAM_)                                           \
+        hipLaunchKernelGGL((k_glm<NT_, FAM_, true, GLM_HIER_NC>), grid, block, 0, stream, hprm);
+    GLM_NC_CASE(1, PBBI_GLM_LOGISTIC) GLM_NC_CASE(2, PBBI_GLM_LOGISTIC) GLM_NC_CASE(4, PBBI_GLM_LOGISTIC)
+    GLM_NC_CASE(1, PBBI_GLM_POISSON) GLM_NC_CASE(2, PBBI_GLM_POISSON) GLM_NC_CASE(4, PBBI_GLM_POISSON)
+#undef GLM_NC_CASE
 #define GLM_CASE(NT_, RICH_, PRM_)                                                                          \
-    if (!disp && !hier && pot->glm_DP == 16 * NT_ && rich == RICH_) {                                       \
+    if (!disp && !hier && !nc && pot->glm_DP == 16 * NT_ && rich == RICH_) {                                \
         if (pot->glm_family == PBBI_GLM_LOGISTIC)                                                           \
             hipLaunchKernelGGL((k_glm<NT_, PBBI_GLM_LOGISTIC, RICH_>), grid, block, 0, stream, PRM_);       \
         else                                                                                                \
@@ -957,10 +1052,13 @@ int glm_build_disp(pbbi_potential* pot, int Dx, int64_t M, const double* X, cons
 }
 
 // ---- host side: the hierarchical prior -------------------------------------------------------------------------
-// the largest state dimension (coefficients + groups) each family's hierarchical kernels serve: k_glm<8, FAM, true, true>
+// the largest state dimension (coefficients + groups) each family's hierarchical kernels serve: k_glm<8, FAM, true, GLM_HIER_CENTRED>
 // cannot be built without scratch for either family (the full model's DP = 128 kernels already fill the register file;
 // 172 and 180 bytes per lane) and is not shipped
 int glm_hier_max_dim(int family) { return (family == PBBI_GLM_LOGISTIC || family == PBBI_GLM_POISSON) ? 64 : 0; }
+// ... the non-centred kernels k_glm<NT, FAM, true, GLM_HIER_NC>: NT = 1, 2, 4 build without scratch for both families (the
+// scaled copy of the state costs KS more registers beside q; profiles/glm_hier_nc_resources.txt)
+int glm_hier_nc_max_dim(int family) { return (family == PBBI_GLM_LOGISTIC || family == PBBI_GLM_POISSON) ? 64 : 0; }
 
 // Every rule of the hierarchical prior's arguments: groups (D entries, -1 or 0 .. J-1, every index used), the fixed rows'
 // {lam, mu}, the J pairs (mean, precision) of the log-scales.
@@ -1018,11 +1116,13 @@ void glm_pack_prior_groups(int D, int J, const double* lam, const double* mu, co
 // the caller has run glm_check_obs and glm_check_hier; pot->D = Dx + J
 int glm_build_hier(pbbi_potential* pot, int Dx, int64_t M, const double* X, const double* y, int family,
                    const double* weights, const double* offset, const double* trials, const double* lam, const double* mu,
-                   const int32_t* groups, int J, const double* tprior) {
+                   const int32_t* groups, int J, const double* tprior, int parametrisation) {
     const int Dt = pot->D;
-    if (pot->dtype != PBBI_F64 || Dt > glm_hier_max_dim(family))
+    const bool nc = parametrisation == PBBI_HIER_NONCENTRED;
+    const int dmax = nc ? glm_hier_nc_max_dim(family) : glm_hier_max_dim(family);
+    if (pot->dtype != PBBI_F64 || Dt > dmax)
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, "hierarchical GLM potentials: float64 and a state dimension (coefficients + "
-                                               "groups) <= " + std::to_string(glm_hier_max_dim(family)) + " only (" +
+                                               "groups) <= " + std::to_string(dmax) + " only (" +
                                                    std::to_string(Dt) + ")");
     const int DP = glm_padded_dim(Dt);
     const int64_t nbp = glm_blocks_padded(M);
@@ -1045,6 +1145,7 @@ int glm_build_hier(pbbi_potential* pot, int Dx, int64_t M, const double* X, cons
     pot->glm_lam = 0.0;  // (these kernels read d_glm_prior)
     pot->glm_terms = (weights ? GLM_TERM_WEIGHTS : 0) | (offset ? GLM_TERM_OFFSET : 0) | (trials ? GLM_TERM_TRIALS : 0);
     pot->glm_hier_J = J;
+    pot->glm_hier_nc = nc ? 1 : 0;
     for (int j = 0; j < 4; ++j) pot->glm_hier_n[j] = nj[j];
     return PBBI_OK;
 }

@@ -97,6 +97,7 @@ int new_handle(int kind, int D, int dtype, int device, pbbi_potential** out) {
     p->glm_K = 0;
     p->glm_trow = -1; p->glm_theta = 0.0;
     p->glm_hier_J = 0;
+    p->glm_hier_nc = 0;
     for (double& n : p->glm_hier_n) n = 0.0;
     *out = p;
     return PBBI_OK;
@@ -827,13 +828,16 @@ int pbbi_potential_create_glm_dispersion(int D, int64_t M, const double* X, cons
     return finish_or_destroy(glm_build_disp(*out, D, M, X, y, family, weights, offset, lam, mu, sample, theta), out);
 }
 
-static int glm_hier_check_dim(int D, int J, int family, int dtype) {
+static int glm_hier_check_dim(int D, int J, int family, int dtype, int parametrisation) {
+    const bool nc = parametrisation == PBBI_HIER_NONCENTRED;
+    const int dmax = nc ? glm_hier_nc_max_dim(family) : glm_hier_max_dim(family);
     if (family != PBBI_GLM_LOGISTIC && family != PBBI_GLM_POISSON)
         return pbbi_fail(PBBI_ERR_INVALID, "hierarchical prior: the family must be logistic (0) or poisson (1)");
     if (dtype != PBBI_F64) return pbbi_fail(PBBI_ERR_UNSUPPORTED, "hierarchical GLM potentials are float64 only");
-    if (D + J > glm_hier_max_dim(family))
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "hierarchical prior: the state dimension (coefficients + groups) must be <= " +
-                                                   std::to_string(glm_hier_max_dim(family)) + " for this family (" +
+    if (D + J > dmax)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string("hierarchical prior") + (nc ? " (non-centred)" : "") +
+                                                   ": the state dimension (coefficients + groups) must be <= " +
+                                                   std::to_string(dmax) + " for this family (" +
                                                    std::to_string(D + J) + ")");
     return PBBI_OK;
 }
@@ -842,17 +846,27 @@ int pbbi_potential_create_glm_hier(int D, int64_t M, const double* X, const doub
                                    const double* offset, const double* trials, const double* prior_precision,
                                    const double* prior_mean, const int32_t* groups, int J, const double* log_scale_prior,
                                    int dtype, int device, pbbi_potential** out) {
+    return pbbi_potential_create_glm_hier_ex(D, M, X, y, family, weights, offset, trials, prior_precision, prior_mean, groups,
+                                             J, log_scale_prior, PBBI_HIER_CENTRED, dtype, device, out);
+}
+
+int pbbi_potential_create_glm_hier_ex(int D, int64_t M, const double* X, const double* y, int family, const double* weights,
+                                      const double* offset, const double* trials, const double* prior_precision,
+                                      const double* prior_mean, const int32_t* groups, int J, const double* log_scale_prior,
+                                      int parametrisation, int dtype, int device, pbbi_potential** out) {
     if (out) *out = nullptr;
+    if (parametrisation != PBBI_HIER_CENTRED && parametrisation != PBBI_HIER_NONCENTRED)
+        return pbbi_fail(PBBI_ERR_INVALID, "parametrisation must be PBBI_HIER_CENTRED (0) or PBBI_HIER_NONCENTRED (1)");
     if (!X || !y) return pbbi_fail(PBBI_ERR_INVALID, "X / y is NULL");
     if (int rc = glm_check_hier(D, J, prior_precision, prior_mean, groups, log_scale_prior)) return rc;
     if (int rc = glm_check_obs(M, family, y, weights, offset, trials)) return rc;
     for (int64_t i = 0; i < M * D; ++i)
         if (!std::isfinite(X[i])) return pbbi_fail(PBBI_ERR_INVALID, "X must be finite");
-    if (int rc = glm_hier_check_dim(D, J, family, dtype)) return rc;
+    if (int rc = glm_hier_check_dim(D, J, family, dtype, parametrisation)) return rc;
     if (int rc = new_handle(KIND_GLM, D + J, dtype, device, out)) return rc;
     DeviceGuard guard(device);
     return finish_or_destroy(glm_build_hier(*out, D, M, X, y, family, weights, offset, trials, prior_precision, prior_mean,
-                                            groups, J, log_scale_prior), out);
+                                            groups, J, log_scale_prior, parametrisation), out);
 }
 
 int pbbi_glm_pack_prior_groups(int D, int J, const double* prior_precision, const double* prior_mean, const int32_t* groups,
@@ -1278,7 +1292,10 @@ int pbbi_describe_run(const pbbi_potential* pot, int method, int64_t N, int64_t 
             const int t = pot->glm_terms;
             d += "; hierarchical prior on the full model's frame: " + std::to_string(pot->glm_hier_J) + " sampled group "
                  "log-scales (state rows " + std::to_string(pot->D - pot->glm_hier_J) + " .. " + std::to_string(pot->D - 1) +
-                 ", each read by one chain sum per gradient, the group sums of squares reduced per chain)";
+                 ", each read by one chain sum per gradient, ";
+            d += pot->glm_hier_nc ? "non-centred: grouped rows hold z with w = mu + exp(t) z, the first product runs on a scaled "
+                                    "copy of the state, the group sums of gL z reduced per chain)"
+                                  : "the group sums of squares reduced per chain)";
             d += (t & GLM_TERM_WEIGHTS) ? ", weights" : "";
             d += (t & GLM_TERM_OFFSET) ? ", offset" : "";
             d += (t & GLM_TERM_TRIALS) ? ", binomial trials" : "";

@@ -62,10 +62,12 @@ struct pbbi_potential {
     // the state dimension (coefficients + the theta row when sampled), d_glm_obs = a | y | o, d_glm_prior covers the theta row
     int glm_trow;      // the state row of theta (= the coefficient count) when it is sampled, -1 when it is held
     double glm_theta;  // the held log-dispersion
-    // the hierarchical prior (pbbi_potential_create_glm_hier), k_glm<NT, FAM, true, true>.  (Appended.)  D = coefficients +
+    // the hierarchical prior (pbbi_potential_create_glm_hier), k_glm<NT, FAM, true, GLM_HIER_CENTRED>.  (Appended.)  D = coefficients +
     // glm_hier_J, the t rows last; d_glm_prior is the table of glm_pack_prior_groups
     int glm_hier_J;        // groups (0 = not a hierarchical handle)
     double glm_hier_n[4];  // members of each group
+    // ... in the non-centred parametrisation (pbbi_potential_create_glm_hier_ex), k_glm<NT, FAM, true, GLM_HIER_NC>.  (Appended.)
+    int glm_hier_nc;       // 1: the grouped rows of the state hold z_d, w_d = mu_d + exp(t_j) z_d
 };
 
 // ---- error plumbing ---------------------------------------------------------
@@ -285,12 +287,13 @@ void glm_pack_obs_disp(int64_t M, const double* y, const double* weights, const 
 int glm_build_disp(pbbi_potential* pot, int Dx, int64_t M, const double* X, const double* y, int family,
                    const double* weights, const double* offset, const double* lam, const double* mu, int sample, double theta);
 int glm_hier_max_dim(int family);  // the largest coefficients + groups the hierarchical kernels of a family serve
+int glm_hier_nc_max_dim(int family);  // ... the non-centred ones
 int glm_check_hier(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior);
 void glm_pack_prior_groups(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior,
                            double* out, double* n_out);        // host only
 int glm_build_hier(pbbi_potential* pot, int Dx, int64_t M, const double* X, const double* y, int family,
                    const double* weights, const double* offset, const double* trials, const double* lam, const double* mu,
-                   const int32_t* groups, int J, const double* tprior);
+                   const int32_t* groups, int J, const double* tprior, int parametrisation);
 int glm_padded_dim(int D);
 int64_t glm_image_len(int D, int64_t M);                       // doubles of the fragment image of an M x D design matrix
 void glm_pack(int D, int64_t M, const double* X, double* out);  // host only

@@ -37,7 +37,7 @@ from . import _lib
 from .potential import Potential, _dptr
 
 __all__ = ["GLM", "SoftmaxGLM", "DispersionGLM", "HierarchicalGLM", "FAMILIES", "DISPERSION_FAMILIES", "HIER_MAX_DIM",
-           "HIER_MAX_GROUPS", "pack_design", "pack_observations", "pack_observations_dispersion", "pack_prior_groups",
+           "HIER_NC_MAX_DIM", "HIER_PARAMETRISATIONS", "HIER_MAX_GROUPS", "pack_design", "pack_observations", "pack_observations_dispersion", "pack_prior_groups",
            "padded_dim", "softmax_layout"]
 
 FAMILIES = {"logistic": _lib.GLM_LOGISTIC, "poisson": _lib.GLM_POISSON}
@@ -49,6 +49,10 @@ DISPERSION_MAX_DIM = {"gaussian": 128, "negbinomial": 64}
 # the largest state dimension (coefficients + groups) of HierarchicalGLM: neither family's kernel at a padded dimension
 # of 128 can be built without register spills to memory, and neither is shipped
 HIER_MAX_DIM = {"logistic": 64, "poisson": 64}
+# ... in the non-centred parametrisation (k_glm<NT, FAM, true, GLM_HIER_NC>): the scaled copy of the state costs KS more
+# registers, and the kernels at 64 rows still build without scratch for both families
+HIER_NC_MAX_DIM = {"logistic": 64, "poisson": 64}
+HIER_PARAMETRISATIONS = {"centred": _lib.HIER_CENTRED, "noncentred": _lib.HIER_NONCENTRED}
 HIER_MAX_GROUPS = 4
 
 
@@ -512,48 +516,112 @@ class HierarchicalGLM(Potential):
     for all groups or J pairs.  The `prior_precision` entries of grouped coefficients are IGNORED (their precision is
     exp(-2 t_j)); their `prior_mean` entries are used.  `weights`, `offset`, `trials` as for `GLM`.
 
-    This is the CENTRED parametrisation, sampled on the log scale.  Where the data say little about a group's
-    coefficients (few observations per level, a weak likelihood) the posterior is a funnel: small t_j with all members
-    near their means is a narrow neck no single step size serves, and the chains under-sample it.  Check the accept rate
-    and the spread of t_j; a tighter `log_scale_prior` or more data per level help, the non-centred form would cure it.
+    That is the CENTRED parametrisation (`parametrisation="centred"`, the default), sampled on the log scale.  Where the
+    data say little about a group's coefficients (few observations per level, a weak likelihood) the posterior is a funnel:
+    small t_j with all members near their means is a narrow neck no single step size serves, and the chains under-sample
+    it.  `parametrisation="noncentred"` cures it: on a grouped row the chain holds z_d in place of w_d,
 
-    Not served: the non-centred parametrisation, sampled group scales on `DispersionGLM` and `SoftmaxGLM`, more than 4
+        w_d = mu_d + exp(t_j) z_d,    z_d ~ N(0, 1) a priori
+        U(z, t) = sum_i a_i [ n_i b(eta_i) - y_i eta_i ]  (at w(z, t))
+                + 0.5 sum_{d: groups_d < 0} lam_d (w_d - mu_d)^2 + 0.5 sum_{d: groups_d >= 0} z_d^2
+                + sum_j 0.5 lam_tj (t_j - m_tj)^2
+
+    the same posterior in other coordinates: U_nc(z, t) = U_c(w(z, t), t) - sum_j n_j t_j, the n_j t_j being the Jacobian
+    of the change of variables.  Fixed rows and the t rows are as above.  Which to choose: weak data per level (few
+    observations, random intercepts of small groups) -- non-centred; many observations per level -- centred (there the
+    likelihood pins w_d, and z_d = (w_d - mu_d) exp(-t_j) is what becomes a funnel).  The scaling runs inside the kernel,
+    on a copy of the state (k_glm<NT, FAM, true, GLM_HIER_NC>).  The sampler's states, `getSamples`' output, `sampleStats`
+    and `RunningStats` of a non-centred potential are in SAMPLER coordinates (z on the grouped rows); `to_natural` maps
+    them to (w; t), `from_natural` back, and `split` returns w and the scales on the natural scale for both forms.
+
+    Not served: a per-group choice of parametrisation, sampled group scales on `DispersionGLM` and `SoftmaxGLM`, more than 4
     groups, group means as parameters, per-chain trajectory lengths and GIST (they raise as for `GLM`).  Shapes:
-    float64; D + J <= 64 for both families (`HIER_MAX_DIM`: the kernels for 65 .. 128 rows cannot be built without
-    register spills to memory and are not shipped).
+    float64; D + J <= 64 for both families and both parametrisations (`HIER_MAX_DIM`, `HIER_NC_MAX_DIM`: the kernels for
+    65 .. 128 rows cannot be built without register spills to memory and are not shipped).
 
     Works wherever `GLM` does (HMC in both rng modes, Leapfrog / StormerVerlet, TemperedSMC, TemperingLadder,
     sampleStats).  Arguments are checked on the host before anything touches the GPU.  It runs on csrc/kernels_glm.hip
-    (k_glm<NT, FAM, true, true>)."""
+    (k_glm<NT, FAM, true, HIER>)."""
 
     kind = "glm"
+    parametrisation = "centred"
 
     def __init__(self, X, y, family="logistic", groups=None, log_scale_prior=(0.0, 1.0), prior_precision=1.0,
-                 prior_mean=None, weights=None, offset=None, trials=None, dtype="float64", device=None):
+                 prior_mean=None, weights=None, offset=None, trials=None, dtype="float64", device=None,
+                 parametrisation="centred"):
+        if not isinstance(parametrisation, str) or parametrisation not in HIER_PARAMETRISATIONS:
+            raise ValueError("parametrisation must be \"centred\" or \"noncentred\" (got %r)" % (parametrisation,))
         if groups is None:
             raise ValueError("groups is required: a (D,) vector of -1 (fixed prior) or group indices 0 .. J-1")
         # X, y and the per-observation vectors: GLM's rules (the prior is checked below, with the groups)
         X, y, _, _, a, o, n = _validate(X, y, family, 0.0, dtype, None, weights, offset, trials)
         M, D = X.shape
         groups, J, tp, lam, mu = _hier_prior(D, groups, log_scale_prior, prior_precision, prior_mean)
-        if D + J > HIER_MAX_DIM[family]:
+        dmax = (HIER_NC_MAX_DIM if parametrisation == "noncentred" else HIER_MAX_DIM)[family]
+        if D + J > dmax:
             raise ValueError("HierarchicalGLM(family=%r) serves a state dimension (coefficients + groups) <= %d (got %d + %d)"
-                             % (family, HIER_MAX_DIM[family], D, J))
+                             % (family, dmax, D, J))
         super().__init__(D + J, dtype, device)
+        self.parametrisation = parametrisation
         self.X, self.y, self.family = X, y, family
         self.weights, self.offset, self.trials = a, o, n
         self.prior_precision, self.prior_mean = lam, mu
         self.groups, self.log_scale_prior = groups, tp
         self.numCoefficients, self.numGroups = D, J
         self.levels = None
-        _lib.call("pbbi_potential_create_glm_hier", D, M, _dptr(X), _dptr(y), FAMILIES[family], _dptr(a), _dptr(o),
-                  _dptr(n), _dptr(lam), _dptr(mu), groups.ctypes.data_as(C.POINTER(C.c_int32)), J, _dptr(tp), self._dt,
-                  self.device, C.byref(self._handle))
+        if parametrisation == "centred":    # the entry point, and so the kernel, every call had before the keyword existed
+            _lib.call("pbbi_potential_create_glm_hier", D, M, _dptr(X), _dptr(y), FAMILIES[family], _dptr(a), _dptr(o),
+                      _dptr(n), _dptr(lam), _dptr(mu), groups.ctypes.data_as(C.POINTER(C.c_int32)), J, _dptr(tp), self._dt,
+                      self.device, C.byref(self._handle))
+        else:
+            _lib.call("pbbi_potential_create_glm_hier_ex", D, M, _dptr(X), _dptr(y), FAMILIES[family], _dptr(a), _dptr(o),
+                      _dptr(n), _dptr(lam), _dptr(mu), groups.ctypes.data_as(C.POINTER(C.c_int32)), J, _dptr(tp),
+                      HIER_PARAMETRISATIONS[parametrisation], self._dt, self.device, C.byref(self._handle))
+
+    def _scale_and_mean(self, q):
+        """(exp(t) of each row's group, mu) shaped to broadcast against q[:D], in q's own array type; and the grouped mask."""
+        D, J = self.numCoefficients, self.numGroups
+        grouped = np.asarray(self.groups) >= 0
+        idx = np.where(grouped, self.groups, 0).astype(np.int64)
+        mu = np.asarray(self.prior_mean, dtype=np.float64).reshape((D,) + (1,) * (q.ndim - 1))
+        mask = grouped.reshape(mu.shape)
+        if isinstance(q, np.ndarray):
+            return np.exp(q[D:D + J])[idx], mu, mask, np.where
+        import torch
+        dev = dict(device=q.device)
+        return (q[D:D + J].exp()[torch.as_tensor(idx, **dev)], torch.as_tensor(mu, dtype=q.dtype, **dev),
+                torch.as_tensor(mask, **dev), torch.where)
+
+    def to_natural(self, q):
+        """A sampler state (numDimensions, ...) -> (w; t), the centred state: w_d = mu_d + exp(t_j) z_d on the grouped rows
+        of a non-centred potential, everything else as it is.  NumPy arrays and torch tensors (device tensors with torch
+        ops) of any trailing shape; a new array.  The identity (a copy) for "centred"."""
+        out = q.copy() if isinstance(q, np.ndarray) else q.clone()
+        if self.parametrisation == "centred":
+            return out
+        D = self.numCoefficients
+        sig, mu, mask, where = self._scale_and_mean(q)
+        out[:D] = where(mask, mu + sig * q[:D], q[:D])
+        return out
+
+    def from_natural(self, qc):
+        """The inverse of `to_natural`: (w; t) -> the sampler's state, z_d = (w_d - mu_d) exp(-t_j) on the grouped rows of
+        a non-centred potential.  A new array; the identity (a copy) for "centred"."""
+        out = qc.copy() if isinstance(qc, np.ndarray) else qc.clone()
+        if self.parametrisation == "centred":
+            return out
+        D = self.numCoefficients
+        sig, mu, mask, where = self._scale_and_mean(qc)
+        out[:D] = where(mask, (qc[:D] - mu) / sig, qc[:D])
+        return out
 
     def split(self, samples):
         """(numDimensions, ...) -> (w, scales): the (D, ...) coefficients (a view wherever the array allows one) and the
-        (J, ...) group scales sigma_j = exp(t_j); NumPy arrays and device tensors alike."""
+        (J, ...) group scales sigma_j = exp(t_j), on the natural scale for both parametrisations ("noncentred": through
+        `to_natural`); NumPy arrays and device tensors alike."""
         D = self.numCoefficients
+        if self.parametrisation != "centred":
+            samples = self.to_natural(samples)
         t = samples[D:D + self.numGroups]
         return samples[:D], (t.exp() if hasattr(t, "exp") and not isinstance(t, np.ndarray) else np.exp(t))
 
@@ -582,7 +650,8 @@ class HierarchicalGLM(Potential):
         """The model with one random intercept per distinct value of `labels` (M,): a one-hot column per level is
         appended to X and those columns form one new group, after any groups given in `kw` (whose `groups`,
         `prior_precision` and `prior_mean` vectors cover the columns of X; the new columns get mean 0).  Built on the
-        host; `pot.levels` keeps the sorted label values, in the order of the appended columns."""
+        host; `pot.levels` keeps the sorted label values, in the order of the appended columns.  `parametrisation` and
+        every other keyword of the constructor pass through: few observations per level want "noncentred"."""
         Xh, groups, levels = cls.random_intercept_design(X, labels, kw.pop("groups", None))
         D, K = np.asarray(X).shape[1], levels.size
         for name, fill in (("prior_precision", 0.0), ("prior_mean", 0.0)):

@@ -24,17 +24,23 @@ the same model as a CustomPotential, alternating in one process, at (M = 256, D 
 N = 16 384) -- state dimensions 16 and 64 -- and writes profiles/glm_dispersion_bench.json (executed 4 M DP flop per
 chain-gradient).  Window lengths per side as for --model softmax (DISPERSION_SHAPES).
 
---model hier times HierarchicalGLM (k_glm<NT, FAM, true, true>: logistic, sampled group scales) against the same model as a
+--model hier times HierarchicalGLM (k_glm<NT, FAM, true, GLM_HIER_CENTRED>: logistic, sampled group scales) against the same model as a
 CustomPotential (how it ran before) and against a fixed-prior GLM of the same X and state dimension ([X | 0], the group
 precisions held at their true values), all three alternating in one process with the same data, starts and step size, at
 (M = 256, D = 14 + J = 2, N = 65 536) and (M = 16 384, D = 60 + J = 4, N = 16 384), and writes profiles/glm_hier_bench.json
 with the accept rates of all sides.  Window lengths per side as for --model softmax (HIER_SHAPES).
 
+--model hier --parametrisation noncentred times the non-centred HierarchicalGLM (k_glm<NT, FAM, true, GLM_HIER_NC>) against
+the centred kernel on the same data (started at the same points in its own coordinates) and against the same non-centred
+model as a CustomPotential, all three alternating in one process, at the two shapes above, and writes
+profiles/glm_hier_nc_bench.json (HIER_NC_SHAPES: each parametrisation has the step size that suits its geometry; the cost
+of a step does not depend on it).
+
 usage: tools/bench_glm.py [--shape small|large|all] [--K 32] [--repeats 5] [--glm-only] [--out FILE]
        tools/bench_glm.py --model rich [--custom] [--label NAME] [--shape ...]
        tools/bench_glm.py --model softmax [--shape k3|k8|k8large|all]
        tools/bench_glm.py --model dispersion [--shape small|large|all]
-       tools/bench_glm.py --model hier [--shape small|large|all]
+       tools/bench_glm.py --model hier [--parametrisation centred|noncentred] [--shape small|large|all]  (noncentred: also mid)
 """
 import argparse
 import json
@@ -471,6 +477,120 @@ def bench_hier(name, M, D, J, N, h, L, per_call, window, repeats, warm):
     return out
 
 
+# the non-centred hierarchical model as user source: prm as for HIER_LOGISTIC_SOURCE; a grouped row of the state holds z_j
+# with w_j = mu_j + exp(t_k) z_j
+HIER_NC_LOGISTIC_SOURCE = """
+template <class Q>
+PBBI_FN T coef(const Q& q, int j, const T* mu, const T* grp, const T* sig) {
+    const int k = (int)grp[j];
+    return k < 0 ? q[j] : mu[j] + sig[k] * q[j];
+}
+template <class Q>
+PBBI_FN T potential(const Q& q, int DT, const T* prm) {
+    const int M = (int)prm[0], D = (int)prm[1];
+    const T *X = prm + 2, *c = X + (long)M * D, *d = c + M, *o = d + M, *lam = o + M, *mu = lam + DT, *grp = mu + DT;
+    T sig[4] = {1, 1, 1, 1};
+    for (int k = 0; k < DT - D; ++k) sig[k] = exp(q[D + k]);
+    T s = 0;
+    for (int i = 0; i < M; ++i) {
+        if (c[i] == 0 && d[i] == 0) continue;
+        T z = o[i];
+        for (int j = 0; j < D; ++j) z += X[i * D + j] * coef(q, j, mu, grp, sig);
+        s += c[i] * ((z > 0 ? z : T(0)) + log1p(exp(-fabs(z)))) - d[i] * z;
+    }
+    T r = 0;
+    for (int j = 0; j < D; ++j) {
+        const T e = q[j] - mu[j];
+        if ((int)grp[j] < 0) { r += lam[j] * e * e; } else { r += q[j] * q[j]; }
+    }
+    for (int j = D; j < DT; ++j) r += lam[j] * (q[j] - mu[j]) * (q[j] - mu[j]);
+    return s + T(0.5) * r;
+}
+template <class Q, class G>
+PBBI_FN void gradient(const Q& q, G& g, int DT, const T* prm) {
+    const int M = (int)prm[0], D = (int)prm[1];
+    const T *X = prm + 2, *c = X + (long)M * D, *d = c + M, *o = d + M, *lam = o + M, *mu = lam + DT, *grp = mu + DT;
+    T sig[4] = {1, 1, 1, 1};
+    for (int k = 0; k < DT - D; ++k) sig[k] = exp(q[D + k]);
+    for (int j = 0; j < D; ++j) g[j] = 0;
+    for (int i = 0; i < M; ++i) {
+        if (c[i] == 0 && d[i] == 0) continue;
+        T z = o[i];
+        for (int j = 0; j < D; ++j) z += X[i * D + j] * coef(q, j, mu, grp, sig);
+        const T w = c[i] / (T(1) + exp(-z)) - d[i];
+        for (int j = 0; j < D; ++j) g[j] += w * X[i * D + j];
+    }
+    for (int j = D; j < DT; ++j) g[j] = lam[j] * (q[j] - mu[j]);
+    for (int j = 0; j < D; ++j) {
+        const int k = (int)grp[j];
+        if (k < 0) { g[j] += lam[j] * (q[j] - mu[j]); } else { g[D + k] += sig[k] * g[j] * q[j]; g[j] = sig[k] * g[j] + q[j]; }
+    }
+}
+"""
+# as HIER_SHAPES, with a step size per parametrisation (h: centred, as there; h_nc: non-centred)
+HIER_NC_SHAPES = {
+    "small": dict(M=256, D=14, J=2, N=65536, h=0.12, h_nc=0.08, per_call=32,
+                  window=dict(noncentred=1024, centred=1024, plugin=64), repeats=5, warm=4),
+    "large": dict(M=16384, D=60, J=4, N=16384, h=0.04, h_nc=0.02, per_call=4,
+                  window=dict(noncentred=48, centred=48, plugin=4), repeats=3, warm=2),
+    # DP = 32, where the non-centred logistic kernel runs one wave per SIMD and the centred one two (not part of "all")
+    "mid": dict(M=2048, D=28, J=4, N=32768, h=0.06, h_nc=0.03, per_call=16,
+                window=dict(noncentred=256, centred=256, plugin=16), repeats=5, warm=4),
+}
+
+
+def hier_nc_setup(M, D, J, N):
+    """hier_problem's data as the keyword arguments of HierarchicalGLM, prm of the user source, and the starts of bench_hier
+    in natural coordinates."""
+    kw, w, t, rs = hier_problem(M, D, J)
+    tprior = (-0.5, 1.0)
+    q0 = np.ascontiguousarray(np.r_[w, t][:, None] + 0.05 * rs.standard_normal((D + J, N)))
+    prm = np.concatenate([[float(M), float(D)], kw["X"].ravel(), kw["weights"] * kw["trials"], kw["weights"] * kw["y"],
+                          kw["offset"], np.r_[np.ones(D), np.full(J, tprior[1])], np.r_[np.zeros(D), np.full(J, tprior[0])],
+                          kw["groups"].astype(float)])
+    return dict(log_scale_prior=tprior, prior_precision=1.0, **kw), prm, q0
+
+
+def bench_hier_nc(name, M, D, J, N, h, h_nc, L, per_call, window, repeats, warm):
+    """The non-centred HierarchicalGLM, the centred one and the non-centred model through CustomPotential alternating in one
+    process: same data and draws, the same starting points (each in its own coordinates)."""
+    from physicsbasedbayesianinference_amd.custom import CustomPotential
+    kw, prm, q0c = hier_nc_setup(M, D, J, N)
+    DT = D + J
+    pot = P.HierarchicalGLM(parametrisation="noncentred", **kw)
+    q0 = np.ascontiguousarray(pot.from_natural(q0c))
+    runners = {"noncentred": Runner(pot, DT, N, q0, h_nc, L, per_call, window["noncentred"]),
+               "centred": Runner(P.HierarchicalGLM(**kw), DT, N, q0c, h, L, per_call, window["centred"]),
+               "plugin": Runner(CustomPotential(DT, HIER_NC_LOGISTIC_SOURCE, prm), DT, N, q0, h_nc, L, per_call, window["plugin"])}
+    for r in runners.values():
+        r.go(warm)
+    torch.cuda.synchronize()
+    series = {k: [] for k in runners}
+    for i in range(repeats):
+        for k, r in runners.items():   # alternating
+            series[k].append(r.timed())
+            print(f"# {name} repeat {i} {k}: {series[k][-1]:.4f} s", flush=True)
+    DP = glm.padded_dim(DT)
+    grads = L + 1
+    out = dict(shape=name, M=M, D=D, J=J, state_dimension=DT, DP=DP, chains=N, L=L, h=dict(centred=h, noncentred=h_nc, plugin=h_nc),
+               iterations_per_call=per_call, iterations_per_window=dict(window), repeats=repeats, warmup_iterations=warm,
+               timing="host clock over whole windows of pbbi_hmc_run calls (synchronised before and after)",
+               accept_rate={k: 1.0 - float(r.rej.float().mean().item()) for k, r in runners.items()})
+    per_it = {}
+    for k, ts in series.items():
+        out[k + "_seconds"] = ts
+        out[k + "_step_chain_per_s"] = [window[k] * L * N / t_ for t_ in ts]
+        per_it[k] = np.array(ts) / window[k]          # seconds per iteration
+    flop_it = 4.0 * M * DP * grads * N
+    out["noncentred_executed_tflops"] = [flop_it / t_ / 1e12 for t_ in per_it["noncentred"]]
+    out["noncentred_share_of_fp64_mfma_peak_executed"] = float(flop_it / np.median(per_it["noncentred"]) / PEAK_F64_MFMA)
+    out["ratio_median"] = float(np.median(per_it["plugin"]) / np.median(per_it["noncentred"]))
+    out["ratio_worst_case"] = float(per_it["plugin"].min() / per_it["noncentred"].max())  # fastest plugin over slowest kernel
+    out["slowest_noncentred_beats_fastest_plugin"] = bool(per_it["noncentred"].max() < per_it["plugin"].min())
+    out["noncentred_over_centred_median"] = float(np.median(per_it["noncentred"]) / np.median(per_it["centred"]))  # reported, not gated
+    return out
+
+
 class Runner:
     def __init__(self, pot, D, N, q0, h, L, K, window=None):
         # K: slabs of the sample / reject buffers = the most iterations one pbbi_hmc_run call may record;
@@ -545,6 +665,8 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=None, help="default 4 (--model softmax: per shape)")
     ap.add_argument("--glm-only", action="store_true")
     ap.add_argument("--model", default="plain", choices=["plain", "rich", "softmax", "dispersion", "hier"])
+    ap.add_argument("--parametrisation", default="centred", choices=["centred", "noncentred"],
+                    help="--model hier: noncentred times the non-centred kernel against the centred one and the plugin")
     ap.add_argument("--custom", action="store_true", help="--model rich: also the full model as a CustomPotential")
     ap.add_argument("--label", default="rich_vs_plain", help="--model rich: key of the record in the output file")
     ap.add_argument("--out", default=None)
@@ -553,8 +675,11 @@ if __name__ == "__main__":
         table, fn, side = {"softmax": (SOFTMAX_SHAPES, bench_softmax, "softmax"),
                            "dispersion": (DISPERSION_SHAPES, bench_dispersion, "dispersion"),
                            "hier": (HIER_SHAPES, bench_hier, "hier")}[a.model]
-        a.out = a.out or os.path.join(ROOT, "profiles", "glm_%s_bench.json" % a.model)
-        names = list(table) if a.shape == "all" else [a.shape]
+        stem = a.model
+        if a.model == "hier" and a.parametrisation == "noncentred":
+            table, fn, side, stem = HIER_NC_SHAPES, bench_hier_nc, "noncentred", "hier_nc"
+        a.out = a.out or os.path.join(ROOT, "profiles", "glm_%s_bench.json" % stem)
+        names = [n for n in table if n != "mid"] if a.shape == "all" else [a.shape]
         results = []
         if os.path.exists(a.out) and a.shape != "all":   # one shape per call: keep the others' records
             with open(a.out) as f:
