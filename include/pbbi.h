@@ -299,6 +299,37 @@ int pbbi_potential_create_glm_hier_ex(int D, int64_t M, const double* X, const d
  * D + j {lam_tj, m_tj}, zeros past D + J; n_out <- n_0 .. n_{J-1}. */
 int pbbi_glm_pack_prior_groups(int D, int J, const double* prior, const double* prior_mean, const int32_t* groups,
                                const double* log_scale_prior, double* out, double* n_out);
+/* Structured group priors: the centred model of pbbi_potential_create_glm_hier with a symmetric positive semi-definite
+ * matrix in each group's quadratic form (k_glm<NT, FAM, true, GLM_HIER_Q>) -- random walks (RW1 / RW2), difference penalties
+ * of splines, ICAR / CAR effects, any correlated effect given by a precision matrix, the smoothing parameter sampled.  With
+ * d_j = (w_d - mu_d) over the members of group j in increasing column order,
+ *     w_j - mu_j | t_j ~ N(0, exp(2 t_j) Q_j^-)                (Q_j possibly rank deficient, r_j = rank(Q_j))
+ *     U(w, t) = sum_i a_i [ n_i b(eta_i) - y_i eta_i ]
+ *             + 0.5 sum_{d: groups_d < 0} lam_d (w_d - mu_d)^2
+ *             + sum_j [ 0.5 exp(-2 t_j) d_j^T Q_j d_j + r_j t_j + 0.5 lam_tj (t_j - m_tj)^2 ]
+ *     dU/dw (members of j) = (likelihood) + exp(-2 t_j) Q_j d_j
+ *     dU/dt_j              = r_j - exp(-2 t_j) d_j^T Q_j d_j + lam_tj (t_j - m_tj)
+ * Q_j = I, r_j = n_j is the model of pbbi_potential_create_glm_hier.  All arguments up to log_scale_prior are that
+ * function's, with its rules.  penalty: a (D x D) row-major matrix in COEFFICIENT indexing -- Q_j on the rows and columns
+ * of the members of group j, the identity on the members of an exchangeable group, zero on fixed rows and between
+ * different groups; entries finite, each block symmetric (max|Q - Q^T| <= 1e-12 max|Q|; (Q + Q^T) / 2 is used), positive
+ * semi-definite (smallest eigenvalue >= -1e-10 x the largest) and not zero.  rank: J values, rank[j] an integer in 1 ..
+ * n_j.  Violations return PBBI_ERR_INVALID before anything is allocated; D + J > 64 or fp32 PBBI_ERR_UNSUPPORTED.  The
+ * device keeps the (DP x DP) image of pbbi_glm_pack_penalty, resident in LDS for the whole launch (8 DP^2 bytes), and the
+ * ranks in the n_j slots of the prior table; Q (w - mu) is one more fp64 MFMA product per gradient evaluation.  The handle
+ * is a GLM handle (same calls served and refused); pbbi_describe_run names the kernel.  Not served: the non-centred
+ * parametrisation, structure across groups, sampled structure (a CAR rho), D + J > 64. */
+int pbbi_potential_create_glm_hier_q(int D, int64_t M, const double* X, const double* y, int family, const double* weights,
+                                     const double* offset, const double* trials, const double* prior,
+                                     const double* prior_mean, const int32_t* groups, int J, const double* log_scale_prior,
+                                     const double* penalty, const double* rank, int dtype, int device, pbbi_potential** out);
+/* The image of the penalty pbbi_potential_create_glm_hier_q uploads, on the HOST (touches no device; checks only D >= 1,
+ * 1 <= J <= 4, D + J <= 128): *len_out <- its length DP * DP in doubles, DP = D + J padded to 16 / 32 / 64 / 128; with
+ * `out` non-NULL (out_len >= that length) the image: one block per 16 rows of Q, each in the order of P1 of
+ * pbbi_glm_pack_design with the rows of Q in the role of observations,
+ *     out[((t * DP/8 + s2) * 64 + lane) * 2 + e] = Q[16 t + (lane & 15)][4 (2 s2 + e) + (lane >> 4)]     t < DP/16, s2 < DP/8
+ * with (Q + Q^T) / 2 for Q; rows and columns >= D are zero. */
+int pbbi_glm_pack_penalty(int D, int J, const double* penalty, double* out, int64_t out_len, int64_t* len_out);
 int pbbi_potential_destroy(pbbi_potential* pot);
 int pbbi_potential_dim(const pbbi_potential* pot);
 int pbbi_potential_dtype(const pbbi_potential* pot);

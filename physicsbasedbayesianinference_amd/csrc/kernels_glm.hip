@@ -71,6 +71,18 @@
 // register, and grouped rows of gacc are multiplied by sig_j (dU/dz_d = sig_j gL_d + z_d).  Kick, evaluation store and
 // energy give a grouped row precision 1 and mean 0 (glm_nc_prior: its mu slot is the mean of w and must not enter the prior
 // of z).  No n_j t_j in U: U_nc(z, t) = U_c(w(z, t), t) - sum_j n_j t_j, the Jacobian of the change of variables.
+//
+// Structured group priors (HIER = GLM_HIER_Q; handles of pbbi_potential_create_glm_hier_q): the centred model with a
+// symmetric PSD matrix in each group's quadratic form, w_j - mu_j | t_j ~ N(0, exp(2 t_j) Q_j^-) -- random walks, ICAR,
+// difference penalties; Q_j = I is the model above.  The host lays the J blocks out as one (D x D) matrix in coefficient
+// indexing (identity on exchangeable groups, zero on fixed rows and between groups) and packs it with the FIRST product's
+// A-fragment writer, one block per 16 rows of Q (glm_pack_penalty): 8 DP^2 bytes that sit in LDS behind plds for the whole
+// launch.  Once per gradient evaluation, after glm_grad: dq[s] = member ? q[s] - mu : 0 (a SELECT on the sign of the lam
+// slot, so a t row or a diverged fixed row never meets a zero of Q as 0 * inf) is the B operand of K-step s exactly as q[s]
+// is for X_b . W, and tile t of Q . dq comes out with register r = row 16t + 4r + g: the state layout, no movement.  Tile by
+// tile the lane adds dq . (Q dq) of its rows to its group sums and tau_j (Q dq) into gacc for member rows, so one tile of
+// the product is live at a time.  dU/dt_j = r_j - tau_j S_j with r_j = rank(Q_j) in the table's {n_j, 0} slot; kick, store
+// and energy apply {lam, mu} to fixed and t rows only (a second select on the sign), the energy adds 0.5 sum_j tau_j S_j.
 #include <cmath>
 #include <cstring>
 #include <type_traits>
@@ -118,11 +130,18 @@ struct GlmPrmHier : GlmPrmRich {  // prior: lam (DP) | mu (DP) | n_j (4, the mem
     int trow0;     // the state row of t_0 (= the coefficient count); t_j is row trow0 + j
     int J;         // groups, 1 .. 4
 };
+// structured group priors: ... | r_j = rank(Q_j) in the n_j slots
+struct GlmPrmHierQ : GlmPrmHier {
+    const double* qimg;  // the (DP x DP) penalty in the first product's A-fragment order, DP / 16 blocks of DP * 16 doubles
+};
 constexpr bool glm_disp(int fam) { return fam == PBBI_GLM_GAUSSIAN || fam == PBBI_GLM_NEGBINOMIAL; }
-// HIER of k_glm: no hierarchical prior, the centred parametrisation (the chain holds w_d), the non-centred one (z_d)
-enum { GLM_HIER_NONE = 0, GLM_HIER_CENTRED = 1, GLM_HIER_NC = 2 };
+// HIER of k_glm: no hierarchical prior, the centred parametrisation (the chain holds w_d), the non-centred one (z_d), the
+// centred one with a penalty matrix in each group's quadratic form
+enum { GLM_HIER_NONE = 0, GLM_HIER_CENTRED = 1, GLM_HIER_NC = 2, GLM_HIER_Q = 3 };
 template <int FAM, bool RICH, int HIER = GLM_HIER_NONE>
-struct GlmArgs { using type = std::conditional_t<HIER != GLM_HIER_NONE, GlmPrmHier, GlmPrm>; };
+struct GlmArgs {
+    using type = std::conditional_t<HIER == GLM_HIER_Q, GlmPrmHierQ, std::conditional_t<HIER != GLM_HIER_NONE, GlmPrmHier, GlmPrm>>;
+};
 template <int FAM>
 struct GlmArgs<FAM, true, GLM_HIER_NONE> { using type = std::conditional_t<glm_disp(FAM), GlmPrmDisp, GlmPrmRich>; };
 enum { GLM_HMC = 0, GLM_INTEGRATE = 1, GLM_EVAL = 2, GLM_ENERGY = 3, GLM_RATIO = 4 };
@@ -375,7 +394,8 @@ __device__ __forceinline__ void glm_grad(const typename GlmArgs<FAM, RICH, HIER>
 // series sit in vector registers beside the state (the scalar file is full), and held to 256 registers it spills; at DP
 // = 128 it spills even with all 512 and is not instantiated (glm_build_disp refuses that shape).
 // Likewise the non-centred logistic kernel at DP = 32: q, its scaled copy and the link's constants need 12 bytes of scratch
-// at 256 registers.
+// at 256 registers.  The structured group priors (GLM_HIER_Q) keep the centred kernels' counts: all six build without scratch
+// at them (profiles/glm_hier_penalty_resources.txt).
 constexpr int glm_waves_per_simd(int NT, int fam, int hier) {
     return (NT <= 2 && !(NT == 2 && (fam == PBBI_GLM_NEGBINOMIAL || (hier == GLM_HIER_NC && fam == PBBI_GLM_LOGISTIC)))) ? 2 : 1;
 }
@@ -390,11 +410,17 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
     constexpr int DP = 16 * NT;
     __shared__ __attribute__((aligned(16))) v2f64 lds[C::CHV];
     __shared__ double ylds[(RICH ? 3 : 1) * C::CB * 16];
-    __shared__ __attribute__((aligned(16))) v2f64 plds[RICH ? DP + (HIER == GLM_HIER_CENTRED ? 4 : 0) : 1];  // RICH: {lam, mu} of each row (else unused); centred HIER: then {n_j, 0}
+    constexpr bool HAS_NJ = HIER == GLM_HIER_CENTRED || HIER == GLM_HIER_Q;
+    // RICH: {lam, mu} of each row (else unused); centred HIER: then {n_j, 0}; HIER_Q: then the penalty's fragments (8 DP^2 bytes)
+    __shared__ __attribute__((aligned(16))) v2f64 plds[RICH ? DP + (HAS_NJ ? 4 : 0) + (HIER == GLM_HIER_Q ? DP * DP / 2 : 0) : 1];
     if constexpr (RICH) {
         for (int i = threadIdx.x; i < DP; i += BLOCK) plds[i] = v2f64{prm.prior[i], prm.prior[DP + i]};
-        if constexpr (HIER == GLM_HIER_CENTRED)
+        if constexpr (HAS_NJ)
             if (threadIdx.x < 4) plds[DP + threadIdx.x] = v2f64{prm.prior[2 * DP + threadIdx.x], 0.0};
+        if constexpr (HIER == GLM_HIER_Q) {
+            const v2f64* __restrict__ qsrc = reinterpret_cast<const v2f64*>(prm.qimg);
+            for (int i = threadIdx.x; i < DP * DP / 2; i += BLOCK) plds[DP + 4 + i] = qsrc[i];
+        }
         __syncthreads();
     }
     const int lane = threadIdx.x & 63;
@@ -478,7 +504,7 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
     const double lam = prm.lam;
     const double h = prm.h;
     double U_old = 0.0, U_new = 0.0;
-    [[maybe_unused]] double htau[4];  // centred HIER: tau_j = exp(-2 t_j) of the evaluation in hand (its store follows the loop)
+    [[maybe_unused]] double htau[4];  // centred HIER, HIER_Q: tau_j = exp(-2 t_j) of the evaluation in hand (its store follows the loop)
     for (int e = 0; e < nev; ++e) {
         double ck = 0.0, hd = 0.0;
         if (traj) {
@@ -564,7 +590,7 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
                 glm_grad<NT, FAM, RICH, HIER>(prm, lds, ylds, lane, g, q, gacc, usum, want_u, none, tnone);
             }
         }
-        [[maybe_unused]] double hnt = 0.0;  // centred HIER: sum_j n_j t_j
+        [[maybe_unused]] double hnt = 0.0;  // centred HIER: sum_j n_j t_j; HIER_Q: sum_j r_j t_j
         if constexpr (HIER == GLM_HIER_CENTRED) {
             // The t rows are J <= 4 consecutive rows, so a lane (rows 4s + g) owns at most one: row trow0 + jo, register
             // so.  It contributes that q to the chain sum of t_jo and 0 to the others' (exact); every lane of the chain
@@ -603,6 +629,70 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
 #pragma unroll
                 for (int r = 0; r < 4; ++r) gacc[t][r] += (4 * t + r == so) ? gown : 0.0;
         }
+        [[maybe_unused]] double hqs = 0.0;  // HIER_Q: sum_j tau_j S_j, S_j = d_j^T Q_j d_j
+        if constexpr (HIER == GLM_HIER_Q) {
+            // t_j to every lane of the chain and tau_j, as in the centred branch -- before the product, whose rows want tau
+            const int jo = (g - prm.trow0) & 3;
+            const int so = (prm.trow0 + jo) >> 2;
+            double th = 0.0;
+#pragma unroll
+            for (int s = 0; s < KS; ++s) th = (s == so) ? q[s] : th;
+            double tj[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                htau[j] = 1.0;
+                tj[j] = 0.0;
+                if (j < prm.J) {
+                    tj[j] = chain_sum(jo == j ? th : 0.0);
+                    htau[j] = exp(-2.0 * tj[j]);
+                }
+            }
+            // the B operand: w - mu on member rows, an exact 0 SELECTED everywhere else (fixed, t and padding rows)
+            double dq[KS];
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                const v2f64 pm = plds[4 * s + g];
+                dq[s] = (pm.x < 0.0) ? q[s] - pm.y : 0.0;
+            }
+            // Q dq tile by tile: register r of tile t is row 16t + 4r + g of this lane's chain.  Consumed at once: the
+            // lane's share of S_j and tau_j (Q dq) into the gradient of member rows.
+            const v2f64* __restrict__ QA = plds + (DP + 4) + lane;
+            double S[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                v4f64 qd = v4f64{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int s2 = 0; s2 < KS / 2; ++s2) {
+                    const v2f64 A = QA[(t * (KS / 2) + s2) * 64];
+                    qd = __builtin_amdgcn_mfma_f64_16x16x4f64(A.x, dq[2 * s2], qd, 0, 0, 0);
+                    qd = __builtin_amdgcn_mfma_f64_16x16x4f64(A.y, dq[2 * s2 + 1], qd, 0, 0, 0);
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double lx = plds[4 * (4 * t + r) + g].x;
+                    const double dqd = dq[4 * t + r] * qd[r];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) S[j] += (lx == -(double)(j + 1)) ? dqd : 0.0;
+                    gacc[t][r] = (lx < 0.0) ? fma(glm_hier_lam(lx, htau), qd[r], gacc[t][r]) : gacc[t][r];
+                }
+            }
+            // dU/dt_j = r_j - tau_j S_j (the t prior's part comes with the row's {lam, mu})
+            double gown = 0.0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (j < prm.J) {
+                    const double Sj = chain_sum(S[j]);
+                    const double rj = plds[DP + j].x;
+                    const double gt = rj - htau[j] * Sj;
+                    gown = (jo == j) ? gt : gown;
+                    hnt = fma(rj, tj[j], hnt);
+                    hqs = fma(htau[j], Sj, hqs);
+                }
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) gacc[t][r] += (4 * t + r == so) ? gown : 0.0;
+        }
         if (want_u) {
             double qq = 0.0;
             if constexpr (HIER == GLM_HIER_NC) {
@@ -621,6 +711,14 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
                     qq = fma(glm_hier_lam(pm.x, htau) * dq, dq, qq);
                 }
                 U_new = (chain_sum(usum) + 0.5 * chain_sum(qq)) + hnt;
+            } else if constexpr (HIER == GLM_HIER_Q) {
+#pragma unroll
+                for (int s = 0; s < KS; ++s) {  // fixed and t rows; the members' quadratic forms are in hqs
+                    const v2f64 pm = plds[4 * s + g];
+                    const double dq = q[s] - pm.y;
+                    qq = (pm.x < 0.0) ? qq : fma(pm.x * dq, dq, qq);
+                }
+                U_new = (chain_sum(usum) + 0.5 * (chain_sum(qq) + hqs)) + hnt;
             } else if constexpr (RICH) {
 #pragma unroll
                 for (int s = 0; s < KS; ++s) {
@@ -652,6 +750,9 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
                 } else if constexpr (HIER == GLM_HIER_CENTRED) {
                     const v2f64 pm = plds[4 * s + g];
                     gt = fma(glm_hier_lam(pm.x, htau), q[s] - pm.y, gacc[t][r]);
+                } else if constexpr (HIER == GLM_HIER_Q) {
+                    const v2f64 pm = plds[4 * s + g];  // a member's prior part is in gacc already
+                    gt = (pm.x < 0.0) ? gacc[t][r] : fma(pm.x, q[s] - pm.y, gacc[t][r]);
                 } else if constexpr (RICH) {
                     const v2f64 pm = plds[4 * s + g];
                     gt = fma(pm.x, q[s] - pm.y, gacc[t][r]);
@@ -678,6 +779,9 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
                     } else if constexpr (HIER == GLM_HIER_CENTRED) {
                         const v2f64 pm = plds[4 * s + g];
                         gt = fma(glm_hier_lam(pm.x, htau), q[s] - pm.y, gacc[t][r]);
+                    } else if constexpr (HIER == GLM_HIER_Q) {
+                        const v2f64 pm = plds[4 * s + g];
+                        gt = (pm.x < 0.0) ? gacc[t][r] : fma(pm.x, q[s] - pm.y, gacc[t][r]);
                     } else if constexpr (RICH) {
                         const v2f64 pm = plds[4 * s + g];
                         gt = fma(pm.x, q[s] - pm.y, gacc[t][r]);
@@ -803,7 +907,8 @@ int glm_launch(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t stream)
     GLM_DISP_CASE(1, PBBI_GLM_NEGBINOMIAL) GLM_DISP_CASE(2, PBBI_GLM_NEGBINOMIAL) GLM_DISP_CASE(4, PBBI_GLM_NEGBINOMIAL)
 #undef GLM_DISP_CASE
     const bool nc = pot->glm_hier_J > 0 && pot->glm_hier_nc;  // handle of pbbi_potential_create_glm_hier_ex, non-centred
-    const bool hier = pot->glm_hier_J > 0 && !nc;             // handle of pbbi_potential_create_glm_hier
+    const bool hq = pot->glm_hier_J > 0 && pot->d_glm_qimg;   // handle of pbbi_potential_create_glm_hier_q
+    const bool hier = pot->glm_hier_J > 0 && !nc && !hq;      // handle of pbbi_potential_create_glm_hier
     GlmPrmHier hprm{};
     static_cast<GlmPrmRich&>(hprm) = rprm;
     hprm.trow0 = pot->D - pot->glm_hier_J;
@@ -824,8 +929,19 @@ int glm_launch(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t stream)
     GLM_NC_CASE(1, PBBI_GLM_LOGISTIC) GLM_NC_CASE(2, PBBI_GLM_LOGISTIC) GLM_NC_CASE(4, PBBI_GLM_LOGISTIC)
     GLM_NC_CASE(1, PBBI_GLM_POISSON) GLM_NC_CASE(2, PBBI_GLM_POISSON) GLM_NC_CASE(4, PBBI_GLM_POISSON)
 #undef GLM_NC_CASE
+    GlmPrmHierQ qprm{};
+    static_cast<GlmPrmHier&>(qprm) = hprm;
+    qprm.qimg = (const double*)pot->d_glm_qimg;
+    if (hq && pot->glm_DP > glm_hier_q_max_dim(pot->glm_family))
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "structured group priors: no kernel at this padded state dimension (internal)");
+#define GLM_HQ_CASE(NT_, FAM_)                                                                              \
+    if (hq && pot->glm_DP == 16 * NT_ && pot->glm_family == FAM_)                                           \
+        hipLaunchKernelGGL((k_glm<NT_, FAM_, true, GLM_HIER_Q>), grid, block, 0, stream, qprm);
+    GLM_HQ_CASE(1, PBBI_GLM_LOGISTIC) GLM_HQ_CASE(2, PBBI_GLM_LOGISTIC) GLM_HQ_CASE(4, PBBI_GLM_LOGISTIC)
+    GLM_HQ_CASE(1, PBBI_GLM_POISSON) GLM_HQ_CASE(2, PBBI_GLM_POISSON) GLM_HQ_CASE(4, PBBI_GLM_POISSON)
+#undef GLM_HQ_CASE
 #define GLM_CASE(NT_, RICH_, PRM_)                                                                          \
-    if (!disp && !hier && !nc && pot->glm_DP == 16 * NT_ && rich == RICH_) {                                \
+    if (!disp && !hier && !nc && !hq && pot->glm_DP == 16 * NT_ && rich == RICH_) {                                \
         if (pot->glm_family == PBBI_GLM_LOGISTIC)                                                           \
             hipLaunchKernelGGL((k_glm<NT_, PBBI_GLM_LOGISTIC, RICH_>), grid, block, 0, stream, PRM_);       \
         else                                                                                                \
@@ -849,6 +965,17 @@ int64_t glm_image_len(int D, int64_t M) { return glm_blocks_padded(M) * (int64_t
 // the file), zero padded to DP columns and to a multiple of 4 blocks.  Host only.
 static void glm_pack_dp(int D, int DP, int64_t M, const double* X, double* out);
 void glm_pack(int D, int64_t M, const double* X, double* out) { glm_pack_dp(D, glm_padded_dim(D), M, X, out); }
+// the first product's A fragments of block b, P1[s2][lane][e] = at(16 b + (lane & 15), 4 (2 s2 + e) + (lane >> 4)): the one
+// statement of that order, for the design (glm_pack_dp) and for the penalty of the structured group priors (glm_pack_penalty)
+template <class At>
+static void glm_pack_p1(int KS, int64_t b, const At& at, double* P1) {
+    for (int l = 0; l < 64; ++l) {
+        const int lo = l & 15, hi = l >> 4;
+        for (int s2 = 0; s2 < KS / 2; ++s2)
+            for (int e = 0; e < 2; ++e)
+                P1[((size_t)s2 * 64 + l) * 2 + e] = at(16 * b + lo, 4 * (2 * s2 + e) + hi);
+    }
+}
 // ... at a padded dimension DP >= D of the caller's: the image of [X | 0]
 static void glm_pack_dp(int D, int DP, int64_t M, const double* X, double* out) {
     const int NT = DP / 16, KS = DP / 4;
@@ -859,11 +986,9 @@ static void glm_pack_dp(int D, int DP, int64_t M, const double* X, double* out) 
     for (int64_t b = 0; b < (M + 15) / 16; ++b) {
         double* P1 = out + b * blk_len;
         double* P2 = P1 + (int64_t)KS * 64;
+        glm_pack_p1(KS, b, at, P1);
         for (int l = 0; l < 64; ++l) {
             const int lo = l & 15, hi = l >> 4;
-            for (int s2 = 0; s2 < KS / 2; ++s2)
-                for (int e = 0; e < 2; ++e)
-                    P1[((size_t)s2 * 64 + l) * 2 + e] = at(16 * b + lo, 4 * (2 * s2 + e) + hi);
             for (int r2 = 0; r2 < 2; ++r2)
                 for (int t = 0; t < NT; ++t)
                     for (int e = 0; e < 2; ++e)
@@ -1113,13 +1238,107 @@ void glm_pack_prior_groups(int D, int J, const double* lam, const double* mu, co
     }
 }
 
-// the caller has run glm_check_obs and glm_check_hier; pot->D = Dx + J
+// ---- host side: structured group priors ----------------------------------------------------------------------------
+// the largest state dimension the kernels k_glm<NT, FAM, true, GLM_HIER_Q> serve: NT = 1, 2, 4 build without scratch for both
+// families (profiles/glm_hier_penalty_resources.txt); there is no centred kernel at 128 rows to extend
+int glm_hier_q_max_dim(int family) { return (family == PBBI_GLM_LOGISTIC || family == PBBI_GLM_POISSON) ? 64 : 0; }
+
+int64_t glm_penalty_image_len(int D, int J) { const int64_t DP = glm_padded_dim(D + J); return DP * DP; }
+
+// The eigenvalues of a symmetric n x n matrix (row-major in a, destroyed) by cyclic Jacobi rotations, into ev.  n <= 63 here.
+static void glm_sym_eigenvalues(int n, std::vector<double>& a, std::vector<double>& ev) {
+    for (int sweep = 0; sweep < 64; ++sweep) {
+        double off = 0.0, diag = 0.0;
+        for (int i = 0; i < n; ++i)
+            for (int k = 0; k < n; ++k) (i == k ? diag : off) += a[(size_t)i * n + k] * a[(size_t)i * n + k];
+        if (off <= 1e-30 * diag || off == 0.0) break;
+        for (int p = 0; p < n - 1; ++p)
+            for (int q = p + 1; q < n; ++q) {
+                const double apq = a[(size_t)p * n + q];
+                if (apq == 0.0) continue;
+                const double theta = (a[(size_t)q * n + q] - a[(size_t)p * n + p]) / (2.0 * apq);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < n; ++k) {  // columns p, q
+                    const double akp = a[(size_t)k * n + p], akq = a[(size_t)k * n + q];
+                    a[(size_t)k * n + p] = c * akp - s * akq;
+                    a[(size_t)k * n + q] = s * akp + c * akq;
+                }
+                for (int k = 0; k < n; ++k) {  // rows p, q
+                    const double apk = a[(size_t)p * n + k], aqk = a[(size_t)q * n + k];
+                    a[(size_t)p * n + k] = c * apk - s * aqk;
+                    a[(size_t)q * n + k] = s * apk + c * aqk;
+                }
+            }
+    }
+    ev.resize((size_t)n);
+    for (int i = 0; i < n; ++i) ev[(size_t)i] = a[(size_t)i * n + i];
+}
+
+// Every rule of the penalty of the structured group priors: a (D x D) row-major matrix in coefficient indexing, finite,
+// zero on fixed rows and between different groups, each group's block symmetric to 1e-12 of its largest entry, positive
+// semi-definite (smallest eigenvalue >= -1e-10 x the largest) and not zero; rank[j] an integer in 1 .. n_j.  The caller has
+// run glm_check_hier.
+int glm_check_penalty(int D, int J, const int32_t* groups, const double* penalty, const double* rank) {
+    if (!penalty) return pbbi_fail(PBBI_ERR_INVALID, "penalty is NULL");
+    if (!rank) return pbbi_fail(PBBI_ERR_INVALID, "penalty_rank is NULL");
+    for (int a = 0; a < D; ++a)
+        for (int b = 0; b < D; ++b) {
+            const double v = penalty[(size_t)a * D + b];
+            if (!std::isfinite(v))
+                return pbbi_fail(PBBI_ERR_INVALID, "penalty must be finite (entry " + std::to_string(a) + ", " + std::to_string(b) + ")");
+            if (v != 0.0 && (groups[a] < 0 || groups[a] != groups[b]))
+                return pbbi_fail(PBBI_ERR_INVALID, "penalty must be zero on fixed rows and between different groups (entry " +
+                                                       std::to_string(a) + ", " + std::to_string(b) + ")");
+        }
+    for (int j = 0; j < J; ++j) {
+        std::vector<int> idx;
+        for (int d = 0; d < D; ++d)
+            if (groups[d] == j) idx.push_back(d);
+        const int n = (int)idx.size();
+        const std::string grp = " (group " + std::to_string(j) + ")";
+        double big = 0.0, asym = 0.0;
+        std::vector<double> blk((size_t)n * n);
+        for (int a = 0; a < n; ++a)
+            for (int b = 0; b < n; ++b) {
+                const double v = penalty[(size_t)idx[a] * D + idx[b]], vt = penalty[(size_t)idx[b] * D + idx[a]];
+                big = std::fmax(big, std::fabs(v));
+                asym = std::fmax(asym, std::fabs(v - vt));
+                blk[(size_t)a * n + b] = 0.5 * (v + vt);
+            }
+        if (big == 0.0) return pbbi_fail(PBBI_ERR_INVALID, "penalty must not be the zero matrix" + grp);
+        if (asym > 1e-12 * big) return pbbi_fail(PBBI_ERR_INVALID, "penalty must be symmetric" + grp);
+        std::vector<double> ev;
+        glm_sym_eigenvalues(n, blk, ev);
+        double lo = ev[0], hi = ev[0];
+        for (double v : ev) { lo = std::fmin(lo, v); hi = std::fmax(hi, v); }
+        if (!(hi > 0.0) || lo < -1e-10 * hi)
+            return pbbi_fail(PBBI_ERR_INVALID, "penalty must be positive semi-definite" + grp);
+        if (!std::isfinite(rank[j]) || rank[j] != std::floor(rank[j]) || rank[j] < 1.0 || rank[j] > (double)n)
+            return pbbi_fail(PBBI_ERR_INVALID, "penalty_rank must be an integer in 1 .. n_j" + grp);
+    }
+    return PBBI_OK;
+}
+
+// The image of the (DP x DP) penalty the kernel keeps in LDS, DP = glm_padded_dim(D + J): DP / 16 blocks of 16 rows, each in
+// the first product's A-fragment order (glm_pack_p1), (Q + Q^T) / 2 on rows and columns < D and zero beyond.  Host only.
+void glm_pack_penalty(int D, int J, const double* penalty, double* out) {
+    const int DP = glm_padded_dim(D + J), KS = DP / 4;
+    auto at = [&](int64_t i, int d) -> double {
+        return (i < D && d < D) ? 0.5 * (penalty[(size_t)i * D + d] + penalty[(size_t)d * D + i]) : 0.0;
+    };
+    for (int b = 0; b < DP / 16; ++b) glm_pack_p1(KS, b, at, out + (size_t)b * KS * 64);
+}
+
+// the caller has run glm_check_obs and glm_check_hier (and glm_check_penalty where penalty is given); pot->D = Dx + J.
+// penalty != NULL: the structured group priors (centred only), rank[j] into the table's n_j slots.
 int glm_build_hier(pbbi_potential* pot, int Dx, int64_t M, const double* X, const double* y, int family,
                    const double* weights, const double* offset, const double* trials, const double* lam, const double* mu,
-                   const int32_t* groups, int J, const double* tprior, int parametrisation) {
+                   const int32_t* groups, int J, const double* tprior, int parametrisation, const double* penalty,
+                   const double* rank) {
     const int Dt = pot->D;
     const bool nc = parametrisation == PBBI_HIER_NONCENTRED;
-    const int dmax = nc ? glm_hier_nc_max_dim(family) : glm_hier_max_dim(family);
+    const int dmax = penalty ? glm_hier_q_max_dim(family) : nc ? glm_hier_nc_max_dim(family) : glm_hier_max_dim(family);
     if (pot->dtype != PBBI_F64 || Dt > dmax)
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, "hierarchical GLM potentials: float64 and a state dimension (coefficients + "
                                                "groups) <= " + std::to_string(dmax) + " only (" +
@@ -1133,6 +1352,14 @@ int glm_build_hier(pbbi_potential* pot, int Dx, int64_t M, const double* X, cons
     std::vector<double> prior((size_t)2 * DP + 4, 0.0);  // lam | mu | n_j
     double* nj = prior.data() + 2 * DP;
     glm_pack_prior_groups(Dx, J, lam, mu, groups, tprior, prior.data(), nj);
+    for (int j = 0; j < 4; ++j) pot->glm_hier_n[j] = nj[j];
+    if (penalty) {
+        for (int j = 0; j < J; ++j) nj[j] = pot->glm_hier_rank[j] = rank[j];  // r_j t_j: the normaliser of a rank-r_j Gaussian
+        std::vector<double> qimg((size_t)glm_penalty_image_len(Dx, J));
+        glm_pack_penalty(Dx, J, penalty, qimg.data());
+        PBBI_HIP(hipMalloc(&pot->d_glm_qimg, qimg.size() * sizeof(double)));
+        PBBI_HIP(hipMemcpy(pot->d_glm_qimg, qimg.data(), qimg.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
     PBBI_HIP(hipMalloc(&pot->d_glm_img, img.size() * sizeof(double)));
     PBBI_HIP(hipMalloc(&pot->d_glm_obs, obs.size() * sizeof(double)));
     PBBI_HIP(hipMalloc(&pot->d_glm_prior, prior.size() * sizeof(double)));
@@ -1146,7 +1373,6 @@ int glm_build_hier(pbbi_potential* pot, int Dx, int64_t M, const double* X, cons
     pot->glm_terms = (weights ? GLM_TERM_WEIGHTS : 0) | (offset ? GLM_TERM_OFFSET : 0) | (trials ? GLM_TERM_TRIALS : 0);
     pot->glm_hier_J = J;
     pot->glm_hier_nc = nc ? 1 : 0;
-    for (int j = 0; j < 4; ++j) pot->glm_hier_n[j] = nj[j];
     return PBBI_OK;
 }
 

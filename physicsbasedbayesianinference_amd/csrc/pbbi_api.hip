@@ -99,6 +99,8 @@ int new_handle(int kind, int D, int dtype, int device, pbbi_potential** out) {
     p->glm_hier_J = 0;
     p->glm_hier_nc = 0;
     for (double& n : p->glm_hier_n) n = 0.0;
+    p->d_glm_qimg = nullptr;
+    for (double& r : p->glm_hier_rank) r = 0.0;
     *out = p;
     return PBBI_OK;
 }
@@ -869,6 +871,39 @@ int pbbi_potential_create_glm_hier_ex(int D, int64_t M, const double* X, const d
                                             groups, J, log_scale_prior, parametrisation), out);
 }
 
+int pbbi_potential_create_glm_hier_q(int D, int64_t M, const double* X, const double* y, int family, const double* weights,
+                                     const double* offset, const double* trials, const double* prior_precision,
+                                     const double* prior_mean, const int32_t* groups, int J, const double* log_scale_prior,
+                                     const double* penalty, const double* rank, int dtype, int device, pbbi_potential** out) {
+    if (out) *out = nullptr;
+    if (!X || !y) return pbbi_fail(PBBI_ERR_INVALID, "X / y is NULL");
+    if (int rc = glm_check_hier(D, J, prior_precision, prior_mean, groups, log_scale_prior)) return rc;
+    if (int rc = glm_check_obs(M, family, y, weights, offset, trials)) return rc;
+    for (int64_t i = 0; i < M * D; ++i)
+        if (!std::isfinite(X[i])) return pbbi_fail(PBBI_ERR_INVALID, "X must be finite");
+    if (int rc = glm_check_penalty(D, J, groups, penalty, rank)) return rc;
+    if (dtype != PBBI_F64) return pbbi_fail(PBBI_ERR_UNSUPPORTED, "hierarchical GLM potentials are float64 only");
+    if (D + J > glm_hier_q_max_dim(family))
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "structured group priors: the state dimension (coefficients + groups) must be <= " +
+                                                   std::to_string(glm_hier_q_max_dim(family)) + " (" + std::to_string(D + J) + ")");
+    if (int rc = new_handle(KIND_GLM, D + J, dtype, device, out)) return rc;
+    DeviceGuard guard(device);
+    return finish_or_destroy(glm_build_hier(*out, D, M, X, y, family, weights, offset, trials, prior_precision, prior_mean,
+                                            groups, J, log_scale_prior, PBBI_HIER_CENTRED, penalty, rank), out);
+}
+
+int pbbi_glm_pack_penalty(int D, int J, const double* penalty, double* out, int64_t out_len, int64_t* len_out) {
+    if (D < 1 || J < 1 || J > 4 || D + J > 128)
+        return pbbi_fail(PBBI_ERR_INVALID, "need D >= 1, 1 <= J <= 4 and D + J <= 128");
+    const int64_t len = glm_penalty_image_len(D, J);
+    if (len_out) *len_out = len;
+    if (!out) return PBBI_OK;
+    if (!penalty) return pbbi_fail(PBBI_ERR_INVALID, "penalty is NULL");
+    if (out_len < len) return pbbi_fail(PBBI_ERR_INVALID, "out is shorter than the image");
+    glm_pack_penalty(D, J, penalty, out);
+    return PBBI_OK;
+}
+
 int pbbi_glm_pack_prior_groups(int D, int J, const double* prior_precision, const double* prior_mean, const int32_t* groups,
                                const double* log_scale_prior, double* out, double* n_out) {
     if (int rc = glm_check_hier(D, J, prior_precision, prior_mean, groups, log_scale_prior)) return rc;
@@ -923,7 +958,8 @@ int pbbi_potential_destroy(pbbi_potential* pot) {
     if (!pot) return PBBI_OK;
     DeviceGuard guard(pot->device);
     for (void* p : {pot->d_mean, pot->d_prec, pot->d_frag, pot->d_mean_pad, pot->d_big_PT, pot->d_big_mu,
-                    pot->d_sfrag, pot->d_smean, pot->d_params, pot->d_glm_img, pot->d_glm_y, pot->d_glm_obs, pot->d_glm_prior})
+                    pot->d_sfrag, pot->d_smean, pot->d_params, pot->d_glm_img, pot->d_glm_y, pot->d_glm_obs, pot->d_glm_prior,
+                    pot->d_glm_qimg})
         if (p) (void)hipFree(p);
     if (pot->plugin) (void)dlclose(pot->plugin);
     delete pot;
@@ -1295,6 +1331,10 @@ int pbbi_describe_run(const pbbi_potential* pot, int method, int64_t N, int64_t 
                  ", each read by one chain sum per gradient, ";
             d += pot->glm_hier_nc ? "non-centred: grouped rows hold z with w = mu + exp(t) z, the first product runs on a scaled "
                                     "copy of the state, the group sums of gL z reduced per chain)"
+                  : pot->d_glm_qimg ? "structured group priors, k_glm<NT, FAM, true, GLM_HIER_Q>: the (" +
+                                          std::to_string(pot->glm_DP) + " x " + std::to_string(pot->glm_DP) + ") penalty resident in "
+                                          "LDS in A-fragment order, Q (w - mu) one more fp64 MFMA product per gradient whose result "
+                                          "lands in the state layout, the quadratic forms d^T Q d reduced per chain)"
                                   : "the group sums of squares reduced per chain)";
             d += (t & GLM_TERM_WEIGHTS) ? ", weights" : "";
             d += (t & GLM_TERM_OFFSET) ? ", offset" : "";

@@ -68,6 +68,9 @@ struct pbbi_potential {
     double glm_hier_n[4];  // members of each group
     // ... in the non-centred parametrisation (pbbi_potential_create_glm_hier_ex), k_glm<NT, FAM, true, GLM_HIER_NC>.  (Appended.)
     int glm_hier_nc;       // 1: the grouped rows of the state hold z_d, w_d = mu_d + exp(t_j) z_d
+    // ... with structured group priors (pbbi_potential_create_glm_hier_q), k_glm<NT, FAM, true, GLM_HIER_Q>.  (Appended.)
+    void* d_glm_qimg;      // the (glm_DP x glm_DP) penalty in A-fragment order (glm_pack_penalty); NULL = not such a handle
+    double glm_hier_rank[4];  // rank(Q_j), what the table's n_j slots hold on such a handle
 };
 
 // ---- error plumbing ---------------------------------------------------------
@@ -293,7 +296,12 @@ void glm_pack_prior_groups(int D, int J, const double* lam, const double* mu, co
                            double* out, double* n_out);        // host only
 int glm_build_hier(pbbi_potential* pot, int Dx, int64_t M, const double* X, const double* y, int family,
                    const double* weights, const double* offset, const double* trials, const double* lam, const double* mu,
-                   const int32_t* groups, int J, const double* tprior, int parametrisation);
+                   const int32_t* groups, int J, const double* tprior, int parametrisation, const double* penalty = nullptr,
+                   const double* rank = nullptr);
+int glm_hier_q_max_dim(int family);  // ... the structured group priors' (k_glm<NT, FAM, true, GLM_HIER_Q>)
+int glm_check_penalty(int D, int J, const int32_t* groups, const double* penalty, const double* rank);
+int64_t glm_penalty_image_len(int D, int J);                   // doubles of the fragment image of the (DP x DP) penalty
+void glm_pack_penalty(int D, int J, const double* penalty, double* out);  // host only
 int glm_padded_dim(int D);
 int64_t glm_image_len(int D, int64_t M);                       // doubles of the fragment image of an M x D design matrix
 void glm_pack(int D, int64_t M, const double* X, double* out);  // host only

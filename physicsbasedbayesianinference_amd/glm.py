@@ -27,7 +27,8 @@ unknown noise and negative-binomial (NB2) counts, the log-dispersion either samp
 chain's state or held at a given value.
 
 `HierarchicalGLM` is the full model with hierarchical priors: blocks of coefficients (random intercepts, random slopes,
-a ridge penalty of unknown strength) share a prior scale that is sampled, on the log scale, as a further row of the state.
+a ridge penalty of unknown strength) share a prior scale that is sampled, on the log scale, as a further row of the state.  With `penalty=` a group's prior is structured: a symmetric positive semi-definite matrix Q_j
+in its quadratic form (random walks, difference penalties of splines, ICAR), Q_j (w - mu) one more product on the matrix cores.
 """
 import ctypes as C
 
@@ -38,7 +39,7 @@ from .potential import Potential, _dptr
 
 __all__ = ["GLM", "SoftmaxGLM", "DispersionGLM", "HierarchicalGLM", "FAMILIES", "DISPERSION_FAMILIES", "HIER_MAX_DIM",
            "HIER_NC_MAX_DIM", "HIER_PARAMETRISATIONS", "HIER_MAX_GROUPS", "pack_design", "pack_observations", "pack_observations_dispersion", "pack_prior_groups",
-           "padded_dim", "softmax_layout"]
+           "HIER_Q_MAX_DIM", "pack_penalty", "padded_dim", "softmax_layout"]
 
 FAMILIES = {"logistic": _lib.GLM_LOGISTIC, "poisson": _lib.GLM_POISSON}
 DISPERSION_FAMILIES = {"gaussian": _lib.GLM_GAUSSIAN, "negbinomial": _lib.GLM_NEGBINOMIAL}   # DispersionGLM only
@@ -52,6 +53,9 @@ HIER_MAX_DIM = {"logistic": 64, "poisson": 64}
 # ... in the non-centred parametrisation (k_glm<NT, FAM, true, GLM_HIER_NC>): the scaled copy of the state costs KS more
 # registers, and the kernels at 64 rows still build without scratch for both families
 HIER_NC_MAX_DIM = {"logistic": 64, "poisson": 64}
+# ... with a penalty matrix (k_glm<NT, FAM, true, GLM_HIER_Q>, centred only): the kernels at 16, 32 and 64 rows build without
+# scratch for both families; there is no centred kernel at 128 rows to extend
+HIER_Q_MAX_DIM = {"logistic": 64, "poisson": 64}
 HIER_PARAMETRISATIONS = {"centred": _lib.HIER_CENTRED, "noncentred": _lib.HIER_NONCENTRED}
 HIER_MAX_GROUPS = 4
 
@@ -492,6 +496,114 @@ def pack_prior_groups(groups, log_scale_prior=(0.0, 1.0), prior_precision=1.0, p
     return out.reshape(2, DP), n
 
 
+def _penalty_blocks(penalty, penalty_rank, groups, J):
+    """(blocks, ranks, full): the J checked and symmetrised matrices (None for an exchangeable group), the J ranks (n_j for an
+    exchangeable group) and the (D, D) matrix in coefficient indexing the C ABI takes (identity on exchangeable groups, zero
+    on fixed rows and between groups) -- or (None, None, None) when no group has a penalty."""
+    if penalty is None:
+        if penalty_rank is not None:
+            raise ValueError("penalty_rank belongs to a penalty: none is given")
+        return None, None, None
+    if isinstance(penalty, dict):
+        for j in penalty:
+            if not (isinstance(j, (int, np.integer)) and 0 <= j < J):
+                raise ValueError("penalty is given for group %r, which is not used (groups 0 .. %d)" % (j, J - 1))
+        blocks = [penalty.get(j) for j in range(J)]
+    else:
+        try:
+            blocks = list(penalty)
+        except TypeError:
+            raise ValueError("penalty must be a dict {group: matrix} or a length-J sequence with None for exchangeable "
+                             "groups") from None
+        if len(blocks) != J:
+            raise ValueError("penalty must have one entry per group used, J = %d (got %d): None for an exchangeable group"
+                             % (J, len(blocks)))
+    if isinstance(penalty_rank, dict):
+        for j in penalty_rank:
+            if not (isinstance(j, (int, np.integer)) and 0 <= j < J):
+                raise ValueError("penalty_rank is given for group %r, which is not used (groups 0 .. %d)" % (j, J - 1))
+        given = [penalty_rank.get(j) for j in range(J)]
+    elif penalty_rank is None:
+        given = [None] * J
+    else:
+        try:
+            given = list(penalty_rank)
+        except TypeError:
+            raise ValueError("penalty_rank must be a dict {group: rank} or a length-J sequence") from None
+        if len(given) != J:
+            raise ValueError("penalty_rank must have one entry per group used, J = %d (got %d)" % (J, len(given)))
+    if all(b is None for b in blocks):
+        if any(r is not None for r in given):
+            raise ValueError("penalty_rank belongs to a penalty: none is given")
+        return None, None, None
+    D = groups.size
+    full = np.zeros((D, D))
+    ranks = np.zeros(J, dtype=np.int64)
+    out = []
+    for j in range(J):
+        idx = np.flatnonzero(groups == j)
+        n = idx.size
+        if blocks[j] is None:
+            if given[j] is not None:
+                raise ValueError("penalty_rank[%d] is given for a group without a penalty" % j)
+            full[idx, idx] = 1.0
+            ranks[j] = n
+            out.append(None)
+            continue
+        try:
+            Q = np.array(blocks[j], dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("penalty[%d] must be an (n_j, n_j) matrix of numbers" % j) from None
+        if Q.shape != (n, n):
+            raise ValueError("penalty[%d] must be (n_j, n_j) = (%d, %d), ordered as the members of the group by column "
+                             "(shape %s)" % (j, n, n, Q.shape))
+        if not np.all(np.isfinite(Q)):
+            raise ValueError("penalty[%d] must be finite" % j)
+        big = float(np.max(np.abs(Q)))
+        if big == 0.0:
+            raise ValueError("penalty[%d] is the zero matrix: no prior at all" % j)
+        if float(np.max(np.abs(Q - Q.T))) > 1e-12 * big:
+            raise ValueError("penalty[%d] must be symmetric (max|Q - Q^T| <= 1e-12 max|Q|)" % j)
+        Q = 0.5 * (Q + Q.T)
+        ev = np.linalg.eigvalsh(Q)
+        if not (ev[-1] > 0.0 and ev[0] >= -1e-10 * ev[-1]):
+            raise ValueError("penalty[%d] must be positive semi-definite (smallest eigenvalue %.3g, largest %.3g)"
+                             % (j, ev[0], ev[-1]))
+        if given[j] is None:
+            r = int(np.sum(ev > 1e-10 * ev[-1]))
+        else:
+            r = given[j]
+            if isinstance(r, (bool, np.bool_)) or not isinstance(r, (int, np.integer, float, np.floating)) \
+                    or not np.isfinite(r) or r != int(r) or not 1 <= int(r) <= n:
+                raise ValueError("penalty_rank[%d] must be an integer in 1 .. n_j = %d (got %r)" % (j, n, r))
+            r = int(r)
+        full[np.ix_(idx, idx)] = Q
+        ranks[j] = r
+        out.append(Q)
+    return out, ranks, np.ascontiguousarray(full)
+
+
+def pack_penalty(penalty, J):
+    """The image of the penalty a HierarchicalGLM handle with structured group priors keeps on the device and its kernel in
+    LDS, computed on the host by libpbbi.so (no GPU involved).  `penalty` is the (D, D) matrix in coefficient indexing (Q_j on
+    the members of group j, the identity on an exchangeable group, zero on fixed rows and between groups), `J` the number of
+    groups.  Returns an array (DP/16, DP/8, 64, 2) with DP = padded_dim(D + J): per block t of 16 rows of Q the A fragments of
+    the product Q_t . (w - mu) in the order of `pack_design`'s first product, [s2][lane][e] = Q[16 t + (lane & 15)][4 (2 s2 +
+    e) + (lane >> 4)]; rows and columns >= D are zero."""
+    Q = np.ascontiguousarray(penalty, dtype=np.float64)
+    if Q.ndim != 2 or Q.shape[0] != Q.shape[1] or Q.shape[0] < 1:
+        raise ValueError("penalty must be a square (D, D) matrix (shape %s)" % (Q.shape,))
+    D, J = Q.shape[0], int(J)
+    if not 1 <= J <= HIER_MAX_GROUPS:
+        raise ValueError("J must be 1 .. %d (got %d)" % (HIER_MAX_GROUPS, J))
+    DP = padded_dim(D + J)
+    n = C.c_int64()
+    _lib.call("pbbi_glm_pack_penalty", D, J, None, None, 0, C.byref(n))
+    out = np.empty(n.value, dtype=np.float64)
+    _lib.call("pbbi_glm_pack_penalty", D, J, _dptr(Q), _dptr(out), out.size, C.byref(n))
+    return out.reshape(DP // 16, DP // 8, 64, 2)
+
+
 class HierarchicalGLM(Potential):
     """-log posterior of a GLM (family "logistic" or "poisson", the full model of `GLM`: weights a_i, trials n_i,
     offsets o_i, eta_i = x_i . w + o_i) in which blocks of coefficients share a prior scale that is sampled:
@@ -534,6 +646,32 @@ class HierarchicalGLM(Potential):
     and `RunningStats` of a non-centred potential are in SAMPLER coordinates (z on the grouped rows); `to_natural` maps
     them to (w; t), `from_natural` back, and `split` returns w and the scales on the natural scale for both forms.
 
+    Structured group priors (`penalty=`, centred only).  The priors above are exchangeable: independent members.  With a
+    symmetric positive semi-definite matrix Q_j in the quadratic form of group j,
+
+        w_j - mu_j | t_j ~ N(0, exp(2 t_j) Q_j^-),    d_j = (w_d - mu_d) over the members of j in increasing column order
+        U(w, t) = ... + sum_j [ 0.5 exp(-2 t_j) d_j^T Q_j d_j + r_j t_j + 0.5 lam_tj (t_j - m_tj)^2 ],    r_j = rank(Q_j)
+
+    the same class serves penalised splines and additive models (a difference penalty, the smoothing parameter sampled),
+    random-walk effects over time, ICAR spatial effects and any correlated effect given by a precision matrix:
+
+        groups = np.r_[-1, np.zeros(12, int)]                                              # an intercept, twelve months
+        pot = HierarchicalGLM(X, y, groups=groups, penalty={0: HierarchicalGLM.random_walk_penalty(12, 2)})
+        pot = HierarchicalGLM.with_random_intercepts(X, y, region, penalty=HierarchicalGLM.icar_penalty(adjacency))
+
+    `penalty` is a dict {j: Q_j} or a length-J sequence with None for the groups that stay exchangeable (Q_j = I, r_j = n_j:
+    the model above exactly); Q_j is (n_j, n_j), finite, symmetric to 1e-12 of its largest entry (it is then symmetrised),
+    positive semi-definite (smallest eigenvalue >= -1e-10 of the largest) and not zero.  It may be rank deficient (an
+    improper prior, as RW2 and ICAR are: the data or a fixed row must then pin the null space).  `penalty_rank` gives r_j
+    (same forms, an integer in 1 .. n_j); by default it is the number of eigenvalues above 1e-10 of the largest
+    (`numpy.linalg.eigvalsh`).  `penalty=None`, or None for every group, is the exchangeable model on the kernels and with
+    the bits it always had.  `pot.penalty` (the J symmetrised matrices or None) and `pot.penalty_rank` are kept.  Helpers, all
+    on the host: `HierarchicalGLM.random_walk_penalty(n, order)`, `HierarchicalGLM.icar_penalty(adjacency)`, and
+    `glm.pack_penalty` (the image the kernel keeps in LDS).  Q_j (w - mu) is one more product on the matrix cores per
+    gradient evaluation (k_glm<NT, FAM, true, GLM_HIER_Q>), the matrix resident in LDS; D + J <= 64 (`HIER_Q_MAX_DIM`).
+    Not served with a penalty: `parametrisation="noncentred"` (it would need w = mu + exp(t) L^-T z with Q = L L^T),
+    structure across groups, sampled structure such as the rho of a proper CAR prior.
+
     Not served: a per-group choice of parametrisation, sampled group scales on `DispersionGLM` and `SoftmaxGLM`, more than 4
     groups, group means as parameters, per-chain trajectory lengths and GIST (they raise as for `GLM`).  Shapes:
     float64; D + J <= 64 for both families and both parametrisations (`HIER_MAX_DIM`, `HIER_NC_MAX_DIM`: the kernels for
@@ -548,7 +686,7 @@ class HierarchicalGLM(Potential):
 
     def __init__(self, X, y, family="logistic", groups=None, log_scale_prior=(0.0, 1.0), prior_precision=1.0,
                  prior_mean=None, weights=None, offset=None, trials=None, dtype="float64", device=None,
-                 parametrisation="centred"):
+                 parametrisation="centred", penalty=None, penalty_rank=None):
         if not isinstance(parametrisation, str) or parametrisation not in HIER_PARAMETRISATIONS:
             raise ValueError("parametrisation must be \"centred\" or \"noncentred\" (got %r)" % (parametrisation,))
         if groups is None:
@@ -557,7 +695,11 @@ class HierarchicalGLM(Potential):
         X, y, _, _, a, o, n = _validate(X, y, family, 0.0, dtype, None, weights, offset, trials)
         M, D = X.shape
         groups, J, tp, lam, mu = _hier_prior(D, groups, log_scale_prior, prior_precision, prior_mean)
-        dmax = (HIER_NC_MAX_DIM if parametrisation == "noncentred" else HIER_MAX_DIM)[family]
+        Qs, ranks, Qfull = _penalty_blocks(penalty, penalty_rank, groups, J)
+        if Qs is not None and parametrisation != "centred":
+            raise ValueError("penalty is served by parametrisation=\"centred\" only (the non-centred form of a structured "
+                             "prior, w = mu + exp(t) L^-T z, is not built)")
+        dmax = (HIER_Q_MAX_DIM if Qs is not None else HIER_NC_MAX_DIM if parametrisation == "noncentred" else HIER_MAX_DIM)[family]
         if D + J > dmax:
             raise ValueError("HierarchicalGLM(family=%r) serves a state dimension (coefficients + groups) <= %d (got %d + %d)"
                              % (family, dmax, D, J))
@@ -569,7 +711,13 @@ class HierarchicalGLM(Potential):
         self.groups, self.log_scale_prior = groups, tp
         self.numCoefficients, self.numGroups = D, J
         self.levels = None
-        if parametrisation == "centred":    # the entry point, and so the kernel, every call had before the keyword existed
+        self.penalty, self.penalty_rank = Qs, ranks
+        if Qs is not None:
+            rk = np.ascontiguousarray(ranks, dtype=np.float64)
+            _lib.call("pbbi_potential_create_glm_hier_q", D, M, _dptr(X), _dptr(y), FAMILIES[family], _dptr(a), _dptr(o),
+                      _dptr(n), _dptr(lam), _dptr(mu), groups.ctypes.data_as(C.POINTER(C.c_int32)), J, _dptr(tp), _dptr(Qfull),
+                      _dptr(rk), self._dt, self.device, C.byref(self._handle))
+        elif parametrisation == "centred":    # the entry point, and so the kernel, every call had before the keyword existed
             _lib.call("pbbi_potential_create_glm_hier", D, M, _dptr(X), _dptr(y), FAMILIES[family], _dptr(a), _dptr(o),
                       _dptr(n), _dptr(lam), _dptr(mu), groups.ctypes.data_as(C.POINTER(C.c_int32)), J, _dptr(tp), self._dt,
                       self.device, C.byref(self._handle))
@@ -645,19 +793,61 @@ class HierarchicalGLM(Potential):
         onehot[np.arange(M), idx] = 1.0
         return np.hstack([X, onehot]), np.r_[base, np.full(levels.size, new, dtype=np.int64)], levels
 
+    @staticmethod
+    def random_walk_penalty(n, order=1):
+        """D^T D of the order-th difference matrix D ((n - order, n)): the precision structure of a first- or second-order
+        random walk over n ordered levels (RW1 / RW2), the difference penalty of a P-spline.  (n, n), banded, rank n - order:
+        constants (and for order 2 linear trends) are not penalised."""
+        if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)):
+            raise ValueError("random_walk_penalty: n must be an integer (got %r)" % (n,))
+        if order not in (1, 2) or isinstance(order, (bool, np.bool_)):
+            raise ValueError("random_walk_penalty: order must be 1 or 2 (got %r)" % (order,))
+        if n <= order:
+            raise ValueError("random_walk_penalty: n must be > order (n = %d, order = %d)" % (n, order))
+        Dm = np.diff(np.eye(int(n)), n=int(order), axis=0)
+        return Dm.T @ Dm
+
+    @staticmethod
+    def icar_penalty(adjacency):
+        """diag(A 1) - A for a symmetric 0/1 adjacency matrix A with zero diagonal: the intrinsic conditional autoregressive
+        (ICAR) structure over the nodes of a graph.  (n, n), rank n - (number of connected components).  Asymmetric
+        adjacencies, other entries than 0 and 1, self-loops and isolated nodes raise ValueError."""
+        A = np.asarray(adjacency, dtype=np.float64)
+        if A.ndim != 2 or A.shape[0] != A.shape[1] or A.shape[0] < 2:
+            raise ValueError("icar_penalty: adjacency must be a square (n, n) matrix with n >= 2 (shape %s)" % (A.shape,))
+        if not np.all((A == 0.0) | (A == 1.0)):
+            raise ValueError("icar_penalty: adjacency must hold 0 and 1 only")
+        if not np.array_equal(A, A.T):
+            raise ValueError("icar_penalty: adjacency must be symmetric")
+        if np.any(np.diag(A) != 0.0):
+            raise ValueError("icar_penalty: adjacency must have a zero diagonal")
+        deg = A.sum(axis=1)
+        if np.any(deg == 0.0):
+            raise ValueError("icar_penalty: node %d is isolated (no neighbour): give it a group of its own or drop it"
+                             % int(np.flatnonzero(deg == 0.0)[0]))
+        return np.diag(deg) - A
+
     @classmethod
-    def with_random_intercepts(cls, X, y, labels, **kw):
+    def with_random_intercepts(cls, X, y, labels, penalty=None, penalty_rank=None, **kw):
         """The model with one random intercept per distinct value of `labels` (M,): a one-hot column per level is
         appended to X and those columns form one new group, after any groups given in `kw` (whose `groups`,
         `prior_precision` and `prior_mean` vectors cover the columns of X; the new columns get mean 0).  Built on the
         host; `pot.levels` keeps the sorted label values, in the order of the appended columns.  `parametrisation` and
-        every other keyword of the constructor pass through: few observations per level want "noncentred"."""
+        every other keyword of the constructor pass through: few observations per level want "noncentred".  `penalty` (and
+        `penalty_rank`) is the matrix Q of the NEW group, (levels, levels) in the order of the sorted label values -- e.g.
+        `icar_penalty(adjacency)` over regions, `random_walk_penalty(levels, 1)` over ordered periods (centred only)."""
         Xh, groups, levels = cls.random_intercept_design(X, labels, kw.pop("groups", None))
         D, K = np.asarray(X).shape[1], levels.size
         for name, fill in (("prior_precision", 0.0), ("prior_mean", 0.0)):
             v = kw.get(name)
             if v is not None and np.ndim(v) == 1:
                 kw[name] = np.r_[_vector(v, D, name, "D"), np.full(K, fill)]
+        if penalty is not None:
+            kw["penalty"] = {int(groups[-1]): penalty}
+            if penalty_rank is not None:
+                kw["penalty_rank"] = {int(groups[-1]): penalty_rank}
+        elif penalty_rank is not None:
+            raise ValueError("penalty_rank belongs to a penalty: none is given")
         pot = cls(Xh, y, groups=groups, **kw)
         pot.levels = levels
         return pot

@@ -36,10 +36,17 @@ model as a CustomPotential, all three alternating in one process, at the two sha
 profiles/glm_hier_nc_bench.json (HIER_NC_SHAPES: each parametrisation has the step size that suits its geometry; the cost
 of a step does not depend on it).
 
+--model hierq times HierarchicalGLM with structured group priors (k_glm<NT, FAM, true, GLM_HIER_Q>: logistic, an RW2 penalty on
+every group) against HierarchicalGLM with the same groups and no penalty (the centred kernel it extends) and against the same
+structured model as a CustomPotential, all three alternating in one process, at the two shapes of --model hier, and writes
+profiles/glm_hier_penalty_bench.json: the project's criterion (the slowest repeat of the kernel beats the fastest of the plugin)
+and the ratio to the centred kernel next to what the MFMA counts predict, 1 + (DP^2 / 64) / (M DP / 32) = 1 + DP / (2 M).
+
 usage: tools/bench_glm.py [--shape small|large|all] [--K 32] [--repeats 5] [--glm-only] [--out FILE]
        tools/bench_glm.py --model rich [--custom] [--label NAME] [--shape ...]
        tools/bench_glm.py --model softmax [--shape k3|k8|k8large|all]
        tools/bench_glm.py --model dispersion [--shape small|large|all]
+       tools/bench_glm.py --model hierq [--shape small|large|all]
        tools/bench_glm.py --model hier [--parametrisation centred|noncentred] [--shape small|large|all]  (noncentred: also mid)
 """
 import argparse
@@ -591,6 +598,117 @@ def bench_hier_nc(name, M, D, J, N, h, h_nc, L, per_call, window, repeats, warm)
     return out
 
 
+# the structured model as user source: prm = [M, D, X, c, d, o, lam(D + J), mu(D + J), groups(D), Q(D x D), rank(J)], Q in
+# coefficient indexing (zero between groups)
+HIERQ_LOGISTIC_SOURCE = """
+template <class Q>
+PBBI_FN T potential(const Q& q, int DT, const T* prm) {
+    const int M = (int)prm[0], D = (int)prm[1];
+    const T *X = prm + 2, *c = X + (long)M * D, *d = c + M, *o = d + M, *lam = o + M, *mu = lam + DT, *grp = mu + DT;
+    const T *P = grp + D, *rank = P + (long)D * D;
+    T s = 0;
+    for (int i = 0; i < M; ++i) {
+        if (c[i] == 0 && d[i] == 0) continue;
+        T z = o[i];
+        for (int j = 0; j < D; ++j) z += X[i * D + j] * q[j];
+        s += c[i] * ((z > 0 ? z : T(0)) + log1p(exp(-fabs(z)))) - d[i] * z;
+    }
+    T r = 0;
+    for (int j = 0; j < D; ++j) {
+        const int k = (int)grp[j];
+        const T e = q[j] - mu[j];
+        if (k < 0) { r += lam[j] * e * e; continue; }
+        T pe = 0;
+        for (int l = 0; l < D; ++l) if ((int)grp[l] == k) pe += P[j * D + l] * (q[l] - mu[l]);
+        r += exp(-2 * q[D + k]) * e * pe;
+    }
+    for (int j = D; j < DT; ++j) { r += lam[j] * (q[j] - mu[j]) * (q[j] - mu[j]); s += rank[j - D] * q[j]; }
+    return s + T(0.5) * r;
+}
+template <class Q, class G>
+PBBI_FN void gradient(const Q& q, G& g, int DT, const T* prm) {
+    const int M = (int)prm[0], D = (int)prm[1];
+    const T *X = prm + 2, *c = X + (long)M * D, *d = c + M, *o = d + M, *lam = o + M, *mu = lam + DT, *grp = mu + DT;
+    const T *P = grp + D, *rank = P + (long)D * D;
+    for (int j = D; j < DT; ++j) g[j] = rank[j - D] + lam[j] * (q[j] - mu[j]);
+    for (int j = 0; j < D; ++j) {
+        const int k = (int)grp[j];
+        const T e = q[j] - mu[j];
+        if (k < 0) { g[j] = lam[j] * e; continue; }
+        T pe = 0;
+        for (int l = 0; l < D; ++l) if ((int)grp[l] == k) pe += P[j * D + l] * (q[l] - mu[l]);
+        const T tau = exp(-2 * q[D + k]);
+        g[j] = tau * pe;
+        g[D + k] -= tau * e * pe;
+    }
+    for (int i = 0; i < M; ++i) {
+        if (c[i] == 0 && d[i] == 0) continue;
+        T z = o[i];
+        for (int j = 0; j < D; ++j) z += X[i * D + j] * q[j];
+        const T w = c[i] / (T(1) + exp(-z)) - d[i];
+        for (int j = 0; j < D; ++j) g[j] += w * X[i * D + j];
+    }
+}
+"""
+# as HIER_SHAPES (the same data and groups); h: the exchangeable side, h_q: the structured sides (an RW2 penalty's largest
+# eigenvalue is 16: the stiffest direction is four times as stiff)
+HIERQ_SHAPES = {
+    "small": dict(M=256, D=14, J=2, N=65536, h=0.12, h_q=0.03, per_call=32,
+                  window=dict(hierq=1024, hier=1024, plugin=32), repeats=5, warm=4),
+    "large": dict(M=16384, D=60, J=4, N=16384, h=0.04, h_q=0.01, per_call=4,
+                  window=dict(hierq=48, hier=48, plugin=4), repeats=3, warm=2),
+}
+
+
+def bench_hierq(name, M, D, J, N, h, h_q, L, per_call, window, repeats, warm):
+    """HierarchicalGLM with an RW2 penalty on every group, the same groups without a penalty (the centred kernel) and the
+    structured model through CustomPotential alternating in one process: same data, starts and draws."""
+    from physicsbasedbayesianinference_amd.custom import CustomPotential
+    kw, prm0, q0 = hier_nc_setup(M, D, J, N)
+    DT = D + J
+    groups = kw["groups"]
+    penalty = {j: P.HierarchicalGLM.random_walk_penalty(int(np.sum(groups == j)), 2) for j in range(J)}
+    pot = P.HierarchicalGLM(penalty=penalty, **kw)
+    full = np.zeros((D, D))
+    for j in range(J):
+        idx = np.flatnonzero(groups == j)
+        full[np.ix_(idx, idx)] = penalty[j]
+    prm = np.concatenate([prm0, full.ravel(), np.asarray(pot.penalty_rank, dtype=np.float64)])
+    runners = {"hierq": Runner(pot, DT, N, q0, h_q, L, per_call, window["hierq"]),
+               "hier": Runner(P.HierarchicalGLM(**kw), DT, N, q0, h, L, per_call, window["hier"]),
+               "plugin": Runner(CustomPotential(DT, HIERQ_LOGISTIC_SOURCE, prm), DT, N, q0, h_q, L, per_call, window["plugin"])}
+    for r in runners.values():
+        r.go(warm)
+    torch.cuda.synchronize()
+    series = {k: [] for k in runners}
+    for i in range(repeats):
+        for k, r in runners.items():   # alternating
+            series[k].append(r.timed())
+            print(f"# {name} repeat {i} {k}: {series[k][-1]:.4f} s", flush=True)
+    DP = glm.padded_dim(DT)
+    grads = L + 1
+    out = dict(shape=name, M=M, D=D, J=J, state_dimension=DT, DP=DP, chains=N, L=L, h=dict(hierq=h_q, hier=h, plugin=h_q),
+               penalty="RW2 on every group", penalty_rank=[int(r) for r in pot.penalty_rank],
+               iterations_per_call=per_call, iterations_per_window=dict(window), repeats=repeats, warmup_iterations=warm,
+               timing="host clock over whole windows of pbbi_hmc_run calls (synchronised before and after)",
+               accept_rate={k: 1.0 - float(r.rej.float().mean().item()) for k, r in runners.items()})
+    per_it = {}
+    for k, ts in series.items():
+        out[k + "_seconds"] = ts
+        out[k + "_step_chain_per_s"] = [window[k] * L * N / t_ for t_ in ts]
+        per_it[k] = np.array(ts) / window[k]          # seconds per iteration
+    flop_it = (4.0 * M * DP + 2.0 * DP * DP) * grads * N
+    out["hierq_executed_tflops"] = [flop_it / t_ / 1e12 for t_ in per_it["hierq"]]
+    out["hierq_share_of_fp64_mfma_peak_executed"] = float(flop_it / np.median(per_it["hierq"]) / PEAK_F64_MFMA)
+    out["ratio_median"] = float(np.median(per_it["plugin"]) / np.median(per_it["hierq"]))
+    out["ratio_worst_case"] = float(per_it["plugin"].min() / per_it["hierq"].max())  # fastest plugin over slowest kernel
+    out["slowest_hierq_beats_fastest_plugin"] = bool(per_it["hierq"].max() < per_it["plugin"].min())
+    out["hierq_over_hier_median"] = float(np.median(per_it["hierq"]) / np.median(per_it["hier"]))
+    out["hierq_over_hier_range"] = [float(per_it["hierq"].min() / per_it["hier"].max()), float(per_it["hierq"].max() / per_it["hier"].min())]
+    out["hierq_over_hier_predicted_by_mfma_count"] = 1.0 + DP / (2.0 * M)   # (DP^2 / 64) / (M DP / 32) more MFMAs per gradient
+    return out
+
+
 class Runner:
     def __init__(self, pot, D, N, q0, h, L, K, window=None):
         # K: slabs of the sample / reject buffers = the most iterations one pbbi_hmc_run call may record;
@@ -664,18 +782,19 @@ if __name__ == "__main__":
     ap.add_argument("--repeats", type=int, default=None, help="default 5 (--model softmax: per shape)")
     ap.add_argument("--warmup", type=int, default=None, help="default 4 (--model softmax: per shape)")
     ap.add_argument("--glm-only", action="store_true")
-    ap.add_argument("--model", default="plain", choices=["plain", "rich", "softmax", "dispersion", "hier"])
+    ap.add_argument("--model", default="plain", choices=["plain", "rich", "softmax", "dispersion", "hier", "hierq"])
     ap.add_argument("--parametrisation", default="centred", choices=["centred", "noncentred"],
                     help="--model hier: noncentred times the non-centred kernel against the centred one and the plugin")
     ap.add_argument("--custom", action="store_true", help="--model rich: also the full model as a CustomPotential")
     ap.add_argument("--label", default="rich_vs_plain", help="--model rich: key of the record in the output file")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.model in ("softmax", "dispersion", "hier"):
+    if a.model in ("softmax", "dispersion", "hier", "hierq"):
         table, fn, side = {"softmax": (SOFTMAX_SHAPES, bench_softmax, "softmax"),
                            "dispersion": (DISPERSION_SHAPES, bench_dispersion, "dispersion"),
-                           "hier": (HIER_SHAPES, bench_hier, "hier")}[a.model]
-        stem = a.model
+                           "hier": (HIER_SHAPES, bench_hier, "hier"),
+                           "hierq": (HIERQ_SHAPES, bench_hierq, "hierq")}[a.model]
+        stem = "hier_penalty" if a.model == "hierq" else a.model
         if a.model == "hier" and a.parametrisation == "noncentred":
             table, fn, side, stem = HIER_NC_SHAPES, bench_hier_nc, "noncentred", "hier_nc"
         a.out = a.out or os.path.join(ROOT, "profiles", "glm_%s_bench.json" % stem)
