@@ -299,6 +299,50 @@ int pbbi_potential_create_glm_hier_ex(int D, int64_t M, const double* X, const d
  * D + j {lam_tj, m_tj}, zeros past D + J; n_out <- n_0 .. n_{J-1}. */
 int pbbi_glm_pack_prior_groups(int D, int J, const double* prior, const double* prior_mean, const int32_t* groups,
                                const double* log_scale_prior, double* out, double* n_out);
+/* Random effects for the dispersion families: the likelihood of pbbi_potential_create_glm_dispersion (gaussian, negbinomial;
+ * theta the LOG-dispersion, weights a_i >= 0, offsets o_i, eta_i = x_i . w + o_i) under the priors of
+ * pbbi_potential_create_glm_hier_ex (csrc/kernels_glm.hip, k_glm<NT, FAM, true, GLM_HIER_CENTRED / GLM_HIER_NC> with FAM = 3, 4)
+ * -- the linear mixed model with unknown residual sigma, its held-sigma form with weights 1 / sigma_i^2 (eight schools),
+ * NB2 counts with a random intercept per site:
+ *     gaussian     U_i = a_i [ 0.5 exp(-2 theta) (y_i - eta_i)^2 + theta ]
+ *     negbinomial  U_i = a_i [ lgamma(phi) - lgamma(y_i + phi) - phi theta - y_i eta_i + (y_i + phi) logaddexp(eta_i, theta) ],
+ *                  phi = exp(theta)
+ *     centred:     U = sum_i U_i + 0.5 sum_{d: groups_d < 0} lam_d (w_d - mu_d)^2
+ *                    + sum_j [ 0.5 exp(-2 t_j) S_j + n_j t_j + 0.5 lam_tj (t_j - m_tj)^2 ]
+ *                    + 0.5 lam_theta (theta - m_theta)^2                        (the last term only when theta is sampled)
+ *     noncentred:  grouped rows hold z_d, w_d = mu_d + exp(t_j) z_d;  U_nc(z, t, theta) = U_c(w(z, t), t, theta) - sum_j n_j t_j
+ * State: rows 0 .. D-1 the coefficients (z_d on grouped rows when non-centred), rows D .. D+J-1 t_0 .. t_{J-1}, and with
+ * sample != 0 row D+J theta, the LAST row; the handle's dimension is D + J + (sample ? 1 : 0).  sample == 0: the dispersion
+ * is held at exp(theta) (theta finite) and the state is [w; t].  The design image on the device is that of [X | 0] at the
+ * padded state dimension, so eta sees neither the t rows nor the theta row.
+ * Arguments: X, y, family, weights, offset with the rules of pbbi_potential_create_glm_dispersion (y finite; negbinomial: non-
+ * negative integers; weights finite >= 0 or NULL; offset finite or NULL; X finite); prior (D doubles, the entries of grouped
+ * coefficients ignored), prior_mean (D doubles or NULL = 0), groups (D entries, -1 or 0 .. J-1, every index used), J (1 .. 4,
+ * else PBBI_ERR_UNSUPPORTED), log_scale_prior (J pairs (m_tj, lam_tj >= 0)) and parametrisation with the rules of
+ * pbbi_potential_create_glm_hier_ex; log_dispersion_prior: the pair (m_theta, lam_theta >= 0) when sample != 0 (`theta` is then
+ * ignored), NULL when sample == 0 (a held dispersion has no prior: non-NULL is PBBI_ERR_INVALID).  Families logistic and
+ * poisson are PBBI_ERR_INVALID here (they are pbbi_potential_create_glm_hier / _hier_ex).  Violations of the value rules return
+ * PBBI_ERR_INVALID before anything is allocated; fp32, or D + J + (sample ? 1 : 0) above
+ * pbbi_glm_hier_dispersion_max_dim(family, parametrisation), PBBI_ERR_UNSUPPORTED.  A kernel is shipped only if it builds
+ * without register spills to memory; all twelve of 16, 32 and 64 rows do, and there is none at 128 rows (64 for both
+ * families and both parametrisations).  The handle is a GLM handle (same calls served and refused: no per-chain trajectory
+ * lengths, no GIST); pbbi_describe_run names the family, the dispersion row or held value, the groups and the parametrisation.
+ * Not served: structured group priors (a penalty matrix) for these families. */
+int pbbi_potential_create_glm_hier_dispersion(int D, int64_t M, const double* X, const double* y, int family,
+                                              const double* weights, const double* offset, const double* prior,
+                                              const double* prior_mean, const int32_t* groups, int J,
+                                              const double* log_scale_prior, int parametrisation, int sample, double theta,
+                                              const double* log_dispersion_prior, int dtype, int device, pbbi_potential** out);
+/* The prior table pbbi_potential_create_glm_hier_dispersion uploads and its kernel keeps in LDS, on the HOST (touches no
+ * device, checks the same rules): out <- lam (DP) | mu (DP) with DP = D + J + (sample ? 1 : 0) padded to 16, 32, 64 or 128 --
+ * rows 0 .. D+J-1 as pbbi_glm_pack_prior_groups writes them, row D + J {lam_theta, m_theta} when sample != 0 (a fixed row: its
+ * lam slot is >= 0), zeros past the state; n_out <- n_0 .. n_{J-1}. */
+int pbbi_glm_pack_prior_groups_dispersion(int D, int J, const double* prior, const double* prior_mean, const int32_t* groups,
+                                          const double* log_scale_prior, int sample, const double* log_dispersion_prior,
+                                          double* out, double* n_out);
+/* The largest state dimension D + J + (sample ? 1 : 0) pbbi_potential_create_glm_hier_dispersion serves for a family
+ * (PBBI_GLM_GAUSSIAN, PBBI_GLM_NEGBINOMIAL) and parametrisation; 0 for any other argument.  Returns the number, not a status. */
+int pbbi_glm_hier_dispersion_max_dim(int family, int parametrisation);
 /* Structured group priors: the centred model of pbbi_potential_create_glm_hier with a symmetric positive semi-definite
  * matrix in each group's quadratic form (k_glm<NT, FAM, true, GLM_HIER_Q>) -- random walks (RW1 / RW2), difference penalties
  * of splines, ICAR / CAR effects, any correlated effect given by a precision matrix, the smoothing parameter sampled.  With

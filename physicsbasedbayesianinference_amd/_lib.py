@@ -72,6 +72,10 @@ PROTOTYPES = {
     "pbbi_potential_create_glm_hier_q": [_i, _i64, _dp, _dp, _i, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32), _i, _dp,
                                          _dp, _dp, _i, _i, _pp],
     "pbbi_glm_pack_penalty": [_i, _i, _dp, _dp, _i64, C.POINTER(C.c_int64)],
+    "pbbi_potential_create_glm_hier_dispersion": [_i, _i64, _dp, _dp, _i, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32), _i, _dp,
+                                                  _i, _i, _d, _dp, _i, _i, _pp],
+    "pbbi_glm_pack_prior_groups_dispersion": [_i, _i, _dp, _dp, C.POINTER(C.c_int32), _dp, _i, _dp, _dp, _dp],
+    "pbbi_glm_hier_dispersion_max_dim": [_i, _i],   # returns the dimension, not a status
     "pbbi_potential_destroy": [_vp],
     "pbbi_potential_dim": [_vp],
     "pbbi_potential_dtype": [_vp],

@@ -83,6 +83,17 @@
 // tile the lane adds dq . (Q dq) of its rows to its group sums and tau_j (Q dq) into gacc for member rows, so one tile of
 // the product is live at a time.  dU/dt_j = r_j - tau_j S_j with r_j = rank(Q_j) in the table's {n_j, 0} slot; kick, store
 // and energy apply {lam, mu} to fixed and t rows only (a second select on the sign), the energy adds 0.5 sum_j tau_j S_j.
+//
+// Random effects for the dispersion families (FAM = 3, 4 with HIER = GLM_HIER_CENTRED / GLM_HIER_NC; handles of
+// pbbi_potential_create_glm_hier_dispersion): the two paragraphs above composed.  The state is [w; t_0 .. t_{J-1}; theta], theta
+// LAST when it is sampled (row trow = trow0 + J) and from the arguments when it is held; the table in plds is lam (DP) | mu
+// (DP) | n_j with DP the padded D + J + sampled, the theta row a fixed row {lam_theta, m_theta} behind a zero column of the
+// image.  Per evaluation: theta is broadcast and glm_disp_chain formed BEFORE glm_grad, whatever HIER is; the t rows are
+// broadcast as above (a lane owns at most one t row; for J = 4 the lane group of t_0 owns theta too, one register on -- the two
+// broadcasts select on their own (s, g) and share nothing); chain_sum(tsum) goes into gacc at theta's owner LAST, after the
+// non-centred branch has taken G[j] from gacc and scaled its grouped rows (the theta row is fixed, so either order is exact;
+// this one keeps the dispersion kernels' sequence of operations).  Nothing else is new: weff leaves the theta row as q, S_j and
+// G_j select on the group codes and never see it, kick / store / energy give it its {lam, mu} like any fixed row.
 #include <cmath>
 #include <cstring>
 #include <type_traits>
@@ -130,6 +141,11 @@ struct GlmPrmHier : GlmPrmRich {  // prior: lam (DP) | mu (DP) | n_j (4, the mem
     int trow0;     // the state row of t_0 (= the coefficient count); t_j is row trow0 + j
     int J;         // groups, 1 .. 4
 };
+// random effects for the dispersion families: the hierarchical prior's arguments plus theta; trow0 + J == trow when sampled
+struct GlmPrmHierDisp : GlmPrmHier {
+    double theta;  // the held log-dispersion (trow < 0)
+    int trow;      // the state row of theta when it is sampled (the LAST row), -1 when it is held
+};
 // structured group priors: ... | r_j = rank(Q_j) in the n_j slots
 struct GlmPrmHierQ : GlmPrmHier {
     const double* qimg;  // the (DP x DP) penalty in the first product's A-fragment order, DP / 16 blocks of DP * 16 doubles
@@ -140,7 +156,8 @@ constexpr bool glm_disp(int fam) { return fam == PBBI_GLM_GAUSSIAN || fam == PBB
 enum { GLM_HIER_NONE = 0, GLM_HIER_CENTRED = 1, GLM_HIER_NC = 2, GLM_HIER_Q = 3 };
 template <int FAM, bool RICH, int HIER = GLM_HIER_NONE>
 struct GlmArgs {
-    using type = std::conditional_t<HIER == GLM_HIER_Q, GlmPrmHierQ, std::conditional_t<HIER != GLM_HIER_NONE, GlmPrmHier, GlmPrm>>;
+    using type = std::conditional_t<HIER == GLM_HIER_Q, GlmPrmHierQ,
+                                    std::conditional_t<HIER != GLM_HIER_NONE, std::conditional_t<glm_disp(FAM), GlmPrmHierDisp, GlmPrmHier>, GlmPrm>>;
 };
 template <int FAM>
 struct GlmArgs<FAM, true, GLM_HIER_NONE> { using type = std::conditional_t<glm_disp(FAM), GlmPrmDisp, GlmPrmRich>; };
@@ -396,6 +413,8 @@ __device__ __forceinline__ void glm_grad(const typename GlmArgs<FAM, RICH, HIER>
 // Likewise the non-centred logistic kernel at DP = 32: q, its scaled copy and the link's constants need 12 bytes of scratch
 // at 256 registers.  The structured group priors (GLM_HIER_Q) keep the centred kernels' counts: all six build without scratch
 // at them (profiles/glm_hier_penalty_resources.txt).
+// The dispersion families with a hierarchical prior (centred and non-centred) need no case of their own: all twelve build without
+// scratch at their families' counts (profiles/glm_hier_dispersion_resources.txt).
 constexpr int glm_waves_per_simd(int NT, int fam, int hier) {
     return (NT <= 2 && !(NT == 2 && (fam == PBBI_GLM_NEGBINOMIAL || (hier == GLM_HIER_NC && fam == PBBI_GLM_LOGISTIC)))) ? 2 : 1;
 }
@@ -404,7 +423,8 @@ constexpr int glm_waves_per_simd(int NT, int fam, int hier) {
 template <int NT, int FAM, bool RICH, int HIER = GLM_HIER_NONE>
 __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_glm(typename GlmArgs<FAM, RICH, HIER>::type prm) {
     static_assert(RICH || !glm_disp(FAM), "the dispersion families live on the full model's frame");
-    static_assert(HIER == GLM_HIER_NONE || (RICH && !glm_disp(FAM)), "the hierarchical prior lives on the full model's frame");
+    static_assert(HIER == GLM_HIER_NONE || RICH, "the hierarchical prior lives on the full model's frame");
+    static_assert(HIER != GLM_HIER_Q || !glm_disp(FAM), "structured group priors: logistic and poisson only");
     using C = GlmCfg<NT>;
     constexpr int KS = C::KS;
     constexpr int DP = 16 * NT;
@@ -518,77 +538,79 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
         ck *= minv;
         const bool want_u = (e == 0 || e == nev - 1) && mode != GLM_INTEGRATE;
         double usum;
+        // the dispersion families: theta to every lane of the chain and what is formed from it, before the likelihood walk
+        [[maybe_unused]] int ts = -1, tg = 0;
+        [[maybe_unused]] GlmDispChain dk{};
+        [[maybe_unused]] double tsum = 0.0;
         if constexpr (glm_disp(FAM)) {
             // theta: the owner of its row contributes q[s], everybody else 0 (exact); held: from the arguments
-            const int ts = prm.trow >> 2, tg = prm.trow & 3;  // trow = -1: no s matches
+            ts = prm.trow >> 2, tg = prm.trow & 3;  // trow = -1: no s matches
             double th = 0.0;
 #pragma unroll
             for (int s = 0; s < KS; ++s) th = (s == ts) ? q[s] : th;
             th = chain_sum(g == tg ? th : 0.0);
             if (prm.trow < 0) th = prm.theta;
-            const GlmDispChain dk = glm_disp_chain<FAM>(th, want_u);
-            double tsum;
-            glm_grad<NT, FAM, RICH>(prm, lds, ylds, lane, g, q, gacc, usum, want_u, dk, tsum);
+            dk = glm_disp_chain<FAM>(th, want_u);
+        }
+        if constexpr (HIER == GLM_HIER_NC) {
+            // The chain holds z_d on a grouped row: w_d = mu_d + sig_j z_d is what the likelihood sees.  The t_j reach
+            // every lane of the chain as below (the owner contributes, the others add exact zeros); weff, the B operand
+            // of the first product, is a scaled COPY of the state -- q itself is what the drift, the stores and the prior
+            // work on, and scaling in place and back is not exact.
+            const int jo = (g - prm.trow0) & 3;
+            const int so = (prm.trow0 + jo) >> 2;
+            double th = 0.0;
+#pragma unroll
+            for (int s = 0; s < KS; ++s) th = (s == so) ? q[s] : th;
+            double sig[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                sig[j] = 1.0;
+                if (j < prm.J) sig[j] = exp(chain_sum(jo == j ? th : 0.0));
+            }
+            double weff[KS];
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                const v2f64 pm = plds[4 * s + g];
+                weff[s] = (pm.x < 0.0) ? fma(glm_hier_lam(pm.x, sig), q[s], pm.y) : q[s];
+            }
+            glm_grad<NT, FAM, RICH, HIER>(prm, lds, ylds, lane, g, weff, gacc, usum, want_u, dk, tsum);
+            // dU/dt_j = sig_j sum_{d in j} gL_d z_d (this lane's rows here, the chain's below) goes to the owner's
+            // register; dU/dz_d = sig_j gL_d (the priors' parts come with the rows below)
+            double G[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                const v2f64 pm = plds[4 * s + g];
+                const double gz = gacc[s >> 2][s & 3] * q[s];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) G[j] += (pm.x == -(double)(j + 1)) ? gz : 0.0;
+            }
+            double gown = 0.0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (j < prm.J) {
+                    const double gt = chain_sum(G[j]) * sig[j];
+                    gown = (jo == j) ? gt : gown;
+                }
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double lx = plds[4 * (4 * t + r) + g].x;
+                    const double gs = (lx < 0.0) ? gacc[t][r] * glm_hier_lam(lx, sig) : gacc[t][r];
+                    gacc[t][r] = gs + ((4 * t + r == so) ? gown : 0.0);
+                }
+        } else {
+            glm_grad<NT, FAM, RICH, HIER>(prm, lds, ylds, lane, g, q, gacc, usum, want_u, dk, tsum);
+        }
+        if constexpr (glm_disp(FAM)) {
+            // dU/dtheta's likelihood part at theta's owner -- after the non-centred branch has read and scaled gacc
             tsum = chain_sum(tsum);
             tsum = (g == tg) ? tsum : 0.0;
 #pragma unroll
             for (int t = 0; t < NT; ++t)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) gacc[t][r] += (4 * t + r == ts) ? tsum : 0.0;
-        } else {
-            const GlmDispChain none{};
-            double tnone;
-            if constexpr (HIER == GLM_HIER_NC) {
-                // The chain holds z_d on a grouped row: w_d = mu_d + sig_j z_d is what the likelihood sees.  The t_j reach
-                // every lane of the chain as below (the owner contributes, the others add exact zeros); weff, the B operand
-                // of the first product, is a scaled COPY of the state -- q itself is what the drift, the stores and the prior
-                // work on, and scaling in place and back is not exact.
-                const int jo = (g - prm.trow0) & 3;
-                const int so = (prm.trow0 + jo) >> 2;
-                double th = 0.0;
-#pragma unroll
-                for (int s = 0; s < KS; ++s) th = (s == so) ? q[s] : th;
-                double sig[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    sig[j] = 1.0;
-                    if (j < prm.J) sig[j] = exp(chain_sum(jo == j ? th : 0.0));
-                }
-                double weff[KS];
-#pragma unroll
-                for (int s = 0; s < KS; ++s) {
-                    const v2f64 pm = plds[4 * s + g];
-                    weff[s] = (pm.x < 0.0) ? fma(glm_hier_lam(pm.x, sig), q[s], pm.y) : q[s];
-                }
-                glm_grad<NT, FAM, RICH, HIER>(prm, lds, ylds, lane, g, weff, gacc, usum, want_u, none, tnone);
-                // dU/dt_j = sig_j sum_{d in j} gL_d z_d (this lane's rows here, the chain's below) goes to the owner's
-                // register; dU/dz_d = sig_j gL_d (the priors' parts come with the rows below)
-                double G[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int s = 0; s < KS; ++s) {
-                    const v2f64 pm = plds[4 * s + g];
-                    const double gz = gacc[s >> 2][s & 3] * q[s];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) G[j] += (pm.x == -(double)(j + 1)) ? gz : 0.0;
-                }
-                double gown = 0.0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (j < prm.J) {
-                        const double gt = chain_sum(G[j]) * sig[j];
-                        gown = (jo == j) ? gt : gown;
-                    }
-#pragma unroll
-                for (int t = 0; t < NT; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const double lx = plds[4 * (4 * t + r) + g].x;
-                        const double gs = (lx < 0.0) ? gacc[t][r] * glm_hier_lam(lx, sig) : gacc[t][r];
-                        gacc[t][r] = gs + ((4 * t + r == so) ? gown : 0.0);
-                    }
-            } else {
-                glm_grad<NT, FAM, RICH, HIER>(prm, lds, ylds, lane, g, q, gacc, usum, want_u, none, tnone);
-            }
         }
         [[maybe_unused]] double hnt = 0.0;  // centred HIER: sum_j n_j t_j; HIER_Q: sum_j r_j t_j
         if constexpr (HIER == GLM_HIER_CENTRED) {
@@ -892,7 +914,8 @@ int glm_launch(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t stream)
     rprm.obs = (const double*)pot->d_glm_obs;
     rprm.prior = (const double*)pot->d_glm_prior;
     rprm.obs_stride = glm_blocks_padded(pot->glm_M) * 16;
-    const bool disp = glm_disp(pot->glm_family);  // handle of pbbi_potential_create_glm_dispersion
+    const bool disp = glm_disp(pot->glm_family);  // handle of pbbi_potential_create_glm_dispersion or _glm_hier_dispersion
+    const bool hd = disp && pot->glm_hier_J > 0;  // ... the latter
     GlmPrmDisp dprm{};
     static_cast<GlmPrmRich&>(dprm) = rprm;
     dprm.theta = pot->glm_theta;
@@ -900,18 +923,18 @@ int glm_launch(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t stream)
     if (disp && pot->glm_family == PBBI_GLM_NEGBINOMIAL && pot->glm_DP > 64)
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, "negbinomial: no kernel at a padded state dimension of 128 (internal)");
 #define GLM_DISP_CASE(NT_, FAM_)                                                                            \
-    if (disp && pot->glm_DP == 16 * NT_ && pot->glm_family == FAM_)                                         \
+    if (disp && !hd && pot->glm_DP == 16 * NT_ && pot->glm_family == FAM_)                                  \
         hipLaunchKernelGGL((k_glm<NT_, FAM_, true>), grid, block, 0, stream, dprm);
     GLM_DISP_CASE(1, PBBI_GLM_GAUSSIAN) GLM_DISP_CASE(2, PBBI_GLM_GAUSSIAN) GLM_DISP_CASE(4, PBBI_GLM_GAUSSIAN)
     GLM_DISP_CASE(8, PBBI_GLM_GAUSSIAN)
     GLM_DISP_CASE(1, PBBI_GLM_NEGBINOMIAL) GLM_DISP_CASE(2, PBBI_GLM_NEGBINOMIAL) GLM_DISP_CASE(4, PBBI_GLM_NEGBINOMIAL)
 #undef GLM_DISP_CASE
-    const bool nc = pot->glm_hier_J > 0 && pot->glm_hier_nc;  // handle of pbbi_potential_create_glm_hier_ex, non-centred
+    const bool nc = pot->glm_hier_J > 0 && pot->glm_hier_nc && !hd;  // handle of pbbi_potential_create_glm_hier_ex, non-centred
     const bool hq = pot->glm_hier_J > 0 && pot->d_glm_qimg;   // handle of pbbi_potential_create_glm_hier_q
-    const bool hier = pot->glm_hier_J > 0 && !nc && !hq;      // handle of pbbi_potential_create_glm_hier
+    const bool hier = pot->glm_hier_J > 0 && !nc && !hq && !hd;  // handle of pbbi_potential_create_glm_hier
     GlmPrmHier hprm{};
     static_cast<GlmPrmRich&>(hprm) = rprm;
-    hprm.trow0 = pot->D - pot->glm_hier_J;
+    hprm.trow0 = pot->D - pot->glm_hier_J - (hd && pot->glm_trow >= 0 ? 1 : 0);  // a sampled theta is the last row, behind the t rows
     hprm.J = pot->glm_hier_J;
     if (hier && pot->glm_DP > glm_hier_max_dim(pot->glm_family))
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, "hierarchical prior: no kernel at this padded state dimension (internal)");
@@ -940,6 +963,22 @@ int glm_launch(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t stream)
     GLM_HQ_CASE(1, PBBI_GLM_LOGISTIC) GLM_HQ_CASE(2, PBBI_GLM_LOGISTIC) GLM_HQ_CASE(4, PBBI_GLM_LOGISTIC)
     GLM_HQ_CASE(1, PBBI_GLM_POISSON) GLM_HQ_CASE(2, PBBI_GLM_POISSON) GLM_HQ_CASE(4, PBBI_GLM_POISSON)
 #undef GLM_HQ_CASE
+    GlmPrmHierDisp hdprm{};
+    static_cast<GlmPrmHier&>(hdprm) = hprm;
+    hdprm.theta = pot->glm_theta;
+    hdprm.trow = pot->glm_trow;
+    if (hd && pot->glm_DP > glm_hier_disp_max_dim(pot->glm_family, pot->glm_hier_nc ? PBBI_HIER_NONCENTRED : PBBI_HIER_CENTRED))
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "random effects for the dispersion families: no kernel at this padded state dimension (internal)");
+#define GLM_HD_CASE(NT_, FAM_)                                                                              \
+    if (hd && pot->glm_DP == 16 * NT_ && pot->glm_family == FAM_) {                                         \
+        if (pot->glm_hier_nc)                                                                               \
+            hipLaunchKernelGGL((k_glm<NT_, FAM_, true, GLM_HIER_NC>), grid, block, 0, stream, hdprm);       \
+        else                                                                                                \
+            hipLaunchKernelGGL((k_glm<NT_, FAM_, true, GLM_HIER_CENTRED>), grid, block, 0, stream, hdprm);  \
+    }
+    GLM_HD_CASE(1, PBBI_GLM_GAUSSIAN) GLM_HD_CASE(2, PBBI_GLM_GAUSSIAN) GLM_HD_CASE(4, PBBI_GLM_GAUSSIAN)
+    GLM_HD_CASE(1, PBBI_GLM_NEGBINOMIAL) GLM_HD_CASE(2, PBBI_GLM_NEGBINOMIAL) GLM_HD_CASE(4, PBBI_GLM_NEGBINOMIAL)
+#undef GLM_HD_CASE
 #define GLM_CASE(NT_, RICH_, PRM_)                                                                          \
     if (!disp && !hier && !nc && !hq && pot->glm_DP == 16 * NT_ && rich == RICH_) {                                \
         if (pot->glm_family == PBBI_GLM_LOGISTIC)                                                           \
@@ -1236,6 +1275,90 @@ void glm_pack_prior_groups(int D, int J, const double* lam, const double* mu, co
         out[D + j] = tprior[2 * j + 1];
         out[DP + D + j] = tprior[2 * j];
     }
+}
+
+// ---- host side: random effects for the dispersion families -----------------------------------------------------------
+// The largest state dimension (coefficients + groups + 1 for a sampled dispersion) the kernels k_glm<NT, FAM, true, HIER> with
+// FAM = gaussian / negbinomial and HIER = GLM_HIER_CENTRED / GLM_HIER_NC serve; 0 = nothing served.  An instantiation ships
+// only if it builds without scratch: all twelve of NT = 1, 2, 4 do (profiles/glm_hier_dispersion_resources.txt).  There is no
+// kernel at 128 rows for either parent's hierarchical form.
+int glm_hier_disp_max_dim(int family, int parametrisation) {
+    if (!glm_disp(family)) return 0;
+    if (parametrisation != PBBI_HIER_CENTRED && parametrisation != PBBI_HIER_NONCENTRED) return 0;
+    return 64;
+}
+
+// Every rule of the log-dispersion's arguments: sampled, a pair (finite mean, finite precision >= 0) is required; held, theta
+// must be finite and there is no prior to give.
+int glm_check_hier_disp_theta(int sample, double theta, const double* dprior) {
+    if (sample) {
+        if (!dprior) return pbbi_fail(PBBI_ERR_INVALID, "log_dispersion_prior is NULL (a sampled dispersion needs its pair (mean, precision))");
+        if (!std::isfinite(dprior[0]) || !(std::isfinite(dprior[1]) && dprior[1] >= 0.0))
+            return pbbi_fail(PBBI_ERR_INVALID, "log_dispersion_prior must be (finite mean, finite precision >= 0)");
+    } else {
+        if (dprior) return pbbi_fail(PBBI_ERR_INVALID, "log_dispersion_prior belongs to a sampled dispersion only: a held one has no prior");
+        if (!std::isfinite(theta))
+            return pbbi_fail(PBBI_ERR_INVALID, "a held dispersion must be finite and > 0 (theta = its logarithm)");
+    }
+    return PBBI_OK;
+}
+
+// The table of glm_pack_prior_groups at DP = glm_padded_dim(D + J + (sample ? 1 : 0)), with theta's {lam_theta, m_theta} at row
+// D + J when it is sampled (a fixed row: a non-negative lam slot) and zeros past the state.  The caller has run glm_check_hier
+// and glm_check_hier_disp_theta.  Host only.
+void glm_pack_prior_groups_disp(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior,
+                                int sample, const double* dprior, double* out, double* n_out) {
+    const int DP = glm_padded_dim(D + J + (sample ? 1 : 0)), DPh = glm_padded_dim(D + J);
+    std::vector<double> tab((size_t)2 * DPh);
+    glm_pack_prior_groups(D, J, lam, mu, groups, tprior, tab.data(), n_out);  // the one statement of the codes
+    std::memset(out, 0, sizeof(double) * (size_t)(2 * DP));
+    for (int d = 0; d < D + J; ++d) {
+        out[d] = tab[(size_t)d];
+        out[DP + d] = tab[(size_t)DPh + d];
+    }
+    if (sample) {
+        out[D + J] = dprior[1];
+        out[DP + D + J] = dprior[0];
+    }
+}
+
+// the caller has run glm_check_obs_disp, glm_check_hier and glm_check_hier_disp_theta; pot->D = Dx + J + (sample ? 1 : 0)
+int glm_build_hier_disp(pbbi_potential* pot, int Dx, int64_t M, const double* X, const double* y, int family,
+                        const double* weights, const double* offset, const double* lam, const double* mu,
+                        const int32_t* groups, int J, const double* tprior, int parametrisation, int sample, double theta,
+                        const double* dprior) {
+    const int Dt = pot->D;
+    const int dmax = glm_hier_disp_max_dim(family, parametrisation);
+    if (pot->dtype != PBBI_F64 || Dt > dmax)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "random effects for the dispersion families: float64 and a state dimension "
+                                               "(coefficients + groups + 1 for a sampled dispersion) <= " + std::to_string(dmax) +
+                                                   " only (" + std::to_string(Dt) + ")");
+    const int DP = glm_padded_dim(Dt);
+    const int64_t nbp = glm_blocks_padded(M);
+    std::vector<double> img((size_t)(nbp * DP * 32));
+    glm_pack_dp(Dx, DP, M, X, img.data());  // [X | 0]: the t rows and the theta row meet zero columns
+    std::vector<double> obs((size_t)glm_obs_len(M));
+    glm_pack_obs_disp(M, y, weights, offset, obs.data());
+    std::vector<double> prior((size_t)2 * DP + 4, 0.0);  // lam | mu | n_j
+    double* nj = prior.data() + 2 * DP;
+    glm_pack_prior_groups_disp(Dx, J, lam, mu, groups, tprior, sample, dprior, prior.data(), nj);
+    for (int j = 0; j < 4; ++j) pot->glm_hier_n[j] = nj[j];
+    PBBI_HIP(hipMalloc(&pot->d_glm_img, img.size() * sizeof(double)));
+    PBBI_HIP(hipMalloc(&pot->d_glm_obs, obs.size() * sizeof(double)));
+    PBBI_HIP(hipMalloc(&pot->d_glm_prior, prior.size() * sizeof(double)));
+    PBBI_HIP(hipMemcpy(pot->d_glm_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
+    PBBI_HIP(hipMemcpy(pot->d_glm_obs, obs.data(), obs.size() * sizeof(double), hipMemcpyHostToDevice));
+    PBBI_HIP(hipMemcpy(pot->d_glm_prior, prior.data(), prior.size() * sizeof(double), hipMemcpyHostToDevice));
+    pot->glm_DP = DP;
+    pot->glm_M = M;
+    pot->glm_family = family;
+    pot->glm_lam = 0.0;  // (these kernels read d_glm_prior)
+    pot->glm_terms = (weights ? GLM_TERM_WEIGHTS : 0) | (offset ? GLM_TERM_OFFSET : 0);
+    pot->glm_hier_J = J;
+    pot->glm_hier_nc = parametrisation == PBBI_HIER_NONCENTRED ? 1 : 0;
+    pot->glm_trow = sample ? Dx + J : -1;
+    pot->glm_theta = sample ? 0.0 : theta;
+    return PBBI_OK;
 }
 
 // ---- host side: structured group priors ----------------------------------------------------------------------------

@@ -892,6 +892,62 @@ int pbbi_potential_create_glm_hier_q(int D, int64_t M, const double* X, const do
                                             groups, J, log_scale_prior, PBBI_HIER_CENTRED, penalty, rank), out);
 }
 
+// the shape rules of pbbi_potential_create_glm_hier_dispersion and its packing entry, stated once
+static int glm_hier_disp_check_dim(int D, int J, int sample, int family, int parametrisation) {
+    const int dmax = glm_hier_disp_max_dim(family, parametrisation);
+    const int Dt = D + J + (sample ? 1 : 0);
+    if (Dt > dmax)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED,
+                         std::string("random effects for the dispersion families (") +
+                             (family == PBBI_GLM_GAUSSIAN ? "gaussian" : "negbinomial") +
+                             (parametrisation == PBBI_HIER_NONCENTRED ? ", non-centred" : ", centred") +
+                             "): the state dimension (coefficients + groups + 1 for a sampled dispersion) must be <= " +
+                             std::to_string(dmax) + " (" + std::to_string(Dt) + "): a kernel is shipped only if it builds "
+                             "without register spills to memory, and there is none at 65 .. 128 rows");
+    return PBBI_OK;
+}
+
+int pbbi_potential_create_glm_hier_dispersion(int D, int64_t M, const double* X, const double* y, int family,
+                                              const double* weights, const double* offset, const double* prior_precision,
+                                              const double* prior_mean, const int32_t* groups, int J,
+                                              const double* log_scale_prior, int parametrisation, int sample, double theta,
+                                              const double* log_dispersion_prior, int dtype, int device, pbbi_potential** out) {
+    if (out) *out = nullptr;
+    if (parametrisation != PBBI_HIER_CENTRED && parametrisation != PBBI_HIER_NONCENTRED)
+        return pbbi_fail(PBBI_ERR_INVALID, "parametrisation must be PBBI_HIER_CENTRED (0) or PBBI_HIER_NONCENTRED (1)");
+    if (!X || !y) return pbbi_fail(PBBI_ERR_INVALID, "X / y is NULL");
+    if (family == PBBI_GLM_LOGISTIC || family == PBBI_GLM_POISSON)
+        return pbbi_fail(PBBI_ERR_INVALID, "the family must be gaussian (3) or negbinomial (4): logistic and poisson with sampled "
+                                           "group scales are pbbi_potential_create_glm_hier / _hier_ex");
+    if (int rc = glm_check_hier(D, J, prior_precision, prior_mean, groups, log_scale_prior)) return rc;
+    if (int rc = glm_check_obs_disp(M, family, y, weights, offset)) return rc;
+    for (int64_t i = 0; i < M * D; ++i)
+        if (!std::isfinite(X[i])) return pbbi_fail(PBBI_ERR_INVALID, "X must be finite");
+    if (int rc = glm_check_hier_disp_theta(sample, theta, log_dispersion_prior)) return rc;
+    if (dtype != PBBI_F64) return pbbi_fail(PBBI_ERR_UNSUPPORTED, "hierarchical GLM potentials are float64 only");
+    if (int rc = glm_hier_disp_check_dim(D, J, sample, family, parametrisation)) return rc;
+    if (int rc = new_handle(KIND_GLM, D + J + (sample ? 1 : 0), dtype, device, out)) return rc;
+    DeviceGuard guard(device);
+    return finish_or_destroy(glm_build_hier_disp(*out, D, M, X, y, family, weights, offset, prior_precision, prior_mean, groups,
+                                                 J, log_scale_prior, parametrisation, sample, theta, log_dispersion_prior), out);
+}
+
+int pbbi_glm_pack_prior_groups_dispersion(int D, int J, const double* prior_precision, const double* prior_mean,
+                                          const int32_t* groups, const double* log_scale_prior, int sample,
+                                          const double* log_dispersion_prior, double* out, double* n_out) {
+    if (int rc = glm_check_hier(D, J, prior_precision, prior_mean, groups, log_scale_prior)) return rc;
+    if (int rc = glm_check_hier_disp_theta(sample, 0.0, log_dispersion_prior)) return rc;
+    if (D + J + (sample ? 1 : 0) > 128)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "hierarchical prior: coefficients + groups + 1 for a sampled dispersion must be "
+                                               "<= 128 (" + std::to_string(D + J + (sample ? 1 : 0)) + ")");
+    if (!out || !n_out) return pbbi_fail(PBBI_ERR_INVALID, "out / n_out is NULL");
+    glm_pack_prior_groups_disp(D, J, prior_precision, prior_mean, groups, log_scale_prior, sample, log_dispersion_prior, out,
+                               n_out);
+    return PBBI_OK;
+}
+
+int pbbi_glm_hier_dispersion_max_dim(int family, int parametrisation) { return glm_hier_disp_max_dim(family, parametrisation); }
+
 int pbbi_glm_pack_penalty(int D, int J, const double* penalty, double* out, int64_t out_len, int64_t* len_out) {
     if (D < 1 || J < 1 || J > 4 || D + J > 128)
         return pbbi_fail(PBBI_ERR_INVALID, "need D >= 1, 1 <= J <= 4 and D + J <= 128");
@@ -1322,6 +1378,15 @@ int pbbi_describe_run(const pbbi_potential* pot, int method, int64_t N, int64_t 
             d += pot->glm_trow >= 0 ? " (log-dispersion sampled: state row " + std::to_string(pot->glm_trow) +
                                           ", read by one chain sum per gradient, its gradient reduced per chain)"
                                     : " (log-dispersion held at " + std::to_string(pot->glm_theta) + ")";
+            if (pot->glm_hier_J) {
+                const int t0 = pot->D - pot->glm_hier_J - (pot->glm_trow >= 0 ? 1 : 0);
+                d += "; random effects, k_glm<NT, FAM, true, " + std::string(pot->glm_hier_nc ? "GLM_HIER_NC" : "GLM_HIER_CENTRED") +
+                     ">: " + std::to_string(pot->glm_hier_J) + " sampled group log-scales (state rows " + std::to_string(t0) +
+                     " .. " + std::to_string(t0 + pot->glm_hier_J - 1) + ", each read by one chain sum per gradient, ";
+                d += pot->glm_hier_nc ? "non-centred: grouped rows hold z with w = mu + exp(t) z, the first product runs on a "
+                                        "scaled copy of the state, the group sums of gL z reduced per chain)"
+                                      : "centred: the group sums of squares reduced per chain)";
+            }
             d += (t & GLM_TERM_WEIGHTS) ? ", weights" : "";
             d += (t & GLM_TERM_OFFSET) ? ", offset" : "";
         } else if (pot->glm_hier_J) {

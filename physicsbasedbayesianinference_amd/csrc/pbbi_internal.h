@@ -71,6 +71,9 @@ struct pbbi_potential {
     // ... with structured group priors (pbbi_potential_create_glm_hier_q), k_glm<NT, FAM, true, GLM_HIER_Q>.  (Appended.)
     void* d_glm_qimg;      // the (glm_DP x glm_DP) penalty in A-fragment order (glm_pack_penalty); NULL = not such a handle
     double glm_hier_rank[4];  // rank(Q_j), what the table's n_j slots hold on such a handle
+    // random effects for the dispersion families (pbbi_potential_create_glm_hier_dispersion) add no field: glm_family 3 / 4 with
+    // glm_hier_J > 0, D = coefficients + glm_hier_J + (glm_trow >= 0), glm_trow the LAST row, d_glm_prior the table of
+    // glm_pack_prior_groups_disp, d_glm_obs = a | y | o
 };
 
 // ---- error plumbing ---------------------------------------------------------
@@ -298,6 +301,15 @@ int glm_build_hier(pbbi_potential* pot, int Dx, int64_t M, const double* X, cons
                    const double* weights, const double* offset, const double* trials, const double* lam, const double* mu,
                    const int32_t* groups, int J, const double* tprior, int parametrisation, const double* penalty = nullptr,
                    const double* rank = nullptr);
+// random effects for the dispersion families (pbbi_potential_create_glm_hier_dispersion): FAM = 3, 4 with HIER = centred / NC
+int glm_hier_disp_max_dim(int family, int parametrisation);  // the largest coefficients + groups + sampled served; 0 = none
+int glm_check_hier_disp_theta(int sample, double theta, const double* dprior);
+void glm_pack_prior_groups_disp(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior,
+                                int sample, const double* dprior, double* out, double* n_out);  // host only
+int glm_build_hier_disp(pbbi_potential* pot, int Dx, int64_t M, const double* X, const double* y, int family,
+                        const double* weights, const double* offset, const double* lam, const double* mu,
+                        const int32_t* groups, int J, const double* tprior, int parametrisation, int sample, double theta,
+                        const double* dprior);
 int glm_hier_q_max_dim(int family);  // ... the structured group priors' (k_glm<NT, FAM, true, GLM_HIER_Q>)
 int glm_check_penalty(int D, int J, const int32_t* groups, const double* penalty, const double* rank);
 int64_t glm_penalty_image_len(int D, int J);                   // doubles of the fragment image of the (DP x DP) penalty

@@ -29,6 +29,9 @@ chain's state or held at a given value.
 `HierarchicalGLM` is the full model with hierarchical priors: blocks of coefficients (random intercepts, random slopes,
 a ridge penalty of unknown strength) share a prior scale that is sampled, on the log scale, as a further row of the state.  With `penalty=` a group's prior is structured: a symmetric positive semi-definite matrix Q_j
 in its quadratic form (random walks, difference penalties of splines, ICAR), Q_j (w - mu) one more product on the matrix cores.
+
+`HierarchicalDispersionGLM` is the product of the two: the likelihood of `DispersionGLM` under the priors of `HierarchicalGLM`
+-- the linear mixed model with unknown residual sigma, eight schools, negative-binomial counts with random intercepts.
 """
 import ctypes as C
 
@@ -37,7 +40,8 @@ import numpy as np
 from . import _lib
 from .potential import Potential, _dptr
 
-__all__ = ["GLM", "SoftmaxGLM", "DispersionGLM", "HierarchicalGLM", "FAMILIES", "DISPERSION_FAMILIES", "HIER_MAX_DIM",
+__all__ = ["GLM", "SoftmaxGLM", "DispersionGLM", "HierarchicalGLM", "HierarchicalDispersionGLM", "HIER_DISP_MAX_DIM",
+           "pack_prior_groups_dispersion", "FAMILIES", "DISPERSION_FAMILIES", "HIER_MAX_DIM",
            "HIER_NC_MAX_DIM", "HIER_PARAMETRISATIONS", "HIER_MAX_GROUPS", "pack_design", "pack_observations", "pack_observations_dispersion", "pack_prior_groups",
            "HIER_Q_MAX_DIM", "pack_penalty", "padded_dim", "softmax_layout"]
 
@@ -56,6 +60,11 @@ HIER_NC_MAX_DIM = {"logistic": 64, "poisson": 64}
 # ... with a penalty matrix (k_glm<NT, FAM, true, GLM_HIER_Q>, centred only): the kernels at 16, 32 and 64 rows build without
 # scratch for both families; there is no centred kernel at 128 rows to extend
 HIER_Q_MAX_DIM = {"logistic": 64, "poisson": 64}
+# the largest state dimension (coefficients + groups + 1 for a sampled dispersion) of HierarchicalDispersionGLM, by family and
+# parametrisation: a kernel is shipped only if it builds without register spills to memory -- all twelve of 16, 32 and 64
+# rows do (profiles/glm_hier_dispersion_resources.txt), and neither parent has a hierarchical kernel at 128 rows.  The library
+# states it (pbbi_glm_hier_dispersion_max_dim); this mirrors it.
+HIER_DISP_MAX_DIM = {"gaussian": {"centred": 64, "noncentred": 64}, "negbinomial": {"centred": 64, "noncentred": 64}}
 HIER_PARAMETRISATIONS = {"centred": _lib.HIER_CENTRED, "noncentred": _lib.HIER_NONCENTRED}
 HIER_MAX_GROUPS = 4
 
@@ -307,6 +316,53 @@ class SoftmaxGLM(Potential):
         return samples.reshape((self.classes, D) + tuple(samples.shape[1:]))
 
 
+def _validate_dispersion(X, y, family, weights, offset):
+    """X, y and the per-observation vectors of a dispersion family, checked: (X, y, weights, offset) as float64 arrays."""
+    if family not in DISPERSION_FAMILIES:
+        raise ValueError("family must be one of %s (got %r)" % (sorted(DISPERSION_FAMILIES), family))
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError("X must be 2-D: (M, D) with at least one row and one column")
+    M, D = X.shape
+    y = np.asarray(y, dtype=np.float64)
+    if y.ndim != 1 or y.size != M:
+        raise ValueError("X has %d rows, y must be 1-D with as many entries (shape %s)" % (M, y.shape))
+    if not np.all(np.isfinite(X)) or not np.all(np.isfinite(y)):
+        raise ValueError("X and y must be finite")
+    if family == "negbinomial" and not (np.all(y >= 0) and np.all(y == np.floor(y))):
+        raise ValueError("negbinomial: y must hold non-negative integers")
+    if weights is not None:
+        weights = _vector(weights, M, "weights", "M")
+        if not np.all(weights >= 0):
+            raise ValueError("weights must be >= 0")
+    if offset is not None:
+        offset = _vector(offset, M, "offset", "M")
+    return X, y, weights, offset
+
+
+def _dispersion_args(dispersion, log_dispersion_prior):
+    """`dispersion` and `log_dispersion_prior` checked: (sample, held value or None, theta, prior pair or None)."""
+    sample = isinstance(dispersion, str)
+    if sample:
+        if dispersion != "sample":
+            raise ValueError('dispersion must be "sample" or a float > 0 (got %r)' % (dispersion,))
+        m_t, l_t = (0.0, 0.25) if log_dispersion_prior is None else _pair(log_dispersion_prior)
+        if not (np.isfinite(m_t) and np.isfinite(l_t) and l_t >= 0):
+            raise ValueError("log_dispersion_prior must be (mean, precision) with a finite mean and a finite precision >= 0")
+        theta = 0.0
+    else:
+        if log_dispersion_prior is not None:
+            raise ValueError("log_dispersion_prior belongs to dispersion=\"sample\" only: a held dispersion has no prior")
+        try:
+            disp = float(dispersion)
+        except (TypeError, ValueError):
+            raise ValueError('dispersion must be "sample" or a float > 0 (got %r)' % (dispersion,)) from None
+        if not (np.isfinite(disp) and disp > 0):
+            raise ValueError("a held dispersion must be finite and > 0 (got %r)" % (dispersion,))
+        theta = float(np.log(disp))
+    return sample, (None if sample else disp), theta, ((m_t, l_t) if sample else None)
+
+
 class DispersionGLM(Potential):
     """-log posterior of a GLM whose family has a free dispersion, with theta = log(dispersion):
 
@@ -340,43 +396,10 @@ class DispersionGLM(Potential):
 
     def __init__(self, X, y, family="negbinomial", dispersion="sample", log_dispersion_prior=None, prior_precision=1.0,
                  prior_mean=None, weights=None, offset=None, dtype="float64", device=None):
-        if family not in DISPERSION_FAMILIES:
-            raise ValueError("family must be one of %s (got %r)" % (sorted(DISPERSION_FAMILIES), family))
-        X = np.asarray(X, dtype=np.float64)
-        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
-            raise ValueError("X must be 2-D: (M, D) with at least one row and one column")
+        X, y, weights, offset = _validate_dispersion(X, y, family, weights, offset)
         M, D = X.shape
-        y = np.asarray(y, dtype=np.float64)
-        if y.ndim != 1 or y.size != M:
-            raise ValueError("X has %d rows, y must be 1-D with as many entries (shape %s)" % (M, y.shape))
-        if not np.all(np.isfinite(X)) or not np.all(np.isfinite(y)):
-            raise ValueError("X and y must be finite")
-        if family == "negbinomial" and not (np.all(y >= 0) and np.all(y == np.floor(y))):
-            raise ValueError("negbinomial: y must hold non-negative integers")
-        if weights is not None:
-            weights = _vector(weights, M, "weights", "M")
-            if not np.all(weights >= 0):
-                raise ValueError("weights must be >= 0")
-        if offset is not None:
-            offset = _vector(offset, M, "offset", "M")
-        sample = isinstance(dispersion, str)
-        if sample:
-            if dispersion != "sample":
-                raise ValueError('dispersion must be "sample" or a float > 0 (got %r)' % (dispersion,))
-            m_t, l_t = (0.0, 0.25) if log_dispersion_prior is None else _pair(log_dispersion_prior)
-            if not (np.isfinite(m_t) and np.isfinite(l_t) and l_t >= 0):
-                raise ValueError("log_dispersion_prior must be (mean, precision) with a finite mean and a finite precision >= 0")
-            theta = 0.0
-        else:
-            if log_dispersion_prior is not None:
-                raise ValueError("log_dispersion_prior belongs to dispersion=\"sample\" only: a held dispersion has no prior")
-            try:
-                disp = float(dispersion)
-            except (TypeError, ValueError):
-                raise ValueError('dispersion must be "sample" or a float > 0 (got %r)' % (dispersion,)) from None
-            if not (np.isfinite(disp) and disp > 0):
-                raise ValueError("a held dispersion must be finite and > 0 (got %r)" % (dispersion,))
-            theta = float(np.log(disp))
+        sample, disp, theta, tprior = _dispersion_args(dispersion, log_dispersion_prior)
+        m_t, l_t = tprior if sample else (None, None)
         lam = np.asarray(prior_precision, dtype=np.float64)
         if lam.ndim == 0:
             if not np.isfinite(lam):
@@ -672,8 +695,8 @@ class HierarchicalGLM(Potential):
     Not served with a penalty: `parametrisation="noncentred"` (it would need w = mu + exp(t) L^-T z with Q = L L^T),
     structure across groups, sampled structure such as the rho of a proper CAR prior.
 
-    Not served: a per-group choice of parametrisation, sampled group scales on `DispersionGLM` and `SoftmaxGLM`, more than 4
-    groups, group means as parameters, per-chain trajectory lengths and GIST (they raise as for `GLM`).  Shapes:
+    Not served: a per-group choice of parametrisation, sampled group scales on `SoftmaxGLM` (for the families of
+    `DispersionGLM` they are `HierarchicalDispersionGLM`), more than 4 groups, group means as parameters, per-chain trajectory lengths and GIST (they raise as for `GLM`).  Shapes:
     float64; D + J <= 64 for both families and both parametrisations (`HIER_MAX_DIM`, `HIER_NC_MAX_DIM`: the kernels for
     65 .. 128 rows cannot be built without register spills to memory and are not shipped).
 
@@ -851,3 +874,116 @@ class HierarchicalGLM(Potential):
         pot = cls(Xh, y, groups=groups, **kw)
         pot.levels = levels
         return pot
+
+
+def pack_prior_groups_dispersion(groups, log_scale_prior=(0.0, 1.0), prior_precision=1.0, prior_mean=None, dispersion="sample",
+                                 log_dispersion_prior=None):
+    """The prior table a HierarchicalDispersionGLM handle keeps on the device and its kernel in LDS, computed (and checked) on
+    the host by libpbbi.so: (table, n) -- table (2, DP) with DP = padded_dim(D + J + sampled): rows 0 .. D+J-1 as in
+    `pack_prior_groups`, and with a sampled dispersion row D + J holds theta's prior (its precision in row 0 of the table,
+    its mean in row 1); zeros past the state; n (J,) the members of each group."""
+    D = np.asarray(groups).size
+    groups, J, tp, lam, mu = _hier_prior(D, groups, log_scale_prior, prior_precision, prior_mean)
+    sample, _, _, dprior = _dispersion_args(dispersion, log_dispersion_prior)
+    DP = padded_dim(D + J + int(sample))
+    dp = np.ascontiguousarray(dprior, dtype=np.float64) if sample else None
+    out, n = np.empty(2 * DP, dtype=np.float64), np.empty(J, dtype=np.float64)
+    try:
+        _lib.call("pbbi_glm_pack_prior_groups_dispersion", D, J, _dptr(lam), _dptr(mu),
+                  groups.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(tp), int(sample), _dptr(dp), _dptr(out), _dptr(n))
+    except RuntimeError as e:
+        raise ValueError(str(e)) from None
+    return out.reshape(2, DP), n
+
+
+class HierarchicalDispersionGLM(HierarchicalGLM):
+    """-log posterior of a GLM with a free dispersion (family "gaussian" or "negbinomial", the likelihood of `DispersionGLM`:
+    theta = log(dispersion), weights a_i, offsets o_i, eta_i = x_i . w + o_i) in which blocks of coefficients share a sampled
+    prior scale (the priors of `HierarchicalGLM`): the linear mixed model with unknown residual sigma, its held-sigma form with
+    weights 1 / sigma_i^2, over-dispersed counts with a random intercept per site or batch.
+
+        gaussian     U_i = a_i [ 0.5 exp(-2 theta) (y_i - eta_i)^2 + theta ]
+        negbinomial  U_i = a_i [ lgamma(phi) - lgamma(y_i + phi) - phi theta - y_i eta_i + (y_i + phi) logaddexp(eta_i, theta) ]
+        centred:     U = sum_i U_i + 0.5 sum_{d: groups_d < 0} lam_d (w_d - mu_d)^2
+                       + sum_j [ 0.5 exp(-2 t_j) S_j + n_j t_j + 0.5 lam_tj (t_j - m_tj)^2 ]
+                       + 0.5 lam_theta (theta - m_theta)^2                     (the last term only when theta is sampled)
+        noncentred:  grouped rows hold z_d, w_d = mu_d + exp(t_j) z_d;  U_nc(z, t, theta) = U_c(w(z, t), t, theta) - sum_j n_j t_j
+
+        pot = HierarchicalDispersionGLM(X, y, family="gaussian", groups=groups, dispersion="sample",
+                                        log_dispersion_prior=(0.0, 0.25), log_scale_prior=(0.0, 1.0))
+        w, scales, dispersion = pot.split(samples)        # natural scale for both parametrisations
+        pot = HierarchicalDispersionGLM.with_random_intercepts(X, y, school, family="gaussian", parametrisation="noncentred")
+        # eight schools: y_i ~ N(mu + b_i, sigma_i^2) with sigma_i known
+        pot = HierarchicalDispersionGLM.with_random_intercepts(np.ones((8, 1)), y8, np.arange(8), family="gaussian",
+                                                               dispersion=1.0, weights=1 / sigma8**2,
+                                                               parametrisation="noncentred")
+
+    The chain's state: rows 0 .. D-1 the coefficients (z on the grouped rows of a non-centred potential), rows D .. D+J-1
+    t_0 .. t_{J-1}, and with `dispersion="sample"` theta as the LAST row; numDimensions == D + J + (1 if sampled else 0).  With
+    `dispersion=` a float > 0 the state is [w; t].  `groups`, `log_scale_prior`, `prior_precision`, `prior_mean` and
+    `parametrisation` are `HierarchicalGLM`'s, `dispersion`, `log_dispersion_prior`, `weights` and `offset` `DispersionGLM`'s,
+    each with its rules.  `to_natural` / `from_natural` map between the sampler's state and (w; t; theta) -- the theta row passes
+    through -- and `split` returns (w, scales, dispersion) on the natural scale for both parametrisations.
+
+    Shapes: float64, 1 <= J <= 4, D + J + sampled <= 64 for both families and both parametrisations (`HIER_DISP_MAX_DIM`; a
+    kernel is shipped only if it builds without register spills to memory, and there is none at 65 .. 128 rows).  Not built:
+    `penalty=` (structured group priors for these families), more than 4 groups, per-chain trajectory lengths and GIST (they
+    raise as for `GLM`).
+
+    Works wherever `GLM` does (HMC in both rng modes, Leapfrog / StormerVerlet, TemperedSMC, TemperingLadder, sampleStats).
+    Arguments are checked on the host before anything touches the GPU.  It runs on csrc/kernels_glm.hip (k_glm<NT, FAM, true,
+    HIER> with FAM = 3, 4)."""
+
+    def __init__(self, X, y, family="gaussian", groups=None, dispersion="sample", log_dispersion_prior=None,
+                 log_scale_prior=(0.0, 1.0), prior_precision=1.0, prior_mean=None, weights=None, offset=None,
+                 parametrisation="centred", penalty=None, penalty_rank=None, dtype="float64", device=None):
+        if family in FAMILIES:
+            raise ValueError("HierarchicalDispersionGLM serves the families %s; family=%r with sampled group scales is "
+                             "HierarchicalGLM" % (sorted(DISPERSION_FAMILIES), family))
+        if penalty is not None or penalty_rank is not None:
+            raise ValueError("penalty= (structured group priors) is not built for HierarchicalDispersionGLM: it is served by "
+                             "HierarchicalGLM (families logistic and poisson) only")
+        if not isinstance(parametrisation, str) or parametrisation not in HIER_PARAMETRISATIONS:
+            raise ValueError("parametrisation must be \"centred\" or \"noncentred\" (got %r)" % (parametrisation,))
+        if groups is None:
+            raise ValueError("groups is required: a (D,) vector of -1 (fixed prior) or group indices 0 .. J-1")
+        X, y, a, o = _validate_dispersion(X, y, family, weights, offset)
+        M, D = X.shape
+        sample, disp, theta, dprior = _dispersion_args(dispersion, log_dispersion_prior)
+        groups, J, tp, lam, mu = _hier_prior(D, groups, log_scale_prior, prior_precision, prior_mean)
+        Dt = D + J + int(sample)
+        dmax = HIER_DISP_MAX_DIM[family][parametrisation]
+        if Dt > dmax:
+            raise ValueError("HierarchicalDispersionGLM(family=%r, parametrisation=%r) serves a state dimension (coefficients + "
+                             "groups%s) <= %d (got %d): a kernel is shipped only if it builds without register spills to memory"
+                             % (family, parametrisation, " + 1 for the sampled dispersion" if sample else "", dmax, Dt))
+        if np.dtype(dtype) != np.dtype("float64"):
+            raise ValueError("GLM potentials are float64 only")
+        X, y = np.ascontiguousarray(X), np.ascontiguousarray(y)
+        Potential.__init__(self, Dt, dtype, device)
+        self.parametrisation = parametrisation
+        self.X, self.y, self.family = X, y, family
+        self.weights, self.offset, self.trials = a, o, None
+        self.prior_precision, self.prior_mean = lam, mu
+        self.groups, self.log_scale_prior = groups, tp
+        self.numCoefficients, self.numGroups = D, J
+        self.levels = None
+        self.penalty, self.penalty_rank = None, None
+        self.sampled = sample
+        self.dispersion = "sample" if sample else disp
+        self.log_dispersion_prior = dprior
+        dp = np.ascontiguousarray(dprior, dtype=np.float64) if sample else None
+        _lib.call("pbbi_potential_create_glm_hier_dispersion", D, M, _dptr(X), _dptr(y), DISPERSION_FAMILIES[family], _dptr(a),
+                  _dptr(o), _dptr(lam), _dptr(mu), groups.ctypes.data_as(C.POINTER(C.c_int32)), J, _dptr(tp),
+                  HIER_PARAMETRISATIONS[parametrisation], int(sample), theta, _dptr(dp), self._dt, self.device,
+                  C.byref(self._handle))
+
+    def split(self, samples):
+        """(numDimensions, ...) -> (w, scales, dispersion): the (D, ...) coefficients and the (J, ...) group scales sigma_j =
+        exp(t_j) as `HierarchicalGLM.split` returns them (natural scale for both parametrisations), and exp(theta) -- sigma for
+        "gaussian", phi for "negbinomial" -- of shape (...); held: the constant itself."""
+        w, scales = super().split(samples)
+        if not self.sampled:
+            return w, scales, self.dispersion
+        theta = samples[self.numCoefficients + self.numGroups]
+        return w, scales, (theta.exp() if hasattr(theta, "exp") and not isinstance(theta, np.ndarray) else np.exp(theta))

@@ -42,11 +42,18 @@ structured model as a CustomPotential, all three alternating in one process, at 
 profiles/glm_hier_penalty_bench.json: the project's criterion (the slowest repeat of the kernel beats the fastest of the plugin)
 and the ratio to the centred kernel next to what the MFMA counts predict, 1 + (DP^2 / 64) / (M DP / 32) = 1 + DP / (2 M).
 
+--model hierdisp times HierarchicalDispersionGLM(family="negbinomial", dispersion="sample") in both parametrisations (k_glm<NT,
+4, true, GLM_HIER_CENTRED / GLM_HIER_NC>) against the centred model as a CustomPotential and against DispersionGLM of [X | 0]
+with the group scales held at their true values -- the parent kernel at the same padded shape, so that ratio is the cost of
+the prior -- all four alternating in one process, at (M = 256, D = 13, J = 2, N = 65 536) and (M = 16 384, D = 59, J = 4, N = 16
+384): 16 and 64 rows with theta the last.  It writes profiles/glm_hier_dispersion_bench.json (HIER_DISP_SHAPES).
+
 usage: tools/bench_glm.py [--shape small|large|all] [--K 32] [--repeats 5] [--glm-only] [--out FILE]
        tools/bench_glm.py --model rich [--custom] [--label NAME] [--shape ...]
        tools/bench_glm.py --model softmax [--shape k3|k8|k8large|all]
        tools/bench_glm.py --model dispersion [--shape small|large|all]
        tools/bench_glm.py --model hierq [--shape small|large|all]
+       tools/bench_glm.py --model hierdisp [--shape small|large|all]
        tools/bench_glm.py --model hier [--parametrisation centred|noncentred] [--shape small|large|all]  (noncentred: also mid)
 """
 import argparse
@@ -370,6 +377,121 @@ def bench_dispersion(name, M, D, N, h, L, per_call, window, repeats, warm):
     out["ratio_worst_case"] = float(per_it["plugin"].min() / per_it["dispersion"].max())  # fastest plugin over slowest kernel
     out["slowest_dispersion_beats_fastest_plugin"] = bool(per_it["dispersion"].max() < per_it["plugin"].min())
     return out
+
+# negative-binomial regression with sampled group scales and a sampled log-dispersion as user source (centred): prm = [M, D, J, X,
+# a, y, o, lam(DT), mu(DT), groups(D)], the state (w, t, theta); nb_psi is NEGBINOMIAL_SOURCE's
+HIER_NEGBINOMIAL_SOURCE = NEGBINOMIAL_SOURCE[:NEGBINOMIAL_SOURCE.index("template <class Q>")] + """
+template <class Q>
+PBBI_FN T potential(const Q& q, int DT, const T* prm) {
+    const int M = (int)prm[0], D = (int)prm[1], J = (int)prm[2];
+    const T *X = prm + 3, *a = X + (long)M * D, *y = a + M, *o = y + M, *lam = o + M, *mu = lam + DT, *grp = mu + DT;
+    const T th = q[D + J], phi = exp(th), lgphi = lgamma(phi);
+    T s = 0;
+    for (int i = 0; i < M; ++i) {
+        if (a[i] == 0) continue;
+        T z = o[i];
+        for (int j = 0; j < D; ++j) z += X[i * D + j] * q[j];
+        const T d = z - th, sp = (d > 0 ? d : T(0)) + log1p(exp(-fabs(d)));
+        s += a[i] * (lgphi - lgamma(y[i] + phi) + (y[i] + phi) * sp - y[i] * d);
+    }
+    T r = 0;
+    for (int j = 0; j < D; ++j) {
+        const int k = (int)grp[j];
+        const T e = q[j] - mu[j];
+        if (k < 0) { r += lam[j] * e * e; } else { r += exp(-2 * q[D + k]) * e * e; s += q[D + k]; }
+    }
+    for (int j = D; j < DT; ++j) r += lam[j] * (q[j] - mu[j]) * (q[j] - mu[j]);
+    return s + T(0.5) * r;
+}
+template <class Q, class G>
+PBBI_FN void gradient(const Q& q, G& g, int DT, const T* prm) {
+    const int M = (int)prm[0], D = (int)prm[1], J = (int)prm[2];
+    const T *X = prm + 3, *a = X + (long)M * D, *y = a + M, *o = y + M, *lam = o + M, *mu = lam + DT, *grp = mu + DT;
+    const T th = q[D + J], phi = exp(th), psi_phi = nb_psi(phi);
+    for (int j = D; j < DT; ++j) g[j] = lam[j] * (q[j] - mu[j]);
+    for (int j = 0; j < D; ++j) {
+        const int k = (int)grp[j];
+        const T e = q[j] - mu[j];
+        if (k < 0) { g[j] = lam[j] * e; } else { const T tau = exp(-2 * q[D + k]); g[j] = tau * e; g[D + k] += T(1) - tau * e * e; }
+    }
+    T gt = 0;
+    for (int i = 0; i < M; ++i) {
+        if (a[i] == 0) continue;
+        T z = o[i];
+        for (int j = 0; j < D; ++j) z += X[i * D + j] * q[j];
+        const T d = z - th, e = exp(-fabs(d)), inv = T(1) / (T(1) + e);
+        const T sg = d >= 0 ? inv : e * inv, sg1 = d >= 0 ? e * inv : inv, sp = (d > 0 ? d : T(0)) + log1p(e);
+        const T w = a[i] * ((y[i] + phi) * sg - y[i]);
+        gt += a[i] * (phi * (psi_phi - nb_psi(y[i] + phi) + sp - sg) + y[i] * sg1);
+        for (int j = 0; j < D; ++j) g[j] += w * X[i * D + j];
+    }
+    g[D + J] += gt;
+}
+"""
+# as DISPERSION_SHAPES; D + J + 1 = 16 and 64: theta is the last row of the DP = 16 and DP = 64 kernels, the t rows before it
+HIER_DISP_SHAPES = {
+    "small": dict(M=256, D=13, J=2, N=65536, h=0.05, per_call=32,
+                  window=dict(centred=256, noncentred=256, plugin=32, parent=256), repeats=5, warm=4),
+    "large": dict(M=16384, D=59, J=4, N=16384, h=0.006, per_call=4,
+                  window=dict(centred=16, noncentred=16, plugin=4, parent=16), repeats=3, warm=2),
+}
+
+
+def bench_hier_dispersion(name, M, D, J, N, h, L, per_call, window, repeats, warm):
+    """HierarchicalDispersionGLM (centred and non-centred), the centred model through CustomPotential and DispersionGLM of
+    [X | 0] with the scales held alternating in one process: same data, step size and draws, the same starts in natural
+    coordinates (the non-centred side starts at from_natural of them)."""
+    from physicsbasedbayesianinference_amd.custom import CustomPotential
+    kw, wt, rs = dispersion_problem(M, D)
+    nfix = (D - 2) % J + 2
+    groups = np.r_[np.full(nfix, -1), np.arange(D - nfix) % J]
+    t = np.log(np.array([np.std(wt[:D][groups == j]) for j in range(J)]))     # scales that fit the coefficients drawn
+    DT = D + J + 1
+    tprior, dprior = (-0.5, 1.0), (0.0, 0.25)
+    q0 = np.ascontiguousarray(np.r_[wt[:D], t, wt[D]][:, None] + 0.05 * rs.standard_normal((DT, N)))
+    lam, mu = np.r_[np.ones(D), np.full(J, tprior[1]), dprior[1]], np.r_[np.zeros(D), np.full(J, tprior[0]), dprior[0]]
+    prm = np.concatenate([[float(M), float(D), float(J)], kw["X"].ravel(), kw["weights"], kw["y"], kw["offset"], lam, mu,
+                          groups.astype(float)])
+    hd = dict(family="negbinomial", groups=groups, dispersion="sample", log_dispersion_prior=dprior, log_scale_prior=tprior,
+              prior_precision=1.0, **kw)
+    cen = P.HierarchicalDispersionGLM(**hd)
+    ncp = P.HierarchicalDispersionGLM(parametrisation="noncentred", **hd)
+    lam_held = np.r_[np.where(groups < 0, 1.0, np.exp(-2.0 * t)[np.maximum(groups, 0)]), np.full(J, tprior[1])]
+    parent = P.DispersionGLM(np.hstack([kw["X"], np.zeros((M, J))]), kw["y"], family="negbinomial", dispersion="sample",
+                             log_dispersion_prior=dprior, prior_precision=lam_held, prior_mean=mu[:D + J],
+                             weights=kw["weights"], offset=kw["offset"])
+    assert parent.numDimensions == DT == cen.numDimensions == ncp.numDimensions
+    runners = {"centred": Runner(cen, DT, N, q0, h, L, per_call, window["centred"]),
+               "noncentred": Runner(ncp, DT, N, np.ascontiguousarray(ncp.from_natural(q0)), h, L, per_call, window["noncentred"]),
+               "plugin": Runner(CustomPotential(DT, HIER_NEGBINOMIAL_SOURCE, prm), DT, N, q0, h, L, per_call, window["plugin"]),
+               "parent": Runner(parent, DT, N, q0, h, L, per_call, window["parent"])}
+    for r in runners.values():
+        r.go(warm)
+    torch.cuda.synchronize()
+    series = {k: [] for k in runners}
+    for i in range(repeats):
+        for k, r in runners.items():   # alternating
+            series[k].append(r.timed())
+            print(f"# {name} repeat {i} {k}: {series[k][-1]:.4f} s", flush=True)
+    DP = glm.padded_dim(DT)
+    grads = L + 1
+    out = dict(shape=name, family="negbinomial", M=M, D=D, J=J, state_dimension=DT, DP=DP, chains=N, L=L, h=h,
+               iterations_per_call=per_call, iterations_per_window=dict(window), repeats=repeats, warmup_iterations=warm,
+               timing="host clock over whole windows of pbbi_hmc_run calls (synchronised before and after)",
+               accept_rate={k: 1.0 - float(r.rej.float().mean().item()) for k, r in runners.items()})
+    per_it = {}
+    for k, ts in series.items():
+        out[k + "_seconds"] = ts
+        out[k + "_step_chain_per_s"] = [window[k] * L * N / t_ for t_ in ts]
+        per_it[k] = np.array(ts) / window[k]          # seconds per iteration
+    flop_it = 4.0 * M * DP * grads * N
+    for k in ("centred", "noncentred"):
+        out[k + "_share_of_fp64_mfma_peak_executed"] = float(flop_it / np.median(per_it[k]) / PEAK_F64_MFMA)
+        out[k + "_over_parent_median"] = float(np.median(per_it[k]) / np.median(per_it["parent"]))   # the cost of the prior
+    out["plugin_over_centred_median"] = float(np.median(per_it["plugin"]) / np.median(per_it["centred"]))
+    out["plugin_over_centred_worst_case"] = float(per_it["plugin"].min() / per_it["centred"].max())
+    return out
+
 
 # the hierarchical model as user source: prm = [M, D, X, c, d, o, lam(D + J), mu(D + J), groups(D)], c = a n, d = a y
 HIER_LOGISTIC_SOURCE = """
@@ -782,19 +904,20 @@ if __name__ == "__main__":
     ap.add_argument("--repeats", type=int, default=None, help="default 5 (--model softmax: per shape)")
     ap.add_argument("--warmup", type=int, default=None, help="default 4 (--model softmax: per shape)")
     ap.add_argument("--glm-only", action="store_true")
-    ap.add_argument("--model", default="plain", choices=["plain", "rich", "softmax", "dispersion", "hier", "hierq"])
+    ap.add_argument("--model", default="plain", choices=["plain", "rich", "softmax", "dispersion", "hier", "hierq", "hierdisp"])
     ap.add_argument("--parametrisation", default="centred", choices=["centred", "noncentred"],
                     help="--model hier: noncentred times the non-centred kernel against the centred one and the plugin")
     ap.add_argument("--custom", action="store_true", help="--model rich: also the full model as a CustomPotential")
     ap.add_argument("--label", default="rich_vs_plain", help="--model rich: key of the record in the output file")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.model in ("softmax", "dispersion", "hier", "hierq"):
+    if a.model in ("softmax", "dispersion", "hier", "hierq", "hierdisp"):
         table, fn, side = {"softmax": (SOFTMAX_SHAPES, bench_softmax, "softmax"),
                            "dispersion": (DISPERSION_SHAPES, bench_dispersion, "dispersion"),
                            "hier": (HIER_SHAPES, bench_hier, "hier"),
-                           "hierq": (HIERQ_SHAPES, bench_hierq, "hierq")}[a.model]
-        stem = "hier_penalty" if a.model == "hierq" else a.model
+                           "hierq": (HIERQ_SHAPES, bench_hierq, "hierq"),
+                           "hierdisp": (HIER_DISP_SHAPES, bench_hier_dispersion, "centred")}[a.model]
+        stem = {"hierq": "hier_penalty", "hierdisp": "hier_dispersion"}.get(a.model, a.model)
         if a.model == "hier" and a.parametrisation == "noncentred":
             table, fn, side, stem = HIER_NC_SHAPES, bench_hier_nc, "noncentred", "hier_nc"
         a.out = a.out or os.path.join(ROOT, "profiles", "glm_%s_bench.json" % stem)
