@@ -1,0 +1,209 @@
+// glm_asan_driver.cpp -- glm_host.cpp under AddressSanitizer + UndefinedBehaviorSanitizer (test infrastructure, CPU only).
+// The packers and checkers compute indices into buffers the caller sized: every one of them is driven here over heap buffers
+// of EXACTLY the documented length (one element more or less is a report), at the dimensions where the padding changes (D = 1,
+// 16, 17, 64, 65, 128 as far as each function's rule allows; M = 1, 16, 65; J = 1 and 4; a sampled and a held dispersion; the
+// softmax shapes (1, 2), (16, 8), (17, 4), (64, 2); a penalty on a group of one and on the largest group there is).  Built
+// together with glm_host.cpp by `make asan_check`; prints "asan ok" and exits 0 when the sanitizers stayed silent (they abort
+// the process otherwise) and every call returned what its arguments deserve.  tests/test_glm_host_asan.py runs it.
+#include <cstdio>
+#include <memory>
+
+#include "glm_host.h"
+
+static std::string g_error;
+int pbbi_fail(int code, const std::string& msg) {
+    g_error = msg;
+    return code;
+}
+
+template <class T>
+using Buf = std::unique_ptr<T[]>;
+static Buf<double> dbuf(int64_t n, double fill, double step = 0.0) {  // exactly n elements (n = 0: a valid empty block)
+    Buf<double> p(new double[(size_t)n]);
+    for (int64_t i = 0; i < n; ++i) p[(size_t)i] = fill + step * (double)(i % 7);
+    return p;
+}
+
+static int bad = 0;
+#define EXPECT(cond)                                                                  \
+    do {                                                                              \
+        if (!(cond)) {                                                                \
+            std::printf("line %d: %s failed (%s)\n", __LINE__, #cond, g_error.c_str()); \
+            ++bad;                                                                    \
+        }                                                                             \
+    } while (0)
+
+static const int DS[] = {1, 16, 17, 64, 65, 128};
+static const int64_t MS[] = {1, 16, 65};
+
+static void design_and_observations() {
+    for (int D : DS)
+        for (int64_t M : MS) {
+            Buf<double> X = dbuf(M * D, 0.25, 0.5);
+            EXPECT(glm_check_design(D, M, X.get()) == PBBI_OK);
+            EXPECT(glm_image_len(D, M) == glm_blocks_padded(M) * glm_padded_dim(D) * 32);
+            Buf<double> img = dbuf(glm_image_len(D, M), -1.0);
+            glm_pack(D, M, X.get(), img.get());
+            EXPECT(img[0] == X[0]);  // P1[0][0][0] = X[0][0]
+            // [X | 0] at every padded dimension that holds D (the hierarchical and dispersion handles' images)
+            for (int DP = glm_padded_dim(D); DP <= 128; DP *= 2) {
+                Buf<double> wide = dbuf(glm_blocks_padded(M) * DP * 32, -1.0);
+                glm_pack_dp(D, DP, M, X.get(), wide.get());
+                EXPECT(wide[0] == X[0]);
+            }
+        }
+    for (int64_t M : MS) {
+        Buf<double> y = dbuf(M, 1.0), w = dbuf(M, 0.5, 0.25), o = dbuf(M, -0.5, 0.125), n = dbuf(M, 2.0);
+        Buf<double> out = dbuf(glm_obs_len(M), -1.0);
+        for (int opt = 0; opt < 2; ++opt) {  // every optional argument given, every one NULL
+            const double *wp = opt ? w.get() : nullptr, *op = opt ? o.get() : nullptr, *np = opt ? n.get() : nullptr;
+            EXPECT(glm_check_obs(M, PBBI_GLM_LOGISTIC, y.get(), wp, op, np) == PBBI_OK);
+            EXPECT(glm_check_obs(M, PBBI_GLM_POISSON, y.get(), wp, op, nullptr) == PBBI_OK);
+            glm_pack_obs(M, y.get(), wp, op, np, out.get());
+            EXPECT(out[(size_t)(glm_obs_len(M) / 3 + M - 1)] == (opt ? w[(size_t)(M - 1)] : 1.0));  // d = a y, y = 1
+            EXPECT(glm_check_obs_disp(M, PBBI_GLM_GAUSSIAN, y.get(), wp, op) == PBBI_OK);
+            EXPECT(glm_check_obs_disp(M, PBBI_GLM_NEGBINOMIAL, y.get(), wp, op) == PBBI_OK);
+            glm_pack_obs_disp(M, y.get(), wp, op, out.get());
+            EXPECT(out[(size_t)(glm_obs_len(M) - 1)] == 0.0);  // the offsets' padding
+        }
+        y[(size_t)(M - 1)] = 3.0;  // the LAST observation is the one found: above its trials, and no integer for the counts
+        EXPECT(glm_check_obs(M, PBBI_GLM_LOGISTIC, y.get(), nullptr, nullptr, n.get()) == PBBI_ERR_INVALID);
+        y[(size_t)(M - 1)] = 0.5;
+        EXPECT(glm_check_obs_disp(M, PBBI_GLM_NEGBINOMIAL, y.get(), nullptr, nullptr) == PBBI_ERR_INVALID);
+    }
+    for (int D : DS) {
+        Buf<double> lam = dbuf(D, 0.5, 0.5), mu = dbuf(D, -1.0, 0.5);
+        EXPECT(glm_check_prior(D, lam.get(), mu.get()) == PBBI_OK);
+        EXPECT(glm_check_prior(D, lam.get(), nullptr) == PBBI_OK);
+        lam[(size_t)(D - 1)] = -1.0;
+        EXPECT(glm_check_prior(D, lam.get(), mu.get()) == PBBI_ERR_INVALID);
+    }
+}
+
+// groups of a D-coefficient model with J groups: coefficient d in group d % (J + 1) - 1 (so -1, fixed, comes round too) once
+// every group has a member; group 0 alone where D < J + 1 leaves no room for that
+static Buf<int32_t> groups_of(int D, int J) {
+    Buf<int32_t> g(new int32_t[(size_t)D]);
+    for (int d = 0; d < D; ++d) g[(size_t)d] = D >= J + 1 ? d % (J + 1) - 1 : d % J;
+    return g;
+}
+
+static void hierarchical_tables() {
+    const int JS[] = {1, 4};
+    for (int D : DS)
+        for (int J : JS) {
+            Buf<double> lam = dbuf(D, 0.5, 0.5), mu = dbuf(D, -1.0, 0.5), tprior = dbuf(2 * J, 0.25, 0.25);
+            Buf<int32_t> groups = groups_of(D, J);
+            const int rc = glm_check_hier(D, J, lam.get(), mu.get(), groups.get(), tprior.get());
+            EXPECT(rc == (D >= J ? PBBI_OK : PBBI_ERR_INVALID));  // fewer coefficients than groups: one is unused
+            if (rc != PBBI_OK) continue;
+            for (int sample = 0; sample < 2; ++sample) {
+                const int Dt = D + J + sample;
+                if (Dt > 128) continue;  // the packers' own limit (the entries refuse it before they pack)
+                const int DP = glm_padded_dim(Dt);
+                Buf<double> dprior = dbuf(2, 0.5), nj = dbuf(J, -1.0);
+                EXPECT(glm_check_hier_disp_theta(sample, 0.25, sample ? dprior.get() : nullptr) == PBBI_OK);
+                EXPECT(glm_check_hier_disp_theta(sample, 0.25, sample ? nullptr : dprior.get()) == PBBI_ERR_INVALID);
+                Buf<double> tab = dbuf(2 * DP, -7.0);
+                glm_pack_prior_groups_disp(D, J, lam.get(), mu.get(), groups.get(), tprior.get(), sample, dprior.get(), tab.get(),
+                                           nj.get());
+                EXPECT(tab[(size_t)(D + J - 1)] == tprior[(size_t)(2 * J - 1)]);         // lam of t_{J-1}
+                EXPECT(tab[(size_t)(DP + D + J - 1)] == tprior[(size_t)(2 * J - 2)]);    // its mean
+                if (sample) EXPECT(tab[(size_t)(D + J)] == dprior[1] && tab[(size_t)(DP + D + J)] == dprior[0]);
+                if (!sample) {  // the table of the logistic / poisson handles is the same one without theta
+                    Buf<double> plain = dbuf(2 * DP, -7.0);
+                    glm_pack_prior_groups(D, J, lam.get(), mu.get(), groups.get(), tprior.get(), plain.get(), nj.get());
+                    for (int i = 0; i < 2 * DP; ++i) EXPECT(plain[(size_t)i] == tab[(size_t)i]);
+                    double members = 0.0;
+                    for (int j = 0; j < J; ++j) members += nj[(size_t)j];
+                    EXPECT(members >= (double)J && members <= (double)D);
+                }
+            }
+        }
+}
+
+// a first-order random walk (RW1, rank n - 1; [1] for n = 1) on every group's coefficients, zero elsewhere
+static Buf<double> rw1_penalty(int D, int J, const int32_t* groups, double* rank) {
+    Buf<double> Q = dbuf((int64_t)D * D, 0.0);
+    for (int j = 0; j < J; ++j) {
+        int prev = -1, n = 0;
+        for (int d = 0; d < D; ++d) {
+            if (groups[d] != j) continue;
+            if (prev >= 0) {
+                Q[(size_t)prev * D + prev] += 1.0; Q[(size_t)d * D + d] += 1.0;
+                Q[(size_t)prev * D + d] -= 1.0; Q[(size_t)d * D + prev] -= 1.0;
+            }
+            prev = d; ++n;
+        }
+        if (n == 1) Q[(size_t)prev * D + prev] = 1.0;
+        rank[j] = n == 1 ? 1.0 : (double)(n - 1);
+    }
+    return Q;
+}
+
+static void penalties() {
+    // {D, J}: one group of one; 16 and 17 coefficients in 1 and 4 groups; four groups of one; the largest group the kernels
+    // serve (D + J <= 64: 63 coefficients, all in one group -- the eigenvalue routine's largest matrix); the most rows with J = 4
+    const int shapes[][2] = {{1, 1}, {16, 1}, {16, 4}, {17, 1}, {17, 4}, {4, 4}, {63, 1}, {60, 4}};
+    for (const auto& sh : shapes) {
+        const int D = sh[0], J = sh[1];
+        Buf<int32_t> groups = groups_of(D, J);
+        if (D == 63) for (int d = 0; d < D; ++d) groups[(size_t)d] = 0;
+        Buf<double> rank = dbuf(J, 0.0);
+        Buf<double> Q = rw1_penalty(D, J, groups.get(), rank.get());
+        EXPECT(glm_check_penalty(D, J, groups.get(), Q.get(), rank.get()) == PBBI_OK);
+        EXPECT(glm_penalty_image_len(D, J) == (int64_t)glm_padded_dim(D + J) * glm_padded_dim(D + J));
+        Buf<double> img = dbuf(glm_penalty_image_len(D, J), -1.0);
+        glm_pack_penalty(D, J, Q.get(), img.get());
+        EXPECT(img[0] == Q[0]);
+        Q[(size_t)D * D - 1] = -1.0;  // the LAST entry: indefinite (or non-zero on a fixed row)
+        EXPECT(glm_check_penalty(D, J, groups.get(), Q.get(), rank.get()) == PBBI_ERR_INVALID);
+    }
+    // the packer alone serves up to D + J = 128
+    for (int D : {65, 124, 127}) {
+        const int J = D == 127 ? 1 : 4;
+        Buf<double> Q = dbuf((int64_t)D * D, 0.5, 0.25), img = dbuf(glm_penalty_image_len(D, J), -1.0);
+        glm_pack_penalty(D, J, Q.get(), img.get());
+        EXPECT(img[0] == Q[0]);
+    }
+}
+
+static void softmax_shapes() {
+    const int shapes[][2] = {{1, 2}, {16, 8}, {17, 4}, {64, 2}};
+    for (const auto& sh : shapes)
+        for (int64_t M : MS) {
+            const int D = sh[0], K = sh[1];
+            int Dc = 0, NT = 0;
+            EXPECT(glm_softmax_layout(D, K, &Dc, &NT, nullptr) == PBBI_OK);
+            EXPECT(Dc == glm_padded_dim(D) && NT == K * Dc / 16);
+            Buf<int32_t> rows(new int32_t[(size_t)NT * 16]);
+            EXPECT(glm_softmax_layout(D, K, nullptr, nullptr, rows.get()) == PBBI_OK);
+            EXPECT(rows[(size_t)NT * 16 - 1] == (D == Dc ? K * D - 1 : -1));
+            Buf<double> X = dbuf(M * D, 0.25, 0.5), y = dbuf(M, (double)(K - 1)), lam = dbuf(D, 0.5);
+            EXPECT(glm_softmax_check(D, K, M, X.get(), y.get(), lam.get()) == PBBI_OK);
+            y[(size_t)(M - 1)] = (double)K;
+            EXPECT(glm_softmax_check(D, K, M, X.get(), y.get(), lam.get()) == PBBI_ERR_INVALID);
+        }
+    EXPECT(glm_softmax_layout(17, 8, nullptr, nullptr, nullptr) == PBBI_ERR_UNSUPPORTED);
+    EXPECT(glm_softmax_layout(65, 2, nullptr, nullptr, nullptr) == PBBI_ERR_UNSUPPORTED);
+}
+
+int main() {
+    design_and_observations();
+    hierarchical_tables();
+    penalties();
+    softmax_shapes();
+    // what is shipped (the one statement the entries and the launch read)
+    EXPECT(glm_max_dim(GLM_V_PLAIN, PBBI_GLM_LOGISTIC) == 128 && glm_max_dim(GLM_V_FULL, PBBI_GLM_POISSON) == 128);
+    EXPECT(glm_max_dim(GLM_V_DISPERSION, PBBI_GLM_GAUSSIAN) == 128 && glm_max_dim(GLM_V_DISPERSION, PBBI_GLM_NEGBINOMIAL) == 64);
+    for (int v : {GLM_V_HIER, GLM_V_HIER_NC, GLM_V_HIER_Q})
+        EXPECT(glm_max_dim(v, PBBI_GLM_LOGISTIC) == 64 && glm_max_dim(v, PBBI_GLM_POISSON) == 64 && glm_max_dim(v, PBBI_GLM_GAUSSIAN) == 0);
+    EXPECT(glm_max_dim(GLM_V_HIER_DISPERSION, PBBI_GLM_GAUSSIAN) == 64 && glm_max_dim(GLM_V_HIER_DISPERSION, PBBI_GLM_LOGISTIC) == 0);
+    EXPECT(glm_max_dim(GLM_V_SOFTMAX, PBBI_GLM_SOFTMAX) == 0 && glm_max_dim(99, PBBI_GLM_LOGISTIC) == 0);
+    if (bad) {
+        std::printf("%d expectation(s) failed\n", bad);
+        return 1;
+    }
+    std::printf("asan ok\n");
+    return 0;
+}

@@ -1,0 +1,366 @@
+// glm_host.cpp -- the host side of the GLM potentials that calls no HIP function: which kernels are shipped, the argument
+// rules of the create entries, and the packers that lay the design matrix, the observation streams, the prior table and the
+// penalty out the way k_glm and k_glm_softmax read them (kernels_glm.hip and kernels_glm_softmax.hip describe the layouts
+// from the device's side).  Plain C++, built once for libpbbi.so and once more, sanitized, with glm_asan_driver.cpp.
+#include "glm_host.h"
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+static bool glm_disp(int fam) { return fam == PBBI_GLM_GAUSSIAN || fam == PBBI_GLM_NEGBINOMIAL; }
+static bool glm_canonical(int fam) { return fam == PBBI_GLM_LOGISTIC || fam == PBBI_GLM_POISSON; }
+
+// An instantiation ships only if it builds without scratch (profiles/glm_*_resources.txt).  The frame's widest kernel has 128
+// rows.  The full model's kernels at 128 rows already fill the register file, so nothing built on them has one there: not the
+// negative binomial (the constants of its exp, log and two series), not the hierarchical priors in any form (172 and 180 bytes
+// of scratch per lane for the centred ones), not the dispersion families with random effects.  The softmax kernels' shapes
+// are a rule on (D, K): glm_softmax_layout.
+int glm_max_dim(int variant, int family) {
+    switch (variant) {
+        case GLM_V_PLAIN:
+        case GLM_V_FULL: return glm_canonical(family) ? 128 : 0;
+        case GLM_V_DISPERSION: return family == PBBI_GLM_GAUSSIAN ? 128 : family == PBBI_GLM_NEGBINOMIAL ? 64 : 0;
+        case GLM_V_HIER:
+        case GLM_V_HIER_NC:
+        case GLM_V_HIER_Q: return glm_canonical(family) ? 64 : 0;
+        case GLM_V_HIER_DISPERSION: return glm_disp(family) ? 64 : 0;
+    }
+    return 0;
+}
+
+// ---- the fragment image of X ------------------------------------------------------------------------------------
+int glm_padded_dim(int D) { return D <= 16 ? 16 : D <= 32 ? 32 : D <= 64 ? 64 : 128; }
+int64_t glm_blocks_padded(int64_t M) { return ((M + 15) / 16 + 3) / 4 * 4; }
+int64_t glm_image_len(int D, int64_t M) { return glm_blocks_padded(M) * (int64_t)glm_padded_dim(D) * 32; }
+
+// X (M x D, row-major) -> per block of 16 observations P1 [KS/2][64][2] then P2 [2][NT][64][2] (see the top of
+// kernels_glm.hip), zero padded to DP columns and to a multiple of 4 blocks.
+void glm_pack(int D, int64_t M, const double* X, double* out) { glm_pack_dp(D, glm_padded_dim(D), M, X, out); }
+// the first product's A fragments of block b, P1[s2][lane][e] = at(16 b + (lane & 15), 4 (2 s2 + e) + (lane >> 4)): the one
+// statement of that order, for the design (glm_pack_dp) and for the penalty of the structured group priors (glm_pack_penalty)
+template <class At>
+static void glm_pack_p1(int KS, int64_t b, const At& at, double* P1) {
+    for (int l = 0; l < 64; ++l) {
+        const int lo = l & 15, hi = l >> 4;
+        for (int s2 = 0; s2 < KS / 2; ++s2)
+            for (int e = 0; e < 2; ++e)
+                P1[((size_t)s2 * 64 + l) * 2 + e] = at(16 * b + lo, 4 * (2 * s2 + e) + hi);
+    }
+}
+// ... at a padded dimension DP >= D of the caller's: the image of [X | 0]
+void glm_pack_dp(int D, int DP, int64_t M, const double* X, double* out) {
+    const int NT = DP / 16, KS = DP / 4;
+    const int64_t nbp = glm_blocks_padded(M);
+    const int64_t blk_len = (int64_t)DP * 32;
+    std::memset(out, 0, sizeof(double) * (size_t)(nbp * blk_len));
+    auto at = [&](int64_t i, int d) -> double { return (i < M && d < D) ? X[(size_t)i * D + d] : 0.0; };
+    for (int64_t b = 0; b < (M + 15) / 16; ++b) {
+        double* P1 = out + b * blk_len;
+        double* P2 = P1 + (int64_t)KS * 64;
+        glm_pack_p1(KS, b, at, P1);
+        for (int l = 0; l < 64; ++l) {
+            const int lo = l & 15, hi = l >> 4;
+            for (int r2 = 0; r2 < 2; ++r2)
+                for (int t = 0; t < NT; ++t)
+                    for (int e = 0; e < 2; ++e)
+                        P2[(((size_t)r2 * NT + t) * 64 + l) * 2 + e] = at(16 * b + 4 * (2 * r2 + e) + hi, 16 * t + lo);
+        }
+    }
+}
+
+int glm_check_design(int D, int64_t M, const double* X) {
+    for (int64_t i = 0; i < M * D; ++i)
+        if (!std::isfinite(X[i])) return pbbi_fail(PBBI_ERR_INVALID, "X must be finite");
+    return PBBI_OK;
+}
+
+// ---- the full model's observation streams and prior vectors -----------------------------------------------------
+int64_t glm_obs_len(int64_t M) { return 3 * glm_blocks_padded(M) * 16; }
+
+// Every rule of the full model's per-observation arguments (NULL = the default: weights 1, offset 0, trials 1).
+int glm_check_obs(int64_t M, int family, const double* y, const double* weights, const double* offset,
+                  const double* trials) {
+    if (M < 1) return pbbi_fail(PBBI_ERR_INVALID, "M must be >= 1");
+    if (!glm_canonical(family)) return pbbi_fail(PBBI_ERR_INVALID, "unknown GLM family");
+    if (!y) return pbbi_fail(PBBI_ERR_INVALID, "y is NULL");
+    if (trials && family != PBBI_GLM_LOGISTIC)
+        return pbbi_fail(PBBI_ERR_INVALID, "trials belong to the logistic (binomial) family only");
+    for (int64_t i = 0; i < M; ++i) {
+        auto at = [i] { return " (observation " + std::to_string(i) + ")"; };
+        const double n = trials ? trials[i] : 1.0;
+        if (!std::isfinite(n) || n < 1.0 || n != std::floor(n))
+            return pbbi_fail(PBBI_ERR_INVALID, "trials must be integers >= 1" + at());
+        if (!std::isfinite(y[i]) || y[i] < 0.0 || y[i] != std::floor(y[i]))
+            return pbbi_fail(PBBI_ERR_INVALID, "y must hold non-negative integers" + at());
+        if (family == PBBI_GLM_LOGISTIC && y[i] > n)
+            return pbbi_fail(PBBI_ERR_INVALID, "logistic: y must not exceed the trials" + at());
+        if (weights && !(std::isfinite(weights[i]) && weights[i] >= 0.0))
+            return pbbi_fail(PBBI_ERR_INVALID, "weights must be finite and >= 0" + at());
+        if (offset && !std::isfinite(offset[i]))
+            return pbbi_fail(PBBI_ERR_INVALID, "offset must be finite" + at());
+    }
+    return PBBI_OK;
+}
+
+// c = a n | d = a y | o, each zero padded to the image's block count (glm_obs_len(M) doubles).
+void glm_pack_obs(int64_t M, const double* y, const double* weights, const double* offset, const double* trials,
+                  double* out) {
+    const int64_t len = glm_blocks_padded(M) * 16;
+    std::memset(out, 0, sizeof(double) * (size_t)(3 * len));
+    for (int64_t i = 0; i < M; ++i) {
+        const double a = weights ? weights[i] : 1.0;
+        out[i] = a * (trials ? trials[i] : 1.0);
+        out[len + i] = a * y[i];
+        out[2 * len + i] = offset ? offset[i] : 0.0;
+    }
+}
+
+int glm_check_prior(int D, const double* lam, const double* mu) {
+    if (!lam) return pbbi_fail(PBBI_ERR_INVALID, "prior_precision is NULL");
+    for (int d = 0; d < D; ++d) {
+        if (!(std::isfinite(lam[d]) && lam[d] >= 0.0))
+            return pbbi_fail(PBBI_ERR_INVALID, "prior_precision must be finite and >= 0 (coefficient " + std::to_string(d) + ")");
+        if (mu && !std::isfinite(mu[d]))
+            return pbbi_fail(PBBI_ERR_INVALID, "prior_mean must be finite (coefficient " + std::to_string(d) + ")");
+    }
+    return PBBI_OK;
+}
+
+// ---- the dispersion families ------------------------------------------------------------------------------------
+int glm_check_obs_disp(int64_t M, int family, const double* y, const double* weights, const double* offset) {
+    if (M < 1) return pbbi_fail(PBBI_ERR_INVALID, "M must be >= 1");
+    if (!glm_disp(family)) return pbbi_fail(PBBI_ERR_INVALID, "unknown dispersion family (gaussian = 3, negbinomial = 4)");
+    if (!y) return pbbi_fail(PBBI_ERR_INVALID, "y is NULL");
+    for (int64_t i = 0; i < M; ++i) {
+        auto at = [i] { return " (observation " + std::to_string(i) + ")"; };
+        if (!std::isfinite(y[i])) return pbbi_fail(PBBI_ERR_INVALID, "y must be finite" + at());
+        if (family == PBBI_GLM_NEGBINOMIAL && (y[i] < 0.0 || y[i] != std::floor(y[i])))
+            return pbbi_fail(PBBI_ERR_INVALID, "negbinomial: y must hold non-negative integers" + at());
+        if (weights && !(std::isfinite(weights[i]) && weights[i] >= 0.0))
+            return pbbi_fail(PBBI_ERR_INVALID, "weights must be finite and >= 0" + at());
+        if (offset && !std::isfinite(offset[i]))
+            return pbbi_fail(PBBI_ERR_INVALID, "offset must be finite" + at());
+    }
+    return PBBI_OK;
+}
+
+// c = a | d = y (raw) | o, each zero padded to the image's block count (glm_obs_len(M) doubles).
+void glm_pack_obs_disp(int64_t M, const double* y, const double* weights, const double* offset, double* out) {
+    const int64_t len = glm_blocks_padded(M) * 16;
+    std::memset(out, 0, sizeof(double) * (size_t)(3 * len));
+    for (int64_t i = 0; i < M; ++i) {
+        out[i] = weights ? weights[i] : 1.0;
+        out[len + i] = y[i];
+        out[2 * len + i] = offset ? offset[i] : 0.0;
+    }
+}
+
+// ---- the hierarchical prior -------------------------------------------------------------------------------------
+// Every rule of the hierarchical prior's arguments: groups (D entries, -1 or 0 .. J-1, every index used), the fixed rows'
+// {lam, mu}, the J pairs (mean, precision) of the log-scales.
+int glm_check_hier(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior) {
+    if (D < 1) return pbbi_fail(PBBI_ERR_INVALID, "D must be >= 1");
+    if (J < 1 || J > 4)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "hierarchical prior: the number of groups J must be 1 .. 4 (J = " +
+                                                   std::to_string(J) + ")");
+    if (!groups) return pbbi_fail(PBBI_ERR_INVALID, "groups is NULL");
+    if (!lam) return pbbi_fail(PBBI_ERR_INVALID, "prior_precision is NULL");
+    if (!tprior) return pbbi_fail(PBBI_ERR_INVALID, "log_scale_prior is NULL");
+    int count[4] = {0, 0, 0, 0};
+    for (int d = 0; d < D; ++d) {
+        if (groups[d] < -1 || groups[d] >= J)
+            return pbbi_fail(PBBI_ERR_INVALID, "groups must hold -1 (fixed prior) or a group index 0 .. J-1 (coefficient " +
+                                                   std::to_string(d) + ": " + std::to_string(groups[d]) + ", J = " +
+                                                   std::to_string(J) + ")");
+        if (groups[d] >= 0) ++count[groups[d]];
+        // a grouped coefficient's fixed precision is not used
+        if (groups[d] < 0 && !(std::isfinite(lam[d]) && lam[d] >= 0.0))
+            return pbbi_fail(PBBI_ERR_INVALID, "prior_precision must be finite and >= 0 (coefficient " + std::to_string(d) + ")");
+        if (mu && !std::isfinite(mu[d]))
+            return pbbi_fail(PBBI_ERR_INVALID, "prior_mean must be finite (coefficient " + std::to_string(d) + ")");
+    }
+    for (int j = 0; j < J; ++j) {
+        if (count[j] == 0)
+            return pbbi_fail(PBBI_ERR_INVALID, "every group index 0 .. J-1 must be used (group " + std::to_string(j) +
+                                                   " has no coefficient)");
+        if (!std::isfinite(tprior[2 * j]) || !(std::isfinite(tprior[2 * j + 1]) && tprior[2 * j + 1] >= 0.0))
+            return pbbi_fail(PBBI_ERR_INVALID, "log_scale_prior must hold J pairs (finite mean, finite precision >= 0) "
+                                               "(group " + std::to_string(j) + ")");
+    }
+    return PBBI_OK;
+}
+
+// The table the hierarchical kernels stage into plds, lam (DP) | mu (DP) with DP = glm_padded_dim(D + J): a fixed row its
+// {lam_d, mu_d}, a member of group j {-(j + 1), mu_d}, row D + j {lam_tj, m_tj}, zeros past D + J; n_out[j] = the members
+// of group j.  The caller has run glm_check_hier.
+void glm_pack_prior_groups(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior,
+                           double* out, double* n_out) {
+    const int DP = glm_padded_dim(D + J);
+    std::memset(out, 0, sizeof(double) * (size_t)(2 * DP));
+    for (int j = 0; j < J; ++j) n_out[j] = 0.0;
+    for (int d = 0; d < D; ++d) {
+        out[d] = groups[d] < 0 ? lam[d] : -(double)(groups[d] + 1);
+        out[DP + d] = mu ? mu[d] : 0.0;
+        if (groups[d] >= 0) n_out[groups[d]] += 1.0;
+    }
+    for (int j = 0; j < J; ++j) {
+        out[D + j] = tprior[2 * j + 1];
+        out[DP + D + j] = tprior[2 * j];
+    }
+}
+
+// ---- random effects for the dispersion families -----------------------------------------------------------------
+// Every rule of the log-dispersion's arguments: sampled, a pair (finite mean, finite precision >= 0) is required; held, theta
+// must be finite and there is no prior to give.
+int glm_check_hier_disp_theta(int sample, double theta, const double* dprior) {
+    if (sample) {
+        if (!dprior) return pbbi_fail(PBBI_ERR_INVALID, "log_dispersion_prior is NULL (a sampled dispersion needs its pair (mean, precision))");
+        if (!std::isfinite(dprior[0]) || !(std::isfinite(dprior[1]) && dprior[1] >= 0.0))
+            return pbbi_fail(PBBI_ERR_INVALID, "log_dispersion_prior must be (finite mean, finite precision >= 0)");
+    } else {
+        if (dprior) return pbbi_fail(PBBI_ERR_INVALID, "log_dispersion_prior belongs to a sampled dispersion only: a held one has no prior");
+        if (!std::isfinite(theta))
+            return pbbi_fail(PBBI_ERR_INVALID, "a held dispersion must be finite and > 0 (theta = its logarithm)");
+    }
+    return PBBI_OK;
+}
+
+// The table of glm_pack_prior_groups at DP = glm_padded_dim(D + J + (sample ? 1 : 0)), with theta's {lam_theta, m_theta} at row
+// D + J when it is sampled (a fixed row: a non-negative lam slot) and zeros past the state.  The caller has run glm_check_hier
+// and glm_check_hier_disp_theta.
+void glm_pack_prior_groups_disp(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior,
+                                int sample, const double* dprior, double* out, double* n_out) {
+    const int DP = glm_padded_dim(D + J + (sample ? 1 : 0)), DPh = glm_padded_dim(D + J);
+    std::vector<double> tab((size_t)2 * DPh);
+    glm_pack_prior_groups(D, J, lam, mu, groups, tprior, tab.data(), n_out);  // the one statement of the codes
+    std::memset(out, 0, sizeof(double) * (size_t)(2 * DP));
+    for (int d = 0; d < D + J; ++d) {
+        out[d] = tab[(size_t)d];
+        out[DP + d] = tab[(size_t)DPh + d];
+    }
+    if (sample) {
+        out[D + J] = dprior[1];
+        out[DP + D + J] = dprior[0];
+    }
+}
+
+// ---- structured group priors ------------------------------------------------------------------------------------
+int64_t glm_penalty_image_len(int D, int J) { const int64_t DP = glm_padded_dim(D + J); return DP * DP; }
+
+// The eigenvalues of a symmetric n x n matrix (row-major in a, destroyed) by cyclic Jacobi rotations, into ev.  n <= 63 here.
+static void glm_sym_eigenvalues(int n, std::vector<double>& a, std::vector<double>& ev) {
+    for (int sweep = 0; sweep < 64; ++sweep) {
+        double off = 0.0, diag = 0.0;
+        for (int i = 0; i < n; ++i)
+            for (int k = 0; k < n; ++k) (i == k ? diag : off) += a[(size_t)i * n + k] * a[(size_t)i * n + k];
+        if (off <= 1e-30 * diag || off == 0.0) break;
+        for (int p = 0; p < n - 1; ++p)
+            for (int q = p + 1; q < n; ++q) {
+                const double apq = a[(size_t)p * n + q];
+                if (apq == 0.0) continue;
+                const double theta = (a[(size_t)q * n + q] - a[(size_t)p * n + p]) / (2.0 * apq);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < n; ++k) {  // columns p, q
+                    const double akp = a[(size_t)k * n + p], akq = a[(size_t)k * n + q];
+                    a[(size_t)k * n + p] = c * akp - s * akq;
+                    a[(size_t)k * n + q] = s * akp + c * akq;
+                }
+                for (int k = 0; k < n; ++k) {  // rows p, q
+                    const double apk = a[(size_t)p * n + k], aqk = a[(size_t)q * n + k];
+                    a[(size_t)p * n + k] = c * apk - s * aqk;
+                    a[(size_t)q * n + k] = s * apk + c * aqk;
+                }
+            }
+    }
+    ev.resize((size_t)n);
+    for (int i = 0; i < n; ++i) ev[(size_t)i] = a[(size_t)i * n + i];
+}
+
+// Every rule of the penalty of the structured group priors: a (D x D) row-major matrix in coefficient indexing, finite,
+// zero on fixed rows and between different groups, each group's block symmetric to 1e-12 of its largest entry, positive
+// semi-definite (smallest eigenvalue >= -1e-10 x the largest) and not zero; rank[j] an integer in 1 .. n_j.  The caller has
+// run glm_check_hier.
+int glm_check_penalty(int D, int J, const int32_t* groups, const double* penalty, const double* rank) {
+    if (!penalty) return pbbi_fail(PBBI_ERR_INVALID, "penalty is NULL");
+    if (!rank) return pbbi_fail(PBBI_ERR_INVALID, "penalty_rank is NULL");
+    for (int a = 0; a < D; ++a)
+        for (int b = 0; b < D; ++b) {
+            const double v = penalty[(size_t)a * D + b];
+            if (!std::isfinite(v))
+                return pbbi_fail(PBBI_ERR_INVALID, "penalty must be finite (entry " + std::to_string(a) + ", " + std::to_string(b) + ")");
+            if (v != 0.0 && (groups[a] < 0 || groups[a] != groups[b]))
+                return pbbi_fail(PBBI_ERR_INVALID, "penalty must be zero on fixed rows and between different groups (entry " +
+                                                       std::to_string(a) + ", " + std::to_string(b) + ")");
+        }
+    for (int j = 0; j < J; ++j) {
+        std::vector<int> idx;
+        for (int d = 0; d < D; ++d)
+            if (groups[d] == j) idx.push_back(d);
+        const int n = (int)idx.size();
+        const std::string grp = " (group " + std::to_string(j) + ")";
+        double big = 0.0, asym = 0.0;
+        std::vector<double> blk((size_t)n * n);
+        for (int a = 0; a < n; ++a)
+            for (int b = 0; b < n; ++b) {
+                const double v = penalty[(size_t)idx[a] * D + idx[b]], vt = penalty[(size_t)idx[b] * D + idx[a]];
+                big = std::fmax(big, std::fabs(v));
+                asym = std::fmax(asym, std::fabs(v - vt));
+                blk[(size_t)a * n + b] = 0.5 * (v + vt);
+            }
+        if (big == 0.0) return pbbi_fail(PBBI_ERR_INVALID, "penalty must not be the zero matrix" + grp);
+        if (asym > 1e-12 * big) return pbbi_fail(PBBI_ERR_INVALID, "penalty must be symmetric" + grp);
+        std::vector<double> ev;
+        glm_sym_eigenvalues(n, blk, ev);
+        double lo = ev[0], hi = ev[0];
+        for (double v : ev) { lo = std::fmin(lo, v); hi = std::fmax(hi, v); }
+        if (!(hi > 0.0) || lo < -1e-10 * hi)
+            return pbbi_fail(PBBI_ERR_INVALID, "penalty must be positive semi-definite" + grp);
+        if (!std::isfinite(rank[j]) || rank[j] != std::floor(rank[j]) || rank[j] < 1.0 || rank[j] > (double)n)
+            return pbbi_fail(PBBI_ERR_INVALID, "penalty_rank must be an integer in 1 .. n_j" + grp);
+    }
+    return PBBI_OK;
+}
+
+// The image of the (DP x DP) penalty the kernel keeps in LDS, DP = glm_padded_dim(D + J): DP / 16 blocks of 16 rows, each in
+// the first product's A-fragment order (glm_pack_p1), (Q + Q^T) / 2 on rows and columns < D and zero beyond.
+void glm_pack_penalty(int D, int J, const double* penalty, double* out) {
+    const int DP = glm_padded_dim(D + J), KS = DP / 4;
+    auto at = [&](int64_t i, int d) -> double {
+        return (i < D && d < D) ? 0.5 * (penalty[(size_t)i * D + d] + penalty[(size_t)d * D + i]) : 0.0;
+    };
+    for (int b = 0; b < DP / 16; ++b) glm_pack_p1(KS, b, at, out + (size_t)b * KS * 64);
+}
+
+// ---- K-class softmax regression ---------------------------------------------------------------------------------
+const char* const GLM_SOFTMAX_RULE = "softmax GLM: float64, 2 <= K <= 8 classes, each padded to Dc = 16, 32 or 64 rows with "
+                                     "K * Dc <= 128 (D <= 16 for K <= 8, D <= 32 for K <= 4, D <= 64 for K = 2)";
+
+// The padded class size and the tile count of a (D, K) model, and the external row of each of the NT * 16 internal
+// rows (-1 = padding).
+int glm_softmax_layout(int D, int K, int* Dc_out, int* NT_out, int32_t* row_map) {
+    if (D < 1 || K < 2 || K > 8 || D > 64) return pbbi_fail(PBBI_ERR_UNSUPPORTED, GLM_SOFTMAX_RULE);
+    const int Dc = glm_padded_dim(D);
+    if (K * Dc > 128) return pbbi_fail(PBBI_ERR_UNSUPPORTED, GLM_SOFTMAX_RULE);
+    if (Dc_out) *Dc_out = Dc;
+    if (NT_out) *NT_out = K * Dc / 16;
+    if (row_map)
+        for (int k = 0; k < K; ++k)
+            for (int d = 0; d < Dc; ++d) row_map[k * Dc + d] = d < D ? k * D + d : -1;
+    return PBBI_OK;
+}
+
+int glm_softmax_check(int D, int K, int64_t M, const double* X, const double* y, const double* lam) {
+    if (!X || !y) return pbbi_fail(PBBI_ERR_INVALID, "X / y is NULL");
+    if (!lam) return pbbi_fail(PBBI_ERR_INVALID, "prior_precision is NULL");
+    if (M < 1) return pbbi_fail(PBBI_ERR_INVALID, "M must be >= 1");
+    if (D < 1) return pbbi_fail(PBBI_ERR_INVALID, "D must be >= 1");
+    if (K < 2) return pbbi_fail(PBBI_ERR_INVALID, "softmax GLM: at least two classes");
+    for (int64_t i = 0; i < M; ++i)
+        if (!(std::isfinite(y[i]) && y[i] >= 0.0 && y[i] < (double)K && y[i] == std::floor(y[i])))
+            return pbbi_fail(PBBI_ERR_INVALID, "labels must be integers in [0, K) (observation " + std::to_string(i) + ")");
+    for (int64_t i = 0; i < M * D; ++i)
+        if (!std::isfinite(X[i])) return pbbi_fail(PBBI_ERR_INVALID, "X must be finite (row " + std::to_string(i / D) + ")");
+    return glm_check_prior(D, lam, nullptr);
+}

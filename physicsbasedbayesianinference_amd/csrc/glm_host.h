@@ -1,0 +1,60 @@
+// glm_host.h -- the host side of the GLM potentials that calls no HIP function (glm_host.cpp): which kernels are shipped,
+// the argument rules of the create entries and the packers of what they upload.  Plain C++: no HIP header here, so the
+// translation unit links into a stand-alone program (glm_asan_driver.cpp) as well as into libpbbi.so.
+#pragma once
+#include <stdint.h>
+
+#include <string>
+
+#include "pbbi.h"
+
+int pbbi_fail(int code, const std::string& msg);  // pbbi_api.hip
+
+// The kind of a GLM handle (pbbi_potential::glm_variant): set once by the builder of its create entry, read by the
+// launch switch of kernels_glm.hip, the routing and pbbi_describe_run.
+enum GlmVariant {
+    GLM_V_PLAIN = 0,            // pbbi_potential_create_glm:                 k_glm<NT, FAM, false>
+    GLM_V_FULL = 1,             // pbbi_potential_create_glm_ex:              k_glm<NT, FAM, true>
+    GLM_V_SOFTMAX = 2,          // pbbi_potential_create_glm_softmax:         k_glm_softmax<NTc, K>
+    GLM_V_DISPERSION = 3,       // pbbi_potential_create_glm_dispersion:      k_glm<NT, FAM, true>, FAM = 3, 4
+    GLM_V_HIER = 4,             // pbbi_potential_create_glm_hier / _hier_ex: k_glm<NT, FAM, true, GLM_HIER_CENTRED>
+    GLM_V_HIER_NC = 5,          // pbbi_potential_create_glm_hier_ex:         k_glm<NT, FAM, true, GLM_HIER_NC>
+    GLM_V_HIER_Q = 6,           // pbbi_potential_create_glm_hier_q:          k_glm<NT, FAM, true, GLM_HIER_Q>
+    GLM_V_HIER_DISPERSION = 7,  // pbbi_potential_create_glm_hier_dispersion: FAM = 3, 4 with GLM_HIER_CENTRED / GLM_HIER_NC
+                                //   (which of the two: pbbi_potential::glm_hier_nc)
+};
+enum { GLM_TERM_WEIGHTS = 1, GLM_TERM_OFFSET = 2, GLM_TERM_TRIALS = 4, GLM_TERM_PRIOR_VECTOR = 8, GLM_TERM_PRIOR_MEAN = 16,
+       GLM_TERM_PRIOR_FLAT = 32 };
+
+// The largest state dimension (every sampled row: coefficients, group log-scales, a sampled log-dispersion) the kernels of a
+// variant serve for a family; 0 = nothing shipped.  The one statement of it: the create entries and the launch read this.
+int glm_max_dim(int variant, int family);
+
+// ---- the design matrix
+int glm_padded_dim(int D);                   // 16, 32, 64 or 128
+int64_t glm_blocks_padded(int64_t M);        // blocks of 16 observations, padded to a multiple of 4
+int64_t glm_image_len(int D, int64_t M);     // doubles of the fragment image of an M x D design matrix
+void glm_pack(int D, int64_t M, const double* X, double* out);
+void glm_pack_dp(int D, int DP, int64_t M, const double* X, double* out);  // ... of [X | 0] at a padded dimension DP >= D
+int glm_check_design(int D, int64_t M, const double* X);                   // every entry finite
+// ---- the observation streams (glm_obs_len(M) doubles) and the prior vectors
+int64_t glm_obs_len(int64_t M);
+int glm_check_obs(int64_t M, int family, const double* y, const double* weights, const double* offset, const double* trials);
+void glm_pack_obs(int64_t M, const double* y, const double* weights, const double* offset, const double* trials, double* out);
+int glm_check_prior(int D, const double* lam, const double* mu);
+int glm_check_obs_disp(int64_t M, int family, const double* y, const double* weights, const double* offset);
+void glm_pack_obs_disp(int64_t M, const double* y, const double* weights, const double* offset, double* out);
+// ---- hierarchical priors: the table the kernels keep in LDS, the log-dispersion's pair, the penalty image
+int glm_check_hier(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior);
+void glm_pack_prior_groups(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior,
+                           double* out, double* n_out);
+int glm_check_hier_disp_theta(int sample, double theta, const double* dprior);
+void glm_pack_prior_groups_disp(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior,
+                                int sample, const double* dprior, double* out, double* n_out);
+int glm_check_penalty(int D, int J, const int32_t* groups, const double* penalty, const double* rank);
+int64_t glm_penalty_image_len(int D, int J);  // doubles of the fragment image of the (DP x DP) penalty
+void glm_pack_penalty(int D, int J, const double* penalty, double* out);
+// ---- K-class softmax regression
+extern const char* const GLM_SOFTMAX_RULE;
+int glm_softmax_layout(int D, int K, int* Dc_out, int* NT_out, int32_t* row_map);
+int glm_softmax_check(int D, int K, int64_t M, const double* X, const double* y, const double* lam);

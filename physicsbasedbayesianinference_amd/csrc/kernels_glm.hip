@@ -7,7 +7,7 @@
 //
 // Layout.  One wave owns 16 chains and keeps q, the half-step velocity vh and the gradient accumulator in
 // registers in the layout of kernels_dense_dev.h: element s of a lane is row 4s + g, g = lane >> 4, chain =
-// lane & 15.  X travels through LDS in blocks of 16 observations, pre-swizzled on the host (glm_pack) into the
+// lane & 15.  X travels through LDS in blocks of 16 observations, pre-swizzled on the host (glm_pack, glm_host.cpp) into the
 // A-fragment order of v_mfma_f64_16x16x4_f64 -- twice, once per product:
 //   P1[s2][lane][e]     = X[16b + (lane & 15)][4 (2 s2 + e) + (lane >> 4)]       eta tile   = X_b (16 x DP) . W
 //   P2[r2][t][lane][e]  = X[16b + 4 (2 r2 + e) + (lane >> 4)][16 t + (lane & 15)] g tile t += X_b^T (DP x 16) . R_b
@@ -76,7 +76,7 @@
 // symmetric PSD matrix in each group's quadratic form, w_j - mu_j | t_j ~ N(0, exp(2 t_j) Q_j^-) -- random walks, ICAR,
 // difference penalties; Q_j = I is the model above.  The host lays the J blocks out as one (D x D) matrix in coefficient
 // indexing (identity on exchangeable groups, zero on fixed rows and between groups) and packs it with the FIRST product's
-// A-fragment writer, one block per 16 rows of Q (glm_pack_penalty): 8 DP^2 bytes that sit in LDS behind plds for the whole
+// A-fragment writer, one block per 16 rows of Q (glm_pack_penalty, glm_host.cpp): 8 DP^2 bytes that sit in LDS behind plds for the whole
 // launch.  Once per gradient evaluation, after glm_grad: dq[s] = member ? q[s] - mu : 0 (a SELECT on the sign of the lam
 // slot, so a t row or a diverged fixed row never meets a zero of Q as 0 * inf) is the B operand of K-step s exactly as q[s]
 // is for X_b . W, and tile t of Q . dq comes out with register r = row 16t + 4r + g: the state layout, no movement.  Tile by
@@ -94,14 +94,16 @@
 // non-centred branch has taken G[j] from gacc and scaled its grouped rows (the theta row is fixed, so either order is exact;
 // this one keeps the dispersion kernels' sequence of operations).  Nothing else is new: weff leaves the theta row as q, S_j and
 // G_j select on the group codes and never see it, kick / store / energy give it its {lam, mu} like any fixed row.
+//
+// This file holds the device code, the kernel-argument structs, glm_check, the launch switch and the entry points.  Which
+// shapes ship, the argument rules and the packers are glm_host.cpp (no HIP there); the builders that upload what the packers
+// make are pbbi_api.hip's; glm_args.h fills the arguments that come from a call.
 #include <cmath>
-#include <cstring>
 #include <type_traits>
 
+#include "glm_args.h"
 #include "kernels_dense_dev.h"
 #include "pbbi_chain.h"
-
-static int64_t glm_blocks_padded(int64_t M);
 
 namespace {
 
@@ -409,7 +411,7 @@ __device__ __forceinline__ void glm_grad(const typename GlmArgs<FAM, RICH, HIER>
 
 // Waves per SIMD: two up to DP = 32, except the negative binomial at DP = 32 -- the constants of its exp, log and two
 // series sit in vector registers beside the state (the scalar file is full), and held to 256 registers it spills; at DP
-// = 128 it spills even with all 512 and is not instantiated (glm_build_disp refuses that shape).
+// = 128 it spills even with all 512 and is not instantiated (glm_max_dim of glm_host.cpp says so to the create entry and to the launch).
 // Likewise the non-centred logistic kernel at DP = 32: q, its scaled copy and the link's constants need 12 bytes of scratch
 // at 256 registers.  The structured group priors (GLM_HIER_Q) keep the centred kernels' counts: all six build without scratch
 // at them (profiles/glm_hier_penalty_resources.txt).
@@ -906,648 +908,126 @@ GlmPrm glm_prm(const pbbi_potential* pot) {
     return prm;
 }
 
+// the full model's part of the arguments, which every kernel but the plain model's takes
+template <class Prm>
+Prm glm_prm_rich(const pbbi_potential* pot, const GlmPrm& prm) {
+    Prm r{};
+    static_cast<GlmPrm&>(r) = prm;
+    r.obs = (const double*)pot->d_glm_obs;
+    r.prior = (const double*)pot->d_glm_prior;
+    r.obs_stride = glm_blocks_padded(pot->glm_M) * 16;
+    return r;
+}
+// ... and the hierarchical prior's: the t rows follow the coefficients, a sampled theta is the last row, behind them
+template <class Prm>
+Prm glm_prm_hier(const pbbi_potential* pot, const GlmPrm& prm) {
+    Prm r = glm_prm_rich<Prm>(pot, prm);
+    r.trow0 = pot->D - pot->glm_hier_J - (pot->glm_trow >= 0 ? 1 : 0);
+    r.J = pot->glm_hier_J;
+    return r;
+}
+
+// One case per variant of handle (glm_host.h), each building the one argument struct its kernels take.  A variant, family or
+// padded dimension with no shipped kernel launches nothing and is PBBI_ERR_UNSUPPORTED.
 int glm_launch(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t stream) {
     const dim3 grid((unsigned)((prm.N + CHAINS_PER_WG - 1) / CHAINS_PER_WG)), block(BLOCK);
-    const bool rich = pot->d_glm_obs != nullptr;  // handle of pbbi_potential_create_glm_ex
-    GlmPrmRich rprm{};
-    static_cast<GlmPrm&>(rprm) = prm;
-    rprm.obs = (const double*)pot->d_glm_obs;
-    rprm.prior = (const double*)pot->d_glm_prior;
-    rprm.obs_stride = glm_blocks_padded(pot->glm_M) * 16;
-    const bool disp = glm_disp(pot->glm_family);  // handle of pbbi_potential_create_glm_dispersion or _glm_hier_dispersion
-    const bool hd = disp && pot->glm_hier_J > 0;  // ... the latter
-    GlmPrmDisp dprm{};
-    static_cast<GlmPrmRich&>(dprm) = rprm;
-    dprm.theta = pot->glm_theta;
-    dprm.trow = pot->glm_trow;
-    if (disp && pot->glm_family == PBBI_GLM_NEGBINOMIAL && pot->glm_DP > 64)
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "negbinomial: no kernel at a padded state dimension of 128 (internal)");
-#define GLM_DISP_CASE(NT_, FAM_)                                                                            \
-    if (disp && !hd && pot->glm_DP == 16 * NT_ && pot->glm_family == FAM_)                                  \
-        hipLaunchKernelGGL((k_glm<NT_, FAM_, true>), grid, block, 0, stream, dprm);
-    GLM_DISP_CASE(1, PBBI_GLM_GAUSSIAN) GLM_DISP_CASE(2, PBBI_GLM_GAUSSIAN) GLM_DISP_CASE(4, PBBI_GLM_GAUSSIAN)
-    GLM_DISP_CASE(8, PBBI_GLM_GAUSSIAN)
-    GLM_DISP_CASE(1, PBBI_GLM_NEGBINOMIAL) GLM_DISP_CASE(2, PBBI_GLM_NEGBINOMIAL) GLM_DISP_CASE(4, PBBI_GLM_NEGBINOMIAL)
-#undef GLM_DISP_CASE
-    const bool nc = pot->glm_hier_J > 0 && pot->glm_hier_nc && !hd;  // handle of pbbi_potential_create_glm_hier_ex, non-centred
-    const bool hq = pot->glm_hier_J > 0 && pot->d_glm_qimg;   // handle of pbbi_potential_create_glm_hier_q
-    const bool hier = pot->glm_hier_J > 0 && !nc && !hq && !hd;  // handle of pbbi_potential_create_glm_hier
-    GlmPrmHier hprm{};
-    static_cast<GlmPrmRich&>(hprm) = rprm;
-    hprm.trow0 = pot->D - pot->glm_hier_J - (hd && pot->glm_trow >= 0 ? 1 : 0);  // a sampled theta is the last row, behind the t rows
-    hprm.J = pot->glm_hier_J;
-    if (hier && pot->glm_DP > glm_hier_max_dim(pot->glm_family))
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "hierarchical prior: no kernel at this padded state dimension (internal)");
-#define GLM_HIER_CASE(NT_, FAM_)                                                                            \
-    if (hier && pot->glm_DP == 16 * NT_ && pot->glm_family == FAM_)                                         \
-        hipLaunchKernelGGL((k_glm<NT_, FAM_, true, GLM_HIER_CENTRED>), grid, block, 0, stream, hprm);
-    GLM_HIER_CASE(1, PBBI_GLM_LOGISTIC) GLM_HIER_CASE(2, PBBI_GLM_LOGISTIC) GLM_HIER_CASE(4, PBBI_GLM_LOGISTIC)
-    GLM_HIER_CASE(1, PBBI_GLM_POISSON) GLM_HIER_CASE(2, PBBI_GLM_POISSON) GLM_HIER_CASE(4, PBBI_GLM_POISSON)
-#undef GLM_HIER_CASE
-    if (nc && pot->glm_DP > glm_hier_nc_max_dim(pot->glm_family))
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "non-centred hierarchical prior: no kernel at this padded state dimension (internal)");
-#define GLM_NC_CASE(NT_, FAM_)                                                                              \
-    if (nc && pot->glm_DP == 16 * NT_ && pot->glm_family == FAM_)                                           \
-        hipLaunchKernelGGL((k_glm<NT_, FAM_, true, GLM_HIER_NC>), grid, block, 0, stream, hprm);
-    GLM_NC_CASE(1, PBBI_GLM_LOGISTIC) GLM_NC_CASE(2, PBBI_GLM_LOGISTIC) GLM_NC_CASE(4, PBBI_GLM_LOGISTIC)
-    GLM_NC_CASE(1, PBBI_GLM_POISSON) GLM_NC_CASE(2, PBBI_GLM_POISSON) GLM_NC_CASE(4, PBBI_GLM_POISSON)
-#undef GLM_NC_CASE
-    GlmPrmHierQ qprm{};
-    static_cast<GlmPrmHier&>(qprm) = hprm;
-    qprm.qimg = (const double*)pot->d_glm_qimg;
-    if (hq && pot->glm_DP > glm_hier_q_max_dim(pot->glm_family))
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "structured group priors: no kernel at this padded state dimension (internal)");
-#define GLM_HQ_CASE(NT_, FAM_)                                                                              \
-    if (hq && pot->glm_DP == 16 * NT_ && pot->glm_family == FAM_)                                           \
-        hipLaunchKernelGGL((k_glm<NT_, FAM_, true, GLM_HIER_Q>), grid, block, 0, stream, qprm);
-    GLM_HQ_CASE(1, PBBI_GLM_LOGISTIC) GLM_HQ_CASE(2, PBBI_GLM_LOGISTIC) GLM_HQ_CASE(4, PBBI_GLM_LOGISTIC)
-    GLM_HQ_CASE(1, PBBI_GLM_POISSON) GLM_HQ_CASE(2, PBBI_GLM_POISSON) GLM_HQ_CASE(4, PBBI_GLM_POISSON)
-#undef GLM_HQ_CASE
-    GlmPrmHierDisp hdprm{};
-    static_cast<GlmPrmHier&>(hdprm) = hprm;
-    hdprm.theta = pot->glm_theta;
-    hdprm.trow = pot->glm_trow;
-    if (hd && pot->glm_DP > glm_hier_disp_max_dim(pot->glm_family, pot->glm_hier_nc ? PBBI_HIER_NONCENTRED : PBBI_HIER_CENTRED))
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "random effects for the dispersion families: no kernel at this padded state dimension (internal)");
-#define GLM_HD_CASE(NT_, FAM_)                                                                              \
-    if (hd && pot->glm_DP == 16 * NT_ && pot->glm_family == FAM_) {                                         \
-        if (pot->glm_hier_nc)                                                                               \
-            hipLaunchKernelGGL((k_glm<NT_, FAM_, true, GLM_HIER_NC>), grid, block, 0, stream, hdprm);       \
-        else                                                                                                \
-            hipLaunchKernelGGL((k_glm<NT_, FAM_, true, GLM_HIER_CENTRED>), grid, block, 0, stream, hdprm);  \
+    const int NT = pot->glm_DP / 16, fam = pot->glm_family;
+    bool done = false;
+#define GLM_CASE(NT_, FAM_, RICH_, HIER_, PRM_)                                                             \
+    if (NT == NT_ && fam == FAM_) {                                                                         \
+        hipLaunchKernelGGL((k_glm<NT_, FAM_, RICH_, HIER_>), grid, block, 0, stream, PRM_);                 \
+        done = true;                                                                                        \
     }
-    GLM_HD_CASE(1, PBBI_GLM_GAUSSIAN) GLM_HD_CASE(2, PBBI_GLM_GAUSSIAN) GLM_HD_CASE(4, PBBI_GLM_GAUSSIAN)
-    GLM_HD_CASE(1, PBBI_GLM_NEGBINOMIAL) GLM_HD_CASE(2, PBBI_GLM_NEGBINOMIAL) GLM_HD_CASE(4, PBBI_GLM_NEGBINOMIAL)
-#undef GLM_HD_CASE
-#define GLM_CASE(NT_, RICH_, PRM_)                                                                          \
-    if (!disp && !hier && !nc && !hq && pot->glm_DP == 16 * NT_ && rich == RICH_) {                                \
-        if (pot->glm_family == PBBI_GLM_LOGISTIC)                                                           \
-            hipLaunchKernelGGL((k_glm<NT_, PBBI_GLM_LOGISTIC, RICH_>), grid, block, 0, stream, PRM_);       \
-        else                                                                                                \
-            hipLaunchKernelGGL((k_glm<NT_, PBBI_GLM_POISSON, RICH_>), grid, block, 0, stream, PRM_);        \
+// (K_ is the case list's kernel of the variant in hand.  The lists keep the order they have always had: it is the order in which
+// the kernels are instantiated and laid out in the code object.)
+    if (pot->D <= glm_max_dim(pot->glm_variant, fam)) switch (pot->glm_variant) {
+        case GLM_V_DISPERSION: {
+            GlmPrmDisp a = glm_prm_rich<GlmPrmDisp>(pot, prm);
+            a.theta = pot->glm_theta;
+            a.trow = pot->glm_trow;
+#define K_(NT_, FAM_) GLM_CASE(NT_, FAM_, true, GLM_HIER_NONE, a)
+            K_(1, PBBI_GLM_GAUSSIAN) K_(2, PBBI_GLM_GAUSSIAN) K_(4, PBBI_GLM_GAUSSIAN) K_(8, PBBI_GLM_GAUSSIAN)
+            K_(1, PBBI_GLM_NEGBINOMIAL) K_(2, PBBI_GLM_NEGBINOMIAL) K_(4, PBBI_GLM_NEGBINOMIAL)
+#undef K_
+        } break;
+        case GLM_V_HIER: {
+            const GlmPrmHier a = glm_prm_hier<GlmPrmHier>(pot, prm);
+#define K_(NT_, FAM_) GLM_CASE(NT_, FAM_, true, GLM_HIER_CENTRED, a)
+            K_(1, PBBI_GLM_LOGISTIC) K_(2, PBBI_GLM_LOGISTIC) K_(4, PBBI_GLM_LOGISTIC)
+            K_(1, PBBI_GLM_POISSON) K_(2, PBBI_GLM_POISSON) K_(4, PBBI_GLM_POISSON)
+#undef K_
+        } break;
+        case GLM_V_HIER_NC: {
+            const GlmPrmHier a = glm_prm_hier<GlmPrmHier>(pot, prm);
+#define K_(NT_, FAM_) GLM_CASE(NT_, FAM_, true, GLM_HIER_NC, a)
+            K_(1, PBBI_GLM_LOGISTIC) K_(2, PBBI_GLM_LOGISTIC) K_(4, PBBI_GLM_LOGISTIC)
+            K_(1, PBBI_GLM_POISSON) K_(2, PBBI_GLM_POISSON) K_(4, PBBI_GLM_POISSON)
+#undef K_
+        } break;
+        case GLM_V_HIER_Q: {
+            GlmPrmHierQ a = glm_prm_hier<GlmPrmHierQ>(pot, prm);
+            a.qimg = (const double*)pot->d_glm_qimg;
+#define K_(NT_, FAM_) GLM_CASE(NT_, FAM_, true, GLM_HIER_Q, a)
+            K_(1, PBBI_GLM_LOGISTIC) K_(2, PBBI_GLM_LOGISTIC) K_(4, PBBI_GLM_LOGISTIC)
+            K_(1, PBBI_GLM_POISSON) K_(2, PBBI_GLM_POISSON) K_(4, PBBI_GLM_POISSON)
+#undef K_
+        } break;
+        case GLM_V_HIER_DISPERSION: {
+            GlmPrmHierDisp a = glm_prm_hier<GlmPrmHierDisp>(pot, prm);
+            a.theta = pot->glm_theta;
+            a.trow = pot->glm_trow;
+#define K_(NT_, FAM_)                                                                                       \
+    if (pot->glm_hier_nc) {                                                                                 \
+        GLM_CASE(NT_, FAM_, true, GLM_HIER_NC, a)                                                           \
+    } else {                                                                                                \
+        GLM_CASE(NT_, FAM_, true, GLM_HIER_CENTRED, a)                                                      \
     }
-    GLM_CASE(1, false, prm) GLM_CASE(2, false, prm) GLM_CASE(4, false, prm) GLM_CASE(8, false, prm)
-    GLM_CASE(1, true, rprm) GLM_CASE(2, true, rprm) GLM_CASE(4, true, rprm) GLM_CASE(8, true, rprm)
+            K_(1, PBBI_GLM_GAUSSIAN) K_(2, PBBI_GLM_GAUSSIAN) K_(4, PBBI_GLM_GAUSSIAN)
+            K_(1, PBBI_GLM_NEGBINOMIAL) K_(2, PBBI_GLM_NEGBINOMIAL) K_(4, PBBI_GLM_NEGBINOMIAL)
+#undef K_
+        } break;
+#define K_(NT_, RICH_, PRM_) \
+    GLM_CASE(NT_, PBBI_GLM_LOGISTIC, RICH_, GLM_HIER_NONE, PRM_) GLM_CASE(NT_, PBBI_GLM_POISSON, RICH_, GLM_HIER_NONE, PRM_)
+        case GLM_V_PLAIN: {
+            K_(1, false, prm) K_(2, false, prm) K_(4, false, prm) K_(8, false, prm)
+        } break;
+        case GLM_V_FULL: {
+            const GlmPrmRich a = glm_prm_rich<GlmPrmRich>(pot, prm);
+            K_(1, true, a) K_(2, true, a) K_(4, true, a) K_(8, true, a)
+        } break;
+#undef K_
+    }
 #undef GLM_CASE
+    if (!done) return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM kernels: no kernel is shipped for this handle's variant, family and "
+                                                      "padded state dimension");
     PBBI_HIP(hipGetLastError());
     return PBBI_OK;
 }
 
+template <class Args>
+int glm_run(const Args& a, int mode) {
+    if (a.N == 0) return PBBI_OK;
+    GlmPrm prm = glm_prm(a.pot);
+    glm_fill(prm, a, mode);
+    return glm_launch(a.pot, prm, a.stream);
+}
+
 }  // namespace
-
-// ---- host side: the fragment image of X ------------------------------------------------------------------
-int glm_padded_dim(int D) { return D <= 16 ? 16 : D <= 32 ? 32 : D <= 64 ? 64 : 128; }
-static int64_t glm_blocks_padded(int64_t M) { return ((M + 15) / 16 + 3) / 4 * 4; }
-int64_t glm_image_len(int D, int64_t M) { return glm_blocks_padded(M) * (int64_t)glm_padded_dim(D) * 32; }
-
-// X (M x D, row-major) -> per block of 16 observations P1 [KS/2][64][2] then P2 [2][NT][64][2] (see the top of
-// the file), zero padded to DP columns and to a multiple of 4 blocks.  Host only.
-static void glm_pack_dp(int D, int DP, int64_t M, const double* X, double* out);
-void glm_pack(int D, int64_t M, const double* X, double* out) { glm_pack_dp(D, glm_padded_dim(D), M, X, out); }
-// the first product's A fragments of block b, P1[s2][lane][e] = at(16 b + (lane & 15), 4 (2 s2 + e) + (lane >> 4)): the one
-// statement of that order, for the design (glm_pack_dp) and for the penalty of the structured group priors (glm_pack_penalty)
-template <class At>
-static void glm_pack_p1(int KS, int64_t b, const At& at, double* P1) {
-    for (int l = 0; l < 64; ++l) {
-        const int lo = l & 15, hi = l >> 4;
-        for (int s2 = 0; s2 < KS / 2; ++s2)
-            for (int e = 0; e < 2; ++e)
-                P1[((size_t)s2 * 64 + l) * 2 + e] = at(16 * b + lo, 4 * (2 * s2 + e) + hi);
-    }
-}
-// ... at a padded dimension DP >= D of the caller's: the image of [X | 0]
-static void glm_pack_dp(int D, int DP, int64_t M, const double* X, double* out) {
-    const int NT = DP / 16, KS = DP / 4;
-    const int64_t nbp = glm_blocks_padded(M);
-    const int64_t blk_len = (int64_t)DP * 32;
-    std::memset(out, 0, sizeof(double) * (size_t)(nbp * blk_len));
-    auto at = [&](int64_t i, int d) -> double { return (i < M && d < D) ? X[(size_t)i * D + d] : 0.0; };
-    for (int64_t b = 0; b < (M + 15) / 16; ++b) {
-        double* P1 = out + b * blk_len;
-        double* P2 = P1 + (int64_t)KS * 64;
-        glm_pack_p1(KS, b, at, P1);
-        for (int l = 0; l < 64; ++l) {
-            const int lo = l & 15, hi = l >> 4;
-            for (int r2 = 0; r2 < 2; ++r2)
-                for (int t = 0; t < NT; ++t)
-                    for (int e = 0; e < 2; ++e)
-                        P2[(((size_t)r2 * NT + t) * 64 + l) * 2 + e] = at(16 * b + 4 * (2 * r2 + e) + hi, 16 * t + lo);
-        }
-    }
-}
-
-int glm_build(pbbi_potential* pot, int64_t M, const double* X, const double* y, int family, double lam) {
-    const int D = pot->D;
-    if (D > 128 || pot->dtype != PBBI_F64)
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials run on the fp64 matrix-core kernels: float64 and "
-                                               "D <= 128 only (D = " + std::to_string(D) + ")");
-    std::vector<double> img((size_t)glm_image_len(D, M));
-    glm_pack(D, M, X, img.data());
-    std::vector<double> yp((size_t)glm_blocks_padded(M) * 16, 0.0);
-    std::memcpy(yp.data(), y, sizeof(double) * (size_t)M);
-    PBBI_HIP(hipMalloc(&pot->d_glm_img, img.size() * sizeof(double)));
-    PBBI_HIP(hipMalloc(&pot->d_glm_y, yp.size() * sizeof(double)));
-    PBBI_HIP(hipMemcpy(pot->d_glm_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
-    PBBI_HIP(hipMemcpy(pot->d_glm_y, yp.data(), yp.size() * sizeof(double), hipMemcpyHostToDevice));
-    pot->glm_DP = glm_padded_dim(D);
-    pot->glm_M = M;
-    pot->glm_family = family;
-    pot->glm_lam = lam;
-    return PBBI_OK;
-}
-
-// ---- host side: the full model's observation streams and prior vectors ------------------------------------
-int64_t glm_obs_len(int64_t M) { return 3 * glm_blocks_padded(M) * 16; }
-
-// Every rule of the full model's per-observation arguments (NULL = the default: weights 1, offset 0, trials 1).
-int glm_check_obs(int64_t M, int family, const double* y, const double* weights, const double* offset,
-                  const double* trials) {
-    if (M < 1) return pbbi_fail(PBBI_ERR_INVALID, "M must be >= 1");
-    if (family != PBBI_GLM_LOGISTIC && family != PBBI_GLM_POISSON)
-        return pbbi_fail(PBBI_ERR_INVALID, "unknown GLM family");
-    if (!y) return pbbi_fail(PBBI_ERR_INVALID, "y is NULL");
-    if (trials && family != PBBI_GLM_LOGISTIC)
-        return pbbi_fail(PBBI_ERR_INVALID, "trials belong to the logistic (binomial) family only");
-    for (int64_t i = 0; i < M; ++i) {
-        auto at = [i] { return " (observation " + std::to_string(i) + ")"; };
-        const double n = trials ? trials[i] : 1.0;
-        if (!std::isfinite(n) || n < 1.0 || n != std::floor(n))
-            return pbbi_fail(PBBI_ERR_INVALID, "trials must be integers >= 1" + at());
-        if (!std::isfinite(y[i]) || y[i] < 0.0 || y[i] != std::floor(y[i]))
-            return pbbi_fail(PBBI_ERR_INVALID, "y must hold non-negative integers" + at());
-        if (family == PBBI_GLM_LOGISTIC && y[i] > n)
-            return pbbi_fail(PBBI_ERR_INVALID, "logistic: y must not exceed the trials" + at());
-        if (weights && !(std::isfinite(weights[i]) && weights[i] >= 0.0))
-            return pbbi_fail(PBBI_ERR_INVALID, "weights must be finite and >= 0" + at());
-        if (offset && !std::isfinite(offset[i]))
-            return pbbi_fail(PBBI_ERR_INVALID, "offset must be finite" + at());
-    }
-    return PBBI_OK;
-}
-
-// c = a n | d = a y | o, each zero padded to the image's block count (glm_obs_len(M) doubles).  Host only.
-void glm_pack_obs(int64_t M, const double* y, const double* weights, const double* offset, const double* trials,
-                  double* out) {
-    const int64_t len = glm_blocks_padded(M) * 16;
-    std::memset(out, 0, sizeof(double) * (size_t)(3 * len));
-    for (int64_t i = 0; i < M; ++i) {
-        const double a = weights ? weights[i] : 1.0;
-        out[i] = a * (trials ? trials[i] : 1.0);
-        out[len + i] = a * y[i];
-        out[2 * len + i] = offset ? offset[i] : 0.0;
-    }
-}
-
-int glm_check_prior(int D, const double* lam, const double* mu) {
-    if (!lam) return pbbi_fail(PBBI_ERR_INVALID, "prior_precision is NULL");
-    for (int d = 0; d < D; ++d) {
-        if (!(std::isfinite(lam[d]) && lam[d] >= 0.0))
-            return pbbi_fail(PBBI_ERR_INVALID, "prior_precision must be finite and >= 0 (coefficient " + std::to_string(d) + ")");
-        if (mu && !std::isfinite(mu[d]))
-            return pbbi_fail(PBBI_ERR_INVALID, "prior_mean must be finite (coefficient " + std::to_string(d) + ")");
-    }
-    return PBBI_OK;
-}
-
-// the caller has run glm_check_obs and glm_check_prior
-int glm_build_ex(pbbi_potential* pot, int64_t M, const double* X, const double* y, int family, const double* weights,
-                 const double* offset, const double* trials, const double* lam, const double* mu) {
-    const int D = pot->D;
-    if (D > 128 || pot->dtype != PBBI_F64)
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials run on the fp64 matrix-core kernels: float64 and "
-                                               "D <= 128 only (D = " + std::to_string(D) + ")");
-    const int DP = glm_padded_dim(D);
-    std::vector<double> img((size_t)glm_image_len(D, M));
-    glm_pack(D, M, X, img.data());
-    std::vector<double> obs((size_t)glm_obs_len(M));
-    glm_pack_obs(M, y, weights, offset, trials, obs.data());
-    std::vector<double> prior((size_t)2 * DP, 0.0);  // lam | mu, zeros past D
-    bool flat = true, centred = true, one = true;
-    for (int d = 0; d < D; ++d) {
-        prior[d] = lam[d];
-        prior[DP + d] = mu ? mu[d] : 0.0;
-        flat = flat && lam[d] == 0.0;
-        one = one && lam[d] == lam[0];
-        centred = centred && prior[DP + d] == 0.0;
-    }
-    PBBI_HIP(hipMalloc(&pot->d_glm_img, img.size() * sizeof(double)));
-    PBBI_HIP(hipMalloc(&pot->d_glm_obs, obs.size() * sizeof(double)));
-    PBBI_HIP(hipMalloc(&pot->d_glm_prior, prior.size() * sizeof(double)));
-    PBBI_HIP(hipMemcpy(pot->d_glm_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
-    PBBI_HIP(hipMemcpy(pot->d_glm_obs, obs.data(), obs.size() * sizeof(double), hipMemcpyHostToDevice));
-    PBBI_HIP(hipMemcpy(pot->d_glm_prior, prior.data(), prior.size() * sizeof(double), hipMemcpyHostToDevice));
-    pot->glm_DP = DP;
-    pot->glm_M = M;
-    pot->glm_family = family;
-    pot->glm_lam = one ? lam[0] : 0.0;  // (the full model's kernels read d_glm_prior)
-    pot->glm_terms = (weights ? GLM_TERM_WEIGHTS : 0) | (offset ? GLM_TERM_OFFSET : 0) | (trials ? GLM_TERM_TRIALS : 0) |
-                     (one ? 0 : GLM_TERM_PRIOR_VECTOR) | (centred ? 0 : GLM_TERM_PRIOR_MEAN) | (flat ? GLM_TERM_PRIOR_FLAT : 0);
-    return PBBI_OK;
-}
-
-// ---- host side: the dispersion families ------------------------------------------------------------------------
-int glm_check_obs_disp(int64_t M, int family, const double* y, const double* weights, const double* offset) {
-    if (M < 1) return pbbi_fail(PBBI_ERR_INVALID, "M must be >= 1");
-    if (!glm_disp(family)) return pbbi_fail(PBBI_ERR_INVALID, "unknown dispersion family (gaussian = 3, negbinomial = 4)");
-    if (!y) return pbbi_fail(PBBI_ERR_INVALID, "y is NULL");
-    for (int64_t i = 0; i < M; ++i) {
-        auto at = [i] { return " (observation " + std::to_string(i) + ")"; };
-        if (!std::isfinite(y[i])) return pbbi_fail(PBBI_ERR_INVALID, "y must be finite" + at());
-        if (family == PBBI_GLM_NEGBINOMIAL && (y[i] < 0.0 || y[i] != std::floor(y[i])))
-            return pbbi_fail(PBBI_ERR_INVALID, "negbinomial: y must hold non-negative integers" + at());
-        if (weights && !(std::isfinite(weights[i]) && weights[i] >= 0.0))
-            return pbbi_fail(PBBI_ERR_INVALID, "weights must be finite and >= 0" + at());
-        if (offset && !std::isfinite(offset[i]))
-            return pbbi_fail(PBBI_ERR_INVALID, "offset must be finite" + at());
-    }
-    return PBBI_OK;
-}
-
-// c = a | d = y (raw) | o, each zero padded to the image's block count (glm_obs_len(M) doubles).  Host only.
-void glm_pack_obs_disp(int64_t M, const double* y, const double* weights, const double* offset, double* out) {
-    const int64_t len = glm_blocks_padded(M) * 16;
-    std::memset(out, 0, sizeof(double) * (size_t)(3 * len));
-    for (int64_t i = 0; i < M; ++i) {
-        out[i] = weights ? weights[i] : 1.0;
-        out[len + i] = y[i];
-        out[2 * len + i] = offset ? offset[i] : 0.0;
-    }
-}
-
-// the caller has run glm_check_obs_disp and glm_check_prior (over pot->D entries); pot->D = Dx + (sample ? 1 : 0)
-int glm_build_disp(pbbi_potential* pot, int Dx, int64_t M, const double* X, const double* y, int family,
-                   const double* weights, const double* offset, const double* lam, const double* mu, int sample,
-                   double theta) {
-    const int Dt = pot->D;
-    if (Dt > 128 || pot->dtype != PBBI_F64)
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials run on the fp64 matrix-core kernels: float64 and a state "
-                                               "dimension <= 128 only (" + std::to_string(Dt) + ")");
-    // k_glm<8, PBBI_GLM_NEGBINOMIAL, true> cannot be built without scratch (the full model's DP = 128 kernel already
-    // fills all 512 registers) and is not shipped
-    if (family == PBBI_GLM_NEGBINOMIAL && Dt > 64)
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "negbinomial: the state dimension (coefficients + 1 for a sampled dispersion) "
-                                               "must be <= 64: its kernel at 65 .. 128 does not fit the register file (" +
-                                                   std::to_string(Dt) + ")");
-    const int DP = glm_padded_dim(Dt);
-    const int64_t nbp = glm_blocks_padded(M);
-    std::vector<double> img((size_t)(nbp * DP * 32));
-    glm_pack_dp(Dx, DP, M, X, img.data());  // [X | 0]: the theta row meets a zero column
-    std::vector<double> obs((size_t)glm_obs_len(M));
-    glm_pack_obs_disp(M, y, weights, offset, obs.data());
-    std::vector<double> prior((size_t)2 * DP, 0.0);  // lam | mu over the Dt state rows, zeros past them
-    for (int d = 0; d < Dt; ++d) {
-        prior[d] = lam[d];
-        prior[DP + d] = mu ? mu[d] : 0.0;
-    }
-    PBBI_HIP(hipMalloc(&pot->d_glm_img, img.size() * sizeof(double)));
-    PBBI_HIP(hipMalloc(&pot->d_glm_obs, obs.size() * sizeof(double)));
-    PBBI_HIP(hipMalloc(&pot->d_glm_prior, prior.size() * sizeof(double)));
-    PBBI_HIP(hipMemcpy(pot->d_glm_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
-    PBBI_HIP(hipMemcpy(pot->d_glm_obs, obs.data(), obs.size() * sizeof(double), hipMemcpyHostToDevice));
-    PBBI_HIP(hipMemcpy(pot->d_glm_prior, prior.data(), prior.size() * sizeof(double), hipMemcpyHostToDevice));
-    pot->glm_DP = DP;
-    pot->glm_M = M;
-    pot->glm_family = family;
-    pot->glm_lam = 0.0;  // (these kernels read d_glm_prior)
-    pot->glm_terms = (weights ? GLM_TERM_WEIGHTS : 0) | (offset ? GLM_TERM_OFFSET : 0);
-    pot->glm_trow = sample ? Dx : -1;
-    pot->glm_theta = sample ? 0.0 : theta;
-    return PBBI_OK;
-}
-
-// ---- host side: the hierarchical prior -------------------------------------------------------------------------
-// the largest state dimension (coefficients + groups) each family's hierarchical kernels serve: k_glm<8, FAM, true, GLM_HIER_CENTRED>
-// cannot be built without scratch for either family (the full model's DP = 128 kernels already fill the register file;
-// 172 and 180 bytes per lane) and is not shipped
-int glm_hier_max_dim(int family) { return (family == PBBI_GLM_LOGISTIC || family == PBBI_GLM_POISSON) ? 64 : 0; }
-// ... the non-centred kernels k_glm<NT, FAM, true, GLM_HIER_NC>: NT = 1, 2, 4 build without scratch for both families (the
-// scaled copy of the state costs KS more registers beside q; profiles/glm_hier_nc_resources.txt)
-int glm_hier_nc_max_dim(int family) { return (family == PBBI_GLM_LOGISTIC || family == PBBI_GLM_POISSON) ? 64 : 0; }
-
-// Every rule of the hierarchical prior's arguments: groups (D entries, -1 or 0 .. J-1, every index used), the fixed rows'
-// {lam, mu}, the J pairs (mean, precision) of the log-scales.
-int glm_check_hier(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior) {
-    if (D < 1) return pbbi_fail(PBBI_ERR_INVALID, "D must be >= 1");
-    if (J < 1 || J > 4)
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "hierarchical prior: the number of groups J must be 1 .. 4 (J = " +
-                                                   std::to_string(J) + ")");
-    if (!groups) return pbbi_fail(PBBI_ERR_INVALID, "groups is NULL");
-    if (!lam) return pbbi_fail(PBBI_ERR_INVALID, "prior_precision is NULL");
-    if (!tprior) return pbbi_fail(PBBI_ERR_INVALID, "log_scale_prior is NULL");
-    int count[4] = {0, 0, 0, 0};
-    for (int d = 0; d < D; ++d) {
-        if (groups[d] < -1 || groups[d] >= J)
-            return pbbi_fail(PBBI_ERR_INVALID, "groups must hold -1 (fixed prior) or a group index 0 .. J-1 (coefficient " +
-                                                   std::to_string(d) + ": " + std::to_string(groups[d]) + ", J = " +
-                                                   std::to_string(J) + ")");
-        if (groups[d] >= 0) ++count[groups[d]];
-        // a grouped coefficient's fixed precision is not used
-        if (groups[d] < 0 && !(std::isfinite(lam[d]) && lam[d] >= 0.0))
-            return pbbi_fail(PBBI_ERR_INVALID, "prior_precision must be finite and >= 0 (coefficient " + std::to_string(d) + ")");
-        if (mu && !std::isfinite(mu[d]))
-            return pbbi_fail(PBBI_ERR_INVALID, "prior_mean must be finite (coefficient " + std::to_string(d) + ")");
-    }
-    for (int j = 0; j < J; ++j) {
-        if (count[j] == 0)
-            return pbbi_fail(PBBI_ERR_INVALID, "every group index 0 .. J-1 must be used (group " + std::to_string(j) +
-                                                   " has no coefficient)");
-        if (!std::isfinite(tprior[2 * j]) || !(std::isfinite(tprior[2 * j + 1]) && tprior[2 * j + 1] >= 0.0))
-            return pbbi_fail(PBBI_ERR_INVALID, "log_scale_prior must hold J pairs (finite mean, finite precision >= 0) "
-                                               "(group " + std::to_string(j) + ")");
-    }
-    return PBBI_OK;
-}
-
-// The table the hierarchical kernels stage into plds, lam (DP) | mu (DP) with DP = glm_padded_dim(D + J): a fixed row its
-// {lam_d, mu_d}, a member of group j {-(j + 1), mu_d}, row D + j {lam_tj, m_tj}, zeros past D + J; n_out[j] = the members
-// of group j.  The caller has run glm_check_hier.  Host only.
-void glm_pack_prior_groups(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior,
-                           double* out, double* n_out) {
-    const int DP = glm_padded_dim(D + J);
-    std::memset(out, 0, sizeof(double) * (size_t)(2 * DP));
-    for (int j = 0; j < J; ++j) n_out[j] = 0.0;
-    for (int d = 0; d < D; ++d) {
-        out[d] = groups[d] < 0 ? lam[d] : -(double)(groups[d] + 1);
-        out[DP + d] = mu ? mu[d] : 0.0;
-        if (groups[d] >= 0) n_out[groups[d]] += 1.0;
-    }
-    for (int j = 0; j < J; ++j) {
-        out[D + j] = tprior[2 * j + 1];
-        out[DP + D + j] = tprior[2 * j];
-    }
-}
-
-// ---- host side: random effects for the dispersion families -----------------------------------------------------------
-// The largest state dimension (coefficients + groups + 1 for a sampled dispersion) the kernels k_glm<NT, FAM, true, HIER> with
-// FAM = gaussian / negbinomial and HIER = GLM_HIER_CENTRED / GLM_HIER_NC serve; 0 = nothing served.  An instantiation ships
-// only if it builds without scratch: all twelve of NT = 1, 2, 4 do (profiles/glm_hier_dispersion_resources.txt).  There is no
-// kernel at 128 rows for either parent's hierarchical form.
-int glm_hier_disp_max_dim(int family, int parametrisation) {
-    if (!glm_disp(family)) return 0;
-    if (parametrisation != PBBI_HIER_CENTRED && parametrisation != PBBI_HIER_NONCENTRED) return 0;
-    return 64;
-}
-
-// Every rule of the log-dispersion's arguments: sampled, a pair (finite mean, finite precision >= 0) is required; held, theta
-// must be finite and there is no prior to give.
-int glm_check_hier_disp_theta(int sample, double theta, const double* dprior) {
-    if (sample) {
-        if (!dprior) return pbbi_fail(PBBI_ERR_INVALID, "log_dispersion_prior is NULL (a sampled dispersion needs its pair (mean, precision))");
-        if (!std::isfinite(dprior[0]) || !(std::isfinite(dprior[1]) && dprior[1] >= 0.0))
-            return pbbi_fail(PBBI_ERR_INVALID, "log_dispersion_prior must be (finite mean, finite precision >= 0)");
-    } else {
-        if (dprior) return pbbi_fail(PBBI_ERR_INVALID, "log_dispersion_prior belongs to a sampled dispersion only: a held one has no prior");
-        if (!std::isfinite(theta))
-            return pbbi_fail(PBBI_ERR_INVALID, "a held dispersion must be finite and > 0 (theta = its logarithm)");
-    }
-    return PBBI_OK;
-}
-
-// The table of glm_pack_prior_groups at DP = glm_padded_dim(D + J + (sample ? 1 : 0)), with theta's {lam_theta, m_theta} at row
-// D + J when it is sampled (a fixed row: a non-negative lam slot) and zeros past the state.  The caller has run glm_check_hier
-// and glm_check_hier_disp_theta.  Host only.
-void glm_pack_prior_groups_disp(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior,
-                                int sample, const double* dprior, double* out, double* n_out) {
-    const int DP = glm_padded_dim(D + J + (sample ? 1 : 0)), DPh = glm_padded_dim(D + J);
-    std::vector<double> tab((size_t)2 * DPh);
-    glm_pack_prior_groups(D, J, lam, mu, groups, tprior, tab.data(), n_out);  // the one statement of the codes
-    std::memset(out, 0, sizeof(double) * (size_t)(2 * DP));
-    for (int d = 0; d < D + J; ++d) {
-        out[d] = tab[(size_t)d];
-        out[DP + d] = tab[(size_t)DPh + d];
-    }
-    if (sample) {
-        out[D + J] = dprior[1];
-        out[DP + D + J] = dprior[0];
-    }
-}
-
-// the caller has run glm_check_obs_disp, glm_check_hier and glm_check_hier_disp_theta; pot->D = Dx + J + (sample ? 1 : 0)
-int glm_build_hier_disp(pbbi_potential* pot, int Dx, int64_t M, const double* X, const double* y, int family,
-                        const double* weights, const double* offset, const double* lam, const double* mu,
-                        const int32_t* groups, int J, const double* tprior, int parametrisation, int sample, double theta,
-                        const double* dprior) {
-    const int Dt = pot->D;
-    const int dmax = glm_hier_disp_max_dim(family, parametrisation);
-    if (pot->dtype != PBBI_F64 || Dt > dmax)
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "random effects for the dispersion families: float64 and a state dimension "
-                                               "(coefficients + groups + 1 for a sampled dispersion) <= " + std::to_string(dmax) +
-                                                   " only (" + std::to_string(Dt) + ")");
-    const int DP = glm_padded_dim(Dt);
-    const int64_t nbp = glm_blocks_padded(M);
-    std::vector<double> img((size_t)(nbp * DP * 32));
-    glm_pack_dp(Dx, DP, M, X, img.data());  // [X | 0]: the t rows and the theta row meet zero columns
-    std::vector<double> obs((size_t)glm_obs_len(M));
-    glm_pack_obs_disp(M, y, weights, offset, obs.data());
-    std::vector<double> prior((size_t)2 * DP + 4, 0.0);  // lam | mu | n_j
-    double* nj = prior.data() + 2 * DP;
-    glm_pack_prior_groups_disp(Dx, J, lam, mu, groups, tprior, sample, dprior, prior.data(), nj);
-    for (int j = 0; j < 4; ++j) pot->glm_hier_n[j] = nj[j];
-    PBBI_HIP(hipMalloc(&pot->d_glm_img, img.size() * sizeof(double)));
-    PBBI_HIP(hipMalloc(&pot->d_glm_obs, obs.size() * sizeof(double)));
-    PBBI_HIP(hipMalloc(&pot->d_glm_prior, prior.size() * sizeof(double)));
-    PBBI_HIP(hipMemcpy(pot->d_glm_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
-    PBBI_HIP(hipMemcpy(pot->d_glm_obs, obs.data(), obs.size() * sizeof(double), hipMemcpyHostToDevice));
-    PBBI_HIP(hipMemcpy(pot->d_glm_prior, prior.data(), prior.size() * sizeof(double), hipMemcpyHostToDevice));
-    pot->glm_DP = DP;
-    pot->glm_M = M;
-    pot->glm_family = family;
-    pot->glm_lam = 0.0;  // (these kernels read d_glm_prior)
-    pot->glm_terms = (weights ? GLM_TERM_WEIGHTS : 0) | (offset ? GLM_TERM_OFFSET : 0);
-    pot->glm_hier_J = J;
-    pot->glm_hier_nc = parametrisation == PBBI_HIER_NONCENTRED ? 1 : 0;
-    pot->glm_trow = sample ? Dx + J : -1;
-    pot->glm_theta = sample ? 0.0 : theta;
-    return PBBI_OK;
-}
-
-// ---- host side: structured group priors ----------------------------------------------------------------------------
-// the largest state dimension the kernels k_glm<NT, FAM, true, GLM_HIER_Q> serve: NT = 1, 2, 4 build without scratch for both
-// families (profiles/glm_hier_penalty_resources.txt); there is no centred kernel at 128 rows to extend
-int glm_hier_q_max_dim(int family) { return (family == PBBI_GLM_LOGISTIC || family == PBBI_GLM_POISSON) ? 64 : 0; }
-
-int64_t glm_penalty_image_len(int D, int J) { const int64_t DP = glm_padded_dim(D + J); return DP * DP; }
-
-// The eigenvalues of a symmetric n x n matrix (row-major in a, destroyed) by cyclic Jacobi rotations, into ev.  n <= 63 here.
-static void glm_sym_eigenvalues(int n, std::vector<double>& a, std::vector<double>& ev) {
-    for (int sweep = 0; sweep < 64; ++sweep) {
-        double off = 0.0, diag = 0.0;
-        for (int i = 0; i < n; ++i)
-            for (int k = 0; k < n; ++k) (i == k ? diag : off) += a[(size_t)i * n + k] * a[(size_t)i * n + k];
-        if (off <= 1e-30 * diag || off == 0.0) break;
-        for (int p = 0; p < n - 1; ++p)
-            for (int q = p + 1; q < n; ++q) {
-                const double apq = a[(size_t)p * n + q];
-                if (apq == 0.0) continue;
-                const double theta = (a[(size_t)q * n + q] - a[(size_t)p * n + p]) / (2.0 * apq);
-                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < n; ++k) {  // columns p, q
-                    const double akp = a[(size_t)k * n + p], akq = a[(size_t)k * n + q];
-                    a[(size_t)k * n + p] = c * akp - s * akq;
-                    a[(size_t)k * n + q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < n; ++k) {  // rows p, q
-                    const double apk = a[(size_t)p * n + k], aqk = a[(size_t)q * n + k];
-                    a[(size_t)p * n + k] = c * apk - s * aqk;
-                    a[(size_t)q * n + k] = s * apk + c * aqk;
-                }
-            }
-    }
-    ev.resize((size_t)n);
-    for (int i = 0; i < n; ++i) ev[(size_t)i] = a[(size_t)i * n + i];
-}
-
-// Every rule of the penalty of the structured group priors: a (D x D) row-major matrix in coefficient indexing, finite,
-// zero on fixed rows and between different groups, each group's block symmetric to 1e-12 of its largest entry, positive
-// semi-definite (smallest eigenvalue >= -1e-10 x the largest) and not zero; rank[j] an integer in 1 .. n_j.  The caller has
-// run glm_check_hier.
-int glm_check_penalty(int D, int J, const int32_t* groups, const double* penalty, const double* rank) {
-    if (!penalty) return pbbi_fail(PBBI_ERR_INVALID, "penalty is NULL");
-    if (!rank) return pbbi_fail(PBBI_ERR_INVALID, "penalty_rank is NULL");
-    for (int a = 0; a < D; ++a)
-        for (int b = 0; b < D; ++b) {
-            const double v = penalty[(size_t)a * D + b];
-            if (!std::isfinite(v))
-                return pbbi_fail(PBBI_ERR_INVALID, "penalty must be finite (entry " + std::to_string(a) + ", " + std::to_string(b) + ")");
-            if (v != 0.0 && (groups[a] < 0 || groups[a] != groups[b]))
-                return pbbi_fail(PBBI_ERR_INVALID, "penalty must be zero on fixed rows and between different groups (entry " +
-                                                       std::to_string(a) + ", " + std::to_string(b) + ")");
-        }
-    for (int j = 0; j < J; ++j) {
-        std::vector<int> idx;
-        for (int d = 0; d < D; ++d)
-            if (groups[d] == j) idx.push_back(d);
-        const int n = (int)idx.size();
-        const std::string grp = " (group " + std::to_string(j) + ")";
-        double big = 0.0, asym = 0.0;
-        std::vector<double> blk((size_t)n * n);
-        for (int a = 0; a < n; ++a)
-            for (int b = 0; b < n; ++b) {
-                const double v = penalty[(size_t)idx[a] * D + idx[b]], vt = penalty[(size_t)idx[b] * D + idx[a]];
-                big = std::fmax(big, std::fabs(v));
-                asym = std::fmax(asym, std::fabs(v - vt));
-                blk[(size_t)a * n + b] = 0.5 * (v + vt);
-            }
-        if (big == 0.0) return pbbi_fail(PBBI_ERR_INVALID, "penalty must not be the zero matrix" + grp);
-        if (asym > 1e-12 * big) return pbbi_fail(PBBI_ERR_INVALID, "penalty must be symmetric" + grp);
-        std::vector<double> ev;
-        glm_sym_eigenvalues(n, blk, ev);
-        double lo = ev[0], hi = ev[0];
-        for (double v : ev) { lo = std::fmin(lo, v); hi = std::fmax(hi, v); }
-        if (!(hi > 0.0) || lo < -1e-10 * hi)
-            return pbbi_fail(PBBI_ERR_INVALID, "penalty must be positive semi-definite" + grp);
-        if (!std::isfinite(rank[j]) || rank[j] != std::floor(rank[j]) || rank[j] < 1.0 || rank[j] > (double)n)
-            return pbbi_fail(PBBI_ERR_INVALID, "penalty_rank must be an integer in 1 .. n_j" + grp);
-    }
-    return PBBI_OK;
-}
-
-// The image of the (DP x DP) penalty the kernel keeps in LDS, DP = glm_padded_dim(D + J): DP / 16 blocks of 16 rows, each in
-// the first product's A-fragment order (glm_pack_p1), (Q + Q^T) / 2 on rows and columns < D and zero beyond.  Host only.
-void glm_pack_penalty(int D, int J, const double* penalty, double* out) {
-    const int DP = glm_padded_dim(D + J), KS = DP / 4;
-    auto at = [&](int64_t i, int d) -> double {
-        return (i < D && d < D) ? 0.5 * (penalty[(size_t)i * D + d] + penalty[(size_t)d * D + i]) : 0.0;
-    };
-    for (int b = 0; b < DP / 16; ++b) glm_pack_p1(KS, b, at, out + (size_t)b * KS * 64);
-}
-
-// the caller has run glm_check_obs and glm_check_hier (and glm_check_penalty where penalty is given); pot->D = Dx + J.
-// penalty != NULL: the structured group priors (centred only), rank[j] into the table's n_j slots.
-int glm_build_hier(pbbi_potential* pot, int Dx, int64_t M, const double* X, const double* y, int family,
-                   const double* weights, const double* offset, const double* trials, const double* lam, const double* mu,
-                   const int32_t* groups, int J, const double* tprior, int parametrisation, const double* penalty,
-                   const double* rank) {
-    const int Dt = pot->D;
-    const bool nc = parametrisation == PBBI_HIER_NONCENTRED;
-    const int dmax = penalty ? glm_hier_q_max_dim(family) : nc ? glm_hier_nc_max_dim(family) : glm_hier_max_dim(family);
-    if (pot->dtype != PBBI_F64 || Dt > dmax)
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "hierarchical GLM potentials: float64 and a state dimension (coefficients + "
-                                               "groups) <= " + std::to_string(dmax) + " only (" +
-                                                   std::to_string(Dt) + ")");
-    const int DP = glm_padded_dim(Dt);
-    const int64_t nbp = glm_blocks_padded(M);
-    std::vector<double> img((size_t)(nbp * DP * 32));
-    glm_pack_dp(Dx, DP, M, X, img.data());  // [X | 0]: the t rows meet zero columns
-    std::vector<double> obs((size_t)glm_obs_len(M));
-    glm_pack_obs(M, y, weights, offset, trials, obs.data());
-    std::vector<double> prior((size_t)2 * DP + 4, 0.0);  // lam | mu | n_j
-    double* nj = prior.data() + 2 * DP;
-    glm_pack_prior_groups(Dx, J, lam, mu, groups, tprior, prior.data(), nj);
-    for (int j = 0; j < 4; ++j) pot->glm_hier_n[j] = nj[j];
-    if (penalty) {
-        for (int j = 0; j < J; ++j) nj[j] = pot->glm_hier_rank[j] = rank[j];  // r_j t_j: the normaliser of a rank-r_j Gaussian
-        std::vector<double> qimg((size_t)glm_penalty_image_len(Dx, J));
-        glm_pack_penalty(Dx, J, penalty, qimg.data());
-        PBBI_HIP(hipMalloc(&pot->d_glm_qimg, qimg.size() * sizeof(double)));
-        PBBI_HIP(hipMemcpy(pot->d_glm_qimg, qimg.data(), qimg.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    PBBI_HIP(hipMalloc(&pot->d_glm_img, img.size() * sizeof(double)));
-    PBBI_HIP(hipMalloc(&pot->d_glm_obs, obs.size() * sizeof(double)));
-    PBBI_HIP(hipMalloc(&pot->d_glm_prior, prior.size() * sizeof(double)));
-    PBBI_HIP(hipMemcpy(pot->d_glm_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
-    PBBI_HIP(hipMemcpy(pot->d_glm_obs, obs.data(), obs.size() * sizeof(double), hipMemcpyHostToDevice));
-    PBBI_HIP(hipMemcpy(pot->d_glm_prior, prior.data(), prior.size() * sizeof(double), hipMemcpyHostToDevice));
-    pot->glm_DP = DP;
-    pot->glm_M = M;
-    pot->glm_family = family;
-    pot->glm_lam = 0.0;  // (these kernels read d_glm_prior)
-    pot->glm_terms = (weights ? GLM_TERM_WEIGHTS : 0) | (offset ? GLM_TERM_OFFSET : 0) | (trials ? GLM_TERM_TRIALS : 0);
-    pot->glm_hier_J = J;
-    pot->glm_hier_nc = nc ? 1 : 0;
-    return PBBI_OK;
-}
 
 int glm_hmc_iter(const IterArgs& a) {
     if (int rc = glm_check(a.pot, a.ldn_in > a.ldn_out ? a.ldn_in : a.ldn_out)) return rc;
-    if (pbbi_dyn(a)) return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials: fixed trajectory lengths only");
-    if (a.fuse_S > 1) return pbbi_fail(PBBI_ERR_INVALID, "the GLM kernel takes one iteration per launch (internal)");
-    if (a.N == 0) return PBBI_OK;
-    GlmPrm prm = glm_prm(a.pot);
-    prm.q_in = (const double*)a.q_in;
-    prm.p_in = (const double*)a.p_in;
-    prm.u_in = (const double*)a.u_in;
-    prm.mass = (const double*)a.mass;
-    prm.q_out = (double*)a.q_out;
-    prm.p_out = (double*)a.p_out;
-    prm.ratio_out = (double*)a.ratio_out;
-    prm.reject_out = a.reject_out;
-    prm.N = a.N; prm.ldn_in = a.ldn_in; prm.ldn_out = a.ldn_out;
-    prm.h = a.h; prm.kT = a.kT; prm.L = a.L; prm.flags = a.flags; prm.rng = a.rng;
-    prm.mode = GLM_HMC; prm.method = a.method;
-    prm.seed = a.seed; prm.iter = a.iter; prm.chain0 = a.chain0;
-    return glm_launch(a.pot, prm, a.stream);
+    if (int rc = glm_check_iter(a)) return rc;
+    return glm_run(a, GLM_HMC);
 }
-
 int glm_integrate(const IntegrateArgs& a) {
     if (int rc = glm_check(a.pot, a.ldn)) return rc;
-    if (a.N == 0) return PBBI_OK;
-    GlmPrm prm = glm_prm(a.pot);
-    prm.q_in = (const double*)a.q;
-    prm.p_in = (const double*)a.p;
-    prm.mass = (const double*)a.mass;
-    prm.q_out = (double*)a.q;
-    prm.p_out = (double*)a.p;
-    prm.v_out = (double*)a.v_out;
-    prm.N = a.N; prm.ldn_in = a.ldn; prm.ldn_out = a.ldn;
-    prm.h = a.h; prm.L = a.L; prm.mode = GLM_INTEGRATE; prm.method = a.method;
-    return glm_launch(a.pot, prm, a.stream);
+    return glm_run(a, GLM_INTEGRATE);
 }
-
-static int glm_eval_launch(const EvalArgs& a, int mode) {
+int glm_eval(const EvalArgs& a) {
     if (int rc = glm_check(a.pot, a.ldn)) return rc;
-    if (a.N == 0) return PBBI_OK;
-    GlmPrm prm = glm_prm(a.pot);
-    prm.q_in = (const double*)a.q;
-    prm.p_in = (const double*)a.p;
-    prm.mass = (const double*)a.mass;
-    prm.U_out = (double*)a.U_out;
-    prm.grad_out = (double*)a.grad_out;
-    prm.w_out = (double*)a.w_out;
-    prm.N = a.N; prm.ldn_in = a.ldn; prm.ldn_out = a.ldn;
-    prm.mode = mode;
-    return glm_launch(a.pot, prm, a.stream);
+    return glm_run(a, GLM_EVAL);
 }
-int glm_eval(const EvalArgs& a) { return glm_eval_launch(a, GLM_EVAL); }
-int glm_energy(const EvalArgs& a) { return glm_eval_launch(a, a.ratio_finish ? GLM_RATIO : GLM_ENERGY); }
+int glm_energy(const EvalArgs& a) {
+    if (int rc = glm_check(a.pot, a.ldn)) return rc;
+    return glm_run(a, a.ratio_finish ? GLM_RATIO : GLM_ENERGY);
+}

@@ -29,8 +29,8 @@
 //
 // An observation >= M is masked out of the residual and of the energy (softmax(0) = 1 / K, log K).
 #include <cmath>
-#include <cstring>
 
+#include "glm_args.h"
 #include "kernels_dense_dev.h"
 #include "pbbi_chain.h"
 
@@ -420,12 +420,9 @@ __global__ void __launch_bounds__(BLOCK, NTc * K <= 2 ? 2 : 1) k_glm_softmax(Smx
     }
 }
 
-const char* const SMX_RULE = "softmax GLM: float64, 2 <= K <= 8 classes, each padded to Dc = 16, 32 or 64 rows with "
-                             "K * Dc <= 128 (D <= 16 for K <= 8, D <= 32 for K <= 4, D <= 64 for K = 2)";
-
 int smx_check(const pbbi_potential* pot, int64_t ld) {
     if (pot->dtype != PBBI_F64 || pot->glm_K < 2 || !pot->d_glm_img || !pot->d_glm_prior)
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, SMX_RULE);
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, GLM_SOFTMAX_RULE);
     if ((int64_t)(pot->D + 4) * ld >= ((int64_t)1 << 29))
         return pbbi_fail(PBBI_ERR_UNSUPPORTED,
                          "GLM kernels address a lane's rows with 32-bit offsets: rows * leading stride must "
@@ -458,116 +455,35 @@ int smx_launch(const pbbi_potential* pot, const SmxPrm& prm, hipStream_t stream)
     SMX_CASE(2, 2) SMX_CASE(2, 3) SMX_CASE(2, 4)
     SMX_CASE(4, 2)
 #undef SMX_CASE
-    if (!done) return pbbi_fail(PBBI_ERR_UNSUPPORTED, SMX_RULE);
+    if (!done) return pbbi_fail(PBBI_ERR_UNSUPPORTED, GLM_SOFTMAX_RULE);
     PBBI_HIP(hipGetLastError());
     return PBBI_OK;
 }
 
+template <class Args>
+int smx_run(const Args& a, int mode) {
+    if (a.N == 0) return PBBI_OK;
+    SmxPrm prm = smx_prm(a.pot);
+    glm_fill(prm, a, mode);
+    return smx_launch(a.pot, prm, a.stream);
+}
+
 }  // namespace
-
-// ---- host side ---------------------------------------------------------------------------------------------
-// The padded class size and the tile count of a (D, K) model, and the external row of each of the NT * 16 internal
-// rows (-1 = padding).  Touches no device.
-int glm_softmax_layout(int D, int K, int* Dc_out, int* NT_out, int32_t* row_map) {
-    if (D < 1 || K < 2 || K > 8 || D > 64) return pbbi_fail(PBBI_ERR_UNSUPPORTED, SMX_RULE);
-    const int Dc = glm_padded_dim(D);
-    if (K * Dc > 128) return pbbi_fail(PBBI_ERR_UNSUPPORTED, SMX_RULE);
-    if (Dc_out) *Dc_out = Dc;
-    if (NT_out) *NT_out = K * Dc / 16;
-    if (row_map)
-        for (int k = 0; k < K; ++k)
-            for (int d = 0; d < Dc; ++d) row_map[k * Dc + d] = d < D ? k * D + d : -1;
-    return PBBI_OK;
-}
-
-int glm_softmax_check(int D, int K, int64_t M, const double* X, const double* y, const double* lam) {
-    if (!X || !y) return pbbi_fail(PBBI_ERR_INVALID, "X / y is NULL");
-    if (!lam) return pbbi_fail(PBBI_ERR_INVALID, "prior_precision is NULL");
-    if (M < 1) return pbbi_fail(PBBI_ERR_INVALID, "M must be >= 1");
-    if (D < 1) return pbbi_fail(PBBI_ERR_INVALID, "D must be >= 1");
-    if (K < 2) return pbbi_fail(PBBI_ERR_INVALID, "softmax GLM: at least two classes");
-    for (int64_t i = 0; i < M; ++i)
-        if (!(std::isfinite(y[i]) && y[i] >= 0.0 && y[i] < (double)K && y[i] == std::floor(y[i])))
-            return pbbi_fail(PBBI_ERR_INVALID, "labels must be integers in [0, K) (observation " + std::to_string(i) + ")");
-    for (int64_t i = 0; i < M * D; ++i)
-        if (!std::isfinite(X[i])) return pbbi_fail(PBBI_ERR_INVALID, "X must be finite (row " + std::to_string(i / D) + ")");
-    return glm_check_prior(D, lam, nullptr);
-}
-
-// the caller has run glm_softmax_check and glm_softmax_layout; pot->D = K * D
-int glm_softmax_build(pbbi_potential* pot, int D, int K, int64_t M, const double* X, const double* y, const double* lam) {
-    int Dc = 0;
-    if (int rc = glm_softmax_layout(D, K, &Dc, nullptr, nullptr)) return rc;
-    if (pot->dtype != PBBI_F64) return pbbi_fail(PBBI_ERR_UNSUPPORTED, SMX_RULE);
-    std::vector<double> img((size_t)glm_image_len(D, M));  // the image of an M x D matrix at DP = Dc
-    glm_pack(D, M, X, img.data());
-    const int64_t nbp = glm_image_len(D, M) / ((int64_t)Dc * 32);
-    std::vector<double> yp((size_t)nbp * 16, 0.0);
-    std::memcpy(yp.data(), y, sizeof(double) * (size_t)M);
-    std::vector<double> prior((size_t)Dc, 0.0);
-    std::memcpy(prior.data(), lam, sizeof(double) * (size_t)D);
-    PBBI_HIP(hipMalloc(&pot->d_glm_img, img.size() * sizeof(double)));
-    PBBI_HIP(hipMalloc(&pot->d_glm_y, yp.size() * sizeof(double)));
-    PBBI_HIP(hipMalloc(&pot->d_glm_prior, prior.size() * sizeof(double)));
-    PBBI_HIP(hipMemcpy(pot->d_glm_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
-    PBBI_HIP(hipMemcpy(pot->d_glm_y, yp.data(), yp.size() * sizeof(double), hipMemcpyHostToDevice));
-    PBBI_HIP(hipMemcpy(pot->d_glm_prior, prior.data(), prior.size() * sizeof(double), hipMemcpyHostToDevice));
-    pot->glm_DP = Dc;
-    pot->glm_K = K;
-    pot->glm_M = M;
-    pot->glm_family = PBBI_GLM_SOFTMAX;
-    return PBBI_OK;
-}
 
 int glm_softmax_hmc_iter(const IterArgs& a) {
     if (int rc = smx_check(a.pot, a.ldn_in > a.ldn_out ? a.ldn_in : a.ldn_out)) return rc;
-    if (pbbi_dyn(a)) return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials: fixed trajectory lengths only");
-    if (a.fuse_S > 1) return pbbi_fail(PBBI_ERR_INVALID, "the GLM kernel takes one iteration per launch (internal)");
-    if (a.N == 0) return PBBI_OK;
-    SmxPrm prm = smx_prm(a.pot);
-    prm.q_in = (const double*)a.q_in;
-    prm.p_in = (const double*)a.p_in;
-    prm.u_in = (const double*)a.u_in;
-    prm.mass = (const double*)a.mass;
-    prm.q_out = (double*)a.q_out;
-    prm.p_out = (double*)a.p_out;
-    prm.ratio_out = (double*)a.ratio_out;
-    prm.reject_out = a.reject_out;
-    prm.N = a.N; prm.ldn_in = a.ldn_in; prm.ldn_out = a.ldn_out;
-    prm.h = a.h; prm.kT = a.kT; prm.L = a.L; prm.flags = a.flags; prm.rng = a.rng;
-    prm.mode = SMX_HMC; prm.method = a.method;
-    prm.seed = a.seed; prm.iter = a.iter; prm.chain0 = a.chain0;
-    return smx_launch(a.pot, prm, a.stream);
+    if (int rc = glm_check_iter(a)) return rc;
+    return smx_run(a, SMX_HMC);
 }
-
 int glm_softmax_integrate(const IntegrateArgs& a) {
     if (int rc = smx_check(a.pot, a.ldn)) return rc;
-    if (a.N == 0) return PBBI_OK;
-    SmxPrm prm = smx_prm(a.pot);
-    prm.q_in = (const double*)a.q;
-    prm.p_in = (const double*)a.p;
-    prm.mass = (const double*)a.mass;
-    prm.q_out = (double*)a.q;
-    prm.p_out = (double*)a.p;
-    prm.v_out = (double*)a.v_out;
-    prm.N = a.N; prm.ldn_in = a.ldn; prm.ldn_out = a.ldn;
-    prm.h = a.h; prm.L = a.L; prm.mode = SMX_INTEGRATE; prm.method = a.method;
-    return smx_launch(a.pot, prm, a.stream);
+    return smx_run(a, SMX_INTEGRATE);
 }
-
-static int smx_eval_launch(const EvalArgs& a, int mode) {
+int glm_softmax_eval(const EvalArgs& a) {
     if (int rc = smx_check(a.pot, a.ldn)) return rc;
-    if (a.N == 0) return PBBI_OK;
-    SmxPrm prm = smx_prm(a.pot);
-    prm.q_in = (const double*)a.q;
-    prm.p_in = (const double*)a.p;
-    prm.mass = (const double*)a.mass;
-    prm.U_out = (double*)a.U_out;
-    prm.grad_out = (double*)a.grad_out;
-    prm.w_out = (double*)a.w_out;
-    prm.N = a.N; prm.ldn_in = a.ldn; prm.ldn_out = a.ldn;
-    prm.mode = mode;
-    return smx_launch(a.pot, prm, a.stream);
+    return smx_run(a, SMX_EVAL);
 }
-int glm_softmax_eval(const EvalArgs& a) { return smx_eval_launch(a, SMX_EVAL); }
-int glm_softmax_energy(const EvalArgs& a) { return smx_eval_launch(a, a.ratio_finish ? SMX_RATIO : SMX_ENERGY); }
+int glm_softmax_energy(const EvalArgs& a) {
+    if (int rc = smx_check(a.pot, a.ldn)) return rc;
+    return smx_run(a, a.ratio_finish ? SMX_RATIO : SMX_ENERGY);
+}

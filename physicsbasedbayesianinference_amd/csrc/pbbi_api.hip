@@ -101,6 +101,7 @@ int new_handle(int kind, int D, int dtype, int device, pbbi_potential** out) {
     for (double& n : p->glm_hier_n) n = 0.0;
     p->d_glm_qimg = nullptr;
     for (double& r : p->glm_hier_rank) r = 0.0;
+    p->glm_variant = GLM_V_PLAIN;  // (means something on a KIND_GLM handle only, and its builder sets it)
     *out = p;
     return PBBI_OK;
 }
@@ -127,6 +128,147 @@ int upload_padded(const double* host, int D, int dtype, void** dev_out) {
 
 int upload_mean(pbbi_potential* p, const double* mean) { return upload_padded(mean, p->D, p->dtype, &p->d_mean); }
 
+// ---- GLM handles: a builder fills the host tables of its variant and sets the variant's fields, glm_upload does the rest.
+// The create entries have checked every argument (glm_host.h) before they make the handle.
+struct GlmTables {              // an empty table is not uploaded and its pointer stays NULL
+    std::vector<double> img;    // the design in fragment order (glm_pack_dp)
+    std::vector<double> y;      // plain model, softmax: y, zero padded to the blocks of the image
+    std::vector<double> obs;    // every other variant: the three observation streams
+    std::vector<double> prior;  // the prior table (the plain model has a scalar)
+    std::vector<double> qimg;   // structured group priors: the penalty in fragment order
+};
+// A failure part way leaves the pointers set so far to finish_or_destroy: pbbi_potential_destroy frees each non-NULL one.
+int glm_upload(pbbi_potential* pot, int variant, int family, int DP, int64_t M, const GlmTables& t) {
+    pot->glm_variant = variant; pot->glm_family = family; pot->glm_DP = DP; pot->glm_M = M;
+    const std::pair<const std::vector<double>*, void**> tables[] = {
+        {&t.img, &pot->d_glm_img}, {&t.y, &pot->d_glm_y}, {&t.obs, &pot->d_glm_obs}, {&t.prior, &pot->d_glm_prior},
+        {&t.qimg, &pot->d_glm_qimg}};
+    for (const auto& tb : tables)
+        if (int rc = upload(tb.first->data(), tb.first->size(), PBBI_F64, tb.second)) return rc;
+    return PBBI_OK;
+}
+GlmTables glm_design_tables(int Dx, int DP, int64_t M, const double* X) {  // the image of [X | 0] at DP >= Dx columns
+    GlmTables t;
+    t.img.resize((size_t)(glm_blocks_padded(M) * DP * 32));
+    glm_pack_dp(Dx, DP, M, X, t.img.data());
+    return t;
+}
+std::vector<double> glm_padded_y(int64_t M, const double* y) {
+    std::vector<double> yp((size_t)glm_blocks_padded(M) * 16, 0.0);
+    std::memcpy(yp.data(), y, sizeof(double) * (size_t)M);
+    return yp;
+}
+std::vector<double> glm_prior_vectors(int D, int DP, const double* lam, const double* mu) {  // lam | mu, zeros past D
+    std::vector<double> prior((size_t)2 * DP, 0.0);
+    for (int d = 0; d < D; ++d) {
+        prior[d] = lam[d];
+        prior[DP + d] = mu ? mu[d] : 0.0;
+    }
+    return prior;
+}
+int glm_terms_of(const double* weights, const double* offset, const double* trials) {
+    return (weights ? GLM_TERM_WEIGHTS : 0) | (offset ? GLM_TERM_OFFSET : 0) | (trials ? GLM_TERM_TRIALS : 0);
+}
+
+int glm_build(pbbi_potential* pot, int64_t M, const double* X, const double* y, int family, double lam) {
+    const int DP = glm_padded_dim(pot->D);
+    GlmTables t = glm_design_tables(pot->D, DP, M, X);
+    t.y = glm_padded_y(M, y);
+    pot->glm_lam = lam;
+    return glm_upload(pot, GLM_V_PLAIN, family, DP, M, t);
+}
+
+int glm_build_ex(pbbi_potential* pot, int64_t M, const double* X, const double* y, int family, const double* weights,
+                 const double* offset, const double* trials, const double* lam, const double* mu) {
+    const int D = pot->D, DP = glm_padded_dim(D);
+    GlmTables t = glm_design_tables(D, DP, M, X);
+    t.obs.resize((size_t)glm_obs_len(M));
+    glm_pack_obs(M, y, weights, offset, trials, t.obs.data());
+    t.prior = glm_prior_vectors(D, DP, lam, mu);
+    bool flat = true, centred = true, one = true;
+    for (int d = 0; d < D; ++d) {
+        flat = flat && lam[d] == 0.0;
+        one = one && lam[d] == lam[0];
+        centred = centred && t.prior[DP + d] == 0.0;
+    }
+    pot->glm_lam = one ? lam[0] : 0.0;  // (the full model's kernels read d_glm_prior)
+    pot->glm_terms = glm_terms_of(weights, offset, trials) | (one ? 0 : GLM_TERM_PRIOR_VECTOR) |
+                     (centred ? 0 : GLM_TERM_PRIOR_MEAN) | (flat ? GLM_TERM_PRIOR_FLAT : 0);
+    return glm_upload(pot, GLM_V_FULL, family, DP, M, t);
+}
+
+// pot->D = K * D
+int glm_softmax_build(pbbi_potential* pot, int D, int K, int64_t M, const double* X, const double* y, const double* lam) {
+    const int Dc = glm_padded_dim(D);  // the image of an M x D matrix at DP = Dc
+    GlmTables t = glm_design_tables(D, Dc, M, X);
+    t.y = glm_padded_y(M, y);
+    t.prior.assign((size_t)Dc, 0.0);
+    std::memcpy(t.prior.data(), lam, sizeof(double) * (size_t)D);
+    pot->glm_K = K;
+    return glm_upload(pot, GLM_V_SOFTMAX, PBBI_GLM_SOFTMAX, Dc, M, t);
+}
+
+// pot->D = Dx + (sample ? 1 : 0); lam and mu cover the theta row
+int glm_build_disp(pbbi_potential* pot, int Dx, int64_t M, const double* X, const double* y, int family,
+                   const double* weights, const double* offset, const double* lam, const double* mu, int sample,
+                   double theta) {
+    const int Dt = pot->D, DP = glm_padded_dim(Dt);
+    GlmTables t = glm_design_tables(Dx, DP, M, X);  // [X | 0]: the theta row meets a zero column
+    t.obs.resize((size_t)glm_obs_len(M));
+    glm_pack_obs_disp(M, y, weights, offset, t.obs.data());
+    t.prior = glm_prior_vectors(Dt, DP, lam, mu);
+    pot->glm_terms = glm_terms_of(weights, offset, nullptr);
+    pot->glm_trow = sample ? Dx : -1;
+    pot->glm_theta = sample ? 0.0 : theta;
+    return glm_upload(pot, GLM_V_DISPERSION, family, DP, M, t);
+}
+
+// pot->D = Dx + J.  penalty != NULL: the structured group priors (centred only), rank[j] into the table's n_j slots.
+int glm_build_hier(pbbi_potential* pot, int Dx, int64_t M, const double* X, const double* y, int family,
+                   const double* weights, const double* offset, const double* trials, const double* lam, const double* mu,
+                   const int32_t* groups, int J, const double* tprior, int parametrisation, const double* penalty = nullptr,
+                   const double* rank = nullptr) {
+    const bool nc = parametrisation == PBBI_HIER_NONCENTRED;
+    const int DP = glm_padded_dim(pot->D);
+    GlmTables t = glm_design_tables(Dx, DP, M, X);  // [X | 0]: the t rows meet zero columns
+    t.obs.resize((size_t)glm_obs_len(M));
+    glm_pack_obs(M, y, weights, offset, trials, t.obs.data());
+    t.prior.assign((size_t)2 * DP + 4, 0.0);  // lam | mu | n_j
+    double* nj = t.prior.data() + 2 * DP;
+    glm_pack_prior_groups(Dx, J, lam, mu, groups, tprior, t.prior.data(), nj);
+    for (int j = 0; j < 4; ++j) pot->glm_hier_n[j] = nj[j];
+    if (penalty) {
+        for (int j = 0; j < J; ++j) nj[j] = pot->glm_hier_rank[j] = rank[j];  // r_j t_j: the normaliser of a rank-r_j Gaussian
+        t.qimg.resize((size_t)glm_penalty_image_len(Dx, J));
+        glm_pack_penalty(Dx, J, penalty, t.qimg.data());
+    }
+    pot->glm_terms = glm_terms_of(weights, offset, trials);
+    pot->glm_hier_J = J;
+    pot->glm_hier_nc = nc ? 1 : 0;
+    return glm_upload(pot, penalty ? GLM_V_HIER_Q : nc ? GLM_V_HIER_NC : GLM_V_HIER, family, DP, M, t);
+}
+
+// pot->D = Dx + J + (sample ? 1 : 0)
+int glm_build_hier_disp(pbbi_potential* pot, int Dx, int64_t M, const double* X, const double* y, int family,
+                        const double* weights, const double* offset, const double* lam, const double* mu,
+                        const int32_t* groups, int J, const double* tprior, int parametrisation, int sample, double theta,
+                        const double* dprior) {
+    const int DP = glm_padded_dim(pot->D);
+    GlmTables t = glm_design_tables(Dx, DP, M, X);  // [X | 0]: the t rows and the theta row meet zero columns
+    t.obs.resize((size_t)glm_obs_len(M));
+    glm_pack_obs_disp(M, y, weights, offset, t.obs.data());
+    t.prior.assign((size_t)2 * DP + 4, 0.0);  // lam | mu | n_j
+    double* nj = t.prior.data() + 2 * DP;
+    glm_pack_prior_groups_disp(Dx, J, lam, mu, groups, tprior, sample, dprior, t.prior.data(), nj);
+    for (int j = 0; j < 4; ++j) pot->glm_hier_n[j] = nj[j];
+    pot->glm_terms = glm_terms_of(weights, offset, nullptr);
+    pot->glm_hier_J = J;
+    pot->glm_hier_nc = parametrisation == PBBI_HIER_NONCENTRED ? 1 : 0;
+    pot->glm_trow = sample ? Dx + J : -1;
+    pot->glm_theta = sample ? 0.0 : theta;
+    return glm_upload(pot, GLM_V_HIER_DISPERSION, family, DP, M, t);
+}
+
 int check_common(const pbbi_potential* pot, int64_t N, int64_t ldn) {
     if (!pot) return pbbi_fail(PBBI_ERR_INVALID, "potential handle is NULL");
     if (N < 0) return pbbi_fail(PBBI_ERR_INVALID, "N must be >= 0");
@@ -150,7 +292,7 @@ int plugin_rc(int rc) {
 }
 int route_hmc(const IterArgs& a) {
     const pbbi_potential* pot = a.pot;
-    if (pot->kind == KIND_GLM) return pot->glm_K ? glm_softmax_hmc_iter(a) : glm_hmc_iter(a);
+    if (pot->kind == KIND_GLM) return pot->glm_variant == GLM_V_SOFTMAX ? glm_softmax_hmc_iter(a) : glm_hmc_iter(a);
     if (pbbi_dyn(a) && (pot->kind == KIND_CUSTOM || (is_big(pot) && !dense_stream_applies(a))))
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, "per-chain trajectory lengths are served by the chain-per-lane "
                                                "kernels (D <= 32) and the dense kernels (fp64, D <= 256) only");
@@ -174,20 +316,20 @@ int route_fused_iterations(const IterArgs& a) {
 }
 int route_integrate(const IntegrateArgs& a) {
     const pbbi_potential* pot = a.pot;
-    if (pot->kind == KIND_GLM) return pot->glm_K ? glm_softmax_integrate(a) : glm_integrate(a);
+    if (pot->kind == KIND_GLM) return pot->glm_variant == GLM_V_SOFTMAX ? glm_softmax_integrate(a) : glm_integrate(a);
     if (pot->kind == KIND_CUSTOM) return a.N ? plugin_rc(pot->plugin_integrate(&a)) : PBBI_OK;
     if (is_big(pot) && dense_stream_integrate_applies(a)) return dense_stream_integrate(a);
     return is_big(pot) ? big_integrate(a) : is_dense(pot) ? dense_integrate(a) : lane_integrate(a);
 }
 int route_eval(const EvalArgs& a) {
     const pbbi_potential* pot = a.pot;
-    if (pot->kind == KIND_GLM) return pot->glm_K ? glm_softmax_eval(a) : glm_eval(a);
+    if (pot->kind == KIND_GLM) return pot->glm_variant == GLM_V_SOFTMAX ? glm_softmax_eval(a) : glm_eval(a);
     if (pot->kind == KIND_CUSTOM) return a.N ? plugin_rc(pot->plugin_eval(&a, 0)) : PBBI_OK;
     return is_big(pot) ? big_eval(a) : is_dense(pot) ? dense_eval(a) : lane_eval(a);
 }
 int route_energy(const EvalArgs& a) {
     const pbbi_potential* pot = a.pot;
-    if (pot->kind == KIND_GLM) return pot->glm_K ? glm_softmax_energy(a) : glm_energy(a);
+    if (pot->kind == KIND_GLM) return pot->glm_variant == GLM_V_SOFTMAX ? glm_softmax_energy(a) : glm_energy(a);
     if (pot->kind == KIND_CUSTOM)
         return a.N ? plugin_rc(pot->plugin_eval(&a, a.ratio_finish ? 2 : 1)) : PBBI_OK;
     return is_big(pot) ? big_energy(a) : is_dense(pot) ? dense_energy(a) : lane_energy(a);
@@ -769,7 +911,7 @@ int pbbi_potential_create_glm(int D, int64_t M, const double* X, const double* y
         return pbbi_fail(PBBI_ERR_INVALID, "unknown GLM family");
     if (!(prior_precision >= 0.0)) return pbbi_fail(PBBI_ERR_INVALID, "prior_precision must be >= 0");
     if (out) *out = nullptr;
-    if (D > 128 || dtype == PBBI_F32)
+    if (D > glm_max_dim(GLM_V_PLAIN, family) || dtype == PBBI_F32)
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials run on the fp64 matrix-core kernels: float64 and "
                                                "D <= 128 only");
     if (int rc = new_handle(KIND_GLM, D, dtype, device, out)) return rc;
@@ -785,7 +927,7 @@ int pbbi_potential_create_glm_ex(int D, int64_t M, const double* X, const double
     if (!X || !y) return pbbi_fail(PBBI_ERR_INVALID, "X / y is NULL");
     if (D < 1) return pbbi_fail(PBBI_ERR_INVALID, "D must be >= 1");
     if (int rc = glm_check_obs(M, family, y, weights, offset, trials)) return rc;
-    if (D > 128 || dtype == PBBI_F32)
+    if (D > glm_max_dim(GLM_V_FULL, family) || dtype == PBBI_F32)
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials run on the fp64 matrix-core kernels: float64 and "
                                                "D <= 128 only");
     if (int rc = glm_check_prior(D, prior_precision, prior_mean)) return rc;
@@ -813,15 +955,14 @@ int pbbi_potential_create_glm_dispersion(int D, int64_t M, const double* X, cons
     if (!X || !y) return pbbi_fail(PBBI_ERR_INVALID, "X / y is NULL");
     if (D < 1) return pbbi_fail(PBBI_ERR_INVALID, "D must be >= 1");
     if (int rc = glm_check_obs_disp(M, family, y, weights, offset)) return rc;
-    for (int64_t i = 0; i < M * D; ++i)
-        if (!std::isfinite(X[i])) return pbbi_fail(PBBI_ERR_INVALID, "X must be finite");
+    if (int rc = glm_check_design(D, M, X)) return rc;
     if (!sample && !std::isfinite(theta))
         return pbbi_fail(PBBI_ERR_INVALID, "a held dispersion must be finite and > 0 (theta = its logarithm)");
     const int Dt = D + (sample ? 1 : 0);
-    if (Dt > 128 || dtype == PBBI_F32)
+    if (Dt > glm_max_dim(GLM_V_DISPERSION, PBBI_GLM_GAUSSIAN) || dtype == PBBI_F32)  // the frame's widest kernel
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials run on the fp64 matrix-core kernels: float64 and a state "
                                                "dimension (coefficients + 1 for a sampled dispersion) <= 128 only");
-    if (family == PBBI_GLM_NEGBINOMIAL && Dt > 64)
+    if (Dt > glm_max_dim(GLM_V_DISPERSION, family))  // the negative binomial's stops short of it
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, "negbinomial: the state dimension (coefficients + 1 for a sampled dispersion) "
                                                "must be <= 64: its kernel at 65 .. 128 does not fit the register file");
     if (int rc = glm_check_prior(Dt, lam, mu)) return rc;
@@ -832,7 +973,7 @@ int pbbi_potential_create_glm_dispersion(int D, int64_t M, const double* X, cons
 
 static int glm_hier_check_dim(int D, int J, int family, int dtype, int parametrisation) {
     const bool nc = parametrisation == PBBI_HIER_NONCENTRED;
-    const int dmax = nc ? glm_hier_nc_max_dim(family) : glm_hier_max_dim(family);
+    const int dmax = glm_max_dim(nc ? GLM_V_HIER_NC : GLM_V_HIER, family);
     if (family != PBBI_GLM_LOGISTIC && family != PBBI_GLM_POISSON)
         return pbbi_fail(PBBI_ERR_INVALID, "hierarchical prior: the family must be logistic (0) or poisson (1)");
     if (dtype != PBBI_F64) return pbbi_fail(PBBI_ERR_UNSUPPORTED, "hierarchical GLM potentials are float64 only");
@@ -862,8 +1003,7 @@ int pbbi_potential_create_glm_hier_ex(int D, int64_t M, const double* X, const d
     if (!X || !y) return pbbi_fail(PBBI_ERR_INVALID, "X / y is NULL");
     if (int rc = glm_check_hier(D, J, prior_precision, prior_mean, groups, log_scale_prior)) return rc;
     if (int rc = glm_check_obs(M, family, y, weights, offset, trials)) return rc;
-    for (int64_t i = 0; i < M * D; ++i)
-        if (!std::isfinite(X[i])) return pbbi_fail(PBBI_ERR_INVALID, "X must be finite");
+    if (int rc = glm_check_design(D, M, X)) return rc;
     if (int rc = glm_hier_check_dim(D, J, family, dtype, parametrisation)) return rc;
     if (int rc = new_handle(KIND_GLM, D + J, dtype, device, out)) return rc;
     DeviceGuard guard(device);
@@ -879,13 +1019,12 @@ int pbbi_potential_create_glm_hier_q(int D, int64_t M, const double* X, const do
     if (!X || !y) return pbbi_fail(PBBI_ERR_INVALID, "X / y is NULL");
     if (int rc = glm_check_hier(D, J, prior_precision, prior_mean, groups, log_scale_prior)) return rc;
     if (int rc = glm_check_obs(M, family, y, weights, offset, trials)) return rc;
-    for (int64_t i = 0; i < M * D; ++i)
-        if (!std::isfinite(X[i])) return pbbi_fail(PBBI_ERR_INVALID, "X must be finite");
+    if (int rc = glm_check_design(D, M, X)) return rc;
     if (int rc = glm_check_penalty(D, J, groups, penalty, rank)) return rc;
     if (dtype != PBBI_F64) return pbbi_fail(PBBI_ERR_UNSUPPORTED, "hierarchical GLM potentials are float64 only");
-    if (D + J > glm_hier_q_max_dim(family))
+    if (D + J > glm_max_dim(GLM_V_HIER_Q, family))
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, "structured group priors: the state dimension (coefficients + groups) must be <= " +
-                                                   std::to_string(glm_hier_q_max_dim(family)) + " (" + std::to_string(D + J) + ")");
+                                                   std::to_string(glm_max_dim(GLM_V_HIER_Q, family)) + " (" + std::to_string(D + J) + ")");
     if (int rc = new_handle(KIND_GLM, D + J, dtype, device, out)) return rc;
     DeviceGuard guard(device);
     return finish_or_destroy(glm_build_hier(*out, D, M, X, y, family, weights, offset, trials, prior_precision, prior_mean,
@@ -894,7 +1033,7 @@ int pbbi_potential_create_glm_hier_q(int D, int64_t M, const double* X, const do
 
 // the shape rules of pbbi_potential_create_glm_hier_dispersion and its packing entry, stated once
 static int glm_hier_disp_check_dim(int D, int J, int sample, int family, int parametrisation) {
-    const int dmax = glm_hier_disp_max_dim(family, parametrisation);
+    const int dmax = pbbi_glm_hier_dispersion_max_dim(family, parametrisation);
     const int Dt = D + J + (sample ? 1 : 0);
     if (Dt > dmax)
         return pbbi_fail(PBBI_ERR_UNSUPPORTED,
@@ -921,8 +1060,7 @@ int pbbi_potential_create_glm_hier_dispersion(int D, int64_t M, const double* X,
                                            "group scales are pbbi_potential_create_glm_hier / _hier_ex");
     if (int rc = glm_check_hier(D, J, prior_precision, prior_mean, groups, log_scale_prior)) return rc;
     if (int rc = glm_check_obs_disp(M, family, y, weights, offset)) return rc;
-    for (int64_t i = 0; i < M * D; ++i)
-        if (!std::isfinite(X[i])) return pbbi_fail(PBBI_ERR_INVALID, "X must be finite");
+    if (int rc = glm_check_design(D, M, X)) return rc;
     if (int rc = glm_check_hier_disp_theta(sample, theta, log_dispersion_prior)) return rc;
     if (dtype != PBBI_F64) return pbbi_fail(PBBI_ERR_UNSUPPORTED, "hierarchical GLM potentials are float64 only");
     if (int rc = glm_hier_disp_check_dim(D, J, sample, family, parametrisation)) return rc;
@@ -946,7 +1084,10 @@ int pbbi_glm_pack_prior_groups_dispersion(int D, int J, const double* prior_prec
     return PBBI_OK;
 }
 
-int pbbi_glm_hier_dispersion_max_dim(int family, int parametrisation) { return glm_hier_disp_max_dim(family, parametrisation); }
+int pbbi_glm_hier_dispersion_max_dim(int family, int parametrisation) {
+    if (parametrisation != PBBI_HIER_CENTRED && parametrisation != PBBI_HIER_NONCENTRED) return 0;
+    return glm_max_dim(GLM_V_HIER_DISPERSION, family);
+}
 
 int pbbi_glm_pack_penalty(int D, int J, const double* penalty, double* out, int64_t out_len, int64_t* len_out) {
     if (D < 1 || J < 1 || J > 4 || D + J > 128)
@@ -1363,7 +1504,7 @@ int pbbi_describe_run(const pbbi_potential* pot, int method, int64_t N, int64_t 
     a.carry = 2; a.carry_g = (void*)(uintptr_t)16; a.carry_sel = (uint8_t*)(uintptr_t)16;
     std::string d;
     int fuse = 1;
-    if (pot->kind == KIND_GLM && pot->glm_K) {
+    if (pot->kind == KIND_GLM && pot->glm_variant == GLM_V_SOFTMAX) {
         d = "k_glm_softmax: K = " + std::to_string(pot->glm_K) + " class softmax regression, per block of 16 observations K eta "
             "tiles from the same fp64 MFMA A fragments (eta_k = X W_k), the softmax in lane, g_k = X^T r_k; 16 chains per "
             "wave, X staged through LDS, " + std::to_string(pot->D / pot->glm_K) + " coefficients per class padded to " +
@@ -1372,13 +1513,14 @@ int pbbi_describe_run(const pbbi_potential* pot, int method, int64_t N, int64_t 
     } else if (pot->kind == KIND_GLM) {
         d = "k_glm: GLM likelihood as two fp64 MFMA products per gradient (eta = X W, g = X^T r), 16 chains per wave, X "
             "staged through LDS in blocks of 16 observations (rows padded to " + std::to_string(pot->glm_DP) + ")";
-        if (pot->glm_family == PBBI_GLM_GAUSSIAN || pot->glm_family == PBBI_GLM_NEGBINOMIAL) {
+        const int v = pot->glm_variant;
+        if (v == GLM_V_DISPERSION || v == GLM_V_HIER_DISPERSION) {
             const int t = pot->glm_terms;
             d += std::string("; dispersion family ") + (pot->glm_family == PBBI_GLM_GAUSSIAN ? "gaussian" : "negbinomial");
             d += pot->glm_trow >= 0 ? " (log-dispersion sampled: state row " + std::to_string(pot->glm_trow) +
                                           ", read by one chain sum per gradient, its gradient reduced per chain)"
                                     : " (log-dispersion held at " + std::to_string(pot->glm_theta) + ")";
-            if (pot->glm_hier_J) {
+            if (v == GLM_V_HIER_DISPERSION) {
                 const int t0 = pot->D - pot->glm_hier_J - (pot->glm_trow >= 0 ? 1 : 0);
                 d += "; random effects, k_glm<NT, FAM, true, " + std::string(pot->glm_hier_nc ? "GLM_HIER_NC" : "GLM_HIER_CENTRED") +
                      ">: " + std::to_string(pot->glm_hier_J) + " sampled group log-scales (state rows " + std::to_string(t0) +
@@ -1389,14 +1531,14 @@ int pbbi_describe_run(const pbbi_potential* pot, int method, int64_t N, int64_t 
             }
             d += (t & GLM_TERM_WEIGHTS) ? ", weights" : "";
             d += (t & GLM_TERM_OFFSET) ? ", offset" : "";
-        } else if (pot->glm_hier_J) {
+        } else if (v == GLM_V_HIER || v == GLM_V_HIER_NC || v == GLM_V_HIER_Q) {
             const int t = pot->glm_terms;
             d += "; hierarchical prior on the full model's frame: " + std::to_string(pot->glm_hier_J) + " sampled group "
                  "log-scales (state rows " + std::to_string(pot->D - pot->glm_hier_J) + " .. " + std::to_string(pot->D - 1) +
                  ", each read by one chain sum per gradient, ";
-            d += pot->glm_hier_nc ? "non-centred: grouped rows hold z with w = mu + exp(t) z, the first product runs on a scaled "
+            d += v == GLM_V_HIER_NC ? "non-centred: grouped rows hold z with w = mu + exp(t) z, the first product runs on a scaled "
                                     "copy of the state, the group sums of gL z reduced per chain)"
-                  : pot->d_glm_qimg ? "structured group priors, k_glm<NT, FAM, true, GLM_HIER_Q>: the (" +
+                  : v == GLM_V_HIER_Q ? "structured group priors, k_glm<NT, FAM, true, GLM_HIER_Q>: the (" +
                                           std::to_string(pot->glm_DP) + " x " + std::to_string(pot->glm_DP) + ") penalty resident in "
                                           "LDS in A-fragment order, Q (w - mu) one more fp64 MFMA product per gradient whose result "
                                           "lands in the state layout, the quadratic forms d^T Q d reduced per chain)"
@@ -1404,7 +1546,7 @@ int pbbi_describe_run(const pbbi_potential* pot, int method, int64_t N, int64_t 
             d += (t & GLM_TERM_WEIGHTS) ? ", weights" : "";
             d += (t & GLM_TERM_OFFSET) ? ", offset" : "";
             d += (t & GLM_TERM_TRIALS) ? ", binomial trials" : "";
-        } else if (pot->d_glm_obs) {
+        } else if (v == GLM_V_FULL) {
             const int t = pot->glm_terms;
             d += "; full model (c | d | o streams beside X, prior vectors in LDS):";
             d += (t & GLM_TERM_WEIGHTS) ? " weights," : "";

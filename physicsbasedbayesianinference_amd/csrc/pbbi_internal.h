@@ -5,6 +5,7 @@
 
 #include <string>
 
+#include "glm_host.h"
 #include "pbbi.h"
 
 enum { KIND_HARMONIC = 0, KIND_GAUSS_DIAG = 1, KIND_GAUSS_DENSE = 2, KIND_ROSENBROCK = 3, KIND_CUSTOM = 4, KIND_GLM = 5 };
@@ -45,7 +46,7 @@ struct pbbi_potential {
     void* d_sfrag;     // DPS*DPS elements: precision in the order the stream consumes it
     void* d_smean;     // DPS elements, zero padded
     // generalised linear model (KIND_GLM), kernels_glm.hip.  (Appended: plugins built against the fields above keep working.)
-    int glm_DP;        // D padded to 16, 32, 64 or 128 (0 = not a GLM handle)
+    int glm_DP;        // D padded to 16, 32, 64 or 128 (0 = not a built GLM handle)
     int glm_family;    // PBBI_GLM_*
     int64_t glm_M;     // observations
     double glm_lam;    // prior precision
@@ -57,23 +58,25 @@ struct pbbi_potential {
     int glm_terms;     // GLM_TERM_*: what pbbi_describe_run names
     // softmax regression (pbbi_potential_create_glm_softmax), kernels_glm_softmax.hip.  (Appended.)  D = glm_K * (coefficients
     // per class), glm_DP = the padded class size Dc, d_glm_y the labels, d_glm_prior lam (Dc values, zeros past D)
-    int glm_K;         // classes (0 = not a softmax handle)
+    int glm_K;         // classes
     // the dispersion families (pbbi_potential_create_glm_dispersion), FAM = 3, 4 of k_glm<NT, FAM, true>.  (Appended.)  D =
     // the state dimension (coefficients + the theta row when sampled), d_glm_obs = a | y | o, d_glm_prior covers the theta row
     int glm_trow;      // the state row of theta (= the coefficient count) when it is sampled, -1 when it is held
     double glm_theta;  // the held log-dispersion
     // the hierarchical prior (pbbi_potential_create_glm_hier), k_glm<NT, FAM, true, GLM_HIER_CENTRED>.  (Appended.)  D = coefficients +
     // glm_hier_J, the t rows last; d_glm_prior is the table of glm_pack_prior_groups
-    int glm_hier_J;        // groups (0 = not a hierarchical handle)
+    int glm_hier_J;        // groups
     double glm_hier_n[4];  // members of each group
     // ... in the non-centred parametrisation (pbbi_potential_create_glm_hier_ex), k_glm<NT, FAM, true, GLM_HIER_NC>.  (Appended.)
     int glm_hier_nc;       // 1: the grouped rows of the state hold z_d, w_d = mu_d + exp(t_j) z_d
     // ... with structured group priors (pbbi_potential_create_glm_hier_q), k_glm<NT, FAM, true, GLM_HIER_Q>.  (Appended.)
-    void* d_glm_qimg;      // the (glm_DP x glm_DP) penalty in A-fragment order (glm_pack_penalty); NULL = not such a handle
+    void* d_glm_qimg;      // the (glm_DP x glm_DP) penalty in A-fragment order (glm_pack_penalty)
     double glm_hier_rank[4];  // rank(Q_j), what the table's n_j slots hold on such a handle
     // random effects for the dispersion families (pbbi_potential_create_glm_hier_dispersion) add no field: glm_family 3 / 4 with
     // glm_hier_J > 0, D = coefficients + glm_hier_J + (glm_trow >= 0), glm_trow the LAST row, d_glm_prior the table of
     // glm_pack_prior_groups_disp, d_glm_obs = a | y | o
+    // which of these kinds of handle this is.  (Appended.)  The one record of it: no other field is asked for the kind.
+    int glm_variant;       // GlmVariant (glm_host.h), set by the builder of the create entry
 };
 
 // ---- error plumbing ---------------------------------------------------------
@@ -276,55 +279,13 @@ int big_integrate(const IntegrateArgs& a);
 int big_eval(const EvalArgs& a);
 int big_energy(const EvalArgs& a);
 int big_build(pbbi_potential* pot, const double* precision_host, const double* mean_host);
-// generalised linear models, likelihood on the fp64 matrix cores (fp64, D <= 128), kernels_glm.hip
-int glm_build(pbbi_potential* pot, int64_t M, const double* X, const double* y, int family, double lam);
-enum { GLM_TERM_WEIGHTS = 1, GLM_TERM_OFFSET = 2, GLM_TERM_TRIALS = 4, GLM_TERM_PRIOR_VECTOR = 8, GLM_TERM_PRIOR_MEAN = 16,
-       GLM_TERM_PRIOR_FLAT = 32 };
-int glm_build_ex(pbbi_potential* pot, int64_t M, const double* X, const double* y, int family, const double* weights,
-                 const double* offset, const double* trials, const double* lam, const double* mu);
-int glm_check_obs(int64_t M, int family, const double* y, const double* weights, const double* offset,
-                  const double* trials);                       // host only: PBBI_ERR_INVALID with a message
-int glm_check_prior(int D, const double* lam, const double* mu);
-int64_t glm_obs_len(int64_t M);                                // doubles of the three observation streams
-void glm_pack_obs(int64_t M, const double* y, const double* weights, const double* offset, const double* trials,
-                  double* out);                                // host only
-int glm_check_obs_disp(int64_t M, int family, const double* y, const double* weights, const double* offset);
-void glm_pack_obs_disp(int64_t M, const double* y, const double* weights, const double* offset, double* out);
-int glm_build_disp(pbbi_potential* pot, int Dx, int64_t M, const double* X, const double* y, int family,
-                   const double* weights, const double* offset, const double* lam, const double* mu, int sample, double theta);
-int glm_hier_max_dim(int family);  // the largest coefficients + groups the hierarchical kernels of a family serve
-int glm_hier_nc_max_dim(int family);  // ... the non-centred ones
-int glm_check_hier(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior);
-void glm_pack_prior_groups(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior,
-                           double* out, double* n_out);        // host only
-int glm_build_hier(pbbi_potential* pot, int Dx, int64_t M, const double* X, const double* y, int family,
-                   const double* weights, const double* offset, const double* trials, const double* lam, const double* mu,
-                   const int32_t* groups, int J, const double* tprior, int parametrisation, const double* penalty = nullptr,
-                   const double* rank = nullptr);
-// random effects for the dispersion families (pbbi_potential_create_glm_hier_dispersion): FAM = 3, 4 with HIER = centred / NC
-int glm_hier_disp_max_dim(int family, int parametrisation);  // the largest coefficients + groups + sampled served; 0 = none
-int glm_check_hier_disp_theta(int sample, double theta, const double* dprior);
-void glm_pack_prior_groups_disp(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior,
-                                int sample, const double* dprior, double* out, double* n_out);  // host only
-int glm_build_hier_disp(pbbi_potential* pot, int Dx, int64_t M, const double* X, const double* y, int family,
-                        const double* weights, const double* offset, const double* lam, const double* mu,
-                        const int32_t* groups, int J, const double* tprior, int parametrisation, int sample, double theta,
-                        const double* dprior);
-int glm_hier_q_max_dim(int family);  // ... the structured group priors' (k_glm<NT, FAM, true, GLM_HIER_Q>)
-int glm_check_penalty(int D, int J, const int32_t* groups, const double* penalty, const double* rank);
-int64_t glm_penalty_image_len(int D, int J);                   // doubles of the fragment image of the (DP x DP) penalty
-void glm_pack_penalty(int D, int J, const double* penalty, double* out);  // host only
-int glm_padded_dim(int D);
-int64_t glm_image_len(int D, int64_t M);                       // doubles of the fragment image of an M x D design matrix
-void glm_pack(int D, int64_t M, const double* X, double* out);  // host only
+// generalised linear models, likelihood on the fp64 matrix cores (fp64, D <= 128), kernels_glm.hip; what of their host side
+// calls no HIP function (shipped shapes, argument rules, packers) is glm_host.h, the builders are pbbi_api.hip's
 int glm_hmc_iter(const IterArgs& a);
 int glm_integrate(const IntegrateArgs& a);
 int glm_eval(const EvalArgs& a);
 int glm_energy(const EvalArgs& a);
 // K-class softmax regression on the same frame (fp64, K * Dc <= 128), kernels_glm_softmax.hip
-int glm_softmax_layout(int D, int K, int* Dc_out, int* NT_out, int32_t* row_map);  // host only
-int glm_softmax_check(int D, int K, int64_t M, const double* X, const double* y, const double* lam);
-int glm_softmax_build(pbbi_potential* pot, int D, int K, int64_t M, const double* X, const double* y, const double* lam);
 int glm_softmax_hmc_iter(const IterArgs& a);
 int glm_softmax_integrate(const IntegrateArgs& a);
 int glm_softmax_eval(const EvalArgs& a);

@@ -63,7 +63,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 _CACHE = os.path.join(_HERE, "_plugins")
-_DEPS = ("pbbi_custom.h", "pbbi_internal.h", "pbbi_rng.h")
+_DEPS = ("pbbi_custom.h", "pbbi_internal.h", "glm_host.h", "pbbi_rng.h")
 
 
 _AD_GRADIENT = """
