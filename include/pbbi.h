@@ -374,6 +374,34 @@ int pbbi_potential_create_glm_hier_q(int D, int64_t M, const double* X, const do
  *     out[((t * DP/8 + s2) * 64 + lane) * 2 + e] = Q[16 t + (lane & 15)][4 (2 s2 + e) + (lane >> 4)]     t < DP/16, s2 < DP/8
  * with (Q + Q^T) / 2 for Q; rows and columns >= D are zero. */
 int pbbi_glm_pack_penalty(int D, int J, const double* penalty, double* out, int64_t out_len, int64_t* len_out);
+/* What a GLM handle says about T = S * N draws of its state, per observation, reduced over the draws on the device
+ * (csrc/kernels_glm_pointwise.hip: eta = X W for 16 draws at a time on the fp64 matrix cores, from the first copy of the
+ * packed design image).  ll_it = minus the per-observation term of the handle's potential at draw t -- the log-likelihood of
+ * observation i WITHOUT the terms that depend on no parameter (a log C(n, y); -a lgamma(y + 1); -a/2 log 2 pi), which the
+ * caller adds -- and exactly 0 for an observation of weight 0.  Outputs, each (M) doubles on the device or NULL:
+ *     lse_out[i]  = log sum_t exp(ll_it)          (lppd_i = lse_i - log T + the constant of observation i)
+ *     mean_out[i] = mean_t ll_it
+ *     var_out[i]  = the unbiased variance over t of ll_it (the WAIC penalty of observation i); needs S * N >= 2
+ *     mu_out[i]   = mean_t of the fitted mean: sigmoid(eta_it) (logistic, per trial), exp(eta_it) (poisson, negbinomial),
+ *                   eta_it (gaussian), eta_it = x_i . w_t + o_i -- for every observation, whatever its weight
+ * samples_sdn: S contiguous (Dt, N) slabs of doubles (the pbbi_sample_moments convention) on the handle's device, Dt >= the
+ * handle's state dimension; rows past it are ignored.  The draws are on the NATURAL scale: for a non-centred handle (w; t),
+ * not (z; t).  Only the coefficient rows are read as coefficients: the log-scales of a hierarchical handle do not enter, a
+ * sampled log-dispersion is read from its own row, a held one comes from the handle.  ranges: 0 = the library chooses how
+ * many ranges the draws are cut into, >= 1 (<= 65535) fixes it; the ranges are merged in index order without atomics, so for
+ * a given `ranges` the results are bit for bit the same from run to run.  A draw with ll_it = -inf leaves lse_i to the other
+ * draws and makes mean_i and var_i non-finite; a NaN draw makes every output of the observations it reaches NaN.
+ * Served: the handles of pbbi_potential_create_glm, _glm_ex, _glm_dispersion, _glm_hier, _glm_hier_ex, _glm_hier_q and
+ * _glm_hier_dispersion.  A softmax handle and a handle that is no GLM handle: PBBI_ERR_UNSUPPORTED.  NULL handle or samples,
+ * S < 1, N < 1, Dt below the state dimension, var_out with S * N < 2, ranges outside 0 .. 65535: PBBI_ERR_INVALID.  Every
+ * rule is checked before the device is touched. */
+int pbbi_pointwise_glm(const pbbi_potential* pot, const void* samples_sdn, int S, int Dt, int64_t N, int ranges,
+                       double* lse_out, double* mean_out, double* var_out, double* mu_out, void* stream);
+/* The argument rules of pbbi_pointwise_glm alone, on the HOST (touches no device), for a handle described by value: handle = 0
+ * (NULL), 1 (a GLM handle of `family` with state dimension `state_dim`) or 2 (a handle of another kind); `samples` is only
+ * compared with NULL; want_var != 0: var_out is asked for.  Returns what pbbi_pointwise_glm would return before it launches. */
+int pbbi_pointwise_glm_check(int handle, int family, int state_dim, const void* samples, int S, int Dt, int64_t N,
+                             int ranges, int want_var);
 int pbbi_potential_destroy(pbbi_potential* pot);
 int pbbi_potential_dim(const pbbi_potential* pot);
 int pbbi_potential_dtype(const pbbi_potential* pot);

@@ -76,6 +76,9 @@ PROTOTYPES = {
                                                   _i, _i, _d, _dp, _i, _i, _pp],
     "pbbi_glm_pack_prior_groups_dispersion": [_i, _i, _dp, _dp, C.POINTER(C.c_int32), _dp, _i, _dp, _dp, _dp],
     "pbbi_glm_hier_dispersion_max_dim": [_i, _i],   # returns the dimension, not a status
+    # what a GLM handle says about posterior draws (glm.py `pointwise`, csrc/kernels_glm_pointwise.hip)
+    "pbbi_pointwise_glm": [_vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp],
+    "pbbi_pointwise_glm_check": [_i, _i, _i, _vp, _i, _i, _i64, _i, _i],
     "pbbi_potential_destroy": [_vp],
     "pbbi_potential_dim": [_vp],
     "pbbi_potential_dtype": [_vp],

@@ -188,11 +188,46 @@ static void softmax_shapes() {
     EXPECT(glm_softmax_layout(65, 2, nullptr, nullptr, nullptr) == PBBI_ERR_UNSUPPORTED);
 }
 
+// every rule of pbbi_pointwise_glm's arguments, in the order the checker states them; `samples` is only compared with NULL
+static void pointwise_rules() {
+    Buf<double> s = dbuf(1, 0.0);
+    const void* p = s.get();
+    const int fams[] = {PBBI_GLM_LOGISTIC, PBBI_GLM_POISSON, PBBI_GLM_GAUSSIAN, PBBI_GLM_NEGBINOMIAL};
+    for (int fam : fams) {
+        EXPECT(glm_check_pointwise(1, fam, 5, p, 3, 5, 150, 0, true) == PBBI_OK);
+        EXPECT(glm_check_pointwise(1, fam, 5, p, 1, 7, 1, 1, false) == PBBI_OK);   // one draw without the variance; Dt > D
+        EXPECT(glm_check_pointwise(1, fam, 128, p, 1, 128, 2, 65535, true) == PBBI_OK);
+    }
+    EXPECT(glm_check_pointwise(0, PBBI_GLM_LOGISTIC, 5, p, 3, 5, 150, 0, true) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("handle is NULL") != std::string::npos);
+    EXPECT(glm_check_pointwise(1, PBBI_GLM_LOGISTIC, 5, nullptr, 3, 5, 150, 0, true) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("samples is NULL") != std::string::npos);
+    EXPECT(glm_check_pointwise(1, PBBI_GLM_LOGISTIC, 5, p, 0, 5, 150, 0, true) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("S must be >= 1") != std::string::npos);
+    EXPECT(glm_check_pointwise(1, PBBI_GLM_LOGISTIC, 5, p, 3, 5, 0, 0, true) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("N must be >= 1") != std::string::npos);
+    EXPECT(glm_check_pointwise(1, PBBI_GLM_LOGISTIC, 5, p, 1, 5, 1, 0, true) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("at least two draws") != std::string::npos);
+    EXPECT(glm_check_pointwise(1, PBBI_GLM_LOGISTIC, 5, p, 3, 5, 150, -1, true) == PBBI_ERR_INVALID);
+    EXPECT(glm_check_pointwise(1, PBBI_GLM_LOGISTIC, 5, p, 3, 5, 150, 65536, true) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("ranges must be") != std::string::npos);
+    EXPECT(glm_check_pointwise(1, PBBI_GLM_LOGISTIC, 5, p, 3, 4, 150, 0, true) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("state dimension") != std::string::npos);
+    EXPECT(glm_check_pointwise(1, PBBI_GLM_SOFTMAX, 6, p, 3, 6, 150, 0, true) == PBBI_ERR_UNSUPPORTED);
+    EXPECT(g_error.find("softmax") != std::string::npos && g_error.find(GLM_POINTWISE_RULE) != std::string::npos);
+    EXPECT(glm_check_pointwise(2, 0, 5, p, 3, 5, 150, 0, true) == PBBI_ERR_UNSUPPORTED);
+    EXPECT(g_error.find("not a GLM handle") != std::string::npos && g_error.find(GLM_POINTWISE_RULE) != std::string::npos);
+    EXPECT(glm_check_pointwise(1, 99, 5, p, 3, 5, 150, 0, true) == PBBI_ERR_UNSUPPORTED);
+    // S * N is formed in 64 bits
+    EXPECT(glm_check_pointwise(1, PBBI_GLM_LOGISTIC, 5, p, 2000000000, 5, (int64_t)1 << 40, 0, true) == PBBI_OK);
+}
+
 int main() {
     design_and_observations();
     hierarchical_tables();
     penalties();
     softmax_shapes();
+    pointwise_rules();
     // what is shipped (the one statement the entries and the launch read)
     EXPECT(glm_max_dim(GLM_V_PLAIN, PBBI_GLM_LOGISTIC) == 128 && glm_max_dim(GLM_V_FULL, PBBI_GLM_POISSON) == 128);
     EXPECT(glm_max_dim(GLM_V_DISPERSION, PBBI_GLM_GAUSSIAN) == 128 && glm_max_dim(GLM_V_DISPERSION, PBBI_GLM_NEGBINOMIAL) == 64);

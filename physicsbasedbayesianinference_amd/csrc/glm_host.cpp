@@ -333,6 +333,34 @@ void glm_pack_penalty(int D, int J, const double* penalty, double* out) {
     for (int b = 0; b < DP / 16; ++b) glm_pack_p1(KS, b, at, out + (size_t)b * KS * 64);
 }
 
+// ---- pointwise log-likelihood over draws ------------------------------------------------------------------------
+const char* const GLM_POINTWISE_RULE = "pbbi_pointwise_glm serves the handles of pbbi_potential_create_glm, _glm_ex, "
+                                       "_glm_dispersion, _glm_hier, _glm_hier_ex, _glm_hier_q and _glm_hier_dispersion "
+                                       "(families logistic, poisson, gaussian, negbinomial; float64)";
+
+int glm_check_pointwise(int handle, int family, int state_dim, const void* sdn, int S, int Dt, int64_t N, int ranges,
+                        bool want_var) {
+    if (handle == 0) return pbbi_fail(PBBI_ERR_INVALID, "potential handle is NULL");
+    if (!sdn) return pbbi_fail(PBBI_ERR_INVALID, "samples is NULL");
+    if (S < 1) return pbbi_fail(PBBI_ERR_INVALID, "S must be >= 1 (S = " + std::to_string(S) + ")");
+    if (N < 1) return pbbi_fail(PBBI_ERR_INVALID, "N must be >= 1 (N = " + std::to_string(N) + ")");
+    if (want_var && S == 1 && N == 1)  // S * N < 2 without forming the product
+        return pbbi_fail(PBBI_ERR_INVALID, "var_out needs at least two draws (S * N = 1): pass NULL");
+    if (ranges < 0 || ranges > 65535)
+        return pbbi_fail(PBBI_ERR_INVALID, "ranges must be 0 (the library chooses) or 1 .. 65535 (ranges = " +
+                                               std::to_string(ranges) + ")");
+    if (handle != 1)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string("not a GLM handle: ") + GLM_POINTWISE_RULE);
+    if (family == PBBI_GLM_SOFTMAX)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string("a softmax handle is not served: ") + GLM_POINTWISE_RULE);
+    if (!glm_canonical(family) && !glm_disp(family))
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string("unknown GLM family: ") + GLM_POINTWISE_RULE);
+    if (Dt < state_dim)
+        return pbbi_fail(PBBI_ERR_INVALID, "Dt must be at least the handle's state dimension (Dt = " + std::to_string(Dt) +
+                                               ", state dimension " + std::to_string(state_dim) + ")");
+    return PBBI_OK;
+}
+
 // ---- K-class softmax regression ---------------------------------------------------------------------------------
 const char* const GLM_SOFTMAX_RULE = "softmax GLM: float64, 2 <= K <= 8 classes, each padded to Dc = 16, 32 or 64 rows with "
                                      "K * Dc <= 128 (D <= 16 for K <= 8, D <= 32 for K <= 4, D <= 64 for K = 2)";

@@ -54,6 +54,11 @@ void glm_pack_prior_groups_disp(int D, int J, const double* lam, const double* m
 int glm_check_penalty(int D, int J, const int32_t* groups, const double* penalty, const double* rank);
 int64_t glm_penalty_image_len(int D, int J);  // doubles of the fragment image of the (DP x DP) penalty
 void glm_pack_penalty(int D, int J, const double* penalty, double* out);
+// ---- pointwise log-likelihood over draws (kernels_glm_pointwise.hip): every argument rule of pbbi_pointwise_glm.  handle: 0 =
+// NULL, 1 = a GLM handle (family, state_dim its own), 2 = a handle of another kind
+extern const char* const GLM_POINTWISE_RULE;
+int glm_check_pointwise(int handle, int family, int state_dim, const void* sdn, int S, int Dt, int64_t N, int ranges,
+                        bool want_var);
 // ---- K-class softmax regression
 extern const char* const GLM_SOFTMAX_RULE;
 int glm_softmax_layout(int D, int K, int* Dc_out, int* NT_out, int32_t* row_map);

@@ -32,6 +32,10 @@ in its quadratic form (random walks, difference penalties of splines, ICAR), Q_j
 
 `HierarchicalDispersionGLM` is the product of the two: the likelihood of `DispersionGLM` under the priors of `HierarchicalGLM`
 -- the linear mixed model with unknown residual sigma, eight schools, negative-binomial counts with random intercepts.
+
+`pot.pointwise(samples)` (every class but `SoftmaxGLM`) puts the draws to use on the device (csrc/kernels_glm_pointwise.hip):
+per observation the log pointwise predictive density, the WAIC penalty and the posterior predictive mean, reduced over all
+draws of a (D, N, S) device view without forming an M x T matrix; a second potential on held-out data takes the same draws.
 """
 import ctypes as C
 
@@ -43,7 +47,7 @@ from .potential import Potential, _dptr
 __all__ = ["GLM", "SoftmaxGLM", "DispersionGLM", "HierarchicalGLM", "HierarchicalDispersionGLM", "HIER_DISP_MAX_DIM",
            "pack_prior_groups_dispersion", "FAMILIES", "DISPERSION_FAMILIES", "HIER_MAX_DIM",
            "HIER_NC_MAX_DIM", "HIER_PARAMETRISATIONS", "HIER_MAX_GROUPS", "pack_design", "pack_observations", "pack_observations_dispersion", "pack_prior_groups",
-           "HIER_Q_MAX_DIM", "pack_penalty", "padded_dim", "softmax_layout"]
+           "HIER_Q_MAX_DIM", "pack_penalty", "padded_dim", "softmax_layout", "PointwiseResult", "pointwise_constants"]
 
 FAMILIES = {"logistic": _lib.GLM_LOGISTIC, "poisson": _lib.GLM_POISSON}
 DISPERSION_FAMILIES = {"gaussian": _lib.GLM_GAUSSIAN, "negbinomial": _lib.GLM_NEGBINOMIAL}   # DispersionGLM only
@@ -200,6 +204,127 @@ def _validate(X, y, family, prior_precision, dtype, prior_mean=None, weights=Non
     return np.ascontiguousarray(X), np.ascontiguousarray(y), lam, prior_mean, weights, offset, trials
 
 
+class PointwiseResult:
+    """What `pointwise` returns: per observation (NumPy (M,) arrays) `lppd_i` (the log pointwise predictive density, log
+    mean_t p(y_i | draw t)), `mean_ll_i` (mean_t log p(y_i | draw t)), `p_waic_i` (the unbiased variance over the draws of
+    log p(y_i | draw t): the WAIC penalty; NaN with a single draw) and `mu_i` (the posterior mean of E[y_i], times the
+    trials for binomial data); `T` the number of draws; and the scalars `lppd`, `p_waic`, `waic = -2 (lppd - p_waic)`."""
+
+    def __init__(self, lppd_i, mean_ll_i, p_waic_i, mu_i, T):
+        self.lppd_i, self.mean_ll_i, self.p_waic_i, self.mu_i, self.T = lppd_i, mean_ll_i, p_waic_i, mu_i, int(T)
+
+    @property
+    def lppd(self):
+        return float(np.sum(self.lppd_i))
+
+    @property
+    def p_waic(self):
+        return float(np.sum(self.p_waic_i))
+
+    @property
+    def waic(self):
+        return -2.0 * (self.lppd - self.p_waic)
+
+    def __repr__(self):
+        return "PointwiseResult(M=%d, T=%d, lppd=%.6g, p_waic=%.6g, waic=%.6g)" % (self.lppd_i.size, self.T, self.lppd,
+                                                                                 self.p_waic, self.waic)
+
+
+def _lgamma(x):
+    import math
+    return np.array([math.lgamma(v) for v in np.asarray(x, dtype=np.float64).ravel()]).reshape(np.shape(x))
+
+
+def pointwise_constants(family, y, weights=None, trials=None):
+    """k_i: the part of observation i's log-likelihood that depends on no parameter, which the kernels drop and `pointwise`
+    adds on the host -- a_i log C(n_i, y_i) (logistic), -a_i lgamma(y_i + 1) (poisson, negbinomial), -a_i / 2 log 2 pi
+    (gaussian); a_i the weights (the likelihood of observation i enters to the power a_i)."""
+    y = np.asarray(y, dtype=np.float64)
+    a = np.ones_like(y) if weights is None else np.asarray(weights, dtype=np.float64)
+    if family == "logistic":
+        n = np.ones_like(y) if trials is None else np.asarray(trials, dtype=np.float64)
+        return a * (_lgamma(n + 1.0) - _lgamma(y + 1.0) - _lgamma(n - y + 1.0))
+    if family in ("poisson", "negbinomial"):
+        return -a * _lgamma(y + 1.0)
+    if family == "gaussian":
+        return -0.5 * np.log(2.0 * np.pi) * a
+    raise ValueError("pointwise_constants: unknown family %r" % (family,))
+
+
+def _pointwise_slabs(pot, samples):
+    """(sdn, S, Dt, N): contiguous (S, Dt, N) float64 slabs on the potential's device holding `samples` on the natural scale --
+    a (D, N, S) device view of such slabs (getSamples(device_output=True), also sliced along S) without a copy."""
+    from . import _device
+    t = _device.torch()
+    natural = getattr(pot, "parametrisation", "centred") != "centred"
+
+    def rows(Dt):
+        if Dt < pot.numDimensions:
+            raise ValueError("samples have %d rows, the potential's state has %d" % (Dt, pot.numDimensions))
+
+    if isinstance(samples, t.Tensor):
+        if samples.dim() == 2:
+            samples = samples.unsqueeze(2)
+        if samples.dim() != 3 or samples.dtype != t.float64:
+            raise ValueError("samples must be a float64 (D, N, S) device view or a NumPy (Dt, N, S) / (Dt, T) array")
+        if not samples.is_cuda or samples.device.index != pot.device:
+            raise ValueError("samples must live on device %d" % pot.device)
+        rows(samples.shape[0])
+        if natural:
+            samples = pot.to_natural(samples)
+        sdn = samples.permute(2, 0, 1)
+        if not sdn.is_contiguous():
+            sdn = sdn.contiguous()
+    else:
+        q = np.asarray(samples, dtype=np.float64)
+        if q.ndim == 2:
+            q = q[:, :, None]
+        if q.ndim != 3:
+            raise ValueError("samples must be (Dt, N, S) or (Dt, T)")
+        rows(q.shape[0])
+        if natural:
+            q = pot.to_natural(q)
+        sdn = _device.as_device(np.ascontiguousarray(np.transpose(q, (2, 0, 1))), pot.device, np.float64)
+    S, Dt, N = (int(v) for v in sdn.shape)
+    if S < 1 or N < 1:
+        raise ValueError("samples hold no draw")
+    return sdn, S, Dt, N
+
+
+def _pointwise(self, samples, ranges=0):
+    """Per-observation log-likelihood statistics over posterior draws, reduced on the device (csrc/kernels_glm_pointwise.hip):
+    the log pointwise predictive density, WAIC and the posterior predictive mean, without an M x T matrix anywhere.
+
+        s = hmc.getSamples(2000, device_output=True)             # (D, N, S) device view
+        r = pot.pointwise(s[:, :, 500:])                          # burn-in dropped; r.waic, r.lppd, r.p_waic, r.mu_i
+        held = GLM(X_new, y_new).pointwise(s[:, :, 500:]).lppd    # held-out log predictive density of the same draws
+        mu = GLM(X_new, np.zeros(len(X_new))).pointwise(s).mu_i   # the fitted mean at new X (a dummy response)
+
+    `samples`: the (D, N, S) device view of getSamples(device_output=True) (any slice along S; no copy), or a NumPy array
+    (Dt, N, S) or (Dt, T), in the SAMPLER's coordinates: `to_natural` is applied where the potential has one.  Rows past the
+    state dimension are ignored.  `ranges`: 0 lets the library choose into how many ranges the draws are cut; >= 1 fixes it
+    (for a given value the result is bit for bit reproducible).  Returns a `PointwiseResult`.  An observation of weight 0 has
+    log-likelihood 0 exactly (it adds nothing to lppd and WAIC); its `mu_i` is formed like any other's."""
+    from . import _device
+    sdn, S, Dt, N = _pointwise_slabs(self, samples)
+    M, T = self.y.size, S * N
+    out = _device.empty((4, M), np.float64, self.device)
+    ptr = [out[k].data_ptr() for k in range(4)]
+    try:
+        _lib.call("pbbi_pointwise_glm", self.handle, sdn.data_ptr(), S, Dt, N, int(ranges), ptr[0], ptr[1],
+                  ptr[2] if T >= 2 else None, ptr[3], _device.stream_ptr(self.device))
+    except _lib.PbbiError as e:
+        if e.code in (_lib.ERR_INVALID, _lib.ERR_UNSUPPORTED):
+            raise ValueError(str(e)) from None
+        raise
+    lse, mean, var, mu = _device.to_numpy(out)
+    trials = getattr(self, "trials", None)
+    k = pointwise_constants(self.family, self.y, self.weights, trials)
+    if trials is not None:
+        mu = mu * trials
+    return PointwiseResult(lse - np.log(T) + k, mean + k, var if T >= 2 else np.full(M, np.nan), mu, T)
+
+
 class GLM(Potential):
     """-log posterior of the weights of a generalised linear model (see the module text).
 
@@ -216,6 +341,7 @@ class GLM(Potential):
     TemperingLadder).  Arguments are checked on the host before anything touches the GPU."""
 
     kind = "glm"
+    pointwise = _pointwise
 
     def __init__(self, X, y, family="logistic", prior_precision=1.0, prior_mean=None, weights=None, offset=None,
                  trials=None, dtype="float64", device=None):
@@ -309,6 +435,10 @@ class SoftmaxGLM(Potential):
         _lib.call("pbbi_potential_create_glm_softmax", D, K, M, _dptr(X), _dptr(y), _dptr(lam), self._dt, self.device,
                   C.byref(self._handle))
 
+    def pointwise(self, samples, ranges=0):
+        """Not built for the softmax family (GLM, DispersionGLM, HierarchicalGLM and HierarchicalDispersionGLM have it)."""
+        raise ValueError("not built")
+
     def coefficients(self, samples):
         """(K * D, ...) -> (K, D, ...): the leading axis of a state, sample or gradient array split by class (a view
         wherever the array allows one)."""
@@ -393,6 +523,7 @@ class DispersionGLM(Potential):
     anything touches the GPU.  It runs on csrc/kernels_glm.hip (FAM = 3, 4 of k_glm<NT, FAM, true>)."""
 
     kind = "glm"
+    pointwise = _pointwise
 
     def __init__(self, X, y, family="negbinomial", dispersion="sample", log_dispersion_prior=None, prior_precision=1.0,
                  prior_mean=None, weights=None, offset=None, dtype="float64", device=None):
@@ -706,6 +837,7 @@ class HierarchicalGLM(Potential):
 
     kind = "glm"
     parametrisation = "centred"
+    pointwise = _pointwise
 
     def __init__(self, X, y, family="logistic", groups=None, log_scale_prior=(0.0, 1.0), prior_precision=1.0,
                  prior_mean=None, weights=None, offset=None, trials=None, dtype="float64", device=None,

@@ -48,12 +48,19 @@ with the group scales held at their true values -- the parent kernel at the same
 the prior -- all four alternating in one process, at (M = 256, D = 13, J = 2, N = 65 536) and (M = 16 384, D = 59, J = 4, N = 16
 384): 16 and 64 rows with theta the last.  It writes profiles/glm_hier_dispersion_bench.json (HIER_DISP_SHAPES).
 
+--model pointwise times pbbi_pointwise_glm (csrc/kernels_glm_pointwise.hip: lse, mean, variance of the pointwise
+log-likelihood and the mean fitted mean of all M observations over S x N draws) on the plain logistic model against the
+same four vectors from torch ops on the same device (chunked matmul, the link elementwise, logsumexp / mean / var over the
+draws: pointwise_torch), alternating in one process, at the two shapes of SHAPES with --slabs 8 slabs of N draws.  It
+writes profiles/glm_pointwise_bench.json.
+
 usage: tools/bench_glm.py [--shape small|large|all] [--K 32] [--repeats 5] [--glm-only] [--out FILE]
        tools/bench_glm.py --model rich [--custom] [--label NAME] [--shape ...]
        tools/bench_glm.py --model softmax [--shape k3|k8|k8large|all]
        tools/bench_glm.py --model dispersion [--shape small|large|all]
        tools/bench_glm.py --model hierq [--shape small|large|all]
        tools/bench_glm.py --model hierdisp [--shape small|large|all]
+       tools/bench_glm.py --model pointwise [--shape small|large|all] [--slabs 8] [--repeats 5]
        tools/bench_glm.py --model hier [--parametrisation centred|noncentred] [--shape small|large|all]  (noncentred: also mid)
 """
 import argparse
@@ -862,6 +869,69 @@ class Runner:
         return time.perf_counter() - t0
 
 
+def pointwise_torch(X, y, sdn, chunk):
+    """The baseline of --model pointwise: the same four (M,) vectors from torch ops on the same device -- matmul over chunks
+    of `chunk` draws (an M x chunk matrix at a time), the logistic link elementwise, logsumexp / mean / var over the draws
+    of a chunk, the chunks merged at the end (Chan's formula on the (chunks, M) stacks; every chunk has as many draws)."""
+    S, D, N = sdn.shape
+    parts = []
+    for s in range(S):
+        for n0 in range(0, N, chunk):
+            eta = X @ sdn[s, :, n0:n0 + chunk]
+            ll = y[:, None] * eta - torch.nn.functional.softplus(eta)
+            parts.append((torch.logsumexp(ll, dim=1), ll.mean(dim=1), ll.var(dim=1, unbiased=False) * ll.shape[1],
+                          torch.sigmoid(eta).mean(dim=1)))
+    n = min(chunk, N)
+    lse, mean, m2, mu = (torch.stack(v) for v in zip(*parts))
+    grand = mean.mean(dim=0)
+    M2 = m2.sum(dim=0) + n * ((mean - grand) ** 2).sum(dim=0)
+    return torch.logsumexp(lse, dim=0), grand, M2 / (len(parts) * n - 1), mu.mean(dim=0)
+
+
+def bench_pointwise(name, M, D, N, S, repeats, warm):
+    """pbbi_pointwise_glm against pointwise_torch on S slabs of N draws of the plain logistic model, alternating in one
+    process; both sides produce lse, mean, var and mu of all M observations over all S * N draws."""
+    from physicsbasedbayesianinference_amd import _device
+    X, y, w, rs = problem(M, D)
+    pot = P.GLM(X, y)
+    sdn = torch.from_numpy(np.ascontiguousarray(w[None, :, None] + 0.3 * rs.standard_normal((S, D, N)))).to("cuda:0")
+    Xd, yd = torch.from_numpy(X).to("cuda:0"), torch.from_numpy(y).to("cuda:0")
+    chunk = N
+    while M * chunk > 2 ** 25 and chunk % 2 == 0:     # an M x chunk matrix of at most 256 MiB (N is a power of two)
+        chunk //= 2
+    out = torch.empty((4, M), dtype=torch.float64, device="cuda:0")
+    st = _device.stream_ptr(0)
+
+    def kernel():
+        _lib.call("pbbi_pointwise_glm", pot.handle, sdn.data_ptr(), S, D, N, 0, out[0].data_ptr(), out[1].data_ptr(),
+                  out[2].data_ptr(), out[3].data_ptr(), st)
+        return out
+
+    def baseline():
+        return pointwise_torch(Xd, yd, sdn, chunk)
+
+    sides = {"kernel": kernel, "torch": baseline}
+    for _ in range(warm):
+        got = [torch.stack(list(f())).cpu().numpy() for f in sides.values()]
+    agree = float(np.max(np.abs(got[0] - got[1]) / np.maximum(1.0, np.abs(got[1]))))
+    series = {k: [] for k in sides}
+    for i in range(repeats):
+        for k, f in sides.items():   # alternating
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            series[k].append(time.perf_counter() - t0)
+            print(f"# {name} repeat {i} {k}: {series[k][-1]:.5f} s", flush=True)
+    tk, tt = np.array(series["kernel"]), np.array(series["torch"])
+    DP, T = glm.padded_dim(D), S * N
+    return dict(shape=name, M=M, D=D, DP=DP, slabs=S, chains=N, draws=T, torch_chunk=chunk, kernel_seconds=series["kernel"],
+                torch_seconds=series["torch"], kernel_values_per_s=float(M * T / np.median(tk)),
+                kernel_executed_tflops=float(2.0 * M * DP * T / np.median(tk) / 1e12),
+                ratio_median=float(np.median(tt) / np.median(tk)), ratio_worst_case=float(tt.min() / tk.max()),
+                max_rel_difference_kernel_vs_torch=agree)
+
+
 def bench_shape(name, M, D, N, h, L, K, repeats, warm, glm_only):
     X, y, w, rs = problem(M, D)
     q0 = np.ascontiguousarray(w[:, None] + 0.3 * rs.standard_normal((D, N)))
@@ -904,13 +974,33 @@ if __name__ == "__main__":
     ap.add_argument("--repeats", type=int, default=None, help="default 5 (--model softmax: per shape)")
     ap.add_argument("--warmup", type=int, default=None, help="default 4 (--model softmax: per shape)")
     ap.add_argument("--glm-only", action="store_true")
-    ap.add_argument("--model", default="plain", choices=["plain", "rich", "softmax", "dispersion", "hier", "hierq", "hierdisp"])
+    ap.add_argument("--model", default="plain", choices=["plain", "rich", "softmax", "dispersion", "hier", "hierq", "hierdisp",
+                                                         "pointwise"])
+    ap.add_argument("--slabs", type=int, default=8, help="--model pointwise: slabs of N draws")
     ap.add_argument("--parametrisation", default="centred", choices=["centred", "noncentred"],
                     help="--model hier: noncentred times the non-centred kernel against the centred one and the plugin")
     ap.add_argument("--custom", action="store_true", help="--model rich: also the full model as a CustomPotential")
     ap.add_argument("--label", default="rich_vs_plain", help="--model rich: key of the record in the output file")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.model == "pointwise":
+        a.out = a.out or os.path.join(ROOT, "profiles", "glm_pointwise_bench.json")
+        names = list(SHAPES) if a.shape == "all" else [a.shape]
+        results = []
+        if os.path.exists(a.out) and a.shape != "all":   # one shape per call: keep the other's record
+            with open(a.out) as f:
+                results = [r for r in json.load(f)["results"] if r["shape"] not in names]
+        for n in names:
+            sh = SHAPES[n]
+            res = bench_pointwise(n, sh["M"], sh["D"], sh["N"], a.slabs, 5 if a.repeats is None else a.repeats,
+                                  2 if a.warmup is None else a.warmup)
+            print(json.dumps(res))
+            results.append(res)
+            with open(a.out, "w") as f:
+                json.dump(dict(device=_lib.device_info(0)["name"], peak_fp64_mfma_flops=PEAK_F64_MFMA,
+                               results=sorted(results, key=lambda r: r["shape"], reverse=True)), f, indent=1)
+                f.write("\n")
+        sys.exit(0)
     if a.model in ("softmax", "dispersion", "hier", "hierq", "hierdisp"):
         table, fn, side = {"softmax": (SOFTMAX_SHAPES, bench_softmax, "softmax"),
                            "dispersion": (DISPERSION_SHAPES, bench_dispersion, "dispersion"),
