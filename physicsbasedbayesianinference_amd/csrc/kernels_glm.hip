@@ -105,6 +105,8 @@
 #include "kernels_dense_dev.h"
 #include "pbbi_chain.h"
 
+int glm_launch_metric(const pbbi_potential* pot, const void* glm_prm, hipStream_t stream);  // glm_prm: a GlmPrm of this file
+
 namespace {
 
 struct GlmPrm {
@@ -163,6 +165,13 @@ struct GlmArgs {
 };
 template <int FAM>
 struct GlmArgs<FAM, true, GLM_HIER_NONE> { using type = std::conditional_t<glm_disp(FAM), GlmPrmDisp, GlmPrmRich>; };
+// the diagonal metric's kernel arguments (METRIC = true of k_glm): the arguments of the same kernel without one, plus the table
+template <class Prm>
+struct GlmPrmMetric : Prm {
+    const double* metric;  // {m_d, 1 / m_d} of each of the DP rows, {1, 1} past D (glm_pack_metric, glm_host.cpp)
+};
+template <int FAM, bool RICH, int HIER, bool METRIC>
+using GlmKernelArgs = std::conditional_t<METRIC, GlmPrmMetric<typename GlmArgs<FAM, RICH, HIER>::type>, typename GlmArgs<FAM, RICH, HIER>::type>;
 enum { GLM_HMC = 0, GLM_INTEGRATE = 1, GLM_EVAL = 2, GLM_ENERGY = 3, GLM_RATIO = 4 };
 
 template <int NT>
@@ -422,8 +431,16 @@ constexpr int glm_waves_per_simd(int NT, int fam, int hier) {
 }
 // TWIN: k_glm_softmax of kernels_glm_softmax.hip restates this frame (ghost waves and ragged tail, momentum first, the
 // kick / drift schedule of the evaluation loop, the five modes, the accept epilogue).  A fix to either belongs in both.
-template <int NT, int FAM, bool RICH, int HIER = GLM_HIER_NONE>
-__global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_glm(typename GlmArgs<FAM, RICH, HIER>::type prm) {
+//
+// The diagonal metric (METRIC = true; a handle that carries one, pbbi_potential_set_metric_diag): row d of chain n has mass
+// m_n m_d.  The table {m_d, 1 / m_d} sits in LDS for the launch (mlds, DP entries of 16 bytes beside plds, loaded once before
+// the first barrier; entry 4s + g is register s of the lane, the indexing of the {lam, mu} reads) and is read where it is
+// used -- KS more values per lane in registers would cost the DP = 64 and 128 kernels theirs.  It enters the draw (p = z sqrt(m_n
+// m_d kT)), the velocity (v = p / (m_n m_d)), the kick (ck / m_d), p = v m_n m_d at the end and both kinetic energies (sum p^2 /
+// m_d, then / m_n); the drift, the gradient and U never see it.  Every one of these is today's operation with one more factor, so
+// a table of ones multiplies by exactly 1.0 and the run is today's bit for bit.  METRIC = false: nothing of it is compiled.
+template <int NT, int FAM, bool RICH, int HIER = GLM_HIER_NONE, bool METRIC = false>
+__global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_glm(GlmKernelArgs<FAM, RICH, HIER, METRIC> prm) {
     static_assert(RICH || !glm_disp(FAM), "the dispersion families live on the full model's frame");
     static_assert(HIER == GLM_HIER_NONE || RICH, "the hierarchical prior lives on the full model's frame");
     static_assert(HIER != GLM_HIER_Q || !glm_disp(FAM), "structured group priors: logistic and poisson only");
@@ -434,7 +451,10 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
     __shared__ double ylds[(RICH ? 3 : 1) * C::CB * 16];
     constexpr bool HAS_NJ = HIER == GLM_HIER_CENTRED || HIER == GLM_HIER_Q;
     // RICH: {lam, mu} of each row (else unused); centred HIER: then {n_j, 0}; HIER_Q: then the penalty's fragments (8 DP^2 bytes)
-    __shared__ __attribute__((aligned(16))) v2f64 plds[RICH ? DP + (HAS_NJ ? 4 : 0) + (HIER == GLM_HIER_Q ? DP * DP / 2 : 0) : 1];
+    // METRIC: behind all of that the metric's table {m_d, 1 / m_d}, DP entries (mlds below) -- one array, so that a kernel without
+    // a metric declares exactly what it always has
+    constexpr int PL = RICH ? DP + (HAS_NJ ? 4 : 0) + (HIER == GLM_HIER_Q ? DP * DP / 2 : 0) : 0;
+    __shared__ __attribute__((aligned(16))) v2f64 plds[PL + (METRIC ? DP : 0) > 0 ? PL + (METRIC ? DP : 0) : 1];
     if constexpr (RICH) {
         for (int i = threadIdx.x; i < DP; i += BLOCK) plds[i] = v2f64{prm.prior[i], prm.prior[DP + i]};
         if constexpr (HAS_NJ)
@@ -443,6 +463,12 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
             const v2f64* __restrict__ qsrc = reinterpret_cast<const v2f64*>(prm.qimg);
             for (int i = threadIdx.x; i < DP * DP / 2; i += BLOCK) plds[DP + 4 + i] = qsrc[i];
         }
+        if constexpr (!METRIC) __syncthreads();
+    }
+    [[maybe_unused]] v2f64* const mlds = plds + PL;
+    if constexpr (METRIC) {
+        const v2f64* __restrict__ msrc = reinterpret_cast<const v2f64*>(prm.metric);
+        for (int i = threadIdx.x; i < DP; i += BLOCK) mlds[i] = msrc[i];
         __syncthreads();
     }
     const int lane = threadIdx.x & 63;
@@ -489,7 +515,14 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
             rng_normal4d(prm.seed, PBBI_STREAM_MOMENTUM, prm.iter, chain, (uint32_t)((k << 2) | g),
                          (prm.flags & PBBI_DRAW_F64) != 0, z);
 #pragma unroll
-            for (int sl = 0; sl < 4; ++sl) vh[4 * k + sl] = (16 * k + 4 * sl + g < D) ? z[sl] * pstd : 0.0;
+            for (int sl = 0; sl < 4; ++sl) {
+                if constexpr (METRIC) {
+                    const double pstd_d = sqrt((m * mlds[4 * (4 * k + sl) + g].x) * prm.kT);
+                    vh[4 * k + sl] = (16 * k + 4 * sl + g < D) ? z[sl] * pstd_d : 0.0;
+                } else {
+                    vh[4 * k + sl] = (16 * k + 4 * sl + g < D) ? z[sl] * pstd : 0.0;
+                }
+            }
         }
         u = rng_uniform(prm.seed, prm.iter, chain);
         if (have_pout && !(prm.flags & PBBI_COMPAT_P_FROM_OLDQ) && valid) {
@@ -509,10 +542,19 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
     for (int s = 0; s < KS; ++s) q[s] = load_row(qin, vin, s4in, s);
     double pp_old = 0.0;
 #pragma unroll
-    for (int s = 0; s < KS; ++s) pp_old = fma(vh[s], vh[s], pp_old);
+    for (int s = 0; s < KS; ++s) {
+        if constexpr (METRIC) pp_old = fma(vh[s] * mlds[4 * s + g].y, vh[s], pp_old);  // sum_d p_d^2 / m_d
+        else pp_old = fma(vh[s], vh[s], pp_old);
+    }
+    // (the sum is FORMED here: left to the compiler it is sunk to the accept test, and the drawn momenta and the table's
+    //  entries stay in registers across the whole trajectory -- 388 bytes of scratch at DP = 128)
+    if constexpr (METRIC) pp_old = vgpr_fresh(pp_old);
     if (traj) {
 #pragma unroll
-        for (int s = 0; s < KS; ++s) vh[s] *= minv;  // v = p/m
+        for (int s = 0; s < KS; ++s) {
+            if constexpr (METRIC) vh[s] *= minv * mlds[4 * s + g].y;  // v = p / (m_n m_d)
+            else vh[s] *= minv;  // v = p/m
+        }
     }
 
     // ---- the trajectory as a list of gradient evaluations, each followed by a kick of ck and a drift of hd:
@@ -762,6 +804,10 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
         // an evaluation for U alone is followed by no update (a product 0 * inf would turn an overflowed
         // gradient, whose energy rejects the proposal, into a NaN momentum)
         if (!(traj && (sv ? e <= L : L >= 1))) continue;
+        // METRIC: the table is READ here, through a copy of the lane's index the compiler cannot see through -- the values
+        // read for the velocity above would otherwise stay in registers across the gradient
+        [[maybe_unused]] int gm = g;
+        if constexpr (METRIC) gm = vgpr_fresh(g);
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -783,7 +829,8 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
                 } else {
                     gt = fma(lam, q[s], gacc[t][r]);
                 }
-                vh[s] = fma(-gt, ck, vh[s]);
+                if constexpr (METRIC) vh[s] = fma(-gt, ck * mlds[4 * s + gm].y, vh[s]);  // (ck != 0 here: no 0 * inf)
+                else vh[s] = fma(-gt, ck, vh[s]);
                 q[s] = fma(vh[s], hd, q[s]);
             }
     }
@@ -835,7 +882,8 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
                 store_row(qout, vout, s4out, s, q[s]);
-                store_row(pout, vout, s4out, s, prm.mass ? vh[s] * m : vh[s]);
+                if constexpr (METRIC) store_row(pout, vout, s4out, s, (prm.mass ? vh[s] * m : vh[s]) * mlds[4 * s + vgpr_fresh(g)].x);
+                else store_row(pout, vout, s4out, s, prm.mass ? vh[s] * m : vh[s]);
             }
             if (prm.v_out) {
                 const __amdgpu_buffer_rsrc_t vo = rows_of<false>(prm.v_out, n0, D, prm.ldn_out, prm.N);
@@ -848,10 +896,18 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
 
     // ---- energies, ratio, decision (src/HMC.py:109-115,166-173)
     double pp_new = 0.0;
+    [[maybe_unused]] int ge = g;
+    if constexpr (METRIC) ge = vgpr_fresh(g);  // (read again, as at the kick)
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
         if (prm.mass) vh[s] *= m;  // p = v*m; vh now holds p
-        pp_new = fma(vh[s], vh[s], pp_new);
+        if constexpr (METRIC) {
+            const v2f64 md = mlds[4 * s + ge];
+            vh[s] *= md.x;  // p = v m_n m_d
+            pp_new = fma(vh[s] * md.y, vh[s], pp_new);
+        } else {
+            pp_new = fma(vh[s], vh[s], pp_new);
+        }
     }
     const double oldH = 0.5 * chain_sum(pp_old) / m + U_old;
     const double newH = 0.5 * chain_sum(pp_new) / m + U_new;
@@ -929,14 +985,24 @@ Prm glm_prm_hier(const pbbi_potential* pot, const GlmPrm& prm) {
 
 // One case per variant of handle (glm_host.h), each building the one argument struct its kernels take.  A variant, family or
 // padded dimension with no shipped kernel launches nothing and is PBBI_ERR_UNSUPPORTED.
-int glm_launch(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t stream) {
+template <bool GLM_METRIC_PASS>
+int glm_launch_pass(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t stream) {
     const dim3 grid((unsigned)((prm.N + CHAINS_PER_WG - 1) / CHAINS_PER_WG)), block(BLOCK);
     const int NT = pot->glm_DP / 16, fam = pot->glm_family;
     bool done = false;
+// a handle without a metric launches the kernel it always has; one with a metric the METRIC twin of the same case, which
+// takes the same arguments plus the table
 #define GLM_CASE(NT_, FAM_, RICH_, HIER_, PRM_)                                                             \
     if (NT == NT_ && fam == FAM_) {                                                                         \
-        hipLaunchKernelGGL((k_glm<NT_, FAM_, RICH_, HIER_>), grid, block, 0, stream, PRM_);                 \
-        done = true;                                                                                        \
+        if constexpr (!GLM_METRIC_PASS) {                                                                   \
+            hipLaunchKernelGGL((k_glm<NT_, FAM_, RICH_, HIER_>), grid, block, 0, stream, PRM_);             \
+        } else if constexpr (16 * NT_ <= glm_metric_max_rows(FAM_, RICH_, HIER_)) {                         \
+            GlmPrmMetric<std::decay_t<decltype(PRM_)>> am{};                                                \
+            static_cast<std::decay_t<decltype(PRM_)>&>(am) = PRM_;                                          \
+            am.metric = (const double*)pot->d_glm_metric;                                                   \
+            hipLaunchKernelGGL((k_glm<NT_, FAM_, RICH_, HIER_, true>), grid, block, 0, stream, am);         \
+        }                                                                                                   \
+        done = !GLM_METRIC_PASS || 16 * NT_ <= glm_metric_max_rows(FAM_, RICH_, HIER_);                     \
     }
 // (K_ is the case list's kernel of the variant in hand.  The lists keep the order they have always had: it is the order in which
 // the kernels are instantiated and laid out in the code object.)
@@ -1003,6 +1069,12 @@ int glm_launch(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t stream)
     PBBI_HIP(hipGetLastError());
     return PBBI_OK;
 }
+#ifndef PBBI_GLM_METRIC_TU
+// the existing case lists here, the METRIC lists in a translation unit of their own (kernels_glm_metric.hip, see the end)
+int glm_launch(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t stream) {
+    if (!pot->d_glm_metric) return glm_launch_pass<false>(pot, prm, stream);
+    return glm_launch_metric(pot, &prm, stream);
+}
 
 template <class Args>
 int glm_run(const Args& a, int mode) {
@@ -1012,7 +1084,19 @@ int glm_run(const Args& a, int mode) {
     return glm_launch(a.pot, prm, a.stream);
 }
 
+#endif  // !PBBI_GLM_METRIC_TU
+
 }  // namespace
+
+// The METRIC instantiations are compiled from this same file as a second translation unit (kernels_glm_metric.hip defines
+// PBBI_GLM_METRIC_TU and includes it): with both lists in one module the compiler lays the kernels without a metric out
+// differently -- 15 of the 53 move by a register or two although their code is the same text -- and the kernels of a handle
+// without a metric must stay what they are.  That unit holds the METRIC case lists and this entry, nothing else.
+#ifdef PBBI_GLM_METRIC_TU
+int glm_launch_metric(const pbbi_potential* pot, const void* glm_prm, hipStream_t stream) {
+    return glm_launch_pass<true>(pot, *static_cast<const GlmPrm*>(glm_prm), stream);
+}
+#else
 
 int glm_hmc_iter(const IterArgs& a) {
     if (int rc = glm_check(a.pot, a.ldn_in > a.ldn_out ? a.ldn_in : a.ldn_out)) return rc;
@@ -1031,3 +1115,4 @@ int glm_energy(const EvalArgs& a) {
     if (int rc = glm_check(a.pot, a.ldn)) return rc;
     return glm_run(a, a.ratio_finish ? GLM_RATIO : GLM_ENERGY);
 }
+#endif  // PBBI_GLM_METRIC_TU

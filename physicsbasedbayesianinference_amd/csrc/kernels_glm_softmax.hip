@@ -29,10 +29,13 @@
 //
 // An observation >= M is masked out of the residual and of the energy (softmax(0) = 1 / K, log K).
 #include <cmath>
+#include <type_traits>
 
 #include "glm_args.h"
 #include "kernels_dense_dev.h"
 #include "pbbi_chain.h"
+
+int glm_softmax_launch_metric(const pbbi_potential* pot, const void* smx_prm, hipStream_t stream);  // smx_prm: a SmxPrm of this file
 
 namespace {
 
@@ -56,6 +59,10 @@ struct SmxPrm {
     double h, kT;
     int L, D, flags, rng, mode, method, nb;  // D: coefficients per class
     uint64_t seed, iter, chain0;
+};
+// the diagonal metric's kernel arguments (METRIC = true of k_glm_softmax): the same arguments plus the table
+struct SmxPrmMetric : SmxPrm {
+    const double* metric;  // {m, 1 / m} of each INTERNAL row (class k padded to Dc rows; {1, 1} on padding), K Dc entries or more
 };
 enum { SMX_HMC = 0, SMX_INTEGRATE = 1, SMX_EVAL = 2, SMX_ENERGY = 3, SMX_RATIO = 4 };
 
@@ -185,8 +192,13 @@ __device__ __forceinline__ void smx_grad(const SmxPrm& prm, v2f64* __restrict__ 
 // TWIN: the frame below (ghost waves and ragged tail, momentum first, the kick / drift schedule of the evaluation loop,
 // the five modes, the accept epilogue) restates k_glm of kernels_glm.hip, which must keep compiling to what it compiles
 // to.  A fix to either frame belongs in both.
-template <int NTc, int K>
-__global__ void __launch_bounds__(BLOCK, NTc * K <= 2 ? 2 : 1) k_glm_softmax(SmxPrm prm) {
+//
+// The diagonal metric (METRIC = true) is k_glm's, statement for statement: the table {m, 1 / m} in LDS for the launch (mlds, one
+// 16-byte entry per INTERNAL row, loaded once before the first barrier; entry 4s + g is register s of the lane), read where it is
+// used, one more factor in the draw, the velocity, the kick, p = v m and both kinetic energies.  A table of ones multiplies by
+// exactly 1.0.  METRIC = false: nothing of it is compiled.
+template <int NTc, int K, bool METRIC = false>
+__global__ void __launch_bounds__(BLOCK, NTc * K <= 2 ? 2 : 1) k_glm_softmax(std::conditional_t<METRIC, SmxPrmMetric, SmxPrm> prm) {
     using C = SmxCfg<NTc>;
     constexpr int NT = NTc * K;
     constexpr int KS = 4 * NT;
@@ -195,8 +207,14 @@ __global__ void __launch_bounds__(BLOCK, NTc * K <= 2 ? 2 : 1) k_glm_softmax(Smx
     static_assert(K >= 2 && K <= 8 && NT <= 8, "2 <= K <= 8 classes of Dc = 16, 32 or 64 rows, K * Dc <= 128");
     __shared__ __attribute__((aligned(16))) v2f64 lds[C::CHV];
     __shared__ double ylds[C::CB * 16];
-    __shared__ double plds[Dc];  // lam of each row of a class, zero past D
+    // lam of each row of a class, zero past D; METRIC: behind it the metric's table, one 16-byte entry per internal row (mlds below)
+    __shared__ __attribute__((aligned(METRIC ? 16 : 8))) double plds[Dc + (METRIC ? 32 * NTc * K : 0)];
     for (int i = threadIdx.x; i < Dc; i += BLOCK) plds[i] = prm.prior[i];
+    [[maybe_unused]] v2f64* const mlds = reinterpret_cast<v2f64*>(plds + Dc);  // (Dc doubles: a multiple of 16 bytes)
+    if constexpr (METRIC) {
+        const v2f64* __restrict__ msrc = reinterpret_cast<const v2f64*>(prm.metric);
+        for (int i = threadIdx.x; i < 16 * NTc * K; i += BLOCK) mlds[i] = msrc[i];
+    }
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -265,7 +283,12 @@ __global__ void __launch_bounds__(BLOCK, NTc * K <= 2 ? 2 : 1) k_glm_softmax(Smx
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const double ze = j == 0 ? z[e] : j == 1 ? z[e + 1] : j == 2 ? z[e + 2] : z[e + 3];
-                vh[4 * t + e] = (16 * tc + 4 * e + g < D) ? ze * pstd : 0.0;
+                if constexpr (METRIC) {
+                    const double pstd_d = sqrt((m * mlds[4 * (4 * t + e) + g].x) * prm.kT);
+                    vh[4 * t + e] = (16 * tc + 4 * e + g < D) ? ze * pstd_d : 0.0;
+                } else {
+                    vh[4 * t + e] = (16 * tc + 4 * e + g < D) ? ze * pstd : 0.0;
+                }
             }
         }
         u = rng_uniform(prm.seed, prm.iter, chain);
@@ -286,10 +309,19 @@ __global__ void __launch_bounds__(BLOCK, NTc * K <= 2 ? 2 : 1) k_glm_softmax(Smx
     for (int s = 0; s < KS; ++s) q[s] = smx_load<NTc>(qin, vin, v0, ld_in, s, g, D);
     double pp_old = 0.0;
 #pragma unroll
-    for (int s = 0; s < KS; ++s) pp_old = fma(vh[s], vh[s], pp_old);
+    for (int s = 0; s < KS; ++s) {
+        if constexpr (METRIC) pp_old = fma(vh[s] * mlds[4 * s + g].y, vh[s], pp_old);  // sum_d p_d^2 / m_d
+        else pp_old = fma(vh[s], vh[s], pp_old);
+    }
+    // (the sum is FORMED here: left to the compiler it is sunk to the accept test, and the drawn momenta and the table's
+    //  entries stay in registers across the whole trajectory -- 388 bytes of scratch at DP = 128)
+    if constexpr (METRIC) pp_old = vgpr_fresh(pp_old);
     if (traj) {
 #pragma unroll
-        for (int s = 0; s < KS; ++s) vh[s] *= minv;  // v = p/m
+        for (int s = 0; s < KS; ++s) {
+            if constexpr (METRIC) vh[s] *= minv * mlds[4 * s + g].y;  // v = p / (m_n m_d)
+            else vh[s] *= minv;  // v = p/m
+        }
     }
 
     // ---- the trajectory as a list of gradient evaluations, each followed by a kick of ck and a drift of hd:
@@ -327,13 +359,18 @@ __global__ void __launch_bounds__(BLOCK, NTc * K <= 2 ? 2 : 1) k_glm_softmax(Smx
         // an evaluation for U alone is followed by no update (a product 0 * inf would turn an overflowed
         // gradient, whose energy rejects the proposal, into a NaN momentum)
         if (!(traj && (sv ? e <= L : L >= 1))) continue;
+        // METRIC: the table is READ here, through a copy of the lane's index the compiler cannot see through -- the values
+        // read for the velocity above would otherwise stay in registers across the gradient
+        [[maybe_unused]] int gm = g;
+        if constexpr (METRIC) gm = vgpr_fresh(g);
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int s = 4 * t + r;
                 const double gt = fma(plds[4 * (s % KSc) + g], q[s], gacc[t][r]);
-                vh[s] = fma(-gt, ck, vh[s]);
+                if constexpr (METRIC) vh[s] = fma(-gt, ck * mlds[4 * s + gm].y, vh[s]);  // (ck != 0 here: no 0 * inf)
+                else vh[s] = fma(-gt, ck, vh[s]);
                 q[s] = fma(vh[s], hd, q[s]);
             }
     }
@@ -369,7 +406,8 @@ __global__ void __launch_bounds__(BLOCK, NTc * K <= 2 ? 2 : 1) k_glm_softmax(Smx
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
                 smx_store<NTc>(qout, vout, ld_out, s, g, D, q[s]);
-                smx_store<NTc>(pout, vout, ld_out, s, g, D, prm.mass ? vh[s] * m : vh[s]);
+                if constexpr (METRIC) smx_store<NTc>(pout, vout, ld_out, s, g, D, (prm.mass ? vh[s] * m : vh[s]) * mlds[4 * s + vgpr_fresh(g)].x);
+                else smx_store<NTc>(pout, vout, ld_out, s, g, D, prm.mass ? vh[s] * m : vh[s]);
             }
             if (prm.v_out) {
                 const __amdgpu_buffer_rsrc_t vo = rows_of<false>(prm.v_out, n0, K * D, prm.ldn_out, prm.N);
@@ -382,10 +420,18 @@ __global__ void __launch_bounds__(BLOCK, NTc * K <= 2 ? 2 : 1) k_glm_softmax(Smx
 
     // ---- energies, ratio, decision (src/HMC.py:109-115,166-173)
     double pp_new = 0.0;
+    [[maybe_unused]] int ge = g;
+    if constexpr (METRIC) ge = vgpr_fresh(g);  // (read again, as at the kick)
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
         if (prm.mass) vh[s] *= m;  // p = v*m; vh now holds p
-        pp_new = fma(vh[s], vh[s], pp_new);
+        if constexpr (METRIC) {
+            const v2f64 md = mlds[4 * s + ge];
+            vh[s] *= md.x;  // p = v m_n m_d
+            pp_new = fma(vh[s] * md.y, vh[s], pp_new);
+        } else {
+            pp_new = fma(vh[s], vh[s], pp_new);
+        }
     }
     const double oldH = 0.5 * chain_sum(pp_old) / m + U_old;
     const double newH = 0.5 * chain_sum(pp_new) / m + U_new;
@@ -442,14 +488,20 @@ SmxPrm smx_prm(const pbbi_potential* pot) {
     return prm;
 }
 
-int smx_launch(const pbbi_potential* pot, const SmxPrm& prm, hipStream_t stream) {
+template <bool METRIC>
+int smx_launch_pass(const pbbi_potential* pot, const SmxPrm& prm0, hipStream_t stream) {
+    std::conditional_t<METRIC, SmxPrmMetric, SmxPrm> prm{};
+    static_cast<SmxPrm&>(prm) = prm0;
+    if constexpr (METRIC) prm.metric = (const double*)pot->d_glm_metric;
     const dim3 grid((unsigned)((prm.N + CHAINS_PER_WG - 1) / CHAINS_PER_WG)), block(BLOCK);
     const int NTc = pot->glm_DP / 16, K = pot->glm_K;
     bool done = false;
 #define SMX_CASE(NTC_, K_)                                                                 \
     if (NTc == NTC_ && K == K_) {                                                          \
-        hipLaunchKernelGGL((k_glm_softmax<NTC_, K_>), grid, block, 0, stream, prm);        \
-        done = true;                                                                       \
+        if constexpr (!METRIC || glm_softmax_metric_ships(16 * NTC_, K_)) {                \
+            hipLaunchKernelGGL((k_glm_softmax<NTC_, K_, METRIC>), grid, block, 0, stream, prm); \
+            done = true;                                                                   \
+        }                                                                                  \
     }
     SMX_CASE(1, 2) SMX_CASE(1, 3) SMX_CASE(1, 4) SMX_CASE(1, 5) SMX_CASE(1, 6) SMX_CASE(1, 7) SMX_CASE(1, 8)
     SMX_CASE(2, 2) SMX_CASE(2, 3) SMX_CASE(2, 4)
@@ -458,6 +510,13 @@ int smx_launch(const pbbi_potential* pot, const SmxPrm& prm, hipStream_t stream)
     if (!done) return pbbi_fail(PBBI_ERR_UNSUPPORTED, GLM_SOFTMAX_RULE);
     PBBI_HIP(hipGetLastError());
     return PBBI_OK;
+}
+#ifndef PBBI_GLM_METRIC_TU
+// the existing case list here, the METRIC list in a translation unit of its own (kernels_glm_softmax_metric.hip, as for k_glm:
+// kernels_glm.hip says why); a handle without a metric launches the kernel it always has
+int smx_launch(const pbbi_potential* pot, const SmxPrm& prm, hipStream_t stream) {
+    if (!pot->d_glm_metric) return smx_launch_pass<false>(pot, prm, stream);
+    return glm_softmax_launch_metric(pot, &prm, stream);
 }
 
 template <class Args>
@@ -468,7 +527,15 @@ int smx_run(const Args& a, int mode) {
     return smx_launch(a.pot, prm, a.stream);
 }
 
+#endif  // !PBBI_GLM_METRIC_TU
+
 }  // namespace
+
+#ifdef PBBI_GLM_METRIC_TU
+int glm_softmax_launch_metric(const pbbi_potential* pot, const void* smx_prm, hipStream_t stream) {
+    return smx_launch_pass<true>(pot, *static_cast<const SmxPrm*>(smx_prm), stream);
+}
+#else
 
 int glm_softmax_hmc_iter(const IterArgs& a) {
     if (int rc = smx_check(a.pot, a.ldn_in > a.ldn_out ? a.ldn_in : a.ldn_out)) return rc;
@@ -487,3 +554,4 @@ int glm_softmax_energy(const EvalArgs& a) {
     if (int rc = smx_check(a.pot, a.ldn)) return rc;
     return smx_run(a, a.ratio_finish ? SMX_RATIO : SMX_ENERGY);
 }
+#endif  // PBBI_GLM_METRIC_TU

@@ -102,6 +102,7 @@ int new_handle(int kind, int D, int dtype, int device, pbbi_potential** out) {
     p->d_glm_qimg = nullptr;
     for (double& r : p->glm_hier_rank) r = 0.0;
     p->glm_variant = GLM_V_PLAIN;  // (means something on a KIND_GLM handle only, and its builder sets it)
+    p->d_glm_metric = nullptr; p->glm_metric_diag = nullptr;
     *out = p;
     return PBBI_OK;
 }
@@ -1151,13 +1152,78 @@ int pbbi_glm_pack_design(int D, int64_t M, const double* X, double* out, int64_t
     return PBBI_OK;
 }
 
+// The diagonal metric of a GLM handle (include/pbbi.h).  Every rule before the device is touched; the new table is uploaded
+// before the old one is let go, so a failure leaves the handle as it was.
+int pbbi_potential_set_metric_diag(pbbi_potential* pot, const double* mass_diag, int D) {
+    if (!pot) return pbbi_fail(PBBI_ERR_INVALID, "potential handle is NULL");
+    if (pot->kind != KIND_GLM || pot->glm_DP == 0)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "a diagonal metric is served on GLM handles only (the METRIC instantiations of k_glm "
+                                               "and k_glm_softmax)");
+    DeviceGuard guard(pot->device);
+    if (!mass_diag) {
+        if (pot->d_glm_metric) PBBI_HIP(hipFree(pot->d_glm_metric));
+        pot->d_glm_metric = nullptr;
+        delete[] pot->glm_metric_diag;
+        pot->glm_metric_diag = nullptr;
+        return PBBI_OK;
+    }
+    if (D != pot->D)
+        return pbbi_fail(PBBI_ERR_INVALID, "metric: D must equal the handle's state dimension (D = " + std::to_string(D) +
+                                               ", state dimension " + std::to_string(pot->D) + ")");
+    if (int rc = glm_check_metric(D, mass_diag)) return rc;
+    const int top = glm_metric_max_dim(pot->glm_variant, pot->glm_family, pot->glm_hier_nc, pot->glm_DP, pot->glm_K);
+    if (pot->D > top)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "metric: the METRIC kernel of this handle's variant, family and padded dimension is "
+                                               "not shipped -- it does not build without register spills to memory (state "
+                                               "dimension " + std::to_string(pot->D) + ", served up to " + std::to_string(top) + ")");
+    std::vector<double> table;
+    if (pot->glm_variant == GLM_V_SOFTMAX) {
+        // the kernel's rows are the INTERNAL ones (class k padded to Dc rows): internal row k Dc + d is row k D + d of the state
+        const int K = pot->glm_K, Dc = pot->glm_DP, rows = K * Dc;
+        std::vector<int32_t> map((size_t)rows);
+        if (int rc = glm_softmax_layout(pot->D / K, K, nullptr, nullptr, map.data())) return rc;
+        std::vector<double> internal((size_t)rows, 1.0);
+        for (int r = 0; r < rows; ++r)
+            if (map[(size_t)r] >= 0) internal[(size_t)r] = mass_diag[map[(size_t)r]];
+        table.resize((size_t)2 * glm_padded_dim(rows));
+        glm_pack_metric(rows, internal.data(), table.data());
+    } else {
+        table.resize((size_t)2 * pot->glm_DP);  // glm_DP = glm_padded_dim(D)
+        glm_pack_metric(D, mass_diag, table.data());
+    }
+    void* fresh = nullptr;
+    if (int rc = upload(table.data(), table.size(), PBBI_F64, &fresh)) return rc;
+    double* keep = new (std::nothrow) double[(size_t)D];
+    if (!keep) {
+        (void)hipFree(fresh);
+        return pbbi_fail(PBBI_ERR_INVALID, "out of host memory");
+    }
+    std::memcpy(keep, mass_diag, sizeof(double) * (size_t)D);
+    if (pot->d_glm_metric) (void)hipFree(pot->d_glm_metric);
+    delete[] pot->glm_metric_diag;
+    pot->d_glm_metric = fresh;
+    pot->glm_metric_diag = keep;
+    return PBBI_OK;
+}
+
+int pbbi_potential_get_metric_diag(const pbbi_potential* pot, double* out, int out_len, int* has_out) {
+    if (!pot) return pbbi_fail(PBBI_ERR_INVALID, "potential handle is NULL");
+    const bool has = pot->kind == KIND_GLM && pot->glm_metric_diag != nullptr;
+    if (has_out) *has_out = has ? 1 : 0;
+    if (!has || !out) return PBBI_OK;
+    if (out_len < pot->D) return pbbi_fail(PBBI_ERR_INVALID, "out is shorter than the handle's state dimension");
+    std::memcpy(out, pot->glm_metric_diag, sizeof(double) * (size_t)pot->D);
+    return PBBI_OK;
+}
+
 int pbbi_potential_destroy(pbbi_potential* pot) {
     if (!pot) return PBBI_OK;
     DeviceGuard guard(pot->device);
     for (void* p : {pot->d_mean, pot->d_prec, pot->d_frag, pot->d_mean_pad, pot->d_big_PT, pot->d_big_mu,
                     pot->d_sfrag, pot->d_smean, pot->d_params, pot->d_glm_img, pot->d_glm_y, pot->d_glm_obs, pot->d_glm_prior,
-                    pot->d_glm_qimg})
+                    pot->d_glm_qimg, pot->d_glm_metric})
         if (p) (void)hipFree(p);
+    delete[] pot->glm_metric_diag;
     if (pot->plugin) (void)dlclose(pot->plugin);
     delete pot;
     return PBBI_OK;
@@ -1595,6 +1661,9 @@ int pbbi_describe_run(const pbbi_potential* pot, int method, int64_t N, int64_t 
         d = lane_route_name(a);
         fuse = lane_fused_iterations(a);
     }
+    if (pot->kind == KIND_GLM && pot->d_glm_metric)
+        d += "; diagonal metric: row d of chain n has mass m_n m_d, the METRIC instantiation of the kernel with the table {m_d, "
+             "1 / m_d} resident in LDS (draw, kick and kinetic energy)";
     d += "; iterations per launch: up to " + std::to_string(fuse < 1 ? 1 : fuse);
     if (flags & PBBI_DRAW_F64) d += "; momentum draw: double precision";
     snprintf(out, (size_t)out_len, "%s", d.c_str());

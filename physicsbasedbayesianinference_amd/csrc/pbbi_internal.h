@@ -77,6 +77,10 @@ struct pbbi_potential {
     // glm_pack_prior_groups_disp, d_glm_obs = a | y | o
     // which of these kinds of handle this is.  (Appended.)  The one record of it: no other field is asked for the kind.
     int glm_variant;       // GlmVariant (glm_host.h), set by the builder of the create entry
+    // the diagonal metric (pbbi_potential_set_metric_diag).  (Appended.)  NULL / NULL on a handle without one, which launches the
+    // kernels it always has
+    void* d_glm_metric;       // {m_d, 1 / m_d} per row in the kernel's row order (glm_pack_metric; softmax: the internal rows)
+    double* glm_metric_diag;  // the D entries as given, on the host (pbbi_potential_get_metric_diag)
 };
 
 // ---- error plumbing ---------------------------------------------------------

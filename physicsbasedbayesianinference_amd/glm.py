@@ -47,7 +47,7 @@ from .potential import Potential, _dptr
 __all__ = ["GLM", "SoftmaxGLM", "DispersionGLM", "HierarchicalGLM", "HierarchicalDispersionGLM", "HIER_DISP_MAX_DIM",
            "pack_prior_groups_dispersion", "FAMILIES", "DISPERSION_FAMILIES", "HIER_MAX_DIM",
            "HIER_NC_MAX_DIM", "HIER_PARAMETRISATIONS", "HIER_MAX_GROUPS", "pack_design", "pack_observations", "pack_observations_dispersion", "pack_prior_groups",
-           "HIER_Q_MAX_DIM", "pack_penalty", "padded_dim", "softmax_layout", "PointwiseResult", "pointwise_constants"]
+           "HIER_Q_MAX_DIM", "pack_penalty", "pack_metric", "padded_dim", "softmax_layout", "PointwiseResult", "pointwise_constants"]
 
 FAMILIES = {"logistic": _lib.GLM_LOGISTIC, "poisson": _lib.GLM_POISSON}
 DISPERSION_FAMILIES = {"gaussian": _lib.GLM_GAUSSIAN, "negbinomial": _lib.GLM_NEGBINOMIAL}   # DispersionGLM only
@@ -79,6 +79,47 @@ def padded_dim(D):
     if not 1 <= D <= MAX_DIM:
         raise ValueError(f"GLM potentials serve 1 <= D <= {MAX_DIM} (D = {D})")
     return 16 if D <= 16 else 32 if D <= 32 else 64 if D <= 64 else 128
+
+
+def pack_metric(diag):
+    """The table {m_d, 1 / m_d} a GLM handle with a diagonal metric keeps on the device and its kernel in LDS, computed
+    (and checked: every entry finite and > 0) on the host by libpbbi.so (no GPU involved): array (DP, 2), {1, 1} on the
+    padding rows."""
+    m = np.ascontiguousarray(diag, dtype=np.float64)
+    if m.ndim != 1 or m.size < 1:
+        raise ValueError("the metric must be a vector of D >= 1 masses")
+    n = C.c_int64()
+    _lib.call("pbbi_glm_pack_metric", m.size, None, None, 0, C.byref(n))
+    out = np.empty(n.value, dtype=np.float64)
+    _lib.call("pbbi_glm_pack_metric", m.size, _dptr(m), _dptr(out), out.size, C.byref(n))
+    return out.reshape(-1, 2)
+
+
+class _Metric:
+    """The diagonal metric of a GLM handle (pbbi_potential_set_metric_diag): row d of chain n has mass m_n m_d in the draw,
+    the kick and the kinetic energy of every sampler call on this potential.  It lives on the handle, so every sampler
+    that shares the potential shares it."""
+
+    def set_metric(self, diag):
+        """diag: one mass > 0 per row of the state (coefficients, group log-scales, a sampled log-dispersion), or None to
+        remove the metric.  Checked on the host before anything touches the GPU."""
+        if diag is None:
+            _lib.call("pbbi_potential_set_metric_diag", self.handle, None, 0)
+            return
+        m = np.ascontiguousarray(diag, dtype=np.float64)
+        if m.ndim != 1 or m.size != self.numDimensions:
+            raise ValueError(f"the metric must hold one mass per row of the state ({self.numDimensions}), got shape {m.shape}")
+        if not (np.all(np.isfinite(m)) and np.all(m > 0.0)):
+            raise ValueError("every entry of the metric must be finite and > 0")
+        _lib.call("pbbi_potential_set_metric_diag", self.handle, _dptr(m), m.size)
+
+    @property
+    def metric(self):
+        """The metric as set (a copy), or None."""
+        out = np.empty(self.numDimensions, dtype=np.float64)
+        has = C.c_int(0)
+        _lib.call("pbbi_potential_get_metric_diag", self.handle, _dptr(out), out.size, C.byref(has))
+        return out if has.value else None
 
 
 def pack_design(X):
@@ -325,7 +366,7 @@ def _pointwise(self, samples, ranges=0):
     return PointwiseResult(lse - np.log(T) + k, mean + k, var if T >= 2 else np.full(M, np.nan), mu, T)
 
 
-class GLM(Potential):
+class GLM(_Metric, Potential):
     """-log posterior of the weights of a generalised linear model (see the module text).
 
         pot = GLM(X, y, family="logistic", prior_precision=1.0)
@@ -375,7 +416,7 @@ def softmax_layout(D, K):
     return Dc.value, NT.value, row_map
 
 
-class SoftmaxGLM(Potential):
+class SoftmaxGLM(_Metric, Potential):
     """-log posterior of the coefficients of K-class (multinomial logistic / softmax) regression:
 
         U(W) = sum_i [ logsumexp_k(x_i . W_k) - x_i . W_{y_i} ] + 0.5 sum_k sum_d lam_d W_kd^2,   y_i in {0 .. K-1}
@@ -493,7 +534,7 @@ def _dispersion_args(dispersion, log_dispersion_prior):
     return sample, (None if sample else disp), theta, ((m_t, l_t) if sample else None)
 
 
-class DispersionGLM(Potential):
+class DispersionGLM(_Metric, Potential):
     """-log posterior of a GLM whose family has a free dispersion, with theta = log(dispersion):
 
         gaussian     y_i ~ N(eta_i, sigma^2 / a_i), sigma = exp(theta):
@@ -758,7 +799,7 @@ def pack_penalty(penalty, J):
     return out.reshape(DP // 16, DP // 8, 64, 2)
 
 
-class HierarchicalGLM(Potential):
+class HierarchicalGLM(_Metric, Potential):
     """-log posterior of a GLM (family "logistic" or "poisson", the full model of `GLM`: weights a_i, trials n_i,
     offsets o_i, eta_i = x_i . w + o_i) in which blocks of coefficients share a prior scale that is sampled:
 
