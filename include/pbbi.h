@@ -658,6 +658,43 @@ int pbbi_stats_finalize(const double* state, int D, int64_t N, int T, int64_t S_
                         double* var_out, double* cov_out, double* acov_out, double* w_out, double* bvar_out,
                         double* chain_mean_out, double* chain_var_out, void* stream);
 
+/* ---- running histogram: quantiles and marginal shapes of a long run, one chunk resident -------
+ * What no moment yields: per dimension a histogram of `bins` equal bins (PBBI_HIST_MIN_BINS <= bins <=
+ * PBBI_HIST_MAX_BINS), pooled over all chains and all draws, accumulated chunk by chunk from the same (c, D, N) slabs
+ * as the running statistics.  Every accumulated quantity is an integer count or an exact extreme, so the state after
+ * a run is bit-identical however the run was cut into chunks and from run to run.
+ *
+ * State: D * (bins + 8) words of 8 bytes (pbbi_hist_state_len; host only, no device needed).  Six arrays of D words,
+ * then the counts:
+ *     lo (D) | hi (D) | inv = bins / (hi - lo) (D) | min (D) | max (D)      doubles
+ *     nan (D)                                                               unsigned 64-bit: the NaNs, in no bin
+ *     counts (D x (bins + 2))                                               unsigned 64-bit
+ *   min / max run over every non-NaN value seen, infinities included (+inf / -inf while there is none).
+ * The bin of a value x (converted to double first) of dimension d:
+ *     x < lo: bin 0;   x >= hi: bin bins + 1;   else bin 1 + min((int64)floor((x - lo) * inv), bins - 1)
+ *   (so -inf lands in bin 0 and +inf in bin bins + 1; the product is not contracted with anything).
+ *
+ * pbbi_hist_set_range: the explicit range.  lo, hi: HOST arrays of D doubles, lo_d < hi_d, both and their difference
+ *   finite.  Writes the header (inv computed on the host in double) and zeroes the counts and nan, min = +inf, max =
+ *   -inf.  Waits for the stream once (the header leaves a host buffer).
+ * pbbi_hist_accumulate: adds the c draws of slabs_sdn ((c, D, N), fp64 or fp32 by `dtype`) to `state`.  Nothing is
+ *   read back.  auto_range = 0 uses the range in the state.  auto_range = 1 (S_before must be 0) starts the state
+ *   from this chunk on the device, whatever the buffer held: with a_d, b_d the smallest and largest FINITE value of
+ *   the chunk in dimension d (0, 0 if there is none),
+ *       span = b - a;  lo = a - margin * span;  hi = b + margin * span;   if !(hi > lo):  lo = a - 0.5, hi = a + 0.5
+ *   in this order of operations, then zeroes the counts and counts the chunk in the same call.  margin is ignored
+ *   with auto_range = 0.  S_before is only checked (the counts carry no draw index).
+ * There is no finalise entry: the state is read once by the caller, quantiles are host arithmetic on the counts.
+ * PBBI_ERR_INVALID before any launch: D < 1, N < 1, bins out of range, c < 1, S_before < 0, a NULL state, slab or
+ * range pointer, an unknown dtype, lo >= hi or a non-finite bound (or difference), margin < 0 or not finite,
+ * auto_range with S_before > 0. */
+#define PBBI_HIST_MIN_BINS 16
+#define PBBI_HIST_MAX_BINS 4096
+int pbbi_hist_state_len(int D, int bins, int64_t* words_out);
+int pbbi_hist_set_range(void* state, int D, int bins, const double* lo, const double* hi, int device, void* stream);
+int pbbi_hist_accumulate(void* state, int D, int64_t N, int bins, int64_t S_before, const void* slabs_sdn, int c,
+                         int dtype, int auto_range, double margin, int device, void* stream);
+
 /* ---- ensemble weights ----------------------------------------------
  * Normalised canonical weights of an ensemble from its per-chain Hamiltonians (pbbi_energy),
  *     w_n = exp(-beta (H_n - H_min)) / sum_m exp(-beta (H_m - H_min)),

@@ -594,8 +594,10 @@ class HMC:
         advancing.  With spill_dir every chunk is also written as samples_00000.npy, ... in the
         reference's (D, N, c) layout (momenta_XXXXX.npy when momenta=True).  stats (a stats.RunningStats of
         this ensemble's D and N) is fed every chunk before it is yielded: the run's mean, covariance, R-hat and
-        ESS without more than one chunk resident."""
+        ESS without more than one chunk resident.  stats may also be a list or tuple of sinks (RunningStats,
+        stats.RunningHistogram: anything with update), each fed every chunk in turn."""
         import os
+        sinks = () if stats is None else tuple(stats) if isinstance(stats, (list, tuple)) else (stats,)
         pot, ens = self._pot, self.ensemble
         D, N = ens.numDimensions, ens.numParticles
         S, chunk = int(numSamples), max(1, int(chunk))
@@ -625,8 +627,8 @@ class HMC:
             n_rej += float(reject[:c].float().sum().item()) if N else 0.0
             s_view = samples[:c].permute(1, 2, 0)
             m_view = mom[:c].permute(1, 2, 0) if momenta else None
-            if stats is not None:
-                stats.update(samples[:c])
+            for sink in sinks:
+                sink.update(samples[:c])
             if spill_dir is not None:
                 np.save(os.path.join(spill_dir, f"samples_{k:05d}.npy"), self._to_dns(samples[:c]))
                 if momenta:
@@ -636,14 +638,17 @@ class HMC:
             self.acceptRate = 1.0 - n_rej / (done * N) if N else None
             yield s_view, m_view
 
-    def sampleStats(self, numSamples, chunk, temperature, qStd, burn_in=0, max_lag=32, seed=None, chain0=0, iter0=0):
+    def sampleStats(self, numSamples, chunk, temperature, qStd, burn_in=0, max_lag=32, seed=None, chain0=0, iter0=0,
+                    hist=None):
         """A long in-kernel-draw run reduced on the device as it goes: numSamples iterations in chunks of `chunk`
         into ONE reused (chunk, D, N) slab, every chunk accumulated into a stats.RunningStats (max_lag: the largest
         autocovariance lag kept), which is returned -- moments(), covariance(), rhat(), ess() of the whole run
         with one chunk resident.  The draws are those of getSamples(numSamples, rng="philox", burn_in=burn_in) for the
         same seed and counters (burn_in unrecorded iterations first, draw indices iter0 .. iter0+burn_in-1, run
         without a sample slab).  Nothing is read back between chunks: the launches of all chunks are queued one
-        after the other, the reject count is summed on the device and read once at the end into acceptRate."""
+        after the other, the reject count is summed on the device and read once at the end into acceptRate.
+        hist (a stats.RunningHistogram of this ensemble's D and N) is fed every recorded chunk after the statistics,
+        queued in the same way: the run's quantiles and marginals beside its moments."""
         import torch
         pot, ens = self._pot, self.ensemble
         D, N = ens.numDimensions, ens.numParticles
@@ -653,6 +658,11 @@ class HMC:
         seed = self.seed if seed is None else int(seed)
         dev, dt = pot.device, pot.dtype
         stats = RunningStats(D, N, max_lag=max_lag, device=dev)
+        if hist is not None:
+            if (hist.D, hist.N, hist.device) != (D, N, dev):
+                raise ValueError(f"hist is for D={hist.D}, N={hist.N} on device {hist.device}, the run has D={D}, N={N} "
+                                 f"on device {dev}")
+            hist.prepare()                                   # an explicit range is uploaded before anything is queued
         stream = stream_ptr(dev)
         kT = float(boltzmannConst * temperature)
         flags, L, h = self._flags(), self.integrator.numSteps, float(self.stepSize)
@@ -677,6 +687,8 @@ class HMC:
                       samples.data_ptr(), None, reject.data_ptr(), None, N, N, h, L, c, flags, seed, it + done,
                       int(chain0), kT, stream)
             stats.update(samples[:c])
+            if hist is not None:
+                hist.update(samples[:c])
             r = reject[:c].sum(dtype=torch.int64)
             n_rej = r if n_rej is None else n_rej + r
             done += c

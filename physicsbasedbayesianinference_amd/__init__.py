@@ -17,7 +17,7 @@ from .integrator import Integrator, Leapfrog, StormerVerlet
 from .HMC import HMC
 from .custom import CustomPotential
 from .glm import GLM, SoftmaxGLM, DispersionGLM, HierarchicalGLM, HierarchicalDispersionGLM, pack_observations_dispersion, pack_prior_groups
-from .stats import RunningStats
+from .stats import RunningHistogram, RunningStats
 from . import trace
 from .trace import grad, trace_potential
 
@@ -25,5 +25,6 @@ __all__ = ["Ensemble", "HMC", "Integrator", "Leapfrog", "StormerVerlet", "Potent
            "Harmonic", "GaussianDiag", "StandardGaussian", "GaussianDense", "Rosenbrock",
            "harmonicPotentialND", "linear_regression_posterior", "CustomPotential", "GLM", "SoftmaxGLM", "DispersionGLM",
            "HierarchicalGLM", "HierarchicalDispersionGLM", "pack_observations_dispersion", "pack_prior_groups", "RunningStats",
+           "RunningHistogram",
            "trace", "grad", "trace_potential"]
 __version__ = "0.1.0"

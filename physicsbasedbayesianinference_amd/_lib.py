@@ -114,6 +114,10 @@ PROTOTYPES = {
     "pbbi_stats_state_len": [_i, _i64, _i, C.POINTER(C.c_int64)],
     "pbbi_stats_accumulate": [_vp, _i, _i64, _i, _i64, _vp, _i, _i, _i, _vp],
     "pbbi_stats_finalize": [_vp, _i, _i64, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    # running histogram (stats.py RunningHistogram)
+    "pbbi_hist_state_len": [_i, _i, C.POINTER(C.c_int64)],
+    "pbbi_hist_set_range": [_vp, _i, _i, _dp, _dp, _i, _vp],
+    "pbbi_hist_accumulate": [_vp, _i, _i64, _i, _i64, _vp, _i, _i, _i, _d, _i, _vp],
     "pbbi_reduce_min": [_vp, _i64, _i, _i, _vp, _vp],
     "pbbi_canonical_weights": [_vp, _i64, _d, _vp, _i, _i, _vp, _vp, _vp],
     "pbbi_scale_inverse": [_vp, _i64, _vp, _i, _i, _vp],
