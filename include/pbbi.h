@@ -594,13 +594,15 @@ int pbbi_transpose_sdn_to_dns(const void* src_sdn, void* dst_dns, int S, int D, 
  * Per-dimension mean and (biased) variance over all S*N draws of (S, D, N) device slabs,
  * without moving the samples off the GPU: mean_out[d], var_out[d] (D elements each, dtype of
  * the slabs; accumulated in fp64, two deterministic stages, no atomics).  The reference only
- * returns the (D, N, S) array (src/HMC.py:136-183); at C2 scale that is 6.7 GB per 100 draws. */
+ * returns the (D, N, S) array (src/HMC.py:136-183); at C2 scale that is 6.7 GB per 100 draws.
+ * Accuracy: the sums run about each dimension's first value, so with kappa = |mean| / sd the variance is within
+ * (1e-12 + 64 * 2^-53 * kappa) of itself and the mean within 1e-12 * max(|mean|, sd), whatever the offset (floats: + 2^-23). */
 int pbbi_sample_moments(const void* samples_sdn, int S, int D, int64_t N, int dtype, int device,
                         void* mean_out, void* var_out, void* stream);
 
 /* Per-CHAIN mean and unbiased variance over the S draws of each (dim, chain): chain_mean_out and
  * chain_var_out are (D, N) device arrays (stride N) in the slabs' dtype, accumulated in fp64
- * (Welford).  The ingredients of the Gelman-Rubin statistic across the ensemble's chains
+ * (sums about the chain's first draw).  The ingredients of the Gelman-Rubin statistic across the ensemble's chains
  * (HMC.rhat in the Python layer); S >= 2. */
 int pbbi_chain_moments(const void* samples_sdn, int S, int D, int64_t N, int dtype, int device,
                        void* chain_mean_out, void* chain_var_out, void* stream);
@@ -608,8 +610,9 @@ int pbbi_chain_moments(const void* samples_sdn, int S, int D, int64_t N, int dty
 /* Ensemble-averaged autocovariance of the chains' draws at lags 0..T (T <= PBBI_MAX_LAG):
  *   acov_out[t*D + d] = mean_n (1/S) sum_{s < S-t} (x[s,d,n] - m[d,n]) (x[s+t,d,n] - m[d,n]),
  * m = chain_mean (D, N) from pbbi_chain_moments.  acov_out: (T+1, D) DOUBLES on the device (fp64
- * accumulation, deterministic two-stage reduction over the chains).  The ingredient of the effective
- * sample size of the ensemble (HMC.ess in the Python layer). */
+ * accumulation, deterministic two-stage reduction over the chains).  chain_mean is in the slabs' dtype: for float slabs
+ * a first pass takes each chain's mean of x - m in fp64 and the sums are centred on m plus that, not on the rounded m.
+ * The ingredient of the effective sample size of the ensemble (HMC.ess in the Python layer). */
 #define PBBI_MAX_LAG 32
 int pbbi_chain_autocov(const void* samples_sdn, const void* chain_mean, int S, int D, int64_t N, int T,
                        int dtype, int device, double* acov_out, void* stream);

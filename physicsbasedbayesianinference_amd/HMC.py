@@ -946,16 +946,17 @@ class HMC:
         if not sdn.is_contiguous():
             sdn = sdn.contiguous()
         S, D, N = sdn.shape
-        mean = empty((D,), pot.dtype, pot.device)
-        var = empty((D,), pot.dtype, pot.device)
-        _lib.call("pbbi_sample_moments", sdn.data_ptr(), S, D, N, pot._dt, pot.device,
+        code, npdt = self._slab_dtype(sdn)  # the slabs' own type, whatever the potential's
+        mean = empty((D,), npdt, pot.device)
+        var = empty((D,), npdt, pot.device)
+        _lib.call("pbbi_sample_moments", sdn.data_ptr(), S, D, N, code, pot.device,
                   mean.data_ptr(), var.data_ptr(), stream_ptr(pot.device))
         return to_numpy(mean).astype(np.float64), to_numpy(var).astype(np.float64)
 
     def rhat(self, samples_dns):
         """Gelman-Rubin potential scale reduction per dimension, across the ensemble's N chains,
         from the (D, N, S) device view of getSamples(device_output=True) / sampleChunks -- computed
-        on the GPU (per-chain Welford moments, then the ensemble moments of those): with
+        on the GPU (per-chain moments, then the ensemble moments of those): with
         W = mean_n var_s, B/S = var_n mean_s,  R = sqrt(((S-1)/S W + B/S) / W).  Values near 1 say
         the chains agree; the ensemble design makes this the natural convergence check
         (SURVEY 8f row 4).  Returns a float64 array of D values."""
@@ -966,15 +967,18 @@ class HMC:
         S, D, N = sdn.shape
         if S < 2 or N < 2:
             raise ValueError("rhat needs at least 2 draws and 2 chains")
-        cm, cv = empty((1, D, N), pot.dtype, pot.device), empty((1, D, N), pot.dtype, pot.device)
+        code, npdt = self._slab_dtype(sdn)
+        if code == _lib.F32:
+            return self._fp64_state(sdn, 0).rhat()
+        cm, cv = empty((1, D, N), npdt, pot.device), empty((1, D, N), npdt, pot.device)
         stream = stream_ptr(pot.device)
-        _lib.call("pbbi_chain_moments", sdn.data_ptr(), S, D, N, pot._dt, pot.device, cm.data_ptr(),
+        _lib.call("pbbi_chain_moments", sdn.data_ptr(), S, D, N, code, pot.device, cm.data_ptr(),
                   cv.data_ptr(), stream)
-        w = empty((D,), pot.dtype, pot.device)
-        bvar = empty((D,), pot.dtype, pot.device)
-        _lib.call("pbbi_sample_moments", cv.data_ptr(), 1, D, N, pot._dt, pot.device, w.data_ptr(), None,
+        w = empty((D,), npdt, pot.device)
+        bvar = empty((D,), npdt, pot.device)
+        _lib.call("pbbi_sample_moments", cv.data_ptr(), 1, D, N, code, pot.device, w.data_ptr(), None,
                   stream)                                     # W = mean over chains of the chain variances
-        _lib.call("pbbi_sample_moments", cm.data_ptr(), 1, D, N, pot._dt, pot.device, None,
+        _lib.call("pbbi_sample_moments", cm.data_ptr(), 1, D, N, code, pot.device, None,
                   bvar.data_ptr(), stream)                    # biased variance over chains of the chain means
         return rhat_from_moments(to_numpy(w).astype(np.float64), to_numpy(bvar).astype(np.float64), S, N)
 
@@ -989,6 +993,8 @@ class HMC:
             sdn = sdn.contiguous()
         S, D, N = sdn.shape
         code, npdt = self._slab_dtype(sdn)
+        if code == _lib.F32:
+            return self._fp64_state(sdn, 0).covariance()
         stream = stream_ptr(pot.device)
         mean = empty((D,), npdt, pot.device)
         _lib.call("pbbi_sample_moments", sdn.data_ptr(), S, D, N, code, pot.device, mean.data_ptr(), None,
@@ -1017,6 +1023,11 @@ class HMC:
             raise ValueError("ess needs at least 4 draws and 2 chains")
         T = int(min(max_lag, 32, S - 2))
         code, npdt = self._slab_dtype(sdn)
+        if code == _lib.F32:
+            rs = self._fp64_state(sdn, T)
+            ess = rs.ess()
+            self.ess_truncated = rs.ess_truncated
+            return ess
         stream = stream_ptr(pot.device)
         cm, cv = empty((1, D, N), npdt, pot.device), empty((1, D, N), npdt, pot.device)
         _lib.call("pbbi_chain_moments", sdn.data_ptr(), S, D, N, code, pot.device, cm.data_ptr(),
@@ -1040,6 +1051,13 @@ class HMC:
         if sdn.dtype == torch.float32:
             return _lib.F32, np.float32
         raise TypeError("sample slabs must be float64 or float32")
+
+    def _fp64_state(self, sdn, max_lag):
+        """Float slabs as ONE chunk of a RunningStats.  The one-shot kernels hand chain means and the ensemble mean
+        on in the slabs' type; 24 bits of a mean of 1e3 at unit spread cost R-hat, the ESS and the covariance five
+        digits.  The running sink keeps them in its fp64 state ((3 max_lag + 3) D N doubles beside the slabs)."""
+        _, D, N = sdn.shape
+        return RunningStats(D, N, max_lag=max_lag, device=self._pot.device).update(sdn)
 
     def _to_dns(self, sdn):
         """(S, D, N) device slabs -> host (D, N, S) array via the LDS-tiled transpose kernel."""

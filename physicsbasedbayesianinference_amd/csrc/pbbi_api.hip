@@ -463,7 +463,10 @@ __global__ void k_transpose(const T* __restrict__ src, T* __restrict__ dst, int 
     }
 }
 
-// moments stage 1: block (d, chunk) sums x and x^2 over its slice of the S*N draws of row d
+// moments stage 1: block (d, chunk) sums y and y^2 over its slice of the S*N draws of row d, y = x - shift_d with
+// shift_d = the row's first value x[0, d, 0] (every block of the row reads the same one).  Sums of x and x^2 about
+// zero lose (mean / sd)^2 * 2^-53 of the variance -- all of it for a quantity known to nine digits; about a value of
+// the sample the loss is that of a spread of a few sd.  A NaN or an infinity, in the shift too, reaches the outputs.
 template <typename T>
 __global__ void k_moments_partial(const T* __restrict__ x, int S, int D, int64_t N, int chunks,
                                   double* __restrict__ part /* [D][chunks][2] */) {
@@ -471,10 +474,11 @@ __global__ void k_moments_partial(const T* __restrict__ x, int S, int D, int64_t
     const int64_t total = (int64_t)S * N;
     const int64_t per = (total + chunks - 1) / chunks;
     const int64_t lo = (int64_t)ch * per, hi = lo + per < total ? lo + per : total;
+    const double shift = (double)x[(int64_t)d * N];
     double s1 = 0.0, s2 = 0.0;
     for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
         const int64_t sidx = i / N, n = i - sidx * N;
-        const double v = (double)x[(sidx * D + d) * N + n];
+        const double v = (double)x[(sidx * D + d) * N + n] - shift;
         s1 += v;
         s2 += v * v;
     }
@@ -495,9 +499,10 @@ __global__ void k_moments_partial(const T* __restrict__ x, int S, int D, int64_t
     }
 }
 
+// moments stage 2: the chunk partials of row d in chunk order; mean = shift + s1/count, var = s2/count - (s1/count)^2
 template <typename T>
-__global__ void k_moments_final(const double* __restrict__ part, int D, int chunks, double count,
-                                T* mean_out, T* var_out) {
+__global__ void k_moments_final(const double* __restrict__ part, const T* __restrict__ x, int D, int64_t N,
+                                int chunks, double count, T* mean_out, T* var_out) {
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= D) return;
     double s1 = 0.0, s2 = 0.0;
@@ -505,9 +510,9 @@ __global__ void k_moments_final(const double* __restrict__ part, int D, int chun
         s1 += part[((size_t)d * chunks + c) * 2 + 0];
         s2 += part[((size_t)d * chunks + c) * 2 + 1];
     }
-    const double mean = s1 / count;
-    if (mean_out) mean_out[d] = (T)mean;
-    if (var_out) var_out[d] = (T)(s2 / count - mean * mean);
+    const double m1 = s1 / count;  // the mean of y = x - shift, as in k_moments_partial
+    if (mean_out) mean_out[d] = (T)((double)x[(int64_t)d * N] + m1);
+    if (var_out) var_out[d] = (T)(s2 / count - m1 * m1);
 }
 
 // per-(dim, chain) mean and unbiased variance over the S slabs; lanes run along the chain axis
@@ -517,15 +522,19 @@ __global__ void k_chain_moments(const T* __restrict__ x, int S, int D, int64_t N
     const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int d = blockIdx.y;
     if (n >= N) return;
-    double mean = 0.0, m2 = 0.0;
-    for (int s = 0; s < S; ++s) {  // Welford
-        const double v = (double)x[((int64_t)s * D + d) * N + n];
-        const double delta = v - mean;
-        mean += delta / (double)(s + 1);
-        m2 += delta * (v - mean);
+    // sums of y = x - c about the chain's first draw c, as the running sink keeps them (kernels_stats.hip): c is a
+    // value of the data, so no rounded mean of size |mean| ever meets differences of the size of the spread.  (A
+    // running mean does: Welford's M2 of two draws h apart is off by 2^-52 |mean| / h of itself.)
+    const double c = (double)x[(int64_t)d * N + n];
+    double s1 = 0.0, s2 = 0.0;
+    for (int s = 1; s < S; ++s) {
+        const double y = (double)x[((int64_t)s * D + d) * N + n] - c;
+        s1 += y;
+        s2 += y * y;
     }
-    if (mean_out) mean_out[(int64_t)d * N + n] = (T)mean;
-    if (var_out) var_out[(int64_t)d * N + n] = (T)(m2 / (double)(S - 1));
+    const double delta = s1 / (double)S;
+    if (mean_out) mean_out[(int64_t)d * N + n] = (T)(c + delta);
+    if (var_out) var_out[(int64_t)d * N + n] = (T)((s2 - delta * s1) / (double)(S - 1));
 }
 
 // lagged products of one (dim, chain) series through a register window: acc[t] += x_s * x_{s-t}
@@ -539,7 +548,14 @@ __global__ void __launch_bounds__(256) k_chain_autocov(const T* __restrict__ x, 
 #pragma unroll
     for (int t = 0; t < TL; ++t) { acc[t] = 0.0; w[t] = 0.0; }
     if (n < N) {
-        const double m = (double)mean[(int64_t)d * N + n];
+        double m = (double)mean[(int64_t)d * N + n];
+        if constexpr (sizeof(T) < sizeof(double)) {
+            // m is the chain mean rounded to a float: 24 bits of a mean of 1e3 at unit spread leave the lag sums six
+            // digits.  A first pass takes the mean of x - m in fp64 and the sums are centred on m plus that.
+            double s1 = 0.0;
+            for (int s = 0; s < S; ++s) s1 += (double)x[((int64_t)s * D + d) * N + n] - m;
+            m += s1 / (double)S;
+        }
         for (int s = 0; s < S; ++s) {
             const double v = (double)x[((int64_t)s * D + d) * N + n] - m;
 #pragma unroll
@@ -1763,14 +1779,14 @@ int pbbi_sample_moments(const void* samples_sdn, int S, int D, int64_t N, int dt
         hipLaunchKernelGGL(k_moments_partial<double>, grid, block, 0, (hipStream_t)stream,
                            (const double*)samples_sdn, S, D, N, chunks, part);
         hipLaunchKernelGGL(k_moments_final<double>, dim3((D + 63) / 64), dim3(64), 0, (hipStream_t)stream,
-                           (const double*)part, D, chunks, (double)S * (double)N, (double*)mean_out,
-                           (double*)var_out);
+                           (const double*)part, (const double*)samples_sdn, D, N, chunks,
+                           (double)S * (double)N, (double*)mean_out, (double*)var_out);
     } else {
         hipLaunchKernelGGL(k_moments_partial<float>, grid, block, 0, (hipStream_t)stream,
                            (const float*)samples_sdn, S, D, N, chunks, part);
         hipLaunchKernelGGL(k_moments_final<float>, dim3((D + 63) / 64), dim3(64), 0, (hipStream_t)stream,
-                           (const double*)part, D, chunks, (double)S * (double)N, (float*)mean_out,
-                           (float*)var_out);
+                           (const double*)part, (const float*)samples_sdn, D, N, chunks,
+                           (double)S * (double)N, (float*)mean_out, (float*)var_out);
     }
     PBBI_HIP(hipGetLastError());
     PBBI_HIP(hipFreeAsync(part, (hipStream_t)stream));
