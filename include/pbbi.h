@@ -402,7 +402,7 @@ int pbbi_pointwise_glm(const pbbi_potential* pot, const void* samples_sdn, int S
  * compared with NULL; want_var != 0: var_out is asked for.  Returns what pbbi_pointwise_glm would return before it launches. */
 int pbbi_pointwise_glm_check(int handle, int family, int state_dim, const void* samples, int S, int Dt, int64_t N,
                              int ranges, int want_var);
-/* A diagonal metric (mass matrix) on a GLM handle.  With m_d > 0 for each of the D = pbbi_potential_dim(pot) rows of the state
+/* A diagonal metric (mass matrix) on a GLM handle or on a user-defined one (pbbi_potential_create_custom).  With m_d > 0 for each of the D = pbbi_potential_dim(pot) rows of the state
  * -- coefficients, group log-scales and a sampled log-dispersion alike; for a softmax handle the K D rows, class-major -- and
  * the per-chain mass m_n of a call (1 where the call passes none), row d of chain n has mass m_n m_d:
  *     draw    p_d = sqrt(m_n m_d kT) z_d     (z_d: the Philox normals drawn without a metric, same counters, same precision rule)
@@ -414,15 +414,22 @@ int pbbi_pointwise_glm_check(int handle, int family, int state_dim, const void* 
  * A metric of all ones reproduces the handle without one bit for bit.  The device keeps the table {m_d, 1 / m_d} of
  * pbbi_glm_pack_metric and the kernels (the METRIC instantiations of k_glm and k_glm_softmax) hold it in LDS for the launch; a
  * handle without a metric launches the kernels it always has.
+ * A user-defined handle keeps the same table in its own dtype (fp64 or fp32), in the same two fields of the handle as a GLM
+ * handle; the METRIC instantiations of its plugin's kernels (csrc/pbbi_custom.h) read it at wave-uniform addresses.  The same
+ * model holds there with the per-chain mass dividing the kinetic sum last, K = 0.5 (sum_d p_d^2 / m_d) / m_n, in every mode
+ * the plugin serves: Leapfrog, Stormer-Verlet and PBBI_KDK_FMA, fused runs, the redraw of a rejected chain.  A register
+ * kernel whose METRIC twin would need scratch memory where it needs none is not launched with a metric: the workspace
+ * kernels serve that shape instead, and pbbi_describe_run says so.  No shape is refused.
  * The metric lives on the HANDLE because pbbi_hmc_run's signature is fixed: two samplers that share a handle share the metric,
  * and setting it is not ordered against launches in flight on other streams -- synchronise first.
  * mass_diag: D doubles on the host, every one finite and > 0 (else PBBI_ERR_INVALID); NULL removes the metric.  D must equal
- * pbbi_potential_dim(pot) (PBBI_ERR_INVALID).  A handle that is no GLM handle, or a GLM handle whose METRIC kernel is not
- * shipped (it would spill registers to memory): PBBI_ERR_UNSUPPORTED with the reason.  Per-chain trajectory lengths and GIST
- * stay refused on GLM handles with or without a metric. */
+ * pbbi_potential_dim(pot) (PBBI_ERR_INVALID).  A handle of any other kind (harmonic, diagonal or dense Gaussian, Rosenbrock), or
+ * a GLM handle whose METRIC kernel is not shipped (it would spill registers to memory): PBBI_ERR_UNSUPPORTED with the reason.
+ * Per-chain trajectory lengths and GIST stay refused on GLM and user-defined handles with or without a metric. */
 int pbbi_potential_set_metric_diag(pbbi_potential* pot, const double* mass_diag, int D);
 /* Copies the handle's metric into out (D = pbbi_potential_dim(pot) doubles, out_len >= D; out may be NULL).  *has_out <- 1 when
- * the handle carries a metric, 0 when it does not (out is then left alone).  A handle that is no GLM handle has none. */
+ * the handle carries a metric, 0 when it does not (out is then left alone).  A handle that is neither a GLM nor a user-defined
+ * handle has none. */
 int pbbi_potential_get_metric_diag(const pbbi_potential* pot, double* out, int out_len, int* has_out);
 /* pbbi_glm_pack_metric, the host-only packer and checker of that table, is declared in pbbi_glm_metric.h (included at the end). */
 int pbbi_potential_destroy(pbbi_potential* pot);

@@ -827,20 +827,26 @@ class HMC:
         return h
 
     # ------------------------------------------------------------------ the diagonal metric
+    _NO_METRIC = "a diagonal metric is served on user-defined potentials and, of the built-in ones, on GLM potentials only, not on "
+
     def setMassMatrix(self, diag):
         """Attach a diagonal metric to the potential (one mass > 0 per row of the state; None removes it): row d of
         chain n then has mass ensemble.mass[n] * diag[d] in the draw, the kick and the kinetic energy of every call.
-        The metric lives on the potential's handle, so every sampler that shares the potential shares it.  GLM
-        potentials only (glm.py); ValueError for a potential without such an entry."""
+        The metric lives on the potential's handle, so every sampler that shares the potential shares it -- two samplers
+        built on the same Python callable included: they share the traced potential (the trace cache) and hence the metric.
+        Served on GLM potentials (glm.py) and on user-defined ones: custom.CustomPotential, and every callable that trace.py
+        turns into generated source (models.eight_schools_potential, a lambda).  A callable that traces to a built-in
+        descriptor (Harmonic / GaussianDiag / GaussianDense) has no metric; trace_potential(f, D, prefer="source") is how
+        such a quadratic lambda gets one.  ValueError for a potential without a set_metric entry."""
         if not hasattr(self._pot, "set_metric"):
-            raise ValueError(f"a diagonal metric is served on GLM potentials only, not on {type(self._pot).__name__}")
+            raise ValueError(self._NO_METRIC + type(self._pot).__name__)
         self._pot.set_metric(diag)
 
     @property
     def massMatrix(self):
         """The potential's diagonal metric (a copy) or None; ValueError for a potential that cannot carry one."""
         if not hasattr(self._pot, "set_metric"):
-            raise ValueError(f"a diagonal metric is served on GLM potentials only, not on {type(self._pot).__name__}")
+            raise ValueError(self._NO_METRIC + type(self._pot).__name__)
         return self._pot.metric
 
     def adaptMassMatrix(self, temperature, qStd, windows=(25, 50, 100), target=0.8, step_iterations=40, chunk=25,
@@ -856,11 +862,13 @@ class HMC:
           5. set_metric.
         A final step-size adaptation follows the last window.  Uses the warm-up Philox key (WARMUP_SEED_MASK) like the
         other adapters, with one run of iteration counters over all phases.  Leaves stepSize and numSteps set (simulTime
-        is kept) and returns the metric.  The warm-up state is discarded."""
+        is kept) and returns the metric.  The warm-up state is discarded.  Potentials as for setMassMatrix: GLM and
+        user-defined ones (CustomPotential, callables traced to source; trace_potential(..., prefer="source") for a
+        quadratic lambda), ValueError otherwise."""
         pot, ens = self._pot, self.ensemble
         D, N = ens.numDimensions, ens.numParticles
         if not hasattr(pot, "set_metric"):
-            raise ValueError(f"a diagonal metric is served on GLM potentials only, not on {type(pot).__name__}")
+            raise ValueError(self._NO_METRIC + type(pot).__name__)
         windows = [int(w) for w in windows]
         if not windows or min(windows) < 2:
             raise ValueError("windows must hold at least one length >= 2")

@@ -88,7 +88,7 @@ int new_handle(int kind, int D, int dtype, int device, pbbi_potential** out) {
     p->d_sfrag = p->d_smean = nullptr;
     p->plugin = p->d_params = nullptr;
     p->n_params = 0;
-    p->plugin_hmc_iter = nullptr; p->plugin_integrate = nullptr; p->plugin_eval = nullptr;
+    p->plugin_hmc_iter = nullptr; p->plugin_integrate = nullptr; p->plugin_eval = nullptr; p->plugin_hmc_route = nullptr;
     p->zero_mean = true;
     p->glm_DP = 0; p->glm_family = 0; p->glm_M = 0; p->glm_lam = 0.0;
     p->d_glm_img = p->d_glm_y = nullptr;
@@ -904,10 +904,11 @@ int pbbi_potential_create_custom(const char* plugin_path, int D, const double* p
     p->plugin_hmc_iter = (int (*)(const IterArgs*))dlsym(p->plugin, "pbbi_plugin_hmc_iter");
     p->plugin_integrate = (int (*)(const IntegrateArgs*))dlsym(p->plugin, "pbbi_plugin_integrate");
     p->plugin_eval = (int (*)(const EvalArgs*, int))dlsym(p->plugin, "pbbi_plugin_eval");
+    p->plugin_hmc_route = (int (*)(const pbbi_potential*, int, int, int))dlsym(p->plugin, "pbbi_plugin_hmc_route");
     int rc = PBBI_OK;
     if (!abi || !pdt || !p->plugin_hmc_iter || !p->plugin_integrate || !p->plugin_eval)
         rc = pbbi_fail(PBBI_ERR_INVALID, "plugin does not export the pbbi_plugin_* entry points");
-    else if (abi() != PBBI_PLUGIN_ABI)
+    else if (abi() != PBBI_PLUGIN_ABI || !p->plugin_hmc_route)
         rc = pbbi_fail(PBBI_ERR_INVALID, "plugin was built against another libpbbi (ABI " +
                                              std::to_string(abi()) + ", expected " +
                                              std::to_string(PBBI_PLUGIN_ABI) + "): rebuild it");
@@ -1168,11 +1169,12 @@ int pbbi_glm_pack_design(int D, int64_t M, const double* X, double* out, int64_t
     return PBBI_OK;
 }
 
-// The diagonal metric of a GLM handle (include/pbbi.h).  Every rule before the device is touched; the new table is uploaded
-// before the old one is let go, so a failure leaves the handle as it was.
+// The diagonal metric of a GLM or user-defined handle (include/pbbi.h).  Every rule before the device is touched; the new table
+// is uploaded before the old one is let go, so a failure leaves the handle as it was.
 int pbbi_potential_set_metric_diag(pbbi_potential* pot, const double* mass_diag, int D) {
     if (!pot) return pbbi_fail(PBBI_ERR_INVALID, "potential handle is NULL");
-    if (pot->kind != KIND_GLM || pot->glm_DP == 0)
+    const bool custom = pot->kind == KIND_CUSTOM;
+    if (!custom && (pot->kind != KIND_GLM || pot->glm_DP == 0))
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, "a diagonal metric is served on GLM handles only (the METRIC instantiations of k_glm "
                                                "and k_glm_softmax)");
     DeviceGuard guard(pot->device);
@@ -1187,13 +1189,21 @@ int pbbi_potential_set_metric_diag(pbbi_potential* pot, const double* mass_diag,
         return pbbi_fail(PBBI_ERR_INVALID, "metric: D must equal the handle's state dimension (D = " + std::to_string(D) +
                                                ", state dimension " + std::to_string(pot->D) + ")");
     if (int rc = glm_check_metric(D, mass_diag)) return rc;
-    const int top = glm_metric_max_dim(pot->glm_variant, pot->glm_family, pot->glm_hier_nc, pot->glm_DP, pot->glm_K);
+    const int top = custom ? pot->D : glm_metric_max_dim(pot->glm_variant, pot->glm_family, pot->glm_hier_nc, pot->glm_DP, pot->glm_K);
     if (pot->D > top)
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, "metric: the METRIC kernel of this handle's variant, family and padded dimension is "
                                                "not shipped -- it does not build without register spills to memory (state "
                                                "dimension " + std::to_string(pot->D) + ", served up to " + std::to_string(top) + ")");
     std::vector<double> table;
-    if (pot->glm_variant == GLM_V_SOFTMAX) {
+    if (custom) {
+        // the plugin kernels' table (pbbi_custom.h): {m_d, 1 / m_d} in row order, in the handle's dtype; 8 pairs of ones behind
+        // row D, so that a batch of rows that reaches past D reads inside the table
+        table.assign((size_t)2 * (D + 8), 1.0);
+        for (int d = 0; d < D; ++d) {
+            table[(size_t)2 * d] = mass_diag[d];
+            table[(size_t)2 * d + 1] = 1.0 / mass_diag[d];
+        }
+    } else if (pot->glm_variant == GLM_V_SOFTMAX) {
         // the kernel's rows are the INTERNAL ones (class k padded to Dc rows): internal row k Dc + d is row k D + d of the state
         const int K = pot->glm_K, Dc = pot->glm_DP, rows = K * Dc;
         std::vector<int32_t> map((size_t)rows);
@@ -1208,7 +1218,7 @@ int pbbi_potential_set_metric_diag(pbbi_potential* pot, const double* mass_diag,
         glm_pack_metric(D, mass_diag, table.data());
     }
     void* fresh = nullptr;
-    if (int rc = upload(table.data(), table.size(), PBBI_F64, &fresh)) return rc;
+    if (int rc = upload(table.data(), table.size(), custom ? pot->dtype : PBBI_F64, &fresh)) return rc;
     double* keep = new (std::nothrow) double[(size_t)D];
     if (!keep) {
         (void)hipFree(fresh);
@@ -1224,7 +1234,7 @@ int pbbi_potential_set_metric_diag(pbbi_potential* pot, const double* mass_diag,
 
 int pbbi_potential_get_metric_diag(const pbbi_potential* pot, double* out, int out_len, int* has_out) {
     if (!pot) return pbbi_fail(PBBI_ERR_INVALID, "potential handle is NULL");
-    const bool has = pot->kind == KIND_GLM && pot->glm_metric_diag != nullptr;
+    const bool has = (pot->kind == KIND_GLM || pot->kind == KIND_CUSTOM) && pot->glm_metric_diag != nullptr;
     if (has_out) *has_out = has ? 1 : 0;
     if (!has || !out) return PBBI_OK;
     if (out_len < pot->D) return pbbi_fail(PBBI_ERR_INVALID, "out is shorter than the handle's state dimension");
@@ -1643,6 +1653,14 @@ int pbbi_describe_run(const pbbi_potential* pot, int method, int64_t N, int64_t 
     } else if (pot->kind == KIND_CUSTOM) {
         d = "user-potential plugin kernels (one chain per lane; registers up to D = 16 / 32, workspace beyond)";
         fuse = route_fused_iterations(a);
+        if (pot->d_glm_metric) {
+            const int route = pot->plugin_hmc_route(pot, a.method, a.flags, a.mass == nullptr);
+            d += "; diagonal metric: row d of chain n has mass m_n m_d, the METRIC instantiation of the ";
+            d += route == 2 ? "register kernel (kick-drift-kick form)" : route == 1 ? "register kernel" : "workspace kernel";
+            d += " with the table {m_d, 1 / m_d} read at wave-uniform addresses (draw, kick and kinetic energy)";
+            if (route == 0 && pot->D <= ((a.flags & PBBI_KDK_FMA) && a.method == PBBI_LEAPFROG ? 2 : 1) * (pot->dtype == PBBI_F64 ? 16 : 32))
+                d += " -- the register kernel with a metric would spill to scratch memory at this shape and is not used";
+        }
     } else if (is_big(pot) && dense_stream_applies(a)) {
         d = "k_dense_hmc (streamed P): register-resident MFMA kernel, 16 chains per wave, one wave per SIMD, the "
             "precision matrix streamed through an LDS ring (rows padded to " + std::to_string(pot->DPS) + ")";

@@ -11,7 +11,8 @@
 enum { KIND_HARMONIC = 0, KIND_GAUSS_DIAG = 1, KIND_GAUSS_DENSE = 2, KIND_ROSENBROCK = 3, KIND_CUSTOM = 4, KIND_GLM = 5 };
 
 // layout version of the structs a user-potential plugin (pbbi_custom.h) shares with libpbbi.so
-#define PBBI_PLUGIN_ABI 4  /* 4: plugins honour IterArgs::fuse_* (several iterations of a run per call) */
+#define PBBI_PLUGIN_ABI 5  /* 4: plugins honour IterArgs::fuse_* (several iterations of a run per call); 5: they serve the
+                              diagonal metric of the handle (d_glm_metric) and export pbbi_plugin_hmc_route */
 
 struct IterArgs;
 struct IntegrateArgs;
@@ -78,9 +79,12 @@ struct pbbi_potential {
     // which of these kinds of handle this is.  (Appended.)  The one record of it: no other field is asked for the kind.
     int glm_variant;       // GlmVariant (glm_host.h), set by the builder of the create entry
     // the diagonal metric (pbbi_potential_set_metric_diag).  (Appended.)  NULL / NULL on a handle without one, which launches the
-    // kernels it always has
-    void* d_glm_metric;       // {m_d, 1 / m_d} per row in the kernel's row order (glm_pack_metric; softmax: the internal rows)
+    // kernels it always has.  GLM and user-defined (KIND_CUSTOM) handles carry one, in these same two fields
+    void* d_glm_metric;       // {m_d, 1 / m_d} per row in the kernel's row order (glm_pack_metric; softmax: the internal rows);
+                              // KIND_CUSTOM: D + 8 pairs in the handle's dtype, ones past row D (the plugin kernels, pbbi_custom.h)
     double* glm_metric_diag;  // the D entries as given, on the host (pbbi_potential_get_metric_diag)
+    // KIND_CUSTOM: which of the plugin's kernels serves an HMC call on the handle as it is now (pbbi_describe_run).  (Appended.)
+    int (*plugin_hmc_route)(const pbbi_potential*, int method, int flags, int unit_mass);
 };
 
 // ---- error plumbing ---------------------------------------------------------

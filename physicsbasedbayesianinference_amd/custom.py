@@ -52,9 +52,9 @@ import subprocess
 import numpy as np
 
 from . import _lib
-from .potential import Potential, _dptr
+from .potential import Potential, _Metric, _dptr
 
-__all__ = ["CustomPotential", "compile_plugin", "plugin_source", "complete_source", "has_gradient",
+__all__ = ["CustomPotential", "compile_plugin", "plugin_resources", "plugin_source", "complete_source", "has_gradient",
            "coin_toss_posterior",
            "logistic_regression_posterior", "COIN_TOSS_SOURCE", "LOGISTIC_REGRESSION_SOURCE",
            "EXAMPLE_SOURCE"]
@@ -109,9 +109,11 @@ def _hipcc():
                        "gfx950 at construction and there is no CPU fallback")
 
 
-def compile_plugin(source, dtype="float64", verbose=False, D=None):
+def compile_plugin(source, dtype="float64", verbose=False, D=None, remarks=False):
     """Build (or find in the in-tree cache) the plugin .so of a user source; needs hipcc, not a
-    GPU.  The cache key covers the source, the dtype, the dimension and the kernel headers."""
+    GPU.  The cache key covers the source, the dtype, the dimension and the kernel headers.
+    remarks=True also keeps hipcc's resource remarks of the build (-Rpass-analysis=kernel-resource-usage,
+    which changes no code) beside the .so, as pot_<key>.remarks: what plugin_resources reads."""
     tu = plugin_source(source, dtype, D)
     h = hashlib.sha256(tu.encode())
     for dep in _DEPS:
@@ -122,7 +124,8 @@ def compile_plugin(source, dtype="float64", verbose=False, D=None):
     key = h.hexdigest()[:20]
     os.makedirs(_CACHE, exist_ok=True)
     so = os.path.join(_CACHE, f"pot_{key}.so")
-    if os.path.exists(so):
+    rem = os.path.join(_CACHE, f"pot_{key}.remarks")
+    if os.path.exists(so) and (not remarks or os.path.exists(rem)):
         return so
     src = os.path.join(_CACHE, f"pot_{key}.hip")
     with open(src, "w") as f:
@@ -134,17 +137,46 @@ def compile_plugin(source, dtype="float64", verbose=False, D=None):
     cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
            "-ffp-contract=off", "-mllvm", "-disable-machine-licm", "-mllvm", "-sink-insts-to-avoid-spills",
            "-mllvm", "-amdgpu-use-amdgpu-trackers=1", f"-I{_CSRC}", f"-I{_INCLUDE}", src, "-o", tmp]
+    if remarks:
+        cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
     if verbose:
         print(" ".join(cmd))
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
         raise RuntimeError("hipcc failed on the user-defined potential:\n" + res.stderr[-4000:])
+    if remarks:
+        with open(rem + f".tmp{os.getpid()}", "w") as f:
+            f.write(res.stderr)
+        os.replace(rem + f".tmp{os.getpid()}", rem)
     os.replace(tmp, so)  # atomic: concurrent ranks may build the same plugin
     return so
 
 
-class CustomPotential(Potential):
-    """A potential given as C++ source (module docstring); `params` is a flat float64 array."""
+def plugin_resources(source, dtype="float64", D=None):
+    """What hipcc reports for every kernel of the plugin of a user source (built with remarks=True if it is not in the
+    cache): {kernel: dict(vgprs, agprs, sgprs, scratch, occupancy)}, scratch in bytes per lane, occupancy in waves per
+    SIMD.  The kernel's name is the template and its arguments as they are mangled, e.g. "k_custom_reg_hmc<0,1,0,1>" for
+    <METHOD = Leapfrog, UNIT, KDK = false, METRIC = true> (csrc/pbbi_custom.h).  Needs hipcc, not a GPU."""
+    so = compile_plugin(source, dtype, D=D, remarks=True)
+    with open(so[:-3] + ".remarks") as f:
+        text = f.read()
+    fields = {"vgprs": r" VGPRs", "agprs": r"AGPRs", "sgprs": r"TotalSGPRs", "scratch": r"ScratchSize \[bytes/lane\]",
+              "occupancy": r"Occupancy \[waves/SIMD\]"}
+    out = {}
+    for block in text.split("Function Name: ")[1:]:
+        mangled = block.split()[0]
+        m = re.search(r"(k_custom\w*?)(?:I((?:L[ib]\d+E)+)E|E)", mangled)
+        if not m:
+            continue
+        args = re.findall(r"L[ib](\d+)E", m.group(2) or "")
+        name = m.group(1) + ("<" + ",".join(args) + ">" if args else "")
+        out[name] = {k: int(re.search(pat + r": (\d+)", block).group(1)) for k, pat in fields.items()}
+    return out
+
+
+class CustomPotential(_Metric, Potential):
+    """A potential given as C++ source (module docstring); `params` is a flat float64 array.  It carries a diagonal metric
+    (set_metric / metric, HMC.setMassMatrix / adaptMassMatrix): the plugin's kernels are built with and without one."""
 
     kind = "custom"
 

@@ -42,7 +42,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .potential import Potential, _dptr
+from .potential import Potential, _Metric, _dptr  # (_Metric: the mixin lives in potential.py)
 
 __all__ = ["GLM", "SoftmaxGLM", "DispersionGLM", "HierarchicalGLM", "HierarchicalDispersionGLM", "HIER_DISP_MAX_DIM",
            "pack_prior_groups_dispersion", "FAMILIES", "DISPERSION_FAMILIES", "HIER_MAX_DIM",
@@ -93,33 +93,6 @@ def pack_metric(diag):
     out = np.empty(n.value, dtype=np.float64)
     _lib.call("pbbi_glm_pack_metric", m.size, _dptr(m), _dptr(out), out.size, C.byref(n))
     return out.reshape(-1, 2)
-
-
-class _Metric:
-    """The diagonal metric of a GLM handle (pbbi_potential_set_metric_diag): row d of chain n has mass m_n m_d in the draw,
-    the kick and the kinetic energy of every sampler call on this potential.  It lives on the handle, so every sampler
-    that shares the potential shares it."""
-
-    def set_metric(self, diag):
-        """diag: one mass > 0 per row of the state (coefficients, group log-scales, a sampled log-dispersion), or None to
-        remove the metric.  Checked on the host before anything touches the GPU."""
-        if diag is None:
-            _lib.call("pbbi_potential_set_metric_diag", self.handle, None, 0)
-            return
-        m = np.ascontiguousarray(diag, dtype=np.float64)
-        if m.ndim != 1 or m.size != self.numDimensions:
-            raise ValueError(f"the metric must hold one mass per row of the state ({self.numDimensions}), got shape {m.shape}")
-        if not (np.all(np.isfinite(m)) and np.all(m > 0.0)):
-            raise ValueError("every entry of the metric must be finite and > 0")
-        _lib.call("pbbi_potential_set_metric_diag", self.handle, _dptr(m), m.size)
-
-    @property
-    def metric(self):
-        """The metric as set (a copy), or None."""
-        out = np.empty(self.numDimensions, dtype=np.float64)
-        has = C.c_int(0)
-        _lib.call("pbbi_potential_get_metric_diag", self.handle, _dptr(out), out.size, C.byref(has))
-        return out if has.value else None
 
 
 def pack_design(X):

@@ -106,6 +106,33 @@ class Potential:
         return np.exp(-self(q))
 
 
+class _Metric:
+    """The diagonal metric of a handle that carries one (pbbi_potential_set_metric_diag: the GLM classes of glm.py and
+    custom.CustomPotential): row d of chain n has mass m_n m_d in the draw, the kick and the kinetic energy of every sampler
+    call on this potential.  It lives on the handle, so every sampler that shares the potential shares it."""
+
+    def set_metric(self, diag):
+        """diag: one mass > 0 per row of the state (for a GLM: coefficients, group log-scales, a sampled log-dispersion), or
+        None to remove the metric.  Checked on the host before anything touches the GPU."""
+        if diag is None:
+            _lib.call("pbbi_potential_set_metric_diag", self.handle, None, 0)
+            return
+        m = np.ascontiguousarray(diag, dtype=np.float64)
+        if m.ndim != 1 or m.size != self.numDimensions:
+            raise ValueError(f"the metric must hold one mass per row of the state ({self.numDimensions}), got shape {m.shape}")
+        if not (np.all(np.isfinite(m)) and np.all(m > 0.0)):
+            raise ValueError("every entry of the metric must be finite and > 0")
+        _lib.call("pbbi_potential_set_metric_diag", self.handle, _dptr(m), m.size)
+
+    @property
+    def metric(self):
+        """The metric as set (a copy), or None."""
+        out = np.empty(self.numDimensions, dtype=np.float64)
+        has = C.c_int(0)
+        _lib.call("pbbi_potential_get_metric_diag", self.handle, _dptr(out), out.size, C.byref(has))
+        return out if has.value else None
+
+
 class Harmonic(Potential):
     """U(q) = 0.5 * dot(springConsts, q**2)   (src/potential.py:18-27)."""
 
