@@ -402,6 +402,47 @@ int pbbi_pointwise_glm(const pbbi_potential* pot, const void* samples_sdn, int S
  * compared with NULL; want_var != 0: var_out is asked for.  Returns what pbbi_pointwise_glm would return before it launches. */
 int pbbi_pointwise_glm_check(int handle, int family, int state_dim, const void* samples, int S, int Dt, int64_t N,
                              int ranges, int want_var);
+/* The likelihood energy of each of S * N draws of a GLM handle's state (csrc/kernels_glm_loglik.hip: a wave keeps 16 draws in
+ * registers and walks the observation blocks, eta = X W on the fp64 matrix cores from the first copy of the packed design image):
+ *     ulik_out[s * N + n] = sum_i U_i(draw n of slab s)            (S * N doubles on the device)
+ * the likelihood part of the handle's potential -- minus the log-likelihood WITHOUT the terms that depend on no parameter (see
+ * pbbi_pointwise_glm), which the caller adds -- with no prior term, no group-scale term and no prior of theta.  An observation of
+ * weight 0 adds exactly 0, whatever its linear predictor is.  samples_sdn, Dt and the rows that are read: as for
+ * pbbi_pointwise_glm (natural scale; only the coefficient rows are read as coefficients, the other rows change no bit; a sampled
+ * log-dispersion is read from its own row, a held one comes from the handle).  The likelihood is ALWAYS at power 1: on a handle
+ * tempered by pbbi_potential_set_likelihood_power the streams as built are read.  ranges: the observation blocks are cut into
+ * `ranges` (0 = the library chooses, else 1 .. 65535; more ranges than blocks leave empty ones) so that few draws still fill the
+ * device; a second kernel adds the partials in index order, without atomics: for a given `ranges` the result is bit for bit the
+ * same from run to run.  A draw with log-likelihood -inf gives +inf, a NaN draw NaN, for that draw only.
+ * Served: the handles pbbi_pointwise_glm serves, in the shapes the handles themselves are shipped in (no kernel reserves scratch
+ * memory).  Rules, in this order, all before the device is touched: NULL handle, NULL samples, NULL ulik_out, S < 1, N < 1,
+ * ranges outside 0 .. 65535: PBBI_ERR_INVALID; a handle that is no GLM handle, a softmax handle, an unknown family:
+ * PBBI_ERR_UNSUPPORTED; Dt below the state dimension: PBBI_ERR_INVALID. */
+int pbbi_loglik_glm(const pbbi_potential* pot, const void* samples_sdn, int S, int Dt, int64_t N, int ranges,
+                    double* ulik_out, void* stream);
+/* Those rules alone, on the HOST, for a handle described by value (as pbbi_pointwise_glm_check); the pointers are only compared
+ * with NULL. */
+int pbbi_loglik_glm_check(int handle, int family, int state_dim, const void* samples, const void* ulik_out, int S, int Dt,
+                          int64_t N, int ranges);
+/* The likelihood power of a GLM handle: the handle's potential becomes -log [ p(w) L(w)^beta ] (prior terms untouched), the path
+ * from the prior (beta -> 0) to the posterior (beta = 1) of likelihood-tempered SMC.  Raising the likelihood to the power beta is
+ * multiplying every observation weight a_i by beta, so no kernel changes: a small kernel writes c <- beta c0 on the handle's
+ * observation streams (and d <- beta d0 where d holds a_i y_i: logistic and poisson; the dispersion families keep d = y raw).  The
+ * streams as built are copied on the first call and kept.  1.0 * x is exact: at beta = 1 the handle is bit for bit the untouched one.
+ * beta_dev != NULL: the kernel reads beta from that device double (a fixed schedule needs no host read; the getter then
+ * reports NaN, and the value is not checked); beta_dev == NULL: the host value `beta`, finite and > 0.
+ * Every kernel that reads the streams sees the power: pbbi_hmc_iter / pbbi_hmc_run, pbbi_integrate, pbbi_potential_eval,
+ * pbbi_energy, pbbi_weights_ratio, pbbi_pointwise_glm.  pbbi_loglik_glm does not (see there).  The power lives on the HANDLE, like
+ * the metric: samplers that share a handle share its power, and setting it is ordered only against work on `stream`.
+ * Rules, in this order: NULL handle: PBBI_ERR_INVALID; a handle that is no GLM handle, a softmax handle, a handle of
+ * pbbi_potential_create_glm (it has no streams: build the model with pbbi_potential_create_glm_ex): PBBI_ERR_UNSUPPORTED with the
+ * reason; a host beta that is not finite and > 0: PBBI_ERR_INVALID. */
+int pbbi_potential_set_likelihood_power(pbbi_potential* pot, double beta, const double* beta_dev, void* stream);
+/* *beta_out <- the power as last set from the host, NaN when it was last read from the device, 1 on a handle never tempered. */
+int pbbi_potential_get_likelihood_power(const pbbi_potential* pot, double* beta_out);
+/* The rules of pbbi_potential_set_likelihood_power alone, on the HOST, by value: handle as for pbbi_pointwise_glm_check, has_streams
+ * != 0: the handle keeps observation streams, beta_on_device != 0: beta_dev is given (beta is then not read). */
+int pbbi_likelihood_power_check(int handle, int family, int has_streams, double beta, int beta_on_device);
 /* A diagonal metric (mass matrix) on a GLM handle or on a user-defined one (pbbi_potential_create_custom).  With m_d > 0 for each of the D = pbbi_potential_dim(pot) rows of the state
  * -- coefficients, group log-scales and a sampled log-dispersion alike; for a softmax handle the K D rows, class-major -- and
  * the per-chain mass m_n of a call (1 where the call passes none), row d of chain n has mass m_n m_d:

@@ -18,6 +18,7 @@ from .HMC import HMC
 from .custom import CustomPotential
 from .glm import GLM, SoftmaxGLM, DispersionGLM, HierarchicalGLM, HierarchicalDispersionGLM, pack_observations_dispersion, pack_prior_groups
 from .stats import RunningHistogram, RunningStats
+from .smc import LikelihoodTemperedSMC
 from . import trace
 from .trace import grad, trace_potential
 
@@ -25,6 +26,6 @@ __all__ = ["Ensemble", "HMC", "Integrator", "Leapfrog", "StormerVerlet", "Potent
            "Harmonic", "GaussianDiag", "StandardGaussian", "GaussianDense", "Rosenbrock",
            "harmonicPotentialND", "linear_regression_posterior", "CustomPotential", "GLM", "SoftmaxGLM", "DispersionGLM",
            "HierarchicalGLM", "HierarchicalDispersionGLM", "pack_observations_dispersion", "pack_prior_groups", "RunningStats",
-           "RunningHistogram",
+           "RunningHistogram", "LikelihoodTemperedSMC",
            "trace", "grad", "trace_potential"]
 __version__ = "0.1.0"

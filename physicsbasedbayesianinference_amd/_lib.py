@@ -79,6 +79,13 @@ PROTOTYPES = {
     # what a GLM handle says about posterior draws (glm.py `pointwise`, csrc/kernels_glm_pointwise.hip)
     "pbbi_pointwise_glm": [_vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp],
     "pbbi_pointwise_glm_check": [_i, _i, _i, _vp, _i, _i, _i64, _i, _i],
+    # the likelihood energy of each draw and the likelihood power of a handle (glm.py `loglik`, `set_likelihood_power`,
+    # smc.LikelihoodTemperedSMC; csrc/kernels_glm_loglik.hip)
+    "pbbi_loglik_glm": [_vp, _vp, _i, _i, _i64, _i, _vp, _vp],
+    "pbbi_loglik_glm_check": [_i, _i, _i, _vp, _vp, _i, _i, _i64, _i],
+    "pbbi_potential_set_likelihood_power": [_vp, _d, _vp, _vp],
+    "pbbi_potential_get_likelihood_power": [_vp, _dp],
+    "pbbi_likelihood_power_check": [_i, _i, _i, _d, _i],
     # the diagonal metric of a GLM handle (glm.py `set_metric`, HMC.adaptMassMatrix)
     "pbbi_potential_set_metric_diag": [_vp, _dp, _i],
     "pbbi_potential_get_metric_diag": [_vp, _dp, _i, C.POINTER(C.c_int)],

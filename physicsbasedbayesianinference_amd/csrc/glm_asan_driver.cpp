@@ -223,6 +223,58 @@ static void pointwise_rules() {
     EXPECT(glm_check_pointwise(1, PBBI_GLM_LOGISTIC, 5, p, 2000000000, 5, (int64_t)1 << 40, 0, true) == PBBI_OK);
 }
 
+// every rule of pbbi_loglik_glm's arguments, in the order the checker states them; the pointers are only compared with NULL
+static void loglik_rules() {
+    Buf<double> s = dbuf(1, 0.0), o = dbuf(1, 0.0);
+    const void *p = s.get(), *u = o.get();
+    for (int fam : {(int)PBBI_GLM_LOGISTIC, (int)PBBI_GLM_POISSON, (int)PBBI_GLM_GAUSSIAN, (int)PBBI_GLM_NEGBINOMIAL}) {
+        EXPECT(glm_check_loglik(1, fam, 5, p, u, 3, 5, 150, 0) == PBBI_OK);
+        EXPECT(glm_check_loglik(1, fam, 5, p, u, 1, 7, 1, 1) == PBBI_OK);  // one draw; Dt > D
+        EXPECT(glm_check_loglik(1, fam, 128, p, u, 1, 128, 2, 65535) == PBBI_OK);
+    }
+    EXPECT(glm_check_loglik(0, PBBI_GLM_LOGISTIC, 5, nullptr, nullptr, 0, 4, 0, -1) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("handle is NULL") != std::string::npos);
+    EXPECT(glm_check_loglik(1, PBBI_GLM_LOGISTIC, 5, nullptr, nullptr, 0, 4, 0, -1) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("samples is NULL") != std::string::npos);
+    EXPECT(glm_check_loglik(1, PBBI_GLM_LOGISTIC, 5, p, nullptr, 0, 4, 0, -1) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("ulik_out is NULL") != std::string::npos);
+    EXPECT(glm_check_loglik(1, PBBI_GLM_LOGISTIC, 5, p, u, 0, 4, 0, -1) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("S must be >= 1") != std::string::npos);
+    EXPECT(glm_check_loglik(1, PBBI_GLM_LOGISTIC, 5, p, u, 3, 4, 0, -1) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("N must be >= 1") != std::string::npos);
+    EXPECT(glm_check_loglik(1, PBBI_GLM_LOGISTIC, 5, p, u, 3, 4, 150, -1) == PBBI_ERR_INVALID);
+    EXPECT(glm_check_loglik(1, PBBI_GLM_LOGISTIC, 5, p, u, 3, 4, 150, 65536) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("ranges must be") != std::string::npos);
+    EXPECT(glm_check_loglik(2, 0, 5, p, u, 3, 4, 150, 0) == PBBI_ERR_UNSUPPORTED);
+    EXPECT(g_error.find("not a GLM handle") != std::string::npos && g_error.find(GLM_POINTWISE_RULE) != std::string::npos);
+    EXPECT(glm_check_loglik(1, PBBI_GLM_SOFTMAX, 6, p, u, 3, 4, 150, 0) == PBBI_ERR_UNSUPPORTED);
+    EXPECT(g_error.find("softmax") != std::string::npos);
+    EXPECT(glm_check_loglik(1, 99, 5, p, u, 3, 4, 150, 0) == PBBI_ERR_UNSUPPORTED);
+    EXPECT(glm_check_loglik(1, PBBI_GLM_LOGISTIC, 5, p, u, 3, 4, 150, 0) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("state dimension") != std::string::npos);
+    EXPECT(glm_check_loglik(1, PBBI_GLM_LOGISTIC, 5, p, u, 2000000000, 5, (int64_t)1 << 40, 0) == PBBI_OK);
+}
+
+// every rule of pbbi_potential_set_likelihood_power, in the checker's order
+static void power_rules() {
+    for (int fam : {(int)PBBI_GLM_LOGISTIC, (int)PBBI_GLM_POISSON, (int)PBBI_GLM_GAUSSIAN, (int)PBBI_GLM_NEGBINOMIAL}) {
+        EXPECT(glm_check_power(1, fam, true, 1.0, false) == PBBI_OK && glm_check_power(1, fam, true, 1e-300, false) == PBBI_OK);
+        EXPECT(glm_check_power(1, fam, true, (double)NAN, true) == PBBI_OK);  // read from the device: not checked
+    }
+    EXPECT(glm_check_power(0, PBBI_GLM_SOFTMAX, false, -1.0, false) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("handle is NULL") != std::string::npos);
+    EXPECT(glm_check_power(2, PBBI_GLM_SOFTMAX, false, -1.0, false) == PBBI_ERR_UNSUPPORTED);
+    EXPECT(g_error.find("not a GLM handle") != std::string::npos && g_error.find(GLM_POWER_RULE) != std::string::npos);
+    EXPECT(glm_check_power(1, PBBI_GLM_SOFTMAX, false, -1.0, false) == PBBI_ERR_UNSUPPORTED);
+    EXPECT(g_error.find("softmax") != std::string::npos);
+    EXPECT(glm_check_power(1, PBBI_GLM_LOGISTIC, false, -1.0, false) == PBBI_ERR_UNSUPPORTED);
+    EXPECT(g_error.find("no observation streams") != std::string::npos);
+    for (double v : {0.0, -1.0, (double)NAN, (double)INFINITY}) {
+        EXPECT(glm_check_power(1, PBBI_GLM_LOGISTIC, true, v, false) == PBBI_ERR_INVALID);
+        EXPECT(g_error.find("finite and > 0") != std::string::npos);
+    }
+}
+
 // the diagonal metric's table: 2 * glm_padded_dim(D) doubles, {m_d, 1 / m_d} then {1, 1}; the last entry is the one found
 static void metric_tables() {
     for (int D : DS) {
@@ -259,6 +311,8 @@ int main() {
     penalties();
     softmax_shapes();
     pointwise_rules();
+    loglik_rules();
+    power_rules();
     // what is shipped (the one statement the entries and the launch read)
     EXPECT(glm_max_dim(GLM_V_PLAIN, PBBI_GLM_LOGISTIC) == 128 && glm_max_dim(GLM_V_FULL, PBBI_GLM_POISSON) == 128);
     EXPECT(glm_max_dim(GLM_V_DISPERSION, PBBI_GLM_GAUSSIAN) == 128 && glm_max_dim(GLM_V_DISPERSION, PBBI_GLM_NEGBINOMIAL) == 64);

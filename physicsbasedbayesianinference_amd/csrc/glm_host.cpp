@@ -409,6 +409,49 @@ int glm_check_pointwise(int handle, int family, int state_dim, const void* sdn, 
     return PBBI_OK;
 }
 
+// ---- the likelihood energy of each draw -------------------------------------------------------------------------
+int glm_check_loglik(int handle, int family, int state_dim, const void* sdn, const void* out, int S, int Dt, int64_t N,
+                     int ranges) {
+    if (handle == 0) return pbbi_fail(PBBI_ERR_INVALID, "potential handle is NULL");
+    if (!sdn) return pbbi_fail(PBBI_ERR_INVALID, "samples is NULL");
+    if (!out) return pbbi_fail(PBBI_ERR_INVALID, "ulik_out is NULL");
+    if (S < 1) return pbbi_fail(PBBI_ERR_INVALID, "S must be >= 1 (S = " + std::to_string(S) + ")");
+    if (N < 1) return pbbi_fail(PBBI_ERR_INVALID, "N must be >= 1 (N = " + std::to_string(N) + ")");
+    if (ranges < 0 || ranges > 65535)
+        return pbbi_fail(PBBI_ERR_INVALID, "ranges must be 0 (the library chooses) or 1 .. 65535 (ranges = " +
+                                               std::to_string(ranges) + ")");
+    if (handle != 1)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string("pbbi_loglik_glm: not a GLM handle: ") + GLM_POINTWISE_RULE);
+    if (family == PBBI_GLM_SOFTMAX)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string("pbbi_loglik_glm: a softmax handle is not served: ") +
+                                                   GLM_POINTWISE_RULE);
+    if (!glm_canonical(family) && !glm_disp(family))
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string("pbbi_loglik_glm: unknown GLM family: ") + GLM_POINTWISE_RULE);
+    if (Dt < state_dim)
+        return pbbi_fail(PBBI_ERR_INVALID, "Dt must be at least the handle's state dimension (Dt = " + std::to_string(Dt) +
+                                               ", state dimension " + std::to_string(state_dim) + ")");
+    return PBBI_OK;
+}
+
+// ---- the likelihood power ---------------------------------------------------------------------------------------
+const char* const GLM_POWER_RULE = "a likelihood power is served on the handles that keep observation streams: "
+                                   "pbbi_potential_create_glm_ex, _glm_dispersion, _glm_hier, _glm_hier_ex, _glm_hier_q and "
+                                   "_glm_hier_dispersion (a plain model is built as _glm_ex with weights 1 for it)";
+
+int glm_check_power(int handle, int family, bool has_streams, double beta, bool beta_on_device) {
+    if (handle == 0) return pbbi_fail(PBBI_ERR_INVALID, "potential handle is NULL");
+    if (handle != 1) return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string("not a GLM handle: ") + GLM_POWER_RULE);
+    if (family == PBBI_GLM_SOFTMAX)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string("a softmax handle has no observation weights: ") + GLM_POWER_RULE);
+    if (!has_streams)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string("a handle of pbbi_potential_create_glm has no observation streams: ") +
+                                                   GLM_POWER_RULE);
+    if (!beta_on_device && !(std::isfinite(beta) && beta > 0.0))
+        return pbbi_fail(PBBI_ERR_INVALID, "the likelihood power must be finite and > 0 (beta = " + std::to_string(beta) +
+                                               "); a power read from the device is not checked");
+    return PBBI_OK;
+}
+
 // ---- K-class softmax regression ---------------------------------------------------------------------------------
 const char* const GLM_SOFTMAX_RULE = "softmax GLM: float64, 2 <= K <= 8 classes, each padded to Dc = 16, 32 or 64 rows with "
                                      "K * Dc <= 128 (D <= 16 for K <= 8, D <= 32 for K <= 4, D <= 64 for K = 2)";

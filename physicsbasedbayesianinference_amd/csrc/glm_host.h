@@ -80,6 +80,13 @@ void glm_pack_penalty(int D, int J, const double* penalty, double* out);
 extern const char* const GLM_POINTWISE_RULE;
 int glm_check_pointwise(int handle, int family, int state_dim, const void* sdn, int S, int Dt, int64_t N, int ranges,
                         bool want_var);
+// ---- the likelihood energy of each draw (kernels_glm_loglik.hip): every argument rule of pbbi_loglik_glm, `handle` as above
+int glm_check_loglik(int handle, int family, int state_dim, const void* sdn, const void* out, int S, int Dt, int64_t N,
+                     int ranges);
+// ---- the likelihood power: every argument rule of pbbi_potential_set_likelihood_power.  has_streams: the handle keeps the
+// c | d | o streams (every GLM handle but the plain model's and the softmax's); beta is read only when it comes from the host
+extern const char* const GLM_POWER_RULE;
+int glm_check_power(int handle, int family, bool has_streams, double beta, bool beta_on_device);
 // ---- K-class softmax regression
 extern const char* const GLM_SOFTMAX_RULE;
 int glm_softmax_layout(int D, int K, int* Dc_out, int* NT_out, int32_t* row_map);

@@ -103,6 +103,7 @@ int new_handle(int kind, int D, int dtype, int device, pbbi_potential** out) {
     for (double& r : p->glm_hier_rank) r = 0.0;
     p->glm_variant = GLM_V_PLAIN;  // (means something on a KIND_GLM handle only, and its builder sets it)
     p->d_glm_metric = nullptr; p->glm_metric_diag = nullptr;
+    p->d_glm_obs0 = nullptr; p->glm_power = 1.0;
     *out = p;
     return PBBI_OK;
 }
@@ -1247,7 +1248,7 @@ int pbbi_potential_destroy(pbbi_potential* pot) {
     DeviceGuard guard(pot->device);
     for (void* p : {pot->d_mean, pot->d_prec, pot->d_frag, pot->d_mean_pad, pot->d_big_PT, pot->d_big_mu,
                     pot->d_sfrag, pot->d_smean, pot->d_params, pot->d_glm_img, pot->d_glm_y, pot->d_glm_obs, pot->d_glm_prior,
-                    pot->d_glm_qimg, pot->d_glm_metric})
+                    pot->d_glm_qimg, pot->d_glm_metric, pot->d_glm_obs0})
         if (p) (void)hipFree(p);
     delete[] pot->glm_metric_diag;
     if (pot->plugin) (void)dlclose(pot->plugin);

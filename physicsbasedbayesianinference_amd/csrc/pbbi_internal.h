@@ -85,6 +85,10 @@ struct pbbi_potential {
     double* glm_metric_diag;  // the D entries as given, on the host (pbbi_potential_get_metric_diag)
     // KIND_CUSTOM: which of the plugin's kernels serves an HMC call on the handle as it is now (pbbi_describe_run).  (Appended.)
     int (*plugin_hmc_route)(const pbbi_potential*, int method, int flags, int unit_mass);
+    // the likelihood power (pbbi_potential_set_likelihood_power, kernels_glm_loglik.hip).  (Appended.)  NULL on a handle that was
+    // never tempered, which then runs the bits it always has
+    void* d_glm_obs0;   // d_glm_obs as built (power 1); d_glm_obs itself then holds c = beta c0 (| d = beta d0)
+    double glm_power;   // the power as set from the host; NaN when it was read from the device
 };
 
 // ---- error plumbing ---------------------------------------------------------

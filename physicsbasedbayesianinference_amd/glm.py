@@ -36,6 +36,10 @@ in its quadratic form (random walks, difference penalties of splines, ICAR), Q_j
 `pot.pointwise(samples)` (every class but `SoftmaxGLM`) puts the draws to use on the device (csrc/kernels_glm_pointwise.hip):
 per observation the log pointwise predictive density, the WAIC penalty and the posterior predictive mean, reduced over all
 draws of a (D, N, S) device view without forming an M x T matrix; a second potential on held-out data takes the same draws.
+
+`pot.loglik(samples)` is the total log-likelihood of each draw (csrc/kernels_glm_loglik.hip), `pot.sample_prior(N)` exact draws
+from a proper prior and `pot.set_likelihood_power(beta)` the potential of p(w) L(w)^beta: the three pieces of
+`smc.LikelihoodTemperedSMC`, which tempers from the prior to the posterior and returns the log marginal likelihood.
 """
 import ctypes as C
 
@@ -339,7 +343,140 @@ def _pointwise(self, samples, ranges=0):
     return PointwiseResult(lse - np.log(T) + k, mean + k, var if T >= 2 else np.full(M, np.nan), mu, T)
 
 
-class GLM(_Metric, Potential):
+def _loglik(self, samples, ranges=0, device_output=False):
+    """The total log-likelihood of every draw, on the device (csrc/kernels_glm_loglik.hip): (N, S), log p(y | draw) with the
+    constants `pointwise_constants` of the observations added -- no prior term.  `samples` as for `pointwise`: the (D, N, S)
+    device view of getSamples(device_output=True) (no copy), a (D, N) state, or NumPy arrays, in the SAMPLER's coordinates
+    (`to_natural` is applied where the potential has one).  `ranges`: 0 lets the library choose into how many ranges the
+    observations are cut; >= 1 fixes it (for a given value the result is bit for bit reproducible).  The likelihood is at power
+    1 whatever `likelihood_power` is.  `device_output=True` keeps the result on the device (a float64 tensor)."""
+    from . import _device
+    if not isinstance(samples, _device.torch().Tensor):
+        # uploaded BEFORE `to_natural`: host and device input then go through the same torch ops and give the same bits
+        q = np.ascontiguousarray(samples, dtype=np.float64)
+        if q.ndim not in (2, 3):
+            raise ValueError("samples must be (Dt, N, S) or (Dt, T)")
+        samples = _device.as_device(q, self.device, np.float64)
+    sdn, S, Dt, N = _pointwise_slabs(self, samples)
+    out = _device.empty((S, N), np.float64, self.device)
+    pot = self._power_target(build=False)
+    try:
+        _lib.call("pbbi_loglik_glm", pot.handle, sdn.data_ptr(), S, Dt, N, int(ranges), out.data_ptr(),
+                  _device.stream_ptr(self.device))
+    except _lib.PbbiError as e:
+        if e.code in (_lib.ERR_INVALID, _lib.ERR_UNSUPPORTED):
+            raise ValueError(str(e)) from None
+        raise
+    k = float(np.sum(pointwise_constants(self.family, self.y, self.weights, getattr(self, "trials", None))))
+    ll = (k - out).t()
+    return ll if device_output else _device.to_numpy(ll.contiguous())
+
+
+def _prior_layout(pot):
+    """(mean, precision, names, D, J, groups) of the rows of the state: what `sample_prior` draws from; the precision of a
+    grouped coefficient is NaN (its scale is exp(t_j))."""
+    Dn = pot.numDimensions
+    D = getattr(pot, "numCoefficients", Dn)
+    J = getattr(pot, "numGroups", 0)
+    groups = getattr(pot, "groups", None)
+    lam = np.full(D, float(pot.prior_precision)) if np.ndim(pot.prior_precision) == 0 else np.array(pot.prior_precision, float)
+    mu = np.zeros(D) if pot.prior_mean is None else np.asarray(pot.prior_mean, dtype=np.float64)
+    names = ["prior_precision[%d]" % d for d in range(D)]
+    if groups is not None:
+        lam = np.where(groups >= 0, np.nan, lam)
+    mean, prec = [mu], [lam]
+    if J:
+        tp = np.asarray(pot.log_scale_prior, dtype=np.float64)
+        mean.append(tp[:, 0]); prec.append(tp[:, 1])
+        names += ["log_scale_prior[%d]" % j for j in range(J)]
+    if getattr(pot, "sampled", False):
+        m_t, l_t = pot.log_dispersion_prior
+        mean.append([m_t]); prec.append([l_t])
+        names.append("log_dispersion_prior")
+    return np.concatenate(mean), np.concatenate(prec), names, D, J, groups
+
+
+def _sample_prior(self, N, seed=0, draw_f64=True):
+    """N exact draws from the prior, in SAMPLER coordinates: a (numDimensions, N) float64 device tensor.  Standard normals z from
+    the device Philox stream (pbbi_philox_normal, PBBI_STREAM_POSITION, iteration 0, chain index n; `draw_f64`: the
+    double-precision draw) transformed with torch ops on the device: a fixed row is mu_d + z / sqrt(lam_d); t_j and a sampled
+    theta are drawn from their (mean, precision) priors; a grouped row is mu_d + exp(t_j) z_d (centred) or z_d (non-centred).
+    Raises ValueError naming the row when the prior is improper: a precision of 0 on a row that uses it, or a `penalty=` group
+    (structured priors, rank deficient or not, are not served)."""
+    from . import _device
+    t = _device.torch()
+    N = int(N)
+    if N < 1:
+        raise ValueError("sample_prior: N must be >= 1")
+    if getattr(self, "penalty", None) is not None:
+        j = [j for j, Q in enumerate(self.penalty) if Q is not None][0]
+        raise ValueError("sample_prior: group %d has a structured prior (penalty[%d]), which is not served" % (j, j))
+    mean, prec, names, D, J, groups = _prior_layout(self)
+    for d, name in enumerate(names):
+        if prec[d] == 0.0:
+            raise ValueError("sample_prior: the prior of row %d is improper (%s = 0)" % (d, name))
+    Dn, dev = self.numDimensions, self.device
+    z = _device.empty((Dn, N), np.float64, dev)
+    stream = _lib.STREAM_POSITION | (_lib.STREAM_DRAW_F64 if draw_f64 else 0)
+    _lib.call("pbbi_philox_normal", int(seed), stream, 0, 0, Dn, N, N, 1.0, None, _lib.F64, dev, z.data_ptr(),
+              _device.stream_ptr(dev))
+    grouped = np.zeros(Dn, dtype=bool) if groups is None else np.r_[groups >= 0, np.zeros(Dn - D, dtype=bool)]
+    sd = np.where(grouped, 1.0, 1.0 / np.sqrt(np.where(grouped, 1.0, prec)))
+    mean_d = _device.as_device(np.ascontiguousarray(mean), dev, np.float64)
+    sd_d = _device.as_device(np.ascontiguousarray(sd), dev, np.float64)
+    q = mean_d[:, None] + z * sd_d[:, None]        # every row that has a (mean, precision) prior of its own
+    if grouped.any():
+        rows = np.flatnonzero(grouped)
+        rows_d = t.as_tensor(rows, device=q.device)
+        if getattr(self, "parametrisation", "centred") == "centred":
+            trow = t.as_tensor(D + np.asarray(groups)[rows].astype(np.int64), device=q.device)
+            q[rows_d] = mean_d[rows_d][:, None] + q[trow].exp() * z[rows_d]
+        else:
+            q[rows_d] = z[rows_d]
+    return q
+
+
+class _Tempered:
+    """The likelihood power of a GLM potential (pbbi_potential_set_likelihood_power): the potential becomes
+    -log [ p(w) L(w)^beta ], the prior-to-posterior path of `smc.LikelihoodTemperedSMC`.  It lives on the handle: every sampler
+    that shares the potential shares it (as it shares the metric).  `loglik` always reports the likelihood at power 1.
+
+    The exception is a plain `GLM` (no weights, offsets, trials or prior vectors): its handle keeps no observation streams and
+    is NEVER tempered.  There only the cached full-model twin `pot._power_target()` carries the power -- `pot(q)`, `pot.handle`
+    and any sampler built on `pot` itself stay at power 1 whatever `pot.likelihood_power` reports; sample the tempered model
+    through the twin, as `smc.LikelihoodTemperedSMC` does."""
+
+    loglik = _loglik
+    sample_prior = _sample_prior
+
+    def _power_target(self, build=True):
+        return self
+
+    def set_likelihood_power(self, beta, beta_dev=None):
+        """beta: finite and > 0 (1 restores the potential bit for bit).  `beta_dev`: the address of a device double to read beta
+        from instead (no host value is involved; `likelihood_power` then reports NaN).  On a plain `GLM` the power is set on the
+        twin `_power_target()` alone (see the class text): the plain handle stays at power 1."""
+        from . import _device
+        if beta_dev is None and not (np.isfinite(beta) and float(beta) > 0.0):
+            raise ValueError("the likelihood power must be finite and > 0 (got %r)" % (beta,))
+        pot = self._power_target()
+        try:
+            _lib.call("pbbi_potential_set_likelihood_power", pot.handle, float(beta), beta_dev, _device.stream_ptr(self.device))
+        except _lib.PbbiError as e:
+            if e.code in (_lib.ERR_INVALID, _lib.ERR_UNSUPPORTED):
+                raise ValueError(str(e)) from None
+            raise
+
+    @property
+    def likelihood_power(self):
+        """The power as last set from the host (1.0 when never set; NaN when it was last read from the device); for a plain `GLM`
+        the power of its twin."""
+        out = C.c_double(1.0)
+        _lib.call("pbbi_potential_get_likelihood_power", self._power_target(build=False).handle, C.byref(out))
+        return out.value
+
+
+class GLM(_Tempered, _Metric, Potential):
     """-log posterior of the weights of a generalised linear model (see the module text).
 
         pot = GLM(X, y, family="logistic", prior_precision=1.0)
@@ -364,13 +501,36 @@ class GLM(_Metric, Potential):
         self.X, self.y, self.family, self.prior_precision = X, y, family, lam
         self.prior_mean, self.weights, self.offset, self.trials = mu, a, o, n
         M, D = X.shape
-        if all(v is None for v in (mu, a, o, n)) and isinstance(lam, float):
+        self._plain = all(v is None for v in (mu, a, o, n)) and isinstance(lam, float)
+        self._twin = None
+        if self._plain:
             _lib.call("pbbi_potential_create_glm", D, M, _dptr(X), _dptr(y),
                       FAMILIES[family], lam, self._dt, self.device, C.byref(self._handle))
         else:
             lam_d = np.full(D, lam) if isinstance(lam, float) else lam
             _lib.call("pbbi_potential_create_glm_ex", D, M, _dptr(X), _dptr(y), FAMILIES[family], _dptr(a), _dptr(o),
                       _dptr(n), _dptr(lam_d), _dptr(mu), self._dt, self.device, C.byref(self._handle))
+
+    def _power_target(self, build=True):
+        """The potential whose handle carries the likelihood power: this one, or -- the plain model's handle keeps no observation
+        streams -- its full-model twin (weights = 1: the same U to rounding, on the full model's kernels), built and cached when
+        the potential is first tempered; the twin inherits the metric."""
+        if not self._plain:
+            return self
+        if self._twin is None:
+            if not build:
+                return self
+            self._twin = GLM(self.X, self.y, self.family, self.prior_precision, weights=np.ones(self.y.size),
+                             dtype=self.dtype, device=self.device)
+            m = self.metric
+            if m is not None:
+                self._twin.set_metric(m)
+        return self._twin
+
+    def set_metric(self, diag):
+        super().set_metric(diag)
+        if self._twin is not None:
+            self._twin.set_metric(diag)
 
 
 def softmax_layout(D, K):
@@ -507,7 +667,7 @@ def _dispersion_args(dispersion, log_dispersion_prior):
     return sample, (None if sample else disp), theta, ((m_t, l_t) if sample else None)
 
 
-class DispersionGLM(_Metric, Potential):
+class DispersionGLM(_Tempered, _Metric, Potential):
     """-log posterior of a GLM whose family has a free dispersion, with theta = log(dispersion):
 
         gaussian     y_i ~ N(eta_i, sigma^2 / a_i), sigma = exp(theta):
@@ -772,7 +932,7 @@ def pack_penalty(penalty, J):
     return out.reshape(DP // 16, DP // 8, 64, 2)
 
 
-class HierarchicalGLM(_Metric, Potential):
+class HierarchicalGLM(_Tempered, _Metric, Potential):
     """-log posterior of a GLM (family "logistic" or "poisson", the full model of `GLM`: weights a_i, trials n_i,
     offsets o_i, eta_i = x_i . w + o_i) in which blocks of coefficients share a prior scale that is sampled:
 

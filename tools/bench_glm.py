@@ -54,6 +54,11 @@ same four vectors from torch ops on the same device (chunked matmul, the link el
 draws: pointwise_torch), alternating in one process, at the two shapes of SHAPES with --slabs 8 slabs of N draws.  It
 writes profiles/glm_pointwise_bench.json.
 
+--model loglik times pbbi_loglik_glm (csrc/kernels_glm_loglik.hip: the likelihood energy of each of the S x N draws, both
+launches, ranges = 0) on the plain logistic model against the same vector from torch ops on the same device (chunked matmul, the
+link elementwise, a sum over the observations: loglik_torch), alternating in one process, at the same two shapes and slabs.  It
+writes profiles/glm_loglik_bench.json.
+
 usage: tools/bench_glm.py [--shape small|large|all] [--K 32] [--repeats 5] [--glm-only] [--out FILE]
        tools/bench_glm.py --model rich [--custom] [--label NAME] [--shape ...]
        tools/bench_glm.py --model softmax [--shape k3|k8|k8large|all]
@@ -61,6 +66,7 @@ usage: tools/bench_glm.py [--shape small|large|all] [--K 32] [--repeats 5] [--gl
        tools/bench_glm.py --model hierq [--shape small|large|all]
        tools/bench_glm.py --model hierdisp [--shape small|large|all]
        tools/bench_glm.py --model pointwise [--shape small|large|all] [--slabs 8] [--repeats 5]
+       tools/bench_glm.py --model loglik [--shape small|large|all] [--slabs 8] [--repeats 5]
        tools/bench_glm.py --model hier [--parametrisation centred|noncentred] [--shape small|large|all]  (noncentred: also mid)
 """
 import argparse
@@ -932,6 +938,74 @@ def bench_pointwise(name, M, D, N, S, repeats, warm):
                 max_rel_difference_kernel_vs_torch=agree)
 
 
+def loglik_torch(X, y, sdn, chunk):
+    """The baseline of --model loglik: the same (S, N) vector from torch ops on the same device -- matmul over chunks of
+    `chunk` draws (an M x chunk matrix at a time), the logistic link elementwise, a sum over the observations."""
+    S, D, N = sdn.shape
+    out = torch.empty((S, N), dtype=torch.float64, device=sdn.device)
+    for s in range(S):
+        for n0 in range(0, N, chunk):
+            eta = X @ sdn[s, :, n0:n0 + chunk]
+            out[s, n0:n0 + chunk] = (torch.nn.functional.softplus(eta) - y[:, None] * eta).sum(dim=0)
+    return out
+
+
+def bench_loglik(name, M, D, N, S, repeats, warm):
+    """pbbi_loglik_glm (both launches, ranges = 0) against loglik_torch on S slabs of N draws of the plain logistic model,
+    alternating in one process; both sides produce the likelihood energy of all S * N draws.  A timed window is several calls
+    (at least a quarter of a second) and one synchronisation; times are per call."""
+    from physicsbasedbayesianinference_amd import _device
+    X, y, w, rs = problem(M, D)
+    pot = P.GLM(X, y)
+    sdn = torch.from_numpy(np.ascontiguousarray(w[None, :, None] + 0.3 * rs.standard_normal((S, D, N)))).to("cuda:0")
+    Xd, yd = torch.from_numpy(X).to("cuda:0"), torch.from_numpy(y).to("cuda:0")
+    chunk = N
+    while M * chunk > 2 ** 25 and chunk % 2 == 0:     # an M x chunk matrix of at most 256 MiB (N is a power of two)
+        chunk //= 2
+    out = torch.empty((S, N), dtype=torch.float64, device="cuda:0")
+    st = _device.stream_ptr(0)
+
+    def kernel():
+        _lib.call("pbbi_loglik_glm", pot.handle, sdn.data_ptr(), S, D, N, 0, out.data_ptr(), st)
+        return out
+
+    def baseline():
+        return loglik_torch(Xd, yd, sdn, chunk)
+
+    sides = {"kernel": kernel, "torch": baseline}
+    for _ in range(warm):
+        got = [f().cpu().numpy() for f in sides.values()]
+    agree = float(np.max(np.abs(got[0] - got[1])) / max(1.0, float(np.max(np.abs(got[1])))))
+    # one call is a millisecond or ten: a timed window is `calls` calls back to back and one synchronisation, at least a
+    # quarter of a second of the faster side (sized from one timed call after the warm-up); the seconds recorded are per call
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    kernel()
+    torch.cuda.synchronize()
+    calls = max(1, int(np.ceil(0.25 / (time.perf_counter() - t0))))
+    series = {k: [] for k in sides}
+    for i in range(repeats):
+        for k, f in sides.items():   # alternating
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                f()
+            torch.cuda.synchronize()
+            series[k].append((time.perf_counter() - t0) / calls)
+            print(f"# {name} repeat {i} {k}: {series[k][-1]:.6f} s per call ({calls} calls)", flush=True)
+    tk, tt = np.array(series["kernel"]), np.array(series["torch"])
+    DP, T = glm.padded_dim(D), S * N
+    # (the rates are over CALL time: both launches and the stream-ordered allocation and release of the partials, not kernel time)
+    return dict(shape=name, M=M, D=D, DP=DP, slabs=S, chains=N, draws=T, torch_chunk=chunk, calls_per_window=calls,
+                kernel_seconds=series["kernel"],
+                torch_seconds=series["torch"], kernel_median_seconds=float(np.median(tk)), torch_median_seconds=float(np.median(tt)),
+                kernel_range_seconds=[float(tk.min()), float(tk.max())], torch_range_seconds=[float(tt.min()), float(tt.max())],
+                kernel_values_per_s_over_call_time=float(M * T / np.median(tk)),
+                kernel_executed_tflops_over_call_time=float(2.0 * M * DP * T / np.median(tk) / 1e12),
+                ratio_median=float(np.median(tt) / np.median(tk)), ratio_worst_case=float(tt.min() / tk.max()),
+                max_rel_difference_kernel_vs_torch=agree)
+
+
 def bench_shape(name, M, D, N, h, L, K, repeats, warm, glm_only):
     X, y, w, rs = problem(M, D)
     q0 = np.ascontiguousarray(w[:, None] + 0.3 * rs.standard_normal((D, N)))
@@ -975,16 +1049,17 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=None, help="default 4 (--model softmax: per shape)")
     ap.add_argument("--glm-only", action="store_true")
     ap.add_argument("--model", default="plain", choices=["plain", "rich", "softmax", "dispersion", "hier", "hierq", "hierdisp",
-                                                         "pointwise"])
-    ap.add_argument("--slabs", type=int, default=8, help="--model pointwise: slabs of N draws")
+                                                         "pointwise", "loglik"])
+    ap.add_argument("--slabs", type=int, default=8, help="--model pointwise / loglik: slabs of N draws")
     ap.add_argument("--parametrisation", default="centred", choices=["centred", "noncentred"],
                     help="--model hier: noncentred times the non-centred kernel against the centred one and the plugin")
     ap.add_argument("--custom", action="store_true", help="--model rich: also the full model as a CustomPotential")
     ap.add_argument("--label", default="rich_vs_plain", help="--model rich: key of the record in the output file")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.model == "pointwise":
-        a.out = a.out or os.path.join(ROOT, "profiles", "glm_pointwise_bench.json")
+    if a.model in ("pointwise", "loglik"):
+        bench_pw = bench_pointwise if a.model == "pointwise" else bench_loglik
+        a.out = a.out or os.path.join(ROOT, "profiles", "glm_%s_bench.json" % a.model)
         names = list(SHAPES) if a.shape == "all" else [a.shape]
         results = []
         if os.path.exists(a.out) and a.shape != "all":   # one shape per call: keep the other's record
@@ -992,8 +1067,8 @@ if __name__ == "__main__":
                 results = [r for r in json.load(f)["results"] if r["shape"] not in names]
         for n in names:
             sh = SHAPES[n]
-            res = bench_pointwise(n, sh["M"], sh["D"], sh["N"], a.slabs, 5 if a.repeats is None else a.repeats,
-                                  2 if a.warmup is None else a.warmup)
+            res = bench_pw(n, sh["M"], sh["D"], sh["N"], a.slabs, 5 if a.repeats is None else a.repeats,
+                           2 if a.warmup is None else a.warmup)
             print(json.dumps(res))
             results.append(res)
             with open(a.out, "w") as f:
