@@ -8,9 +8,6 @@
 #include <cstring>
 #include <vector>
 
-static bool glm_disp(int fam) { return fam == PBBI_GLM_GAUSSIAN || fam == PBBI_GLM_NEGBINOMIAL; }
-static bool glm_canonical(int fam) { return fam == PBBI_GLM_LOGISTIC || fam == PBBI_GLM_POISSON; }
-
 // An instantiation ships only if it builds without scratch (profiles/glm_*_resources.txt).  The frame's widest kernel has 128
 // rows.  The full model's kernels at 128 rows already fill the register file, so nothing built on them has one there: not the
 // negative binomial (the constants of its exp, log and two series), not the hierarchical priors in any form (172 and 180 bytes
@@ -386,10 +383,15 @@ const char* const GLM_POINTWISE_RULE = "pbbi_pointwise_glm serves the handles of
                                        "_glm_dispersion, _glm_hier, _glm_hier_ex, _glm_hier_q and _glm_hier_dispersion "
                                        "(families logistic, poisson, gaussian, negbinomial; float64)";
 
-int glm_check_pointwise(int handle, int family, int state_dim, const void* sdn, int S, int Dt, int64_t N, int ranges,
-                        bool want_var) {
+// The rules of the two entries that take draws, in the order both state them.  Each entry has one rule of its own, at its own
+// place: pbbi_loglik_glm's output (out_null: never set by pbbi_pointwise_glm, whose four outputs are all optional) and
+// pbbi_pointwise_glm's var_out (want_var: never set by pbbi_loglik_glm).  `entry` is what pbbi_loglik_glm puts before the rules
+// on the handle's kind ("pbbi_loglik_glm: "); pbbi_pointwise_glm puts nothing there.
+static int glm_check_draws(const char* entry, int handle, int family, int state_dim, const void* sdn, bool out_null, int S,
+                           int Dt, int64_t N, int ranges, bool want_var) {
     if (handle == 0) return pbbi_fail(PBBI_ERR_INVALID, "potential handle is NULL");
     if (!sdn) return pbbi_fail(PBBI_ERR_INVALID, "samples is NULL");
+    if (out_null) return pbbi_fail(PBBI_ERR_INVALID, "ulik_out is NULL");
     if (S < 1) return pbbi_fail(PBBI_ERR_INVALID, "S must be >= 1 (S = " + std::to_string(S) + ")");
     if (N < 1) return pbbi_fail(PBBI_ERR_INVALID, "N must be >= 1 (N = " + std::to_string(N) + ")");
     if (want_var && S == 1 && N == 1)  // S * N < 2 without forming the product
@@ -398,39 +400,26 @@ int glm_check_pointwise(int handle, int family, int state_dim, const void* sdn, 
         return pbbi_fail(PBBI_ERR_INVALID, "ranges must be 0 (the library chooses) or 1 .. 65535 (ranges = " +
                                                std::to_string(ranges) + ")");
     if (handle != 1)
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string("not a GLM handle: ") + GLM_POINTWISE_RULE);
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string(entry) + "not a GLM handle: " + GLM_POINTWISE_RULE);
     if (family == PBBI_GLM_SOFTMAX)
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string("a softmax handle is not served: ") + GLM_POINTWISE_RULE);
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string(entry) + "a softmax handle is not served: " + GLM_POINTWISE_RULE);
     if (!glm_canonical(family) && !glm_disp(family))
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string("unknown GLM family: ") + GLM_POINTWISE_RULE);
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string(entry) + "unknown GLM family: " + GLM_POINTWISE_RULE);
     if (Dt < state_dim)
         return pbbi_fail(PBBI_ERR_INVALID, "Dt must be at least the handle's state dimension (Dt = " + std::to_string(Dt) +
                                                ", state dimension " + std::to_string(state_dim) + ")");
     return PBBI_OK;
 }
 
+int glm_check_pointwise(int handle, int family, int state_dim, const void* sdn, int S, int Dt, int64_t N, int ranges,
+                        bool want_var) {
+    return glm_check_draws("", handle, family, state_dim, sdn, false, S, Dt, N, ranges, want_var);
+}
+
 // ---- the likelihood energy of each draw -------------------------------------------------------------------------
 int glm_check_loglik(int handle, int family, int state_dim, const void* sdn, const void* out, int S, int Dt, int64_t N,
                      int ranges) {
-    if (handle == 0) return pbbi_fail(PBBI_ERR_INVALID, "potential handle is NULL");
-    if (!sdn) return pbbi_fail(PBBI_ERR_INVALID, "samples is NULL");
-    if (!out) return pbbi_fail(PBBI_ERR_INVALID, "ulik_out is NULL");
-    if (S < 1) return pbbi_fail(PBBI_ERR_INVALID, "S must be >= 1 (S = " + std::to_string(S) + ")");
-    if (N < 1) return pbbi_fail(PBBI_ERR_INVALID, "N must be >= 1 (N = " + std::to_string(N) + ")");
-    if (ranges < 0 || ranges > 65535)
-        return pbbi_fail(PBBI_ERR_INVALID, "ranges must be 0 (the library chooses) or 1 .. 65535 (ranges = " +
-                                               std::to_string(ranges) + ")");
-    if (handle != 1)
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string("pbbi_loglik_glm: not a GLM handle: ") + GLM_POINTWISE_RULE);
-    if (family == PBBI_GLM_SOFTMAX)
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string("pbbi_loglik_glm: a softmax handle is not served: ") +
-                                                   GLM_POINTWISE_RULE);
-    if (!glm_canonical(family) && !glm_disp(family))
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string("pbbi_loglik_glm: unknown GLM family: ") + GLM_POINTWISE_RULE);
-    if (Dt < state_dim)
-        return pbbi_fail(PBBI_ERR_INVALID, "Dt must be at least the handle's state dimension (Dt = " + std::to_string(Dt) +
-                                               ", state dimension " + std::to_string(state_dim) + ")");
-    return PBBI_OK;
+    return glm_check_draws("pbbi_loglik_glm: ", handle, family, state_dim, sdn, out == nullptr, S, Dt, N, ranges, false);
 }
 
 // ---- the likelihood power ---------------------------------------------------------------------------------------

@@ -26,6 +26,11 @@ enum GlmVariant {
 enum { GLM_TERM_WEIGHTS = 1, GLM_TERM_OFFSET = 2, GLM_TERM_TRIALS = 4, GLM_TERM_PRIOR_VECTOR = 8, GLM_TERM_PRIOR_MEAN = 16,
        GLM_TERM_PRIOR_FLAT = 32 };
 
+// The families by the shape of their link: the canonical ones (b(eta) alone) and the ones with a dispersion theta.  The one
+// statement of both, for the rules of glm_host.cpp and for the kernels' `if constexpr` (glm_family_dev.h, kernels_glm.hip).
+constexpr bool glm_disp(int fam) { return fam == PBBI_GLM_GAUSSIAN || fam == PBBI_GLM_NEGBINOMIAL; }
+constexpr bool glm_canonical(int fam) { return fam == PBBI_GLM_LOGISTIC || fam == PBBI_GLM_POISSON; }
+
 // The largest state dimension (every sampled row: coefficients, group log-scales, a sampled log-dispersion) the kernels of a
 // variant serve for a family; 0 = nothing shipped.  The one statement of it: the create entries and the launch read this.
 int glm_max_dim(int variant, int family);

@@ -97,11 +97,13 @@
 //
 // This file holds the device code, the kernel-argument structs, glm_check, the launch switch and the entry points.  Which
 // shapes ship, the argument rules and the packers are glm_host.cpp (no HIP there); the builders that upload what the packers
-// make are pbbi_api.hip's; glm_args.h fills the arguments that come from a call.
+// make are pbbi_api.hip's; glm_args.h fills the arguments that come from a call.  The family arithmetic (glm_link, glm_link_rich,
+// glm_link_disp, glm_disp_chain, glm_psi, glm_lgamma) is glm_family_dev.h's, shared with the kernels that take draws.
 #include <cmath>
 #include <type_traits>
 
 #include "glm_args.h"
+#include "glm_family_dev.h"
 #include "kernels_dense_dev.h"
 #include "pbbi_chain.h"
 
@@ -154,7 +156,6 @@ struct GlmPrmHierDisp : GlmPrmHier {
 struct GlmPrmHierQ : GlmPrmHier {
     const double* qimg;  // the (DP x DP) penalty in the first product's A-fragment order, DP / 16 blocks of DP * 16 doubles
 };
-constexpr bool glm_disp(int fam) { return fam == PBBI_GLM_GAUSSIAN || fam == PBBI_GLM_NEGBINOMIAL; }
 // HIER of k_glm: no hierarchical prior, the centred parametrisation (the chain holds w_d), the non-centred one (z_d), the
 // centred one with a penalty matrix in each group's quadratic form
 enum { GLM_HIER_NONE = 0, GLM_HIER_CENTRED = 1, GLM_HIER_NC = 2, GLM_HIER_Q = 3 };
@@ -185,113 +186,6 @@ struct GlmCfg {
     static constexpr int OBS = CB * 16;                // observations per chunk
     static_assert(3 * OBS <= BLOCK, "one thread per staged value of c | d | o");
 };
-
-// b(eta) - y eta and b'(eta) - y of one observation
-template <int FAM>
-__device__ __forceinline__ void glm_link(double eta, double yv, bool want_u, double& resid, double& uterm) {
-    if constexpr (FAM == PBBI_GLM_LOGISTIC) {
-        const double e = exp(-fabs(eta));
-        const double inv = 1.0 / (1.0 + e);
-        resid = (eta >= 0.0 ? inv : e * inv) - yv;
-        uterm = 0.0;
-        if (want_u) uterm = ((eta > 0.0 ? eta : 0.0) + log1p(e)) - yv * eta;
-    } else {
-        const double e = exp(eta);
-        resid = e - yv;
-        uterm = e - yv * eta;
-    }
-}
-
-// the full model's c b(eta) - d eta and c b'(eta) - d
-template <int FAM>
-__device__ __forceinline__ void glm_link_rich(double eta, double cv, double dv, bool want_u, double& resid,
-                                              double& uterm) {
-    if constexpr (FAM == PBBI_GLM_LOGISTIC) {
-        const double e = exp(-fabs(eta));
-        const double inv = 1.0 / (1.0 + e);
-        resid = cv * (eta >= 0.0 ? inv : e * inv) - dv;
-        uterm = 0.0;
-        if (want_u) uterm = cv * ((eta > 0.0 ? eta : 0.0) + log1p(e)) - dv * eta;
-    } else {
-        const double e = exp(eta);
-        resid = cv * e - dv;
-        uterm = cv * e - dv * eta;
-    }
-}
-
-// psi and log Gamma for x > 0: the recurrences psi(x) = psi(x + 1) - 1/x and lgamma(x) = lgamma(x + 1) - log x, two steps
-// at a time (one division per pair, at most three pairs), up to an argument >= 6, then the asymptotic series: psi
-// through x^-14 (the first term left out is 3617 / (8160 x^16): 1.6e-13 at 6), Stirling's through x^-13 (3617 / (122400
-// x^15): 6e-14 at 6).  The library's lgamma, inlined once per accumulator register, costs these kernels their registers.
-__device__ __forceinline__ double glm_psi(double x) {
-    double acc = 0.0;
-    while (x < 6.0) {
-        acc -= (2.0 * x + 1.0) / (x * (x + 1.0));  // 1/x + 1/(x + 1)
-        x += 2.0;
-    }
-    const double r = 1.0 / x, r2 = r * r;
-    const double tail = r2 * (1.0 / 12 - r2 * (1.0 / 120 - r2 * (1.0 / 252 - r2 * (1.0 / 240 - r2 * (1.0 / 132 -
-                        r2 * (691.0 / 32760 - r2 * (1.0 / 12)))))));
-    return acc + ((log(x) - 0.5 * r) - tail);
-}
-__device__ __forceinline__ double glm_lgamma(double x) {
-    double prod = 1.0;
-    while (x < 6.0) {
-        prod *= x * (x + 1.0);
-        x += 2.0;
-    }
-    const double r = 1.0 / x, r2 = r * r;
-    const double tail = r * (1.0 / 12 - r2 * (1.0 / 360 - r2 * (1.0 / 1260 - r2 * (1.0 / 1680 - r2 * (1.0 / 1188 -
-                        r2 * (691.0 / 360360 - r2 * (1.0 / 156)))))));
-    return ((((x - 0.5) * log(x) - x) + 0.91893853320467274178) + tail) - log(prod);
-}
-
-// what a dispersion family forms once per chain and gradient evaluation
-//   gaussian:     a = tau = exp(-2 theta)
-//   negbinomial:  a = phi = exp(theta), b = psi(phi), c = lgamma(phi) (an evaluation that wants U only)
-struct GlmDispChain { double theta, a, b, c; };
-
-template <int FAM>
-__device__ __forceinline__ GlmDispChain glm_disp_chain(double theta, bool want_u) {
-    GlmDispChain k{theta, 0.0, 0.0, 0.0};
-    if constexpr (FAM == PBBI_GLM_GAUSSIAN) {
-        k.a = exp(-2.0 * theta);
-    } else {
-        k.a = exp(theta);
-        k.b = glm_psi(k.a);
-        if (want_u) k.c = glm_lgamma(k.a);
-    }
-    return k;
-}
-
-// the dispersion families' U_i, dU_i/deta and dU_i/dtheta (cv = a_i, yv = y_i)
-template <int FAM>
-__device__ __forceinline__ void glm_link_disp(double eta, double cv, double yv, const GlmDispChain& k, bool want_u,
-                                              double& resid, double& uterm, double& tterm) {
-    if constexpr (FAM == PBBI_GLM_GAUSSIAN) {
-        const double r = yv - eta;
-        const double tr = k.a * r;
-        const double trr = tr * r;  // tau (y - eta)^2
-        resid = -(cv * tr);
-        tterm = cv * (1.0 - trr);
-        uterm = cv * (0.5 * trr + k.theta);
-    } else {
-        // z = eta - theta: s = sigmoid(z), sp = softplus(z); logaddexp(eta, theta) = theta + sp, so
-        // -phi theta - y eta + (y + phi) logaddexp = (y + phi) sp - y z
-        const double z = eta - k.theta;
-        const double e = exp(-fabs(z));
-        const double ope = 1.0 + e;  // in [1, 2]: log(ope) is log1p(e) to 1.2e-16 ABSOLUTE, which is what sp needs, and
-        const double inv = 1.0 / ope;  // keeps these kernels to one logarithm's constants
-        const double s = z >= 0.0 ? inv : e * inv;
-        const double s1 = z >= 0.0 ? e * inv : inv;  // 1 - s
-        const double sp = (z > 0.0 ? z : 0.0) + log(ope);
-        const double yp = yv + k.a;
-        resid = cv * (yp * s - yv);
-        tterm = cv * (k.a * (((k.b - glm_psi(yp)) + sp) - s) + yv * s1);
-        uterm = 0.0;
-        if (want_u) uterm = cv * (((k.c - glm_lgamma(yp)) + yp * sp) - yv * z);
-    }
-}
 
 // hierarchical prior: the precision of a row from the lam slot of its plds entry -- lam >= 0 is a fixed row's own,
 // -(j + 1) marks a member of group j, whose precision is tau_j = exp(-2 t_j) of this chain

@@ -244,9 +244,10 @@ def test_loglik_non_finite_draws(P, lib):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["logistic", "poisson_full"])
+@pytest.mark.parametrize("name", ["logistic", "poisson_full", "gaussian_held"])
 def test_loglik_device_against_device(P, lib, name):
-    """ulik + prior (NumPy) = U of pbbi_potential_eval on the same draws, on the plain and the full model."""
+    """ulik + prior (NumPy) = U of pbbi_potential_eval on the same draws, on the plain and the full model and on a dispersion
+    family (held: the state is the coefficients, under the full model's Gaussian prior)."""
     make, sp, sdn, nat, _ = kind(name)
     pot = make(P)
     W = t_pw.flat(nat)

@@ -496,10 +496,11 @@ def test_pointwise_non_finite_draws(P, lib):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["logistic", "poisson_full"])
+@pytest.mark.parametrize("name", ["logistic", "poisson_full", "gaussian_held"])
 def test_pointwise_device_against_device(P, lib, name):
-    """sum_i mean_i = -mean_t (U_t - prior_t): U from pbbi_potential_eval on the same draws, the prior on the host."""
-    make, sp, sdn, _ = kind(name)
+    """sum_i mean_i = -mean_t (U_t - prior_t): U from pbbi_potential_eval on the same draws, the prior on the host.
+    gaussian_held: a dispersion family (held: the state is the coefficients, under the full model's Gaussian prior)."""
+    make, sp, sdn = _dispersion("gaussian", False) if name == "gaussian_held" else kind(name)[:3]
     pot = make(P)
     W = flat(sdn)
     if name == "logistic":
