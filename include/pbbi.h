@@ -222,33 +222,37 @@ int pbbi_potential_create_glm_softmax(int D, int K, int64_t M, const double* X, 
 /* host only, no GPU: the padded class size, the tile count and (row_map != NULL) the external row of each of the
    NT*16 internal rows, -1 for padding */
 int pbbi_glm_softmax_layout(int D, int K, int* Dc_out, int* NT_out, int32_t* row_map);
-/* The two families with a free dispersion, on the full model's kernel frame (csrc/kernels_glm.hip, FAM = 3, 4 of
+/* The three families with a free dispersion, on the full model's kernel frame (csrc/kernels_glm.hip, FAM = 3, 4, 5 of
  * k_glm<NT, FAM, true>).  theta is the LOG-dispersion, a_i >= 0 observation weights, o_i offsets, eta_i = x_i . w + o_i;
  * constants that depend on neither w nor theta are dropped:
  *     gaussian     sigma = exp(theta), tau = exp(-2 theta), y real:
  *                  U_i = a_i [ 0.5 tau (y_i - eta_i)^2 + theta ]
  *     negbinomial  NB2, log link: mu_i = exp(eta_i), phi = exp(theta), Var = mu + mu^2 / phi, y non-negative integers:
  *                  U_i = a_i [ lgamma(phi) - lgamma(y_i + phi) - phi theta - y_i eta_i + (y_i + phi) logaddexp(eta_i, theta) ]
+ *     gamma        log link: mu_i = exp(eta_i), shape alpha = exp(theta), Var = mu^2 / alpha, y > 0; with z_i = eta_i - log y_i
+ *                  U_i = a_i [ lgamma(alpha) - alpha theta + alpha (z_i + exp(-z_i)) ]      (the dropped constant: + a_i log y_i)
+ *                  alpha held at 1 is exponential regression
  *     U = sum_i U_i + 0.5 sum_d lam_d (w_d - mu_d)^2  [ + 0.5 lam_theta (theta - m_theta)^2  when theta is sampled ]
  * sample != 0: theta is the LAST component of the chain's state, the handle's dimension is D + 1 and lam / mu hold D + 1
  * entries (the last: precision and mean of theta's Gaussian prior; mu may be NULL = 0); `theta` is ignored.
  * sample == 0: the dispersion is held at exp(theta) (theta finite), the state is w alone (dimension D), lam / mu hold D
  * entries.  The design image on the device is that of [X | 0] at the padded state dimension: the theta row meets a
  * zero column, so eta does not see it; its gradient, sum_i dU_i / dtheta, is reduced per chain in the kernel.  The
- * device keeps c_i = a_i, d_i = y_i (raw, not a_i y_i) and o_i; a row of weight 0 contributes exactly 0.  weights /
+ * device keeps c_i = a_i, d_i = y_i (raw, not a_i y_i; gamma: d_i = log y_i, taken once on the host -- the kernel needs
+ * nothing else of y) and o_i; a row of weight 0 contributes exactly 0.  weights /
  * offset: M doubles or NULL = all 1 / all 0.  fp64 only; the state dimension (D + 1 when sampled) is at most 128 for
- * gaussian and at most 64 for negbinomial, whose kernel for 65 .. 128 rows cannot be built without register spills to
- * memory and is not shipped (PBBI_ERR_UNSUPPORTED).  Violations of the value rules return PBBI_ERR_INVALID before
+ * gaussian and gamma and at most 64 for negbinomial, whose kernel for 65 .. 128 rows cannot be built without register
+ * spills to memory and is not shipped (PBBI_ERR_UNSUPPORTED).  Violations of the value rules return PBBI_ERR_INVALID before
  * anything is allocated.  The handle is a GLM handle (same calls served and refused); pbbi_describe_run names the
  * family.  pbbi_potential_create_glm / _glm_ex do not accept these families. */
-enum { PBBI_GLM_GAUSSIAN = 3, PBBI_GLM_NEGBINOMIAL = 4 };
+enum { PBBI_GLM_GAUSSIAN = 3, PBBI_GLM_NEGBINOMIAL = 4, PBBI_GLM_GAMMA = 5 };
 int pbbi_potential_create_glm_dispersion(int D, int64_t M, const double* X, const double* y, int family,
                                          const double* weights, const double* offset, const double* lam,
                                          const double* mu, int sample, double theta, int dtype, int device,
                                          pbbi_potential** out);
 /* The three observation streams pbbi_potential_create_glm_dispersion uploads, on the HOST (touches no device, checks the
- * same rules): *len_out <- their total length, as for pbbi_glm_pack_observations; with `out` non-NULL c = a | d = y | o,
- * each stream zero padded past M. */
+ * same rules): *len_out <- their total length, as for pbbi_glm_pack_observations; with `out` non-NULL c = a | d = y | o
+ * (gamma: d = log y), each stream zero padded past M. */
 int pbbi_glm_pack_observations_dispersion(int64_t M, int family, const double* y, const double* weights,
                                           const double* offset, double* out, int64_t out_len, int64_t* len_out);
 /* Hierarchical priors with sampled group scales (random effects, a learned ridge penalty) on the full model's kernel frame
@@ -377,12 +381,12 @@ int pbbi_glm_pack_penalty(int D, int J, const double* penalty, double* out, int6
 /* What a GLM handle says about T = S * N draws of its state, per observation, reduced over the draws on the device
  * (csrc/kernels_glm_pointwise.hip: eta = X W for 16 draws at a time on the fp64 matrix cores, from the first copy of the
  * packed design image).  ll_it = minus the per-observation term of the handle's potential at draw t -- the log-likelihood of
- * observation i WITHOUT the terms that depend on no parameter (a log C(n, y); -a lgamma(y + 1); -a/2 log 2 pi), which the
+ * observation i WITHOUT the terms that depend on no parameter (a log C(n, y); -a lgamma(y + 1); -a/2 log 2 pi; gamma: -a log y), which the
  * caller adds -- and exactly 0 for an observation of weight 0.  Outputs, each (M) doubles on the device or NULL:
  *     lse_out[i]  = log sum_t exp(ll_it)          (lppd_i = lse_i - log T + the constant of observation i)
  *     mean_out[i] = mean_t ll_it
  *     var_out[i]  = the unbiased variance over t of ll_it (the WAIC penalty of observation i); needs S * N >= 2
- *     mu_out[i]   = mean_t of the fitted mean: sigmoid(eta_it) (logistic, per trial), exp(eta_it) (poisson, negbinomial),
+ *     mu_out[i]   = mean_t of the fitted mean: sigmoid(eta_it) (logistic, per trial), exp(eta_it) (poisson, negbinomial, gamma),
  *                   eta_it (gaussian), eta_it = x_i . w_t + o_i -- for every observation, whatever its weight
  * samples_sdn: S contiguous (Dt, N) slabs of doubles (the pbbi_sample_moments convention) on the handle's device, Dt >= the
  * handle's state dimension; rows past it are ignored.  The draws are on the NATURAL scale: for a non-centred handle (w; t),

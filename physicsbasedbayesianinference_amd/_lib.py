@@ -15,7 +15,7 @@ F64, F32 = 0, 1
 LEAPFROG, STORMER_VERLET = 0, 1
 GLM_LOGISTIC, GLM_POISSON = 0, 1
 GLM_SOFTMAX = 2         # pbbi_potential_create_glm_softmax only
-GLM_GAUSSIAN, GLM_NEGBINOMIAL = 3, 4   # pbbi_potential_create_glm_dispersion only
+GLM_GAUSSIAN, GLM_NEGBINOMIAL, GLM_GAMMA = 3, 4, 5   # pbbi_potential_create_glm_dispersion (_hier_dispersion: 3, 4)
 HIER_CENTRED, HIER_NONCENTRED = 0, 1    # pbbi_potential_create_glm_hier_ex
 ERR_INVALID, ERR_UNSUPPORTED, ERR_HIP = -1, -2, -3
 COMPAT_P_FROM_OLDQ = 1

@@ -64,13 +64,26 @@ static void design_and_observations() {
             EXPECT(out[(size_t)(glm_obs_len(M) / 3 + M - 1)] == (opt ? w[(size_t)(M - 1)] : 1.0));  // d = a y, y = 1
             EXPECT(glm_check_obs_disp(M, PBBI_GLM_GAUSSIAN, y.get(), wp, op) == PBBI_OK);
             EXPECT(glm_check_obs_disp(M, PBBI_GLM_NEGBINOMIAL, y.get(), wp, op) == PBBI_OK);
-            glm_pack_obs_disp(M, y.get(), wp, op, out.get());
+            glm_pack_obs_disp(M, PBBI_GLM_NEGBINOMIAL, y.get(), wp, op, out.get());
             EXPECT(out[(size_t)(glm_obs_len(M) - 1)] == 0.0);  // the offsets' padding
+            EXPECT(out[(size_t)(glm_obs_len(M) / 3 + M - 1)] == 1.0);  // d = y (raw), y = 1
+            EXPECT(glm_check_obs_disp(M, PBBI_GLM_GAMMA, y.get(), wp, op) == PBBI_OK);
+            glm_pack_obs_disp(M, PBBI_GLM_GAMMA, y.get(), wp, op, out.get());
+            EXPECT(out[(size_t)(glm_obs_len(M) / 3 + M - 1)] == 0.0);  // gamma: d = log y, y = 1
+            EXPECT(out[(size_t)(glm_obs_len(M) / 3 + M)] == 0.0 && out[(size_t)(glm_obs_len(M) - 1)] == 0.0);  // padding
         }
         y[(size_t)(M - 1)] = 3.0;  // the LAST observation is the one found: above its trials, and no integer for the counts
         EXPECT(glm_check_obs(M, PBBI_GLM_LOGISTIC, y.get(), nullptr, nullptr, n.get()) == PBBI_ERR_INVALID);
         y[(size_t)(M - 1)] = 0.5;
         EXPECT(glm_check_obs_disp(M, PBBI_GLM_NEGBINOMIAL, y.get(), nullptr, nullptr) == PBBI_ERR_INVALID);
+        EXPECT(glm_check_obs_disp(M, PBBI_GLM_GAMMA, y.get(), nullptr, nullptr) == PBBI_OK);  // gamma: any y > 0
+        for (double v : {0.0, -1.0, (double)NAN, (double)INFINITY}) {  // ... and nothing else; the LAST observation is named
+            y[(size_t)(M - 1)] = v;
+            EXPECT(glm_check_obs_disp(M, PBBI_GLM_GAMMA, y.get(), nullptr, nullptr) == PBBI_ERR_INVALID);
+            EXPECT(g_error.find("(observation " + std::to_string(M - 1) + ")") != std::string::npos);
+            EXPECT((g_error.find("gamma: y must be > 0") != std::string::npos) == std::isfinite(v));
+        }
+        EXPECT(glm_check_obs_disp(M, 7, y.get(), nullptr, nullptr) == PBBI_ERR_INVALID);
     }
     for (int D : DS) {
         Buf<double> lam = dbuf(D, 0.5, 0.5), mu = dbuf(D, -1.0, 0.5);
@@ -301,6 +314,7 @@ static void metric_tables() {
     for (int v : {GLM_V_HIER, GLM_V_HIER_NC, GLM_V_HIER_Q})
         EXPECT(glm_metric_max_dim(v, PBBI_GLM_LOGISTIC, 0, 64, 0) == 64 && glm_metric_max_dim(v, PBBI_GLM_GAUSSIAN, 0, 64, 0) == 0);
     EXPECT(glm_metric_max_dim(GLM_V_DISPERSION, PBBI_GLM_NEGBINOMIAL, 0, 64, 0) == 64 && glm_metric_max_dim(99, PBBI_GLM_LOGISTIC, 0, 16, 0) == 0);
+    EXPECT(glm_metric_max_dim(GLM_V_DISPERSION, PBBI_GLM_GAMMA, 0, 128, 0) == 128 && glm_metric_max_dim(GLM_V_HIER_DISPERSION, PBBI_GLM_GAMMA, 0, 64, 0) == 0);
     EXPECT(glm_metric_max_dim(GLM_V_SOFTMAX, PBBI_GLM_SOFTMAX, 0, 64, 2) == 0 && glm_metric_max_dim(GLM_V_SOFTMAX, PBBI_GLM_SOFTMAX, 0, 32, 4) == 128);
 }
 
@@ -319,6 +333,10 @@ int main() {
     for (int v : {GLM_V_HIER, GLM_V_HIER_NC, GLM_V_HIER_Q})
         EXPECT(glm_max_dim(v, PBBI_GLM_LOGISTIC) == 64 && glm_max_dim(v, PBBI_GLM_POISSON) == 64 && glm_max_dim(v, PBBI_GLM_GAUSSIAN) == 0);
     EXPECT(glm_max_dim(GLM_V_HIER_DISPERSION, PBBI_GLM_GAUSSIAN) == 64 && glm_max_dim(GLM_V_HIER_DISPERSION, PBBI_GLM_LOGISTIC) == 0);
+    // the Gamma family: the Gaussian's shapes without random effects, and on no other frame
+    EXPECT(glm_max_dim(GLM_V_DISPERSION, PBBI_GLM_GAMMA) == 128 && glm_max_dim(GLM_V_HIER_DISPERSION, PBBI_GLM_GAMMA) == 0);
+    EXPECT(glm_max_dim(GLM_V_FULL, PBBI_GLM_GAMMA) == 0 && glm_max_dim(GLM_V_HIER, PBBI_GLM_GAMMA) == 0);
+    EXPECT(glm_disp(PBBI_GLM_GAMMA) && !glm_canonical(PBBI_GLM_GAMMA) && std::string(glm_family_name(PBBI_GLM_GAMMA)) == "gamma");
     EXPECT(glm_max_dim(GLM_V_SOFTMAX, PBBI_GLM_SOFTMAX) == 0 && glm_max_dim(99, PBBI_GLM_LOGISTIC) == 0);
     if (bad) {
         std::printf("%d expectation(s) failed\n", bad);

@@ -8,9 +8,9 @@
 // the eta tile and the energy term -- glm_link_rich / glm_link_disp of glm_family_dev.h with want_u, the functions k_glm calls.
 // The plain model is the full model's formula at c = 1, d = y, o = 0, which is the plain formula bit for bit (1 * x and x + 0
 // are exact), so the model is a runtime choice of what is staged, not an instantiation.
-// Host side: the filler of the common arguments, the preflight of an entry and the (NT, family) dispatch of the 15 shipped
-// shapes -- NT = DP / 16 in {1, 2, 4, 8} for logistic, poisson and gaussian, {1, 2, 4} for negbinomial: the shapes the handles
-// themselves are shipped in (glm_max_dim).
+// Host side: the filler of the common arguments, the preflight of an entry and the (NT, family) dispatch of the 19 shipped
+// shapes -- NT = DP / 16 in {1, 2, 4, 8} for logistic, poisson, gaussian and gamma, {1, 2, 4} for negbinomial: the shapes the
+// handles themselves are shipped in (glm_max_dim).
 #pragma once
 #include <cmath>
 #include <type_traits>
@@ -183,6 +183,7 @@ bool glm_draw_dispatch(int NT, int fam, Launch&& launch) {
         case PBBI_GLM_POISSON: return tiles(std::integral_constant<int, PBBI_GLM_POISSON>{});
         case PBBI_GLM_GAUSSIAN: return tiles(std::integral_constant<int, PBBI_GLM_GAUSSIAN>{});
         case PBBI_GLM_NEGBINOMIAL: return tiles(std::integral_constant<int, PBBI_GLM_NEGBINOMIAL>{});
+        case PBBI_GLM_GAMMA: return tiles(std::integral_constant<int, PBBI_GLM_GAMMA>{});
     }
     return false;
 }

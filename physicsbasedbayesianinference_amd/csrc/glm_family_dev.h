@@ -70,6 +70,7 @@ __device__ __forceinline__ double glm_lgamma(double x) {
 // what a dispersion family forms once per chain and gradient evaluation
 //   gaussian:     a = tau = exp(-2 theta)
 //   negbinomial:  a = phi = exp(theta), b = psi(phi), c = lgamma(phi) (an evaluation that wants U only)
+//   gamma:        a = alpha = exp(theta), b = psi(alpha) - theta - 1, c = lgamma(alpha) - alpha theta (wants U only)
 struct GlmDispChain { double theta, a, b, c; };
 
 template <int FAM>
@@ -77,7 +78,12 @@ __device__ __forceinline__ GlmDispChain glm_disp_chain(double theta, bool want_u
     GlmDispChain k{theta, 0.0, 0.0, 0.0};
     if constexpr (FAM == PBBI_GLM_GAUSSIAN) {
         k.a = exp(-2.0 * theta);
+    } else if constexpr (FAM == PBBI_GLM_GAMMA) {
+        k.a = exp(theta);
+        k.b = (glm_psi(k.a) - theta) - 1.0;
+        if (want_u) k.c = glm_lgamma(k.a) - k.a * theta;
     } else {
+        static_assert(FAM == PBBI_GLM_NEGBINOMIAL, "a dispersion family");
         k.a = exp(theta);
         k.b = glm_psi(k.a);
         if (want_u) k.c = glm_lgamma(k.a);
@@ -85,7 +91,7 @@ __device__ __forceinline__ GlmDispChain glm_disp_chain(double theta, bool want_u
     return k;
 }
 
-// the dispersion families' U_i, dU_i/deta and dU_i/dtheta (cv = a_i, yv = y_i)
+// the dispersion families' U_i, dU_i/deta and dU_i/dtheta (cv = a_i, yv = y_i; gamma: yv = log y_i, the stream its packer writes)
 template <int FAM>
 __device__ __forceinline__ void glm_link_disp(double eta, double cv, double yv, const GlmDispChain& k, bool want_u,
                                               double& resid, double& uterm, double& tterm) {
@@ -96,7 +102,17 @@ __device__ __forceinline__ void glm_link_disp(double eta, double cv, double yv, 
         resid = -(cv * tr);
         tterm = cv * (1.0 - trr);
         uterm = cv * (0.5 * trr + k.theta);
+    } else if constexpr (FAM == PBBI_GLM_GAMMA) {
+        // z = eta - log y: U_i = a [lgamma(alpha) - alpha theta + alpha (z + exp(-z))], one exp per observation.  An exp(-z) that
+        // overflows makes the chain's energy inf / NaN and the proposal is rejected, as for Poisson's exp(eta).
+        const double z = eta - yv;
+        const double e = exp(-z);
+        const double ze = z + e;
+        resid = cv * (k.a * (1.0 - e));
+        tterm = cv * (k.a * (k.b + ze));
+        uterm = cv * (k.c + k.a * ze);
     } else {
+        static_assert(FAM == PBBI_GLM_NEGBINOMIAL, "a dispersion family");
         // z = eta - theta: s = sigmoid(z), sp = softplus(z); logaddexp(eta, theta) = theta + sp, so
         // -phi theta - y eta + (y + phi) logaddexp = (y + phi) sp - y z
         const double z = eta - k.theta;
@@ -114,7 +130,8 @@ __device__ __forceinline__ void glm_link_disp(double eta, double cv, double yv, 
     }
 }
 
-// the fitted mean b'(eta) of one observation: the sigmoid as glm_link_rich forms it, exp(eta), eta
+// the fitted mean of one observation: the sigmoid as glm_link_rich forms it, eta (gaussian), exp(eta) (every log link:
+// poisson, negbinomial, gamma)
 template <int FAM>
 __device__ __forceinline__ double glm_mean(double eta) {
     if constexpr (FAM == PBBI_GLM_LOGISTIC) {
@@ -129,7 +146,7 @@ __device__ __forceinline__ double glm_mean(double eta) {
 }
 
 // Does the row have weight?  A row without adds exactly nothing, whatever b() gave: its terms are SELECTED out, not multiplied
-// (0 * inf is NaN).  The streams are c = a n, d = a y (canonical families) and c = a, d = y (dispersion families).
+// (0 * inf is NaN).  The streams are c = a n, d = a y (canonical families) and c = a, d = y (dispersion families; gamma: d = log y).
 template <int FAM>
 __device__ __forceinline__ bool glm_row_on(double cv, double dv) {
     if constexpr (glm_disp(FAM)) return cv != 0.0;

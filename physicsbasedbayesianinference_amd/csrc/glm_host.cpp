@@ -17,11 +17,13 @@ int glm_max_dim(int variant, int family) {
     switch (variant) {
         case GLM_V_PLAIN:
         case GLM_V_FULL: return glm_canonical(family) ? 128 : 0;
-        case GLM_V_DISPERSION: return family == PBBI_GLM_GAUSSIAN ? 128 : family == PBBI_GLM_NEGBINOMIAL ? 64 : 0;
+        case GLM_V_DISPERSION:
+            return family == PBBI_GLM_GAUSSIAN || family == PBBI_GLM_GAMMA ? 128 : family == PBBI_GLM_NEGBINOMIAL ? 64 : 0;
         case GLM_V_HIER:
         case GLM_V_HIER_NC:
         case GLM_V_HIER_Q: return glm_canonical(family) ? 64 : 0;
-        case GLM_V_HIER_DISPERSION: return glm_disp(family) ? 64 : 0;
+        // (random effects for the Gamma family are not built)
+        case GLM_V_HIER_DISPERSION: return family == PBBI_GLM_GAUSSIAN || family == PBBI_GLM_NEGBINOMIAL ? 64 : 0;
     }
     return 0;
 }
@@ -182,6 +184,7 @@ int glm_check_obs_disp(int64_t M, int family, const double* y, const double* wei
         if (!std::isfinite(y[i])) return pbbi_fail(PBBI_ERR_INVALID, "y must be finite" + at());
         if (family == PBBI_GLM_NEGBINOMIAL && (y[i] < 0.0 || y[i] != std::floor(y[i])))
             return pbbi_fail(PBBI_ERR_INVALID, "negbinomial: y must hold non-negative integers" + at());
+        if (family == PBBI_GLM_GAMMA && !(y[i] > 0.0)) return pbbi_fail(PBBI_ERR_INVALID, "gamma: y must be > 0" + at());
         if (weights && !(std::isfinite(weights[i]) && weights[i] >= 0.0))
             return pbbi_fail(PBBI_ERR_INVALID, "weights must be finite and >= 0" + at());
         if (offset && !std::isfinite(offset[i]))
@@ -190,13 +193,14 @@ int glm_check_obs_disp(int64_t M, int family, const double* y, const double* wei
     return PBBI_OK;
 }
 
-// c = a | d = y (raw) | o, each zero padded to the image's block count (glm_obs_len(M) doubles).
-void glm_pack_obs_disp(int64_t M, const double* y, const double* weights, const double* offset, double* out) {
+// c = a | d = y (raw; gamma: log y, all its kernels need of y) | o, each zero padded to the image's block count
+// (glm_obs_len(M) doubles).  The caller has run glm_check_obs_disp: a Gamma family's y is > 0.
+void glm_pack_obs_disp(int64_t M, int family, const double* y, const double* weights, const double* offset, double* out) {
     const int64_t len = glm_blocks_padded(M) * 16;
     std::memset(out, 0, sizeof(double) * (size_t)(3 * len));
     for (int64_t i = 0; i < M; ++i) {
         out[i] = weights ? weights[i] : 1.0;
-        out[len + i] = y[i];
+        out[len + i] = family == PBBI_GLM_GAMMA ? std::log(y[i]) : y[i];
         out[2 * len + i] = offset ? offset[i] : 0.0;
     }
 }
@@ -381,7 +385,7 @@ void glm_pack_penalty(int D, int J, const double* penalty, double* out) {
 // ---- pointwise log-likelihood over draws ------------------------------------------------------------------------
 const char* const GLM_POINTWISE_RULE = "pbbi_pointwise_glm serves the handles of pbbi_potential_create_glm, _glm_ex, "
                                        "_glm_dispersion, _glm_hier, _glm_hier_ex, _glm_hier_q and _glm_hier_dispersion "
-                                       "(families logistic, poisson, gaussian, negbinomial; float64)";
+                                       "(families logistic, poisson, gaussian, negbinomial, gamma; float64)";
 
 // The rules of the two entries that take draws, in the order both state them.  Each entry has one rule of its own, at its own
 // place: pbbi_loglik_glm's output (out_null: never set by pbbi_pointwise_glm, whose four outputs are all optional) and

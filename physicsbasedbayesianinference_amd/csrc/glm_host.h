@@ -16,7 +16,7 @@ enum GlmVariant {
     GLM_V_PLAIN = 0,            // pbbi_potential_create_glm:                 k_glm<NT, FAM, false>
     GLM_V_FULL = 1,             // pbbi_potential_create_glm_ex:              k_glm<NT, FAM, true>
     GLM_V_SOFTMAX = 2,          // pbbi_potential_create_glm_softmax:         k_glm_softmax<NTc, K>
-    GLM_V_DISPERSION = 3,       // pbbi_potential_create_glm_dispersion:      k_glm<NT, FAM, true>, FAM = 3, 4
+    GLM_V_DISPERSION = 3,       // pbbi_potential_create_glm_dispersion:      k_glm<NT, FAM, true>, FAM = 3, 4, 5
     GLM_V_HIER = 4,             // pbbi_potential_create_glm_hier / _hier_ex: k_glm<NT, FAM, true, GLM_HIER_CENTRED>
     GLM_V_HIER_NC = 5,          // pbbi_potential_create_glm_hier_ex:         k_glm<NT, FAM, true, GLM_HIER_NC>
     GLM_V_HIER_Q = 6,           // pbbi_potential_create_glm_hier_q:          k_glm<NT, FAM, true, GLM_HIER_Q>
@@ -28,8 +28,13 @@ enum { GLM_TERM_WEIGHTS = 1, GLM_TERM_OFFSET = 2, GLM_TERM_TRIALS = 4, GLM_TERM_
 
 // The families by the shape of their link: the canonical ones (b(eta) alone) and the ones with a dispersion theta.  The one
 // statement of both, for the rules of glm_host.cpp and for the kernels' `if constexpr` (glm_family_dev.h, kernels_glm.hip).
-constexpr bool glm_disp(int fam) { return fam == PBBI_GLM_GAUSSIAN || fam == PBBI_GLM_NEGBINOMIAL; }
+constexpr bool glm_disp(int fam) { return fam == PBBI_GLM_GAUSSIAN || fam == PBBI_GLM_NEGBINOMIAL || fam == PBBI_GLM_GAMMA; }
 constexpr bool glm_canonical(int fam) { return fam == PBBI_GLM_LOGISTIC || fam == PBBI_GLM_POISSON; }
+// the families' names as the error texts and pbbi_describe_run write them: the one table
+constexpr const char* glm_family_name(int fam) {
+    constexpr const char* names[] = {"logistic", "poisson", "softmax", "gaussian", "negbinomial", "gamma"};
+    return fam >= 0 && fam < (int)(sizeof(names) / sizeof(names[0])) ? names[fam] : "unknown";
+}
 
 // The largest state dimension (every sampled row: coefficients, group log-scales, a sampled log-dispersion) the kernels of a
 // variant serve for a family; 0 = nothing shipped.  The one statement of it: the create entries and the launch read this.
@@ -69,7 +74,7 @@ int glm_check_obs(int64_t M, int family, const double* y, const double* weights,
 void glm_pack_obs(int64_t M, const double* y, const double* weights, const double* offset, const double* trials, double* out);
 int glm_check_prior(int D, const double* lam, const double* mu);
 int glm_check_obs_disp(int64_t M, int family, const double* y, const double* weights, const double* offset);
-void glm_pack_obs_disp(int64_t M, const double* y, const double* weights, const double* offset, double* out);
+void glm_pack_obs_disp(int64_t M, int family, const double* y, const double* weights, const double* offset, double* out);
 // ---- hierarchical priors: the table the kernels keep in LDS, the log-dispersion's pair, the penalty image
 int glm_check_hier(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior);
 void glm_pack_prior_groups(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior,

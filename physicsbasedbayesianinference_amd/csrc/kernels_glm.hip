@@ -40,17 +40,18 @@
 // 128 kernels into scratch, and they are read KS times per gradient next to M DP / 8 MFMAs.  The plain model's
 // instantiations (RICH = false) hold none of this: their code is what it was before the full model existed.
 //
-// The dispersion families (FAM = PBBI_GLM_GAUSSIAN, PBBI_GLM_NEGBINOMIAL of k_glm<NT, FAM, true>; handles of
+// The dispersion families (FAM = PBBI_GLM_GAUSSIAN, PBBI_GLM_NEGBINOMIAL, PBBI_GLM_GAMMA of k_glm<NT, FAM, true>; handles of
 // pbbi_potential_create_glm_dispersion) add a parameter that is no coefficient of X: theta, the log-dispersion, which
 // enters every observation's link and whose gradient is a sum over observations per chain (include/pbbi.h has the model).
 // Sampled, theta is row D of the state (D = the coefficient count): the image is that of [X | 0], so eta does not see the
 // row, while the momentum draw, kick, drift, stores and the {lam, mu} prior in plds treat it like any other.  Once per
 // gradient evaluation the lane that owns row D (s = D >> 2, g = D & 3) contributes its q[s] to a chain_sum, the other
 // three lane groups contribute 0 (adding zeros is exact), and every lane of the chain has theta; the per-chain
-// quantities (tau; phi, psi(phi), lgamma(phi)) are formed there, once.  Each lane accumulates dU_i/dtheta of its
+// quantities (tau; phi, psi(phi), lgamma(phi); alpha, psi(alpha) - theta - 1, lgamma(alpha) - alpha theta) are formed there, once.  Each lane accumulates dU_i/dtheta of its
 // observations next to usum, and chain_sum of that goes into the gradient accumulator at (s, g) before the kick and the
 // evaluation's store.  Held, theta comes from the kernel arguments (a wave-uniform switch, no further instantiations)
-// and the state is w alone.  The streams are c = a, d = y (raw), o; a row with c = 0 is selected out.
+// and the state is w alone.  The streams are c = a, d = y (raw; gamma: log y, taken once on the host), o; a row with c = 0 is
+// selected out.
 //
 // Hierarchical priors (HIER = GLM_HIER_CENTRED of k_glm<NT, FAM, true, HIER>, FAM logistic / poisson; handles of
 // pbbi_potential_create_glm_hier; include/pbbi.h has the model): a block of coefficients shares the prior scale exp(t_j),
@@ -320,6 +321,7 @@ __device__ __forceinline__ void glm_grad(const typename GlmArgs<FAM, RICH, HIER>
 // at them (profiles/glm_hier_penalty_resources.txt).
 // The dispersion families with a hierarchical prior (centred and non-centred) need no case of their own: all twelve build without
 // scratch at their families' counts (profiles/glm_hier_dispersion_resources.txt).
+// The Gamma family runs at the Gaussian's counts, DP = 128 included (profiles/glm_gamma_resources.txt).
 constexpr int glm_waves_per_simd(int NT, int fam, int hier) {
     return (NT <= 2 && !(NT == 2 && (fam == PBBI_GLM_NEGBINOMIAL || (hier == GLM_HIER_NC && fam == PBBI_GLM_LOGISTIC)))) ? 2 : 1;
 }
@@ -908,6 +910,7 @@ int glm_launch_pass(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t st
 #define K_(NT_, FAM_) GLM_CASE(NT_, FAM_, true, GLM_HIER_NONE, a)
             K_(1, PBBI_GLM_GAUSSIAN) K_(2, PBBI_GLM_GAUSSIAN) K_(4, PBBI_GLM_GAUSSIAN) K_(8, PBBI_GLM_GAUSSIAN)
             K_(1, PBBI_GLM_NEGBINOMIAL) K_(2, PBBI_GLM_NEGBINOMIAL) K_(4, PBBI_GLM_NEGBINOMIAL)
+            K_(1, PBBI_GLM_GAMMA) K_(2, PBBI_GLM_GAMMA) K_(4, PBBI_GLM_GAMMA) K_(8, PBBI_GLM_GAMMA)
 #undef K_
         } break;
         case GLM_V_HIER: {

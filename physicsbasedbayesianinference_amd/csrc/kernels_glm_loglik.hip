@@ -14,7 +14,7 @@
 //
 // Loop order: k_glm_pw's turned round.  A wave owns ONE tile of 16 consecutive draws (chains n0 .. n0 + 15 of one (Dt, N)
 // slab): the B operand of K-step s -- row 4s + g, chain lane & 15, KS = DP / 4 doubles per lane -- is loaded once and stays
-// in registers for the whole walk, and the per-draw constants (exp(-2 theta), or phi and lgamma(phi)) are formed once.  The four
+// in registers for the whole walk, and the per-draw constants (exp(-2 theta), phi and lgamma(phi), or the Gamma's) are formed once.  The four
 // waves of a workgroup (64 draws) walk the same observation blocks: LLB blocks of 16 observations at a time, their
 // first-product fragments P1 of the packed design image (glm_pack, glm_host.cpp; P2 is not read) and their c | d | o values
 // staged through LDS between two barriers and shared by the four waves, as k_glm stages X.  The eta tile comes out with
@@ -31,7 +31,8 @@
 // clamped chain and write nothing; a wave whose tile is past the last one does the same (it still meets every barrier).
 // Non-finite draws stay in their own column of the product: ll = -inf gives +inf, a NaN gives NaN, for that draw only.
 //
-// Shipped: the 15 shapes of glm_draw_dispatch.  None reserves scratch (profiles/glm_loglik_resources.txt).
+// Shipped: the 19 shapes of glm_draw_dispatch.  None reserves scratch (profiles/glm_loglik_resources.txt, the Gamma's four in
+// profiles/glm_gamma_resources.txt).
 #include <cmath>
 
 #include "glm_draws_dev.h"

@@ -217,7 +217,7 @@ int glm_build_disp(pbbi_potential* pot, int Dx, int64_t M, const double* X, cons
     const int Dt = pot->D, DP = glm_padded_dim(Dt);
     GlmTables t = glm_design_tables(Dx, DP, M, X);  // [X | 0]: the theta row meets a zero column
     t.obs.resize((size_t)glm_obs_len(M));
-    glm_pack_obs_disp(M, y, weights, offset, t.obs.data());
+    glm_pack_obs_disp(M, family, y, weights, offset, t.obs.data());
     t.prior = glm_prior_vectors(Dt, DP, lam, mu);
     pot->glm_terms = glm_terms_of(weights, offset, nullptr);
     pot->glm_trow = sample ? Dx : -1;
@@ -258,7 +258,7 @@ int glm_build_hier_disp(pbbi_potential* pot, int Dx, int64_t M, const double* X,
     const int DP = glm_padded_dim(pot->D);
     GlmTables t = glm_design_tables(Dx, DP, M, X);  // [X | 0]: the t rows and the theta row meet zero columns
     t.obs.resize((size_t)glm_obs_len(M));
-    glm_pack_obs_disp(M, y, weights, offset, t.obs.data());
+    glm_pack_obs_disp(M, family, y, weights, offset, t.obs.data());
     t.prior.assign((size_t)2 * DP + 4, 0.0);  // lam | mu | n_j
     double* nj = t.prior.data() + 2 * DP;
     glm_pack_prior_groups_disp(Dx, J, lam, mu, groups, tprior, sample, dprior, t.prior.data(), nj);
@@ -982,8 +982,9 @@ int pbbi_potential_create_glm_dispersion(int D, int64_t M, const double* X, cons
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials run on the fp64 matrix-core kernels: float64 and a state "
                                                "dimension (coefficients + 1 for a sampled dispersion) <= 128 only");
     if (Dt > glm_max_dim(GLM_V_DISPERSION, family))  // the negative binomial's stops short of it
-        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "negbinomial: the state dimension (coefficients + 1 for a sampled dispersion) "
-                                               "must be <= 64: its kernel at 65 .. 128 does not fit the register file");
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string(glm_family_name(family)) + ": the state dimension (coefficients + 1 for "
+                                               "a sampled dispersion) must be <= " + std::to_string(glm_max_dim(GLM_V_DISPERSION, family)) +
+                                               ": its kernel at 65 .. 128 does not fit the register file");
     if (int rc = glm_check_prior(Dt, lam, mu)) return rc;
     if (int rc = new_handle(KIND_GLM, Dt, dtype, device, out)) return rc;
     DeviceGuard guard(device);
@@ -1057,7 +1058,7 @@ static int glm_hier_disp_check_dim(int D, int J, int sample, int family, int par
     if (Dt > dmax)
         return pbbi_fail(PBBI_ERR_UNSUPPORTED,
                          std::string("random effects for the dispersion families (") +
-                             (family == PBBI_GLM_GAUSSIAN ? "gaussian" : "negbinomial") +
+                             glm_family_name(family) +
                              (parametrisation == PBBI_HIER_NONCENTRED ? ", non-centred" : ", centred") +
                              "): the state dimension (coefficients + groups + 1 for a sampled dispersion) must be <= " +
                              std::to_string(dmax) + " (" + std::to_string(Dt) + "): a kernel is shipped only if it builds "
@@ -1077,6 +1078,9 @@ int pbbi_potential_create_glm_hier_dispersion(int D, int64_t M, const double* X,
     if (family == PBBI_GLM_LOGISTIC || family == PBBI_GLM_POISSON)
         return pbbi_fail(PBBI_ERR_INVALID, "the family must be gaussian (3) or negbinomial (4): logistic and poisson with sampled "
                                            "group scales are pbbi_potential_create_glm_hier / _hier_ex");
+    if (family == PBBI_GLM_GAMMA)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "random effects for the gamma family are not built: the families are gaussian (3) "
+                                               "and negbinomial (4); pbbi_potential_create_glm_dispersion serves gamma");
     if (int rc = glm_check_hier(D, J, prior_precision, prior_mean, groups, log_scale_prior)) return rc;
     if (int rc = glm_check_obs_disp(M, family, y, weights, offset)) return rc;
     if (int rc = glm_check_design(D, M, X)) return rc;
@@ -1139,7 +1143,7 @@ int pbbi_glm_pack_observations_dispersion(int64_t M, int family, const double* y
     if (!out) return PBBI_OK;
     if (int rc = glm_check_obs_disp(M, family, y, weights, offset)) return rc;
     if (out_len < len) return pbbi_fail(PBBI_ERR_INVALID, "out is shorter than the three streams");
-    glm_pack_obs_disp(M, y, weights, offset, out);
+    glm_pack_obs_disp(M, family, y, weights, offset, out);
     return PBBI_OK;
 }
 
@@ -1609,7 +1613,7 @@ int pbbi_describe_run(const pbbi_potential* pot, int method, int64_t N, int64_t 
         const int v = pot->glm_variant;
         if (v == GLM_V_DISPERSION || v == GLM_V_HIER_DISPERSION) {
             const int t = pot->glm_terms;
-            d += std::string("; dispersion family ") + (pot->glm_family == PBBI_GLM_GAUSSIAN ? "gaussian" : "negbinomial");
+            d += std::string("; dispersion family ") + glm_family_name(pot->glm_family);
             d += pot->glm_trow >= 0 ? " (log-dispersion sampled: state row " + std::to_string(pot->glm_trow) +
                                           ", read by one chain sum per gradient, its gradient reduced per chain)"
                                     : " (log-dispersion held at " + std::to_string(pot->glm_theta) + ")";

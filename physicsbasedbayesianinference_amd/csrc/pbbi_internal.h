@@ -60,7 +60,7 @@ struct pbbi_potential {
     // softmax regression (pbbi_potential_create_glm_softmax), kernels_glm_softmax.hip.  (Appended.)  D = glm_K * (coefficients
     // per class), glm_DP = the padded class size Dc, d_glm_y the labels, d_glm_prior lam (Dc values, zeros past D)
     int glm_K;         // classes
-    // the dispersion families (pbbi_potential_create_glm_dispersion), FAM = 3, 4 of k_glm<NT, FAM, true>.  (Appended.)  D =
+    // the dispersion families (pbbi_potential_create_glm_dispersion), FAM = 3, 4, 5 of k_glm<NT, FAM, true>.  (Appended.)  D =
     // the state dimension (coefficients + the theta row when sampled), d_glm_obs = a | y | o, d_glm_prior covers the theta row
     int glm_trow;      // the state row of theta (= the coefficient count) when it is sampled, -1 when it is held
     double glm_theta;  // the held log-dispersion

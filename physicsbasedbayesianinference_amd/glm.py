@@ -22,9 +22,10 @@ staged through LDS -- the data set is read once per 64 chains, not once per chai
 `SoftmaxGLM` is the categorical family on the same frame (csrc/kernels_glm_softmax.hip): K-class softmax regression,
 every class with its own coefficient vector, the chain's state the K vectors class-major.
 
-`DispersionGLM` serves the two families with a free dispersion on the full model's frame: Gaussian regression with
-unknown noise and negative-binomial (NB2) counts, the log-dispersion either sampled as the last component of the
-chain's state or held at a given value.
+`DispersionGLM` serves the three families with a free dispersion on the full model's frame: Gaussian regression with
+unknown noise, negative-binomial (NB2) counts and Gamma regression with a log link (positive, right-skewed responses;
+shape 1 is exponential regression), the log-dispersion either sampled as the last component of the chain's state or
+held at a given value.
 
 `HierarchicalGLM` is the full model with hierarchical priors: blocks of coefficients (random intercepts, random slopes,
 a ridge penalty of unknown strength) share a prior scale that is sampled, on the log scale, as a further row of the state.  With `penalty=` a group's prior is structured: a symmetric positive semi-definite matrix Q_j
@@ -54,11 +55,13 @@ __all__ = ["GLM", "SoftmaxGLM", "DispersionGLM", "HierarchicalGLM", "Hierarchica
            "HIER_Q_MAX_DIM", "pack_penalty", "pack_metric", "padded_dim", "softmax_layout", "PointwiseResult", "pointwise_constants"]
 
 FAMILIES = {"logistic": _lib.GLM_LOGISTIC, "poisson": _lib.GLM_POISSON}
-DISPERSION_FAMILIES = {"gaussian": _lib.GLM_GAUSSIAN, "negbinomial": _lib.GLM_NEGBINOMIAL}   # DispersionGLM only
+DISPERSION_FAMILIES = {"gaussian": _lib.GLM_GAUSSIAN, "negbinomial": _lib.GLM_NEGBINOMIAL,
+                       "gamma": _lib.GLM_GAMMA}   # DispersionGLM; HierarchicalDispersionGLM serves those of HIER_DISP_MAX_DIM
 MAX_DIM = 128
 # the largest state dimension (coefficients + 1 for a sampled dispersion) of each dispersion family: the negative
-# binomial's kernel at a padded dimension of 128 does not fit the register file and is not shipped
-DISPERSION_MAX_DIM = {"gaussian": 128, "negbinomial": 64}
+# binomial's kernel at a padded dimension of 128 does not fit the register file and is not shipped; the Gamma family's does
+# (profiles/glm_gamma_resources.txt)
+DISPERSION_MAX_DIM = {"gaussian": 128, "negbinomial": 64, "gamma": 128}
 # the largest state dimension (coefficients + groups) of HierarchicalGLM: neither family's kernel at a padded dimension
 # of 128 can be built without register spills to memory, and neither is shipped
 HIER_MAX_DIM = {"logistic": 64, "poisson": 64}
@@ -141,8 +144,9 @@ def pack_observations(y, family="logistic", weights=None, offset=None, trials=No
 
 def pack_observations_dispersion(y, family="negbinomial", weights=None, offset=None):
     """The three per-observation streams a DispersionGLM handle keeps on the device, computed (and checked) on the host
-    by libpbbi.so: array (3, L) -- c = weights, d = y (raw, not weights * y) and the offset, each zero padded to L as
-    for `pack_observations`."""
+    by libpbbi.so: array (3, L) -- c = weights, d = y (raw, not weights * y; family "gamma": log y, which is all its
+    kernels need of y) and the offset, each zero padded to L as for `pack_observations`.  "gamma" requires y > 0.
+    `HierarchicalDispersionGLM` keeps the same streams."""
     if family not in DISPERSION_FAMILIES:
         raise ValueError("family must be one of %s (got %r)" % (sorted(DISPERSION_FAMILIES), family))
     y = np.ascontiguousarray(y, dtype=np.float64)
@@ -256,7 +260,7 @@ def _lgamma(x):
 def pointwise_constants(family, y, weights=None, trials=None):
     """k_i: the part of observation i's log-likelihood that depends on no parameter, which the kernels drop and `pointwise`
     adds on the host -- a_i log C(n_i, y_i) (logistic), -a_i lgamma(y_i + 1) (poisson, negbinomial), -a_i / 2 log 2 pi
-    (gaussian); a_i the weights (the likelihood of observation i enters to the power a_i)."""
+    (gaussian), -a_i log y_i (gamma); a_i the weights (the likelihood of observation i enters to the power a_i)."""
     y = np.asarray(y, dtype=np.float64)
     a = np.ones_like(y) if weights is None else np.asarray(weights, dtype=np.float64)
     if family == "logistic":
@@ -266,6 +270,8 @@ def pointwise_constants(family, y, weights=None, trials=None):
         return -a * _lgamma(y + 1.0)
     if family == "gaussian":
         return -0.5 * np.log(2.0 * np.pi) * a
+    if family == "gamma":
+        return -a * np.log(y)
     raise ValueError("pointwise_constants: unknown family %r" % (family,))
 
 
@@ -635,6 +641,8 @@ def _validate_dispersion(X, y, family, weights, offset):
         raise ValueError("X and y must be finite")
     if family == "negbinomial" and not (np.all(y >= 0) and np.all(y == np.floor(y))):
         raise ValueError("negbinomial: y must hold non-negative integers")
+    if family == "gamma" and not np.all(y > 0):
+        raise ValueError("gamma: y must be > 0")
     if weights is not None:
         weights = _vector(weights, M, "weights", "M")
         if not np.all(weights >= 0):
@@ -674,6 +682,8 @@ class DispersionGLM(_Tempered, _Metric, Potential):
                      U_i = a_i [ 0.5 exp(-2 theta) (y_i - eta_i)^2 + theta ]
         negbinomial  y_i ~ NB2(mu_i = exp(eta_i), phi = exp(theta)), Var = mu + mu^2 / phi, y non-negative integers:
                      U_i = a_i [ lgamma(phi) - lgamma(y_i + phi) - phi theta - y_i eta_i + (y_i + phi) logaddexp(eta_i, theta) ]
+        gamma        y_i ~ Gamma(shape alpha = exp(theta), mean mu_i = exp(eta_i)), Var = mu^2 / alpha, y > 0; z_i = eta_i - log y_i:
+                     U_i = a_i [ lgamma(alpha) - alpha theta + alpha (z_i + exp(-z_i)) ]
         U = sum_i U_i + 0.5 sum_d lam_d (w_d - mu_d)^2 + 0.5 lam_theta (theta - m_theta)^2,    eta_i = x_i . w + o_i
 
     (constants that depend on neither w nor theta dropped; the theta prior only when theta is sampled).
@@ -682,19 +692,23 @@ class DispersionGLM(_Tempered, _Metric, Potential):
         hmc = HMC(Ensemble(pot.numDimensions, N), 1.0, 0.05, None, potential=pot, rng="philox")
         w, phi = pot.split(samples)             # (D, ...) coefficients and exp(theta): sigma resp. phi
         pot = DispersionGLM(X, y, family="gaussian", dispersion=0.7)      # sigma held at 0.7: the state is w alone
+        pot = DispersionGLM(X, cost, family="gamma", offset=np.log(exposure))   # positive, right-skewed data; the shape sampled
+        pot = DispersionGLM(X, duration, family="gamma", dispersion=1.0)  # shape 1: exponential regression
 
     `dispersion="sample"`: theta is the LAST component of the chain's state, numDimensions == D + 1, and
     `log_dispersion_prior=(mean, precision >= 0)` is theta's Gaussian prior (default (0, 0.25); precision 0 = flat in
-    theta, p(sigma) proportional to 1 / sigma).  `dispersion=` a float > 0: sigma resp. phi is held there, numDimensions
+    theta, p(sigma) proportional to 1 / sigma).  `dispersion=` a float > 0: sigma, phi resp. alpha is held there, numDimensions
     == D, and `log_dispersion_prior` must not be given.  `prior_precision` is a scalar or a (D,) vector, `prior_mean` a
     (D,) vector (default 0), `weights` (>= 0; a row of weight 0 is held out exactly) and `offset` (M,) vectors.
 
-    Shapes: float64; the state dimension is at most 128 for "gaussian" and at most 64 for "negbinomial" (the negative
-    binomial's kernel for 65 .. 128 rows cannot be built without register spills to memory and is not shipped).
+    Shapes: float64; the state dimension is at most 128 for "gaussian" and "gamma" and at most 64 for "negbinomial" (the
+    negative binomial's kernel for 65 .. 128 rows cannot be built without register spills to memory and is not shipped).
+    As with phi, a large alpha means little dispersion.  The device keeps log y for "gamma" (the kernels need nothing else
+    of y); an exp(-z_i) that overflows rejects the proposal, like Poisson's exp(eta).
 
     Works wherever `GLM` does (HMC in both rng modes, Leapfrog / StormerVerlet, TemperedSMC, TemperingLadder,
     sampleStats); per-chain trajectory lengths and GIST raise as for `GLM`.  Arguments are checked on the host before
-    anything touches the GPU.  It runs on csrc/kernels_glm.hip (FAM = 3, 4 of k_glm<NT, FAM, true>)."""
+    anything touches the GPU.  It runs on csrc/kernels_glm.hip (FAM = 3, 4, 5 of k_glm<NT, FAM, true>)."""
 
     kind = "glm"
     pointwise = _pointwise
@@ -737,7 +751,8 @@ class DispersionGLM(_Tempered, _Metric, Potential):
 
     def split(self, samples):
         """(numDimensions, ...) -> (w, dispersion): the (D, ...) coefficients (a view wherever the array allows one) and
-        exp(theta) -- sigma for "gaussian", phi for "negbinomial" -- of shape (...); held: the constant itself."""
+        exp(theta) -- sigma for "gaussian", phi for "negbinomial", the shape alpha for "gamma" -- of shape (...); held: the
+        constant itself."""
         D = self.numCoefficients
         if not self.sampled:
             return samples, self.dispersion
@@ -1245,7 +1260,7 @@ class HierarchicalDispersionGLM(HierarchicalGLM):
                  parametrisation="centred", penalty=None, penalty_rank=None, dtype="float64", device=None):
         if family in FAMILIES:
             raise ValueError("HierarchicalDispersionGLM serves the families %s; family=%r with sampled group scales is "
-                             "HierarchicalGLM" % (sorted(DISPERSION_FAMILIES), family))
+                             "HierarchicalGLM" % (sorted(HIER_DISP_MAX_DIM), family))
         if penalty is not None or penalty_rank is not None:
             raise ValueError("penalty= (structured group priors) is not built for HierarchicalDispersionGLM: it is served by "
                              "HierarchicalGLM (families logistic and poisson) only")
@@ -1253,6 +1268,9 @@ class HierarchicalDispersionGLM(HierarchicalGLM):
             raise ValueError("parametrisation must be \"centred\" or \"noncentred\" (got %r)" % (parametrisation,))
         if groups is None:
             raise ValueError("groups is required: a (D,) vector of -1 (fixed prior) or group indices 0 .. J-1")
+        if family in DISPERSION_FAMILIES and family not in HIER_DISP_MAX_DIM:
+            raise ValueError("HierarchicalDispersionGLM serves the families %s: random effects for family=%r are not built "
+                             "(DispersionGLM serves it)" % (sorted(HIER_DISP_MAX_DIM), family))
         X, y, a, o = _validate_dispersion(X, y, family, weights, offset)
         M, D = X.shape
         sample, disp, theta, dprior = _dispersion_args(dispersion, log_dispersion_prior)

@@ -42,6 +42,10 @@ structured model as a CustomPotential, all three alternating in one process, at 
 profiles/glm_hier_penalty_bench.json: the project's criterion (the slowest repeat of the kernel beats the fastest of the plugin)
 and the ratio to the centred kernel next to what the MFMA counts predict, 1 + (DP^2 / 64) / (M DP / 32) = 1 + DP / (2 M).
 
+--model gamma times DispersionGLM's three families (gaussian, gamma, negbinomial; FAM = 3, 5, 4 of k_glm<NT, FAM, true>) beside
+each other at the shapes of --model dispersion and writes profiles/glm_gamma_bench.json: what each family's link costs on the
+same frame.
+
 --model hierdisp times HierarchicalDispersionGLM(family="negbinomial", dispersion="sample") in both parametrisations (k_glm<NT,
 4, true, GLM_HIER_CENTRED / GLM_HIER_NC>) against the centred model as a CustomPotential and against DispersionGLM of [X | 0]
 with the group scales held at their true values -- the parent kernel at the same padded shape, so that ratio is the cost of
@@ -63,6 +67,7 @@ usage: tools/bench_glm.py [--shape small|large|all] [--K 32] [--repeats 5] [--gl
        tools/bench_glm.py --model rich [--custom] [--label NAME] [--shape ...]
        tools/bench_glm.py --model softmax [--shape k3|k8|k8large|all]
        tools/bench_glm.py --model dispersion [--shape small|large|all]
+       tools/bench_glm.py --model gamma [--shape small|large|all]
        tools/bench_glm.py --model hierq [--shape small|large|all]
        tools/bench_glm.py --model hierdisp [--shape small|large|all]
        tools/bench_glm.py --model pointwise [--shape small|large|all] [--slabs 8] [--repeats 5]
@@ -390,6 +395,51 @@ def bench_dispersion(name, M, D, N, h, L, per_call, window, repeats, warm):
     out["ratio_worst_case"] = float(per_it["plugin"].min() / per_it["dispersion"].max())  # fastest plugin over slowest kernel
     out["slowest_dispersion_beats_fastest_plugin"] = bool(per_it["dispersion"].max() < per_it["plugin"].min())
     return out
+
+def bench_gamma(name, M, D, N, h, L, per_call, window, repeats, warm):
+    """The three dispersion families of DispersionGLM (sampled dispersion) alternating in one process after warm-up: the same
+    X, weights, offsets, starts, step size and draws; y from each family's own model at the same linear predictor (sigma = 0.5,
+    phi = 2, alpha = 2).  No plugin side: what is measured is the cost of each family's link on the same kernel frame."""
+    kw, wt, rs = dispersion_problem(M, D)
+    DT = D + 1
+    q0 = np.ascontiguousarray(wt[:, None] + 0.05 * rs.standard_normal((DT, N)))
+    eta = kw["X"] @ wt[:D] + kw["offset"]
+    ys = {"gaussian": eta + 0.5 * rs.standard_normal(M), "negbinomial": kw["y"],
+          "gamma": np.maximum(rs.gamma(2.0, np.exp(eta) / 2.0), 1e-6)}
+    theta0 = {"gaussian": np.log(0.5), "negbinomial": np.log(2.0), "gamma": np.log(2.0)}
+    prior = (0.0, 0.25)
+    W = window["dispersion"]
+    runners = {}
+    for fam in ("gaussian", "gamma", "negbinomial"):
+        q = q0.copy()
+        q[D] += theta0[fam] - wt[D]
+        pot = P.DispersionGLM(**dict(kw, y=ys[fam]), family=fam, dispersion="sample", log_dispersion_prior=prior)
+        runners[fam] = Runner(pot, DT, N, q, h, L, per_call, W)
+    for r in runners.values():
+        r.go(warm)
+    torch.cuda.synchronize()
+    series = {k: [] for k in runners}
+    for i in range(repeats):
+        for k, r in runners.items():   # alternating
+            series[k].append(r.timed())
+            print(f"# {name} repeat {i} {k}: {series[k][-1]:.4f} s", flush=True)
+    DP = glm.padded_dim(DT)
+    out = dict(shape=name, M=M, D=D, state_dimension=DT, DP=DP, chains=N, L=L, h=h, iterations_per_call=per_call,
+               iterations_per_window=W, repeats=repeats, warmup_iterations=warm,
+               timing="host clock over whole windows of pbbi_hmc_run calls (synchronised before and after)",
+               accept_rate={k: 1.0 - float(r.rej.float().mean().item()) for k, r in runners.items()})
+    flop_it = 4.0 * M * DP * (L + 1) * N
+    med = {}
+    for k, ts in series.items():
+        out[k + "_seconds"] = ts
+        out[k + "_step_chain_per_s"] = [W * L * N / t for t in ts]
+        med[k] = float(np.median(ts))
+        out[k + "_executed_tflops_median"] = flop_it * W / med[k] / 1e12
+    out["gamma_over_gaussian_time_median"] = med["gamma"] / med["gaussian"]
+    out["negbinomial_over_gamma_time_median"] = med["negbinomial"] / med["gamma"]
+    out["gamma_lies_between"] = bool(med["gaussian"] <= med["gamma"] <= med["negbinomial"])
+    return out
+
 
 # negative-binomial regression with sampled group scales and a sampled log-dispersion as user source (centred): prm = [M, D, J, X,
 # a, y, o, lam(DT), mu(DT), groups(D)], the state (w, t, theta); nb_psi is NEGBINOMIAL_SOURCE's
@@ -1048,7 +1098,7 @@ if __name__ == "__main__":
     ap.add_argument("--repeats", type=int, default=None, help="default 5 (--model softmax: per shape)")
     ap.add_argument("--warmup", type=int, default=None, help="default 4 (--model softmax: per shape)")
     ap.add_argument("--glm-only", action="store_true")
-    ap.add_argument("--model", default="plain", choices=["plain", "rich", "softmax", "dispersion", "hier", "hierq", "hierdisp",
+    ap.add_argument("--model", default="plain", choices=["plain", "rich", "softmax", "dispersion", "gamma", "hier", "hierq", "hierdisp",
                                                          "pointwise", "loglik"])
     ap.add_argument("--slabs", type=int, default=8, help="--model pointwise / loglik: slabs of N draws")
     ap.add_argument("--parametrisation", default="centred", choices=["centred", "noncentred"],
@@ -1076,9 +1126,10 @@ if __name__ == "__main__":
                                results=sorted(results, key=lambda r: r["shape"], reverse=True)), f, indent=1)
                 f.write("\n")
         sys.exit(0)
-    if a.model in ("softmax", "dispersion", "hier", "hierq", "hierdisp"):
+    if a.model in ("softmax", "dispersion", "gamma", "hier", "hierq", "hierdisp"):
         table, fn, side = {"softmax": (SOFTMAX_SHAPES, bench_softmax, "softmax"),
                            "dispersion": (DISPERSION_SHAPES, bench_dispersion, "dispersion"),
+                           "gamma": (DISPERSION_SHAPES, bench_gamma, "gamma"),
                            "hier": (HIER_SHAPES, bench_hier, "hier"),
                            "hierq": (HIERQ_SHAPES, bench_hierq, "hierq"),
                            "hierdisp": (HIER_DISP_SHAPES, bench_hier_dispersion, "centred")}[a.model]
