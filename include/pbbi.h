@@ -255,6 +255,34 @@ int pbbi_potential_create_glm_dispersion(int D, int64_t M, const double* X, cons
  * (gamma: d = log y), each stream zero padded past M. */
 int pbbi_glm_pack_observations_dispersion(int64_t M, int family, const double* y, const double* weights,
                                           const double* offset, double* out, int64_t out_len, int64_t* len_out);
+/* Ordinal (cumulative-logit, proportional-odds) regression with sampled cutpoints, on the full model's kernel frame
+ * (csrc/kernels_glm.hip, FAM = 6 of k_glm<NT, FAM, true>).  Categories y_i in {0 .. K-1}, 2 <= K <= 8, cutpoints kappa_1 < .. <
+ * kappa_{K-1} with kappa_0 = -inf and kappa_K = +inf, observation weights a_i >= 0, offsets o_i, eta_i = x_i . w + o_i:
+ *     P(y_i = k) = sigma(kappa_{k+1} - eta_i) - sigma(kappa_k - eta_i)
+ * X carries NO intercept column: the cutpoints are the intercepts (a column of ones is not identified against them; X is not
+ * tested for one).  The chain's state is [w (D rows); zeta (K - 1 rows)], the cutpoint rows LAST and unconstrained:
+ *     zeta_1 = kappa_1,  zeta_j = log(kappa_j - kappa_{j-1}) (j >= 2),  so  kappa_j = zeta_1 + sum_{m = 2 .. j} exp(zeta_m)
+ * and the ordering holds by construction.  The priors are Gaussian on these rows -- lam / mu hold D + K - 1 entries, the last
+ * K - 1 the precision and mean of zeta_1 and of the log-gaps (mu may be NULL = 0) -- and stated on zeta, so there is no Jacobian
+ * term.  With sp = softplus and Delta_k = kappa_{k+1} - kappa_k = exp(zeta_{k+1}), an observation of category k has
+ *     U_i = a_i [ sp(eta_i - kappa_{k+1}) + sp(kappa_k - eta_i) - log(1 - exp(-Delta_k)) ]
+ * (sigma(b) - sigma(a) = sigma(b) sigma(-a) (1 - exp(-(b - a))): no logarithm of a difference of two sigmoids), the terms of an
+ * infinite cutpoint absent: k = 0 keeps the first softplus, k = K - 1 the second, neither has the last term.
+ *     U = sum_i U_i + 0.5 sum_d lam_d (s_d - mu_d)^2  over the D + K - 1 rows s of the state.
+ * K = 2 is logistic regression with intercept -kappa_1.  The handle's dimension is D + K - 1.  The design image on the device
+ * is that of [X | 0] at the padded state dimension; the device keeps c_i = a_i, d_i = y_i (the category) and o_i, and the
+ * weighted category counts A_k = sum_{i: y_i = k} a_i behind the prior table; a row of weight 0 contributes exactly 0, a
+ * category without observations is allowed.  Checked before anything is allocated, with the observation's index in the message
+ * (PBBI_ERR_INVALID): y integers in [0, K), weights finite and >= 0, offsets finite, lam finite and >= 0, 2 <= K <= 8.  fp64
+ * only; the state dimension D + K - 1 is at most 64: the kernel for 65 .. 128 rows cannot be built without register spills to
+ * memory and is not shipped (PBBI_ERR_UNSUPPORTED).  The handle is a GLM handle: per-
+ * chain lengths and GIST are refused; pbbi_potential_set_metric_diag, pbbi_pointwise_glm (whose fitted mean is the expected
+ * category sum_j sigma(eta - kappa_j)), pbbi_loglik_glm and pbbi_potential_set_likelihood_power are served;
+ * pbbi_describe_run names the family.  Random effects on this family are not built: the hierarchical entries answer
+ * PBBI_ERR_UNSUPPORTED for family 6. */
+enum { PBBI_GLM_ORDINAL = 6 };
+/* pbbi_potential_create_glm_ordinal(D, K, M, X, y, weights, offset, lam, mu, dtype, device, out) and its host-only packer
+ * pbbi_glm_pack_observations_ordinal are declared in pbbi_glm_ordinal.h (included at the end). */
 /* Hierarchical priors with sampled group scales (random effects, a learned ridge penalty) on the full model's kernel frame
  * (csrc/kernels_glm.hip, k_glm<NT, FAM, true, GLM_HIER_CENTRED>); families logistic and poisson, weights a_i, trials n_i, offsets o_i
  * and eta_i = x_i . w + o_i as for pbbi_potential_create_glm_ex.  groups[d] is -1 (coefficient d keeps the fixed prior
@@ -818,4 +846,5 @@ int pbbi_smc_resample_systematic(double* logw, int64_t N, uint64_t seed, uint64_
 }
 #endif
 #include "pbbi_glm_metric.h"
+#include "pbbi_glm_ordinal.h"
 #endif /* PBBI_H */

@@ -16,7 +16,7 @@ from .potential import (GaussianDense, GaussianDiag, Harmonic, Potential, Rosenb
 from .integrator import Integrator, Leapfrog, StormerVerlet
 from .HMC import HMC
 from .custom import CustomPotential
-from .glm import GLM, SoftmaxGLM, DispersionGLM, HierarchicalGLM, HierarchicalDispersionGLM, pack_observations_dispersion, pack_prior_groups
+from .glm import GLM, SoftmaxGLM, DispersionGLM, OrdinalGLM, HierarchicalGLM, HierarchicalDispersionGLM, pack_observations_dispersion, pack_prior_groups
 from .stats import RunningHistogram, RunningStats
 from .smc import LikelihoodTemperedSMC
 from . import trace
@@ -24,7 +24,7 @@ from .trace import grad, trace_potential
 
 __all__ = ["Ensemble", "HMC", "Integrator", "Leapfrog", "StormerVerlet", "Potential",
            "Harmonic", "GaussianDiag", "StandardGaussian", "GaussianDense", "Rosenbrock",
-           "harmonicPotentialND", "linear_regression_posterior", "CustomPotential", "GLM", "SoftmaxGLM", "DispersionGLM",
+           "harmonicPotentialND", "linear_regression_posterior", "CustomPotential", "GLM", "SoftmaxGLM", "DispersionGLM", "OrdinalGLM",
            "HierarchicalGLM", "HierarchicalDispersionGLM", "pack_observations_dispersion", "pack_prior_groups", "RunningStats",
            "RunningHistogram", "LikelihoodTemperedSMC",
            "trace", "grad", "trace_potential"]

@@ -16,6 +16,7 @@ LEAPFROG, STORMER_VERLET = 0, 1
 GLM_LOGISTIC, GLM_POISSON = 0, 1
 GLM_SOFTMAX = 2         # pbbi_potential_create_glm_softmax only
 GLM_GAUSSIAN, GLM_NEGBINOMIAL, GLM_GAMMA = 3, 4, 5   # pbbi_potential_create_glm_dispersion (_hier_dispersion: 3, 4)
+GLM_ORDINAL = 6                                      # pbbi_potential_create_glm_ordinal
 HIER_CENTRED, HIER_NONCENTRED = 0, 1    # pbbi_potential_create_glm_hier_ex
 ERR_INVALID, ERR_UNSUPPORTED, ERR_HIP = -1, -2, -3
 COMPAT_P_FROM_OLDQ = 1
@@ -142,6 +143,13 @@ HOST_PACKER_PROTOTYPES = {
     "pbbi_glm_pack_metric": [_i, _dp, _dp, _i64, C.POINTER(C.c_int64)],   # the diagonal metric's table (glm.pack_metric)
 }
 
+# ... and the two entries of ordinal regression (include/pbbi_glm_ordinal.h): the order of their rejections is spelt out in
+# tests/test_glm_ordinal_host.py
+ORDINAL_PROTOTYPES = {
+    "pbbi_potential_create_glm_ordinal": [_i, _i, _i64, _dp, _dp, _dp, _dp, _dp, _dp, _i, _i, _pp],
+    "pbbi_glm_pack_observations_ordinal": [_i64, _i, _dp, _dp, _dp, _dp, _i64, C.POINTER(C.c_int64), _dp],
+}
+
 _lib = None
 
 
@@ -160,7 +168,7 @@ def load():
     # dependency to that already-loaded copy instead of mapping a second runtime.
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, argtypes in {**PROTOTYPES, **HOST_PACKER_PROTOTYPES}.items():
+    for name, argtypes in {**PROTOTYPES, **HOST_PACKER_PROTOTYPES, **ORDINAL_PROTOTYPES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI and this table drift apart
         fn.argtypes = argtypes
         fn.restype = C.c_int

@@ -84,6 +84,37 @@ static void design_and_observations() {
             EXPECT((g_error.find("gamma: y must be > 0") != std::string::npos) == std::isfinite(v));
         }
         EXPECT(glm_check_obs_disp(M, 7, y.get(), nullptr, nullptr) == PBBI_ERR_INVALID);
+        // the ordinal family: categories 0 .. K-1 in turn, exactly-sized streams and the 8 weighted category counts
+        for (int K : {2, 5, 8}) {
+            Buf<double> cat = dbuf(M, 0.0), counts = dbuf(8, -1.0);
+            double want[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            for (int64_t i = 0; i < M; ++i) {
+                cat[(size_t)i] = (double)(i % K);
+                want[i % K] += w[(size_t)i];
+            }
+            EXPECT(glm_check_obs_ordinal(M, K, cat.get(), w.get(), o.get()) == PBBI_OK);
+            EXPECT(glm_check_obs_ordinal(M, K, cat.get(), nullptr, nullptr) == PBBI_OK);
+            glm_pack_obs_ordinal(M, K, cat.get(), w.get(), o.get(), out.get(), counts.get());
+            EXPECT(out[0] == w[0] && out[(size_t)(glm_obs_len(M) / 3 + M - 1)] == (double)((M - 1) % K));  // c = a, d = the category
+            EXPECT(out[(size_t)(glm_obs_len(M) - 1)] == 0.0);  // the offsets' padding
+            for (int k = 0; k < 8; ++k) EXPECT(counts[(size_t)k] == want[k]);  // (same order of additions; 0 past K)
+            for (double v : {-1.0, (double)K, 0.5, (double)NAN, (double)INFINITY}) {  // the LAST observation is named
+                cat[(size_t)(M - 1)] = v;
+                EXPECT(glm_check_obs_ordinal(M, K, cat.get(), nullptr, nullptr) == PBBI_ERR_INVALID);
+                EXPECT(g_error.find("integer categories in [0, K) (observation " + std::to_string(M - 1) + ")") != std::string::npos);
+            }
+            cat[(size_t)(M - 1)] = 0.0;
+            w[(size_t)(M - 1)] = -0.5;
+            EXPECT(glm_check_obs_ordinal(M, K, cat.get(), w.get(), nullptr) == PBBI_ERR_INVALID);
+            EXPECT(g_error.find("weights must be finite and >= 0 (observation " + std::to_string(M - 1) + ")") != std::string::npos);
+            w[(size_t)(M - 1)] = 0.5 + 0.25 * (double)(M - 1);
+            o[(size_t)(M - 1)] = (double)INFINITY;
+            EXPECT(glm_check_obs_ordinal(M, K, cat.get(), nullptr, o.get()) == PBBI_ERR_INVALID);
+            o[(size_t)(M - 1)] = 0.0;
+        }
+        EXPECT(glm_check_obs_ordinal(M, 1, y.get(), nullptr, nullptr) == PBBI_ERR_INVALID);
+        EXPECT(glm_check_obs_ordinal(M, 9, y.get(), nullptr, nullptr) == PBBI_ERR_INVALID);
+        EXPECT(glm_check_obs_ordinal(M, 3, nullptr, nullptr, nullptr) == PBBI_ERR_INVALID);
     }
     for (int D : DS) {
         Buf<double> lam = dbuf(D, 0.5, 0.5), mu = dbuf(D, -1.0, 0.5);
@@ -338,6 +369,17 @@ int main() {
     EXPECT(glm_max_dim(GLM_V_FULL, PBBI_GLM_GAMMA) == 0 && glm_max_dim(GLM_V_HIER, PBBI_GLM_GAMMA) == 0);
     EXPECT(glm_disp(PBBI_GLM_GAMMA) && !glm_canonical(PBBI_GLM_GAMMA) && std::string(glm_family_name(PBBI_GLM_GAMMA)) == "gamma");
     EXPECT(glm_max_dim(GLM_V_SOFTMAX, PBBI_GLM_SOFTMAX) == 0 && glm_max_dim(99, PBBI_GLM_LOGISTIC) == 0);
+    // the ordinal family: 64 rows on its own variant, with the metric where it ships, and on no other frame
+    EXPECT(glm_max_dim(GLM_V_ORDINAL, PBBI_GLM_ORDINAL) == 64 && GLM_ORDINAL_MAX_ROWS == 64);
+    EXPECT(glm_max_dim(GLM_V_ORDINAL, PBBI_GLM_LOGISTIC) == 0 && glm_max_dim(GLM_V_FULL, PBBI_GLM_ORDINAL) == 0);
+    EXPECT(glm_max_dim(GLM_V_DISPERSION, PBBI_GLM_ORDINAL) == 0 && glm_max_dim(GLM_V_HIER, PBBI_GLM_ORDINAL) == 0);
+    EXPECT(glm_max_dim(GLM_V_HIER_DISPERSION, PBBI_GLM_ORDINAL) == 0);
+    EXPECT(glm_metric_max_dim(GLM_V_ORDINAL, PBBI_GLM_ORDINAL, 0, 64, 8) == 64 && glm_metric_max_rows(PBBI_GLM_ORDINAL, true, 0) == 64);
+    EXPECT(!glm_disp(PBBI_GLM_ORDINAL) && !glm_canonical(PBBI_GLM_ORDINAL) && std::string(glm_family_name(PBBI_GLM_ORDINAL)) == "ordinal");
+    EXPECT(glm_check_ordinal_shape(60, 5) == PBBI_OK && glm_check_ordinal_shape(57, 8) == PBBI_OK && glm_check_ordinal_shape(1, 2) == PBBI_OK);
+    EXPECT(glm_check_ordinal_shape(61, 5) == PBBI_ERR_UNSUPPORTED && g_error.find("<= 64 (65)") != std::string::npos);
+    EXPECT(glm_check_ordinal_shape(5, 1) == PBBI_ERR_INVALID && glm_check_ordinal_shape(5, 9) == PBBI_ERR_INVALID);
+    EXPECT(glm_check_ordinal_shape(0, 3) == PBBI_ERR_INVALID);
     if (bad) {
         std::printf("%d expectation(s) failed\n", bad);
         return 1;

@@ -8,8 +8,8 @@
 // the eta tile and the energy term -- glm_link_rich / glm_link_disp of glm_family_dev.h with want_u, the functions k_glm calls.
 // The plain model is the full model's formula at c = 1, d = y, o = 0, which is the plain formula bit for bit (1 * x and x + 0
 // are exact), so the model is a runtime choice of what is staged, not an instantiation.
-// Host side: the filler of the common arguments, the preflight of an entry and the (NT, family) dispatch of the 19 shipped
-// shapes -- NT = DP / 16 in {1, 2, 4, 8} for logistic, poisson, gaussian and gamma, {1, 2, 4} for negbinomial: the shapes the
+// Host side: the filler of the common arguments, the preflight of an entry and the (NT, family) dispatch of the 22 shipped
+// shapes -- NT = DP / 16 in {1, 2, 4, 8} for logistic, poisson, gaussian and gamma, {1, 2, 4} for negbinomial and ordinal: the shapes the
 // handles themselves are shipped in (glm_max_dim).
 #pragma once
 #include <cmath>
@@ -34,6 +34,7 @@ struct GlmDrawPrm {
     int Dx;              // coefficient rows
     int trow;            // the state row of a sampled theta, -1: held (or no dispersion)
     int ranges;
+    int K;               // ordinal family: categories; the K - 1 cutpoint rows are rows Dx .. Dx + K - 2 of a draw (else 0)
 };
 
 // Tile t of 16 consecutive draws (chains n0 .. n0 + 15 of one (Dt, N) slab) as lane c = lane & 15 sees it.  Ragged tail of a
@@ -68,10 +69,25 @@ __device__ __forceinline__ void glm_draw_load(const GlmDrawPrm& prm, const doubl
 
 // What a dispersion family forms once per draw (glm_disp_chain with want_u): a sampled theta is read from its own row (trow), a
 // held one comes from the handle.  The canonical families form nothing.
+// The ordinal family forms its cutpoints (glm_ord_chain with want_u) from the K - 1 rows behind the coefficients, read as they lie.
 template <int FAM>
-__device__ __forceinline__ GlmDispChain glm_draw_disp(const GlmDrawPrm& prm, const double* __restrict__ col) {
-    if constexpr (glm_disp(FAM)) return glm_disp_chain<FAM>(prm.trow >= 0 ? col[(int64_t)prm.trow * prm.N] : prm.theta, true);
-    else return GlmDispChain{0.0, 0.0, 0.0, 0.0};
+using GlmDrawChain = std::conditional_t<FAM == PBBI_GLM_ORDINAL, GlmOrdChain, GlmDispChain>;
+template <int FAM>
+__device__ __forceinline__ GlmDrawChain<FAM> glm_draw_disp(const GlmDrawPrm& prm, const double* __restrict__ col) {
+    if constexpr (FAM == PBBI_GLM_ORDINAL) {
+        double z[7];
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            const bool in = j < prm.K - 1;  // the address clamped to a row of the draw
+            const double v = col[(int64_t)(prm.Dx + (in ? j : 0)) * prm.N];
+            z[j] = in ? v : 0.0;
+        }
+        return glm_ord_chain(z, prm.K, true);
+    } else if constexpr (glm_disp(FAM)) {
+        return glm_disp_chain<FAM>(prm.trow >= 0 ? col[(int64_t)prm.trow * prm.N] : prm.theta, true);
+    } else {
+        return GlmDispChain{0.0, 0.0, 0.0, 0.0};
+    }
 }
 
 // Blocks blk0 .. blk0 + NB - 1 of 16 observations into LDS, by the whole workgroup: their P1 fragments (P1V 16-byte elements
@@ -112,10 +128,11 @@ __device__ __forceinline__ glm_v4 glm_draw_eta(const glm_v2* __restrict__ P1, co
 // The energy term of k_glm of one observation at one draw -- minus its log-likelihood with the constants k_i dropped -- by the
 // functions k_glm calls; the residual and dU_i/dtheta are not read and the compiler drops them
 template <int FAM>
-__device__ __forceinline__ double glm_draw_uterm(double eta, double cv, double dv, [[maybe_unused]] const GlmDispChain& dk) {
-    [[maybe_unused]] double resid, tterm;
+__device__ __forceinline__ double glm_draw_uterm(double eta, double cv, double dv, [[maybe_unused]] const GlmDrawChain<FAM>& dk) {
+    [[maybe_unused]] double resid, tterm, tlo;
     double uterm;
-    if constexpr (glm_disp(FAM)) glm_link_disp<FAM>(eta, cv, dv, dk, true, resid, uterm, tterm);
+    if constexpr (FAM == PBBI_GLM_ORDINAL) glm_link_ord(eta, cv, dv, dk, true, resid, uterm, tterm, tlo);
+    else if constexpr (glm_disp(FAM)) glm_link_disp<FAM>(eta, cv, dv, dk, true, resid, uterm, tterm);
     else glm_link_rich<FAM>(eta, cv, dv, true, resid, uterm);
     return uterm;
 }
@@ -157,7 +174,15 @@ inline void glm_draw_fill(GlmDrawPrm& prm, const pbbi_potential* pot, const void
     prm.slab_len = (int64_t)Dt * N;
     prm.theta = pot->glm_theta;
     prm.trow = pot->glm_trow;
-    prm.Dx = pot->D - pot->glm_hier_J - (pot->glm_trow >= 0 ? 1 : 0);
+    prm.K = pot->glm_variant == GLM_V_ORDINAL ? pot->glm_K : 0;
+    prm.Dx = pot->D - pot->glm_hier_J - (pot->glm_trow >= 0 ? 1 : 0) - (prm.K ? prm.K - 1 : 0);
+}
+
+// the fitted mean of one observation at one draw: glm_mean of glm_family_dev.h; the ordinal family's is the expected category
+template <int FAM>
+__device__ __forceinline__ double glm_draw_mean(double eta, [[maybe_unused]] const GlmDrawChain<FAM>& dk) {
+    if constexpr (FAM == PBBI_GLM_ORDINAL) return glm_mean_ord(eta, dk);
+    else return glm_mean<FAM>(eta);
 }
 
 // The (NT, family) switch of the shipped shapes: launch(NT, FAM) with both as std::integral_constant, so the entry names its
@@ -171,7 +196,7 @@ bool glm_draw_dispatch(int NT, int fam, Launch&& launch) {
             case 2: launch(std::integral_constant<int, 2>{}, f); return true;
             case 4: launch(std::integral_constant<int, 4>{}, f); return true;
             case 8:
-                if constexpr (FAM != PBBI_GLM_NEGBINOMIAL) {
+                if constexpr (FAM != PBBI_GLM_NEGBINOMIAL && (FAM != PBBI_GLM_ORDINAL || GLM_ORDINAL_MAX_ROWS >= 128)) {
                     launch(std::integral_constant<int, 8>{}, f);
                     return true;
                 }
@@ -184,6 +209,7 @@ bool glm_draw_dispatch(int NT, int fam, Launch&& launch) {
         case PBBI_GLM_GAUSSIAN: return tiles(std::integral_constant<int, PBBI_GLM_GAUSSIAN>{});
         case PBBI_GLM_NEGBINOMIAL: return tiles(std::integral_constant<int, PBBI_GLM_NEGBINOMIAL>{});
         case PBBI_GLM_GAMMA: return tiles(std::integral_constant<int, PBBI_GLM_GAMMA>{});
+        case PBBI_GLM_ORDINAL: return tiles(std::integral_constant<int, PBBI_GLM_ORDINAL>{});
     }
     return false;
 }

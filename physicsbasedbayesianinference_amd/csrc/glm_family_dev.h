@@ -1,6 +1,6 @@
 // glm_family_dev.h -- the family arithmetic of the GLM kernels (gfx950), stated once: the per-observation energy term U_i of
 // each family with its derivatives, psi and log Gamma, what a dispersion family forms once per chain, the fitted mean and the
-// rule that selects a row of weight 0 out.  k_glm (kernels_glm.hip, kernels_glm_metric.hip) takes U_i, dU_i/deta and
+// rule that selects a row of weight 0 out; the ordinal family's cutpoints, link and expected category.  k_glm (kernels_glm.hip, kernels_glm_metric.hip) takes U_i, dU_i/deta and
 // dU_i/dtheta; the kernels that take draws (k_glm_pw, k_glm_ll; glm_draws_dev.h) call the same functions with want_u and keep
 // U_i alone -- the compiler drops the derivatives they do not read, and -ffp-contract=off keeps what is left operation for
 // operation, so the three kernels agree on U_i bit for bit by construction.  glm_disp() and glm_canonical() are glm_host.h's.
@@ -130,6 +130,91 @@ __device__ __forceinline__ void glm_link_disp(double eta, double cv, double yv, 
     }
 }
 
+// ---- ordinal (cumulative-logit) regression: K ordered categories, cutpoints kappa_1 < .. < kappa_{K-1} carried by the chain as
+// zeta_1 = kappa_1, zeta_m = log(kappa_m - kappa_{m-1}) (include/pbbi.h has the model).  What a chain forms once per gradient
+// evaluation from its K - 1 zeta rows z[0 .. K-2] (z[j] = zeta_{j+1}; entries past K - 1 are not read), before the likelihood walk:
+//   kap[j] = kappa_{j+1};  G[m] = -log(1 - exp(-Delta_m)) = -log(-expm1(-Delta_m)) of the interior category m, 1 <= m <= K - 2,
+//   whose width is Delta_m = exp(z[m]) (an evaluation that wants U only)
+// and after it, where the cutpoints' gradient is assembled (glm_ord_widths: held across the walk they would cost its registers):
+//   gap[m] = Delta_m;  iem[m] = 1 / expm1(Delta_m)
+// Entries past the model's are SELECTED to finite constants (kap: the last cutpoint again; gap 1; iem, G 0), never multiplied
+// out, so a padding row's content reaches nothing.  km1 = K - 1, as the double the category stream is compared with.
+struct GlmOrdChain { double kap[7], G[7], km1; };
+struct GlmOrdAcc { double c[7]; };  // this lane's share of sum_i dU_i/dkappa_{j+1}, j = 0 .. 6
+
+__device__ __forceinline__ GlmOrdChain glm_ord_chain(const double (&z)[7], int K, bool want_u) {
+    GlmOrdChain k;
+    k.km1 = (double)(K - 1);
+    k.kap[0] = z[0];
+    k.G[0] = 0.0;
+#pragma unroll
+    for (int m = 1; m < 7; ++m) {
+        const bool in = m < K - 1;  // wave-uniform
+        const double d = in ? exp(z[m]) : 1.0;
+        k.kap[m] = in ? k.kap[m - 1] + d : k.kap[m - 1];
+        k.G[m] = 0.0;
+        if (want_u) k.G[m] = in ? -log(-expm1(-d)) : 0.0;
+    }
+    return k;
+}
+__device__ __forceinline__ void glm_ord_widths(const double (&z)[7], int K, double (&gap)[7], double (&iem)[7]) {
+    gap[0] = 1.0;
+    iem[0] = 0.0;
+#pragma unroll
+    for (int m = 1; m < 7; ++m) {
+        const bool in = m < K - 1;
+        gap[m] = in ? exp(z[m]) : 1.0;
+        iem[m] = in ? 1.0 / expm1(gap[m]) : 0.0;
+    }
+}
+
+// U_i, dU_i/deta and the two sigmoid terms of one observation of category yv (cv = a_i):
+//   U_i = a [ sp(eta - kappa_{k+1}) + sp(kappa_k - eta) + G_k ],  s_hi = sigma(eta - kappa_{k+1}),  s_lo = sigma(kappa_k - eta)
+// the term of an infinite cutpoint absent (k = 0: no s_lo; k = K - 1: no s_hi).  The observation's two cutpoints are selected
+// out of the chain's by the category; two exp per observation, two log more where U is wanted.
+// t_hi = a s_hi is what dU/dkappa_{k+1} loses, t_lo = a s_lo what dU/dkappa_k gains.
+__device__ __forceinline__ void glm_link_ord(double eta, double cv, double yv, const GlmOrdChain& k, bool want_u, double& resid,
+                                             double& uterm, double& t_hi, double& t_lo) {
+    double khi = k.kap[0], klo = k.kap[0];
+#pragma unroll
+    for (int j = 1; j < 7; ++j) {
+        khi = (yv == (double)j) ? k.kap[j] : khi;        // kappa_{k+1} of category j is kap[j]
+        klo = (yv == (double)(j + 1)) ? k.kap[j] : klo;  // kappa_k of category j + 1 is kap[j]
+    }
+    const bool has_hi = yv < k.km1, has_lo = yv > 0.0;
+    const double a = eta - khi, b = klo - eta;
+    const double ea = exp(-fabs(a)), eb = exp(-fabs(b));
+    const double oa = 1.0 + ea, ob = 1.0 + eb;  // in [1, 2]: log(oa) is log1p(ea) to 1.2e-16 ABSOLUTE, which is what sp needs (as
+    const double ia = 1.0 / oa, ib = 1.0 / ob;  // for the negative binomial), and keeps these kernels to one logarithm's constants
+    const double s_hi = has_hi ? (a >= 0.0 ? ia : ea * ia) : 0.0;
+    const double s_lo = has_lo ? (b >= 0.0 ? ib : eb * ib) : 0.0;
+    t_hi = cv * s_hi;
+    t_lo = cv * s_lo;
+    resid = cv * (s_hi - s_lo);
+    uterm = 0.0;
+    if (want_u) {
+        double Gk = 0.0;
+#pragma unroll
+        for (int j = 1; j < 7; ++j) Gk = (yv == (double)j) ? k.G[j] : Gk;
+        const double sp_hi = has_hi ? (a > 0.0 ? a : 0.0) + log(oa) : 0.0;
+        const double sp_lo = has_lo ? (b > 0.0 ? b : 0.0) + log(ob) : 0.0;
+        uterm = cv * ((sp_hi + sp_lo) + Gk);
+    }
+}
+
+// the ordinal family's fitted mean: the expected category sum_{j = 1 .. K-1} P(y >= j) = sum_j sigma(eta - kappa_j)
+__device__ __forceinline__ double glm_mean_ord(double eta, const GlmOrdChain& k) {
+    double m = 0.0;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+        const double a = eta - k.kap[j];
+        const double e = exp(-fabs(a));
+        const double inv = 1.0 / (1.0 + e);
+        m += ((double)j < k.km1) ? (a >= 0.0 ? inv : e * inv) : 0.0;
+    }
+    return m;
+}
+
 // the fitted mean of one observation: the sigmoid as glm_link_rich forms it, eta (gaussian), exp(eta) (every log link:
 // poisson, negbinomial, gamma)
 template <int FAM>
@@ -146,9 +231,9 @@ __device__ __forceinline__ double glm_mean(double eta) {
 }
 
 // Does the row have weight?  A row without adds exactly nothing, whatever b() gave: its terms are SELECTED out, not multiplied
-// (0 * inf is NaN).  The streams are c = a n, d = a y (canonical families) and c = a, d = y (dispersion families; gamma: d = log y).
+// (0 * inf is NaN).  The streams are c = a n, d = a y (canonical families) and c = a, d = y (dispersion families; gamma: d = log y; ordinal: d = the category).
 template <int FAM>
 __device__ __forceinline__ bool glm_row_on(double cv, double dv) {
-    if constexpr (glm_disp(FAM)) return cv != 0.0;
+    if constexpr (glm_disp(FAM) || FAM == PBBI_GLM_ORDINAL) return cv != 0.0;
     else return !(cv == 0.0 && dv == 0.0);
 }

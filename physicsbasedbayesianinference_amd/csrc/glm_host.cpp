@@ -24,6 +24,7 @@ int glm_max_dim(int variant, int family) {
         case GLM_V_HIER_Q: return glm_canonical(family) ? 64 : 0;
         // (random effects for the Gamma family are not built)
         case GLM_V_HIER_DISPERSION: return family == PBBI_GLM_GAUSSIAN || family == PBBI_GLM_NEGBINOMIAL ? 64 : 0;
+        case GLM_V_ORDINAL: return family == PBBI_GLM_ORDINAL ? GLM_ORDINAL_MAX_ROWS : 0;
     }
     return 0;
 }
@@ -35,7 +36,8 @@ int glm_metric_max_dim(int variant, int family, int hier_nc, int dp, int K) {
     switch (variant) {
         case GLM_V_PLAIN: rows = glm_metric_max_rows(family, false, 0); break;
         case GLM_V_FULL:
-        case GLM_V_DISPERSION: rows = glm_metric_max_rows(family, true, 0); break;
+        case GLM_V_DISPERSION:
+        case GLM_V_ORDINAL: rows = glm_metric_max_rows(family, true, 0); break;
         case GLM_V_HIER: rows = glm_metric_max_rows(family, true, 1); break;
         case GLM_V_HIER_NC: rows = glm_metric_max_rows(family, true, 2); break;
         case GLM_V_HIER_Q: rows = glm_metric_max_rows(family, true, 3); break;
@@ -202,6 +204,52 @@ void glm_pack_obs_disp(int64_t M, int family, const double* y, const double* wei
         out[i] = weights ? weights[i] : 1.0;
         out[len + i] = family == PBBI_GLM_GAMMA ? std::log(y[i]) : y[i];
         out[2 * len + i] = offset ? offset[i] : 0.0;
+    }
+}
+
+// ---- the ordinal family -----------------------------------------------------------------------------------------
+int glm_check_ordinal_shape(int D, int K) {
+    if (D < 1) return pbbi_fail(PBBI_ERR_INVALID, "D must be >= 1");
+    if (K < 2 || K > 8)
+        return pbbi_fail(PBBI_ERR_INVALID, "ordinal: the number of categories K must be 2 .. 8 (K = " + std::to_string(K) + ")");
+    const int top = glm_max_dim(GLM_V_ORDINAL, PBBI_GLM_ORDINAL);
+    if (D + K - 1 > top)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "ordinal: the state dimension (coefficients + K - 1 cutpoint rows) must be <= " +
+                                                   std::to_string(top) + " (" + std::to_string(D + K - 1) + ")");
+    return PBBI_OK;
+}
+
+int glm_check_obs_ordinal(int64_t M, int K, const double* y, const double* weights, const double* offset) {
+    if (M < 1) return pbbi_fail(PBBI_ERR_INVALID, "M must be >= 1");
+    if (K < 2 || K > 8)
+        return pbbi_fail(PBBI_ERR_INVALID, "ordinal: the number of categories K must be 2 .. 8 (K = " + std::to_string(K) + ")");
+    if (!y) return pbbi_fail(PBBI_ERR_INVALID, "y is NULL");
+    for (int64_t i = 0; i < M; ++i) {
+        auto at = [i] { return " (observation " + std::to_string(i) + ")"; };
+        if (!(std::isfinite(y[i]) && y[i] >= 0.0 && y[i] < (double)K && y[i] == std::floor(y[i])))
+            return pbbi_fail(PBBI_ERR_INVALID, "ordinal: y must hold integer categories in [0, K)" + at());
+        if (weights && !(std::isfinite(weights[i]) && weights[i] >= 0.0))
+            return pbbi_fail(PBBI_ERR_INVALID, "weights must be finite and >= 0" + at());
+        if (offset && !std::isfinite(offset[i]))
+            return pbbi_fail(PBBI_ERR_INVALID, "offset must be finite" + at());
+    }
+    return PBBI_OK;
+}
+
+// c = a | d = y (the category) | o, each zero padded to the image's block count (glm_obs_len(M) doubles); counts_out[k] = A_k =
+// the sum of the weights of category k, 8 doubles, 0 past K.  The caller has run glm_check_obs_ordinal.
+void glm_pack_obs_ordinal(int64_t M, int K, const double* y, const double* weights, const double* offset, double* out,
+                          double* counts_out) {
+    (void)K;
+    const int64_t len = glm_blocks_padded(M) * 16;
+    std::memset(out, 0, sizeof(double) * (size_t)(3 * len));
+    for (int k = 0; k < 8; ++k) counts_out[k] = 0.0;
+    for (int64_t i = 0; i < M; ++i) {
+        const double a = weights ? weights[i] : 1.0;
+        out[i] = a;
+        out[len + i] = y[i];
+        out[2 * len + i] = offset ? offset[i] : 0.0;
+        counts_out[(int)y[i]] += a;
     }
 }
 
@@ -407,7 +455,7 @@ static int glm_check_draws(const char* entry, int handle, int family, int state_
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string(entry) + "not a GLM handle: " + GLM_POINTWISE_RULE);
     if (family == PBBI_GLM_SOFTMAX)
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string(entry) + "a softmax handle is not served: " + GLM_POINTWISE_RULE);
-    if (!glm_canonical(family) && !glm_disp(family))
+    if (!glm_canonical(family) && !glm_disp(family) && family != PBBI_GLM_ORDINAL)
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, std::string(entry) + "unknown GLM family: " + GLM_POINTWISE_RULE);
     if (Dt < state_dim)
         return pbbi_fail(PBBI_ERR_INVALID, "Dt must be at least the handle's state dimension (Dt = " + std::to_string(Dt) +

@@ -22,6 +22,7 @@ enum GlmVariant {
     GLM_V_HIER_Q = 6,           // pbbi_potential_create_glm_hier_q:          k_glm<NT, FAM, true, GLM_HIER_Q>
     GLM_V_HIER_DISPERSION = 7,  // pbbi_potential_create_glm_hier_dispersion: FAM = 3, 4 with GLM_HIER_CENTRED / GLM_HIER_NC
                                 //   (which of the two: pbbi_potential::glm_hier_nc)
+    GLM_V_ORDINAL = 8,          // pbbi_potential_create_glm_ordinal:         k_glm<NT, PBBI_GLM_ORDINAL, true>
 };
 enum { GLM_TERM_WEIGHTS = 1, GLM_TERM_OFFSET = 2, GLM_TERM_TRIALS = 4, GLM_TERM_PRIOR_VECTOR = 8, GLM_TERM_PRIOR_MEAN = 16,
        GLM_TERM_PRIOR_FLAT = 32 };
@@ -32,9 +33,15 @@ constexpr bool glm_disp(int fam) { return fam == PBBI_GLM_GAUSSIAN || fam == PBB
 constexpr bool glm_canonical(int fam) { return fam == PBBI_GLM_LOGISTIC || fam == PBBI_GLM_POISSON; }
 // the families' names as the error texts and pbbi_describe_run write them: the one table
 constexpr const char* glm_family_name(int fam) {
-    constexpr const char* names[] = {"logistic", "poisson", "softmax", "gaussian", "negbinomial", "gamma"};
+    constexpr const char* names[] = {"logistic", "poisson", "softmax", "gaussian", "negbinomial", "gamma", "ordinal"};
     return fam >= 0 && fam < (int)(sizeof(names) / sizeof(names[0])) ? names[fam] : "unknown";
 }
+
+// The ordinal family's widest shipped kernel, in padded rows: the state is the coefficients and the K - 1 cutpoint rows.  At 128
+// rows the kernel reserves 292 bytes of scratch per lane even with all 512 registers (the full model's kernel there already fills
+// the file, and the walk adds the cutpoints, the G terms and seven accumulators) and is not shipped
+// (profiles/glm_ordinal_resources.txt).
+constexpr int GLM_ORDINAL_MAX_ROWS = 64;
 
 // The largest state dimension (every sampled row: coefficients, group log-scales, a sampled log-dispersion) the kernels of a
 // variant serve for a family; 0 = nothing shipped.  The one statement of it: the create entries and the launch read this.
@@ -49,6 +56,7 @@ constexpr int glm_metric_max_rows(int family, bool rich, int hier) {
     const bool canonical = family == PBBI_GLM_LOGISTIC || family == PBBI_GLM_POISSON;
     if (hier != 0) return 64;
     if (!rich) return canonical ? 128 : 0;
+    if (family == PBBI_GLM_ORDINAL) return GLM_ORDINAL_MAX_ROWS;
     return family == PBBI_GLM_NEGBINOMIAL ? 64 : 128;
 }
 // ... and of k_glm_softmax<Dc / 16, K>: every shape of glm_softmax_layout but the one with Dc = 64 rows per class (K = 2), whose
@@ -75,6 +83,12 @@ void glm_pack_obs(int64_t M, const double* y, const double* weights, const doubl
 int glm_check_prior(int D, const double* lam, const double* mu);
 int glm_check_obs_disp(int64_t M, int family, const double* y, const double* weights, const double* offset);
 void glm_pack_obs_disp(int64_t M, int family, const double* y, const double* weights, const double* offset, double* out);
+// ---- the ordinal family: the shape rule (K, and D + K - 1 against glm_max_dim), the observation rules, the streams a | y | o with
+// the weighted category counts A_k (8 doubles, 0 past K), and the prior table lam (DP) | mu (DP) | A_k (8) | A_k as built (8)
+int glm_check_ordinal_shape(int D, int K);
+int glm_check_obs_ordinal(int64_t M, int K, const double* y, const double* weights, const double* offset);
+void glm_pack_obs_ordinal(int64_t M, int K, const double* y, const double* weights, const double* offset, double* out,
+                          double* counts_out);
 // ---- hierarchical priors: the table the kernels keep in LDS, the log-dispersion's pair, the penalty image
 int glm_check_hier(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior);
 void glm_pack_prior_groups(int D, int J, const double* lam, const double* mu, const int32_t* groups, const double* tprior,

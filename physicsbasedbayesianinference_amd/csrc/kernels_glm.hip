@@ -53,6 +53,17 @@
 // and the state is w alone.  The streams are c = a, d = y (raw; gamma: log y, taken once on the host), o; a row with c = 0 is
 // selected out.
 //
+// Ordinal regression (FAM = PBBI_GLM_ORDINAL of k_glm<NT, FAM, true>; handles of pbbi_potential_create_glm_ordinal; include/pbbi.h
+// has the model): K ordered categories, the K - 1 cutpoints carried as rows crow0 .. crow0 + K - 2 of the state -- zeta_1 = kappa_1,
+// then the log-gaps -- behind zero columns of the image like theta above, with Gaussian priors in the {lam, mu} table.  Once per
+// gradient evaluation the rows reach every lane of the chain (glm_ord_rows: a lane group owns one of them, two for K - 1 > 4) and
+// kappa_j and, where U is wanted, G_k = -log(1 - exp(-Delta_k)) are formed (glm_ord_chain).  In the walk the streams are c = a, d =
+// the category, o; the observation's two cutpoints are SELECTED out of the lane's kappa registers by its category, U_i = a [sp(eta
+// - kappa_{k+1}) + sp(kappa_k - eta) + G_k] (glm_link_ord), and the two sigmoid terms go into seven cutpoint accumulators beside
+// usum.  After it: chain_sum of each, the A_k / expm1(Delta_k) parts (A_k, the weighted category counts, follow the table in plds
+// as the n_j do), the chain rule to zeta, and the results into gacc at the owning registers.  One wave per SIMD at every size; no
+// kernel at 128 rows (profiles/glm_ordinal_resources.txt).
+//
 // Hierarchical priors (HIER = GLM_HIER_CENTRED of k_glm<NT, FAM, true, HIER>, FAM logistic / poisson; handles of
 // pbbi_potential_create_glm_hier; include/pbbi.h has the model): a block of coefficients shares the prior scale exp(t_j),
 // and t_0 .. t_{J-1} (J <= 4) are rows D .. D+J-1 of the state, behind zero columns of the image like theta above.  The
@@ -143,6 +154,12 @@ struct GlmPrmDisp : GlmPrmRich {
     double theta;  // the held log-dispersion (trow < 0)
     int trow;      // the state row of theta when it is sampled, -1 when it is held
 };
+// the ordinal family's kernel arguments (the full model's kernels keep theirs as they are); prior: lam (DP) | mu (DP) | A_k (8,
+// the weighted category counts sum_{i: y_i = k} a_i, 0 past K)
+struct GlmPrmOrd : GlmPrmRich {
+    int crow0;  // the state row of zeta_1 (= the coefficient count); zeta_{j+1} is row crow0 + j
+    int K;      // categories, 2 .. 8
+};
 // the hierarchical prior's kernel arguments (the full model's kernels keep theirs as they are)
 struct GlmPrmHier : GlmPrmRich {  // prior: lam (DP) | mu (DP) | n_j (4, the members of each group, 0 past J)
     int trow0;     // the state row of t_0 (= the coefficient count); t_j is row trow0 + j
@@ -166,7 +183,13 @@ struct GlmArgs {
                                     std::conditional_t<HIER != GLM_HIER_NONE, std::conditional_t<glm_disp(FAM), GlmPrmHierDisp, GlmPrmHier>, GlmPrm>>;
 };
 template <int FAM>
-struct GlmArgs<FAM, true, GLM_HIER_NONE> { using type = std::conditional_t<glm_disp(FAM), GlmPrmDisp, GlmPrmRich>; };
+struct GlmArgs<FAM, true, GLM_HIER_NONE> {
+    using type = std::conditional_t<glm_disp(FAM), GlmPrmDisp, std::conditional_t<FAM == PBBI_GLM_ORDINAL, GlmPrmOrd, GlmPrmRich>>;
+};
+// what a family forms once per chain and gradient evaluation, and what a lane accumulates beside usum for the rows that are no
+// coefficients of X: theta's (a double) or the cutpoints' (GlmOrdAcc)
+template <int FAM> using GlmFamChain = std::conditional_t<FAM == PBBI_GLM_ORDINAL, GlmOrdChain, GlmDispChain>;
+template <int FAM> using GlmFamAcc = std::conditional_t<FAM == PBBI_GLM_ORDINAL, GlmOrdAcc, double>;
 // the diagonal metric's kernel arguments (METRIC = true of k_glm): the arguments of the same kernel without one, plus the table
 template <class Prm>
 struct GlmPrmMetric : Prm {
@@ -206,17 +229,35 @@ __device__ __forceinline__ v2f64 glm_nc_prior(v2f64 pm) {
     return v2f64{grouped ? 1.0 : pm.x, grouped ? 0.0 : pm.y};
 }
 
+// the ordinal family's K - 1 cutpoint rows to every lane of the chain: lane group g owns zeta row jo in register so and, for
+// K - 1 > 4, row jo + 4 one register on; the owner contributes its q to that row's chain_sum, everybody else an exact 0
+template <int KS>
+__device__ __forceinline__ void glm_ord_rows(const double (&q)[KS], int jo, int so, int K, double (&z)[7]) {
+    double th0 = 0.0, th1 = 0.0;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+        th0 = (s == so) ? q[s] : th0;
+        th1 = (s == so + 1) ? q[s] : th1;
+    }
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+        z[j] = 0.0;
+        if (j < K - 1) z[j] = chain_sum(jo == (j & 3) ? (j < 4 ? th0 : th1) : 0.0);  // rows past K - 1 are not summed
+    }
+}
+
 // gacc[t][r] (row 16t + 4r + g) = sum_i X[i][row] (b'(eta_i) - y_i) for the wave's 16 chains, usum = this lane's
 // share of sum_i b(eta_i) - y_i eta_i (observations {4r + g} of every block; chain_sum completes it).
 // Every wave of the workgroup takes part in the staging: one chunk of CB blocks is in LDS while the next waits
 // in registers (fetched before the MFMAs of the current one, written after the barrier that ends its reads).
 // RICH: ylds holds the chunk's c | d | o (OBS values each); thread j < 3 OBS stages value j % OBS of stream j / OBS.
 // Dispersion families: dk = the chain's theta-derived values, tsum = this lane's share of sum_i dU_i/dtheta.
+// Ordinal family: dk = the chain's cutpoints and what is formed from them, tsum.c[j] = this lane's share of sum_i dU_i/dkappa_{j+1}.
 template <int NT, int FAM, bool RICH, int HIER = GLM_HIER_NONE>
 __device__ __forceinline__ void glm_grad(const typename GlmArgs<FAM, RICH, HIER>::type& prm, v2f64* __restrict__ lds,
                                          double* __restrict__ ylds, int lane, int g, const double (&q)[4 * NT], v4f64 (&gacc)[NT],
-                                         double& usum, bool want_u, [[maybe_unused]] const GlmDispChain& dk,
-                                         [[maybe_unused]] double& tsum) {
+                                         double& usum, bool want_u, [[maybe_unused]] const GlmFamChain<FAM>& dk,
+                                         [[maybe_unused]] GlmFamAcc<FAM>& tsum) {
     using C = GlmCfg<NT>;
     constexpr int KS = C::KS;
     const v2f64* __restrict__ src = reinterpret_cast<const v2f64*>(prm.img);
@@ -237,6 +278,10 @@ __device__ __forceinline__ void glm_grad(const typename GlmArgs<FAM, RICH, HIER>
     for (int t = 0; t < NT; ++t) gacc[t] = v4f64{0.0, 0.0, 0.0, 0.0};
     usum = 0.0;
     if constexpr (glm_disp(FAM)) tsum = 0.0;
+    if constexpr (FAM == PBBI_GLM_ORDINAL) {
+#pragma unroll
+        for (int j = 0; j < 7; ++j) tsum.c[j] = 0.0;
+    }
     for (int ch = 0; ch < nch; ++ch) {
         __syncthreads();  // everybody has finished reading the previous chunk
 #pragma unroll
@@ -287,6 +332,20 @@ __device__ __forceinline__ void glm_grad(const typename GlmArgs<FAM, RICH, HIER>
                     res[r] = on ? rr : 0.0;
                     usum += on ? ut : 0.0;
                     tsum += on ? tt : 0.0;
+                } else if constexpr (FAM == PBBI_GLM_ORDINAL) {
+                    const int i = bi * 16 + 4 * r + g;
+                    const double cv = ylds[i], yv = ylds[C::OBS + i], ov = ylds[2 * C::OBS + i];
+                    double thi, tlo;
+                    glm_link_ord(eta[r] + ov, cv, yv, dk, want_u, rr, ut, thi, tlo);
+                    const bool on = ok && cv != 0.0;  // weight 0: exactly nothing
+                    res[r] = on ? rr : 0.0;
+                    usum += on ? ut : 0.0;
+                    // category k loses a s_hi from dU/dkappa_{k+1} and gains a s_lo in dU/dkappa_k (absent terms are 0)
+                    thi = on ? thi : 0.0;
+                    tlo = on ? tlo : 0.0;
+#pragma unroll
+                    for (int j = 0; j < 7; ++j)
+                        tsum.c[j] += (yv == (double)j) ? -thi : (yv == (double)(j + 1)) ? tlo : 0.0;
                 } else if constexpr (RICH) {
                     const int i = bi * 16 + 4 * r + g;
                     const double cv = ylds[i], dv = ylds[C::OBS + i], ov = ylds[2 * C::OBS + i];
@@ -323,6 +382,7 @@ __device__ __forceinline__ void glm_grad(const typename GlmArgs<FAM, RICH, HIER>
 // scratch at their families' counts (profiles/glm_hier_dispersion_resources.txt).
 // The Gamma family runs at the Gaussian's counts, DP = 128 included (profiles/glm_gamma_resources.txt).
 constexpr int glm_waves_per_simd(int NT, int fam, int hier) {
+    if (fam == PBBI_GLM_ORDINAL) return 1;  // at the logistic's two waves the 16- and 32-row kernels reserve 212 / 324 bytes of scratch
     return (NT <= 2 && !(NT == 2 && (fam == PBBI_GLM_NEGBINOMIAL || (hier == GLM_HIER_NC && fam == PBBI_GLM_LOGISTIC)))) ? 2 : 1;
 }
 // TWIN: k_glm_softmax of kernels_glm_softmax.hip restates this frame (ghost waves and ragged tail, momentum first, the
@@ -340,6 +400,7 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
     static_assert(RICH || !glm_disp(FAM), "the dispersion families live on the full model's frame");
     static_assert(HIER == GLM_HIER_NONE || RICH, "the hierarchical prior lives on the full model's frame");
     static_assert(HIER != GLM_HIER_Q || !glm_disp(FAM), "structured group priors: logistic and poisson only");
+    static_assert(FAM != PBBI_GLM_ORDINAL || (RICH && HIER == GLM_HIER_NONE), "the ordinal family: the full model's frame, no random effects");
     using C = GlmCfg<NT>;
     constexpr int KS = C::KS;
     constexpr int DP = 16 * NT;
@@ -349,12 +410,16 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
     // RICH: {lam, mu} of each row (else unused); centred HIER: then {n_j, 0}; HIER_Q: then the penalty's fragments (8 DP^2 bytes)
     // METRIC: behind all of that the metric's table {m_d, 1 / m_d}, DP entries (mlds below) -- one array, so that a kernel without
     // a metric declares exactly what it always has
-    constexpr int PL = RICH ? DP + (HAS_NJ ? 4 : 0) + (HIER == GLM_HIER_Q ? DP * DP / 2 : 0) : 0;
+    // ordinal family: then {A_k, 0}, 8 entries
+    constexpr bool ORD = FAM == PBBI_GLM_ORDINAL;
+    constexpr int PL = RICH ? DP + (HAS_NJ ? 4 : 0) + (HIER == GLM_HIER_Q ? DP * DP / 2 : 0) + (ORD ? 8 : 0) : 0;
     __shared__ __attribute__((aligned(16))) v2f64 plds[PL + (METRIC ? DP : 0) > 0 ? PL + (METRIC ? DP : 0) : 1];
     if constexpr (RICH) {
         for (int i = threadIdx.x; i < DP; i += BLOCK) plds[i] = v2f64{prm.prior[i], prm.prior[DP + i]};
         if constexpr (HAS_NJ)
             if (threadIdx.x < 4) plds[DP + threadIdx.x] = v2f64{prm.prior[2 * DP + threadIdx.x], 0.0};
+        if constexpr (ORD)
+            if (threadIdx.x < 8) plds[DP + threadIdx.x] = v2f64{prm.prior[2 * DP + threadIdx.x], 0.0};
         if constexpr (HIER == GLM_HIER_Q) {
             const v2f64* __restrict__ qsrc = reinterpret_cast<const v2f64*>(prm.qimg);
             for (int i = threadIdx.x; i < DP * DP / 2; i += BLOCK) plds[DP + 4 + i] = qsrc[i];
@@ -480,8 +545,8 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
         double usum;
         // the dispersion families: theta to every lane of the chain and what is formed from it, before the likelihood walk
         [[maybe_unused]] int ts = -1, tg = 0;
-        [[maybe_unused]] GlmDispChain dk{};
-        [[maybe_unused]] double tsum = 0.0;
+        [[maybe_unused]] GlmFamChain<FAM> dk{};
+        [[maybe_unused]] GlmFamAcc<FAM> tsum{};
         if constexpr (glm_disp(FAM)) {
             // theta: the owner of its row contributes q[s], everybody else 0 (exact); held: from the arguments
             ts = prm.trow >> 2, tg = prm.trow & 3;  // trow = -1: no s matches
@@ -491,6 +556,17 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
             th = chain_sum(g == tg ? th : 0.0);
             if (prm.trow < 0) th = prm.theta;
             dk = glm_disp_chain<FAM>(th, want_u);
+        }
+        // the ordinal family: the K - 1 cutpoint rows to every lane of the chain.  They are consecutive rows crow0 + j, a lane's rows
+        // 4 apart: lane group g owns zeta row jo = (g - crow0) & 3 in register so and, for K - 1 > 4, row jo + 4 one register on.
+        // The owner contributes its q to that row's chain_sum, everybody else an exact 0; rows past K - 1 are not summed.
+        [[maybe_unused]] int ojo = 0, oso = -1;
+        if constexpr (ORD) {
+            ojo = (g - prm.crow0) & 3;
+            oso = (prm.crow0 + ojo) >> 2;
+            double z[7];
+            glm_ord_rows<KS>(q, ojo, oso, prm.K, z);
+            dk = glm_ord_chain(z, prm.K, want_u);
         }
         if constexpr (HIER == GLM_HIER_NC) {
             // The chain holds z_d on a grouped row: w_d = mu_d + sig_j z_d is what the likelihood sees.  The t_j reach
@@ -551,6 +627,36 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
             for (int t = 0; t < NT; ++t)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) gacc[t][r] += (4 * t + r == ts) ? tsum : 0.0;
+        }
+        if constexpr (ORD) {
+            // dU/dkappa_{j+1}: the chain's sum of the lanes' shares, plus A_{j+1} / expm1(Delta_{j+1}) - A_j / expm1(Delta_j) from
+            // the G terms of the interior categories (an empty category is SELECTED out: its width may have underflowed to 0).
+            // Then the chain rule to zeta, dU/dzeta_1 = sum_j dU/dkappa_j, dU/dzeta_m = Delta_{m-1} sum_{j >= m} dU/dkappa_j, into
+            // gacc at the owning register of each row (the prior's part comes with the row's {lam, mu} like any fixed row's).
+            // (the rows are read again and the widths formed here: q has not moved since the broadcast before the walk)
+            double z[7], gap[7], iem[7];
+            glm_ord_rows<KS>(q, ojo, oso, prm.K, z);
+            glm_ord_widths(z, prm.K, gap, iem);
+            double ai[8];
+            ai[0] = 0.0;
+#pragma unroll
+            for (int m = 1; m < 7; ++m) {
+                const double A = plds[DP + m].x;
+                ai[m] = (A != 0.0) ? A * iem[m] : 0.0;  // (iem is 0 past the interior categories)
+            }
+            ai[7] = 0.0;
+            double suf = 0.0, gown0 = 0.0, gown1 = 0.0;
+#pragma unroll
+            for (int j = 6; j >= 0; --j) {
+                if (j < prm.K - 1) suf += chain_sum(tsum.c[j]) + (ai[j + 1] - ai[j]);
+                const double gz = (j < prm.K - 1) ? (j == 0 ? suf : gap[j] * suf) : 0.0;
+                if (j < 4) gown0 = (ojo == j) ? gz : gown0;
+                else gown1 = (ojo == j - 4) ? gz : gown1;
+            }
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) gacc[t][r] += (4 * t + r == oso) ? gown0 : (4 * t + r == oso + 1) ? gown1 : 0.0;
         }
         [[maybe_unused]] double hnt = 0.0;  // centred HIER: sum_j n_j t_j; HIER_Q: sum_j r_j t_j
         if constexpr (HIER == GLM_HIER_CENTRED) {
@@ -806,7 +912,12 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
         }
     }
     const double oldH = 0.5 * chain_sum(pp_old) / m + U_old;
-    const double newH = 0.5 * chain_sum(pp_new) / m + U_new;
+    double newH = 0.5 * chain_sum(pp_new) / m + U_new;
+    // ordinal: a trajectory that diverged -- a width exp(zeta) that overflowed, inf - inf in a cutpoint, a NaN momentum behind
+    // them -- ends in a NaN energy, and a NaN ratio is ACCEPTED (metropolis_reject).  The widths are exponentials of the state,
+    // so the step that rejects a fifth of the proposals is close to the one that diverges, and a chain that accepted a NaN never
+    // leaves it: here a NaN energy is an infinite one, a rejected proposal.
+    if constexpr (FAM == PBBI_GLM_ORDINAL) newH = (newH == newH) ? newH : __builtin_inf();
     const double ratio = exp((oldH - newH) * pbbi_accept_beta(prm.flags, prm.kT));
     const bool reject = metropolis_reject(ratio, u);
     const bool compat = (prm.flags & PBBI_COMPAT_P_FROM_OLDQ) != 0;
@@ -911,6 +1022,14 @@ int glm_launch_pass(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t st
             K_(1, PBBI_GLM_GAUSSIAN) K_(2, PBBI_GLM_GAUSSIAN) K_(4, PBBI_GLM_GAUSSIAN) K_(8, PBBI_GLM_GAUSSIAN)
             K_(1, PBBI_GLM_NEGBINOMIAL) K_(2, PBBI_GLM_NEGBINOMIAL) K_(4, PBBI_GLM_NEGBINOMIAL)
             K_(1, PBBI_GLM_GAMMA) K_(2, PBBI_GLM_GAMMA) K_(4, PBBI_GLM_GAMMA) K_(8, PBBI_GLM_GAMMA)
+#undef K_
+        } break;
+        case GLM_V_ORDINAL: {
+            GlmPrmOrd a = glm_prm_rich<GlmPrmOrd>(pot, prm);
+            a.K = pot->glm_K;
+            a.crow0 = pot->D - (pot->glm_K - 1);
+#define K_(NT_) GLM_CASE(NT_, PBBI_GLM_ORDINAL, true, GLM_HIER_NONE, a)
+            K_(1) K_(2) K_(4)
 #undef K_
         } break;
         case GLM_V_HIER: {

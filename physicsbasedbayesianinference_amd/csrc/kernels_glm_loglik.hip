@@ -31,8 +31,8 @@
 // clamped chain and write nothing; a wave whose tile is past the last one does the same (it still meets every barrier).
 // Non-finite draws stay in their own column of the product: ll = -inf gives +inf, a NaN gives NaN, for that draw only.
 //
-// Shipped: the 19 shapes of glm_draw_dispatch.  None reserves scratch (profiles/glm_loglik_resources.txt, the Gamma's four in
-// profiles/glm_gamma_resources.txt).
+// Shipped: the 22 shapes of glm_draw_dispatch.  None reserves scratch (profiles/glm_loglik_resources.txt, the Gamma's four in
+// profiles/glm_gamma_resources.txt, the ordinal family's three in profiles/glm_ordinal_resources.txt).
 #include <cmath>
 
 #include "glm_draws_dev.h"
@@ -71,7 +71,7 @@ __global__ void __launch_bounds__(LL_BLOCK) k_glm_ll(LlPrm prm) {
     const bool valid = tile_ok && tile.valid;
     double q[KS];
     glm_draw_load<KS>(prm, tile.col, g, q);
-    const GlmDispChain dk = glm_draw_disp<FAM>(prm, tile.col);
+    const GlmDrawChain<FAM> dk = glm_draw_disp<FAM>(prm, tile.col);
 
     // ---- the walk over this range's observation blocks, LB at a time
     const int64_t nstage = prm.nblk / LB;
@@ -119,6 +119,12 @@ __global__ void __launch_bounds__(256) k_glm_power(const double* __restrict__ ob
     const double b = beta_dev ? *beta_dev : beta;
     obs[i] = b * obs0[i];
     if (scale_d) obs[len + i] = b * obs0[len + i];
+}
+
+// the ordinal family's weighted category counts, which its gradient reads beside the streams: A_k <- beta A_k as built
+// (tail: 8 current values, then the 8 as built -- the end of the handle's prior table)
+__global__ void __launch_bounds__(64) k_glm_power_counts(double* __restrict__ tail, double beta, const double* __restrict__ beta_dev) {
+    if (threadIdx.x < 8) tail[threadIdx.x] = (beta_dev ? *beta_dev : beta) * tail[8 + threadIdx.x];
 }
 
 }  // namespace
@@ -205,6 +211,8 @@ extern "C" int pbbi_potential_set_likelihood_power(pbbi_potential* pot, double b
     const int scale_d = (pot->glm_family == PBBI_GLM_LOGISTIC || pot->glm_family == PBBI_GLM_POISSON) ? 1 : 0;
     hipLaunchKernelGGL(k_glm_power, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, st, (const double*)pot->d_glm_obs0,
                        (double*)pot->d_glm_obs, len, scale_d, beta, beta_dev);
+    if (pot->glm_variant == GLM_V_ORDINAL)
+        hipLaunchKernelGGL(k_glm_power_counts, dim3(1), dim3(64), 0, st, (double*)pot->d_glm_prior + 2 * pot->glm_DP, beta, beta_dev);
     PBBI_HIP(hipGetLastError());
     pot->glm_power = beta_dev ? NAN : beta;
     return PBBI_OK;

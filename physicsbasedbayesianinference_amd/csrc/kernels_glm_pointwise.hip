@@ -120,7 +120,7 @@ __global__ void __launch_bounds__(PW_BLOCK) k_glm_pw(PwPrm prm) {
         const bool valid = tile.valid;
         double q[KS];
         glm_draw_load<KS>(prm, tile.col, g, q);
-        const GlmDispChain dk = glm_draw_disp<FAM>(prm, tile.col);
+        const GlmDrawChain<FAM> dk = glm_draw_disp<FAM>(prm, tile.col);
         const double ninv = 1.0 / (n + 1.0);
 #pragma unroll
         for (int bi = 0; bi < PW_OB; ++bi) {
@@ -129,7 +129,7 @@ __global__ void __launch_bounds__(PW_BLOCK) k_glm_pw(PwPrm prm) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const double e = eta[r] + ov[bi][r];
-                    const double mu = glm_mean<FAM>(e);
+                    const double mu = glm_draw_mean<FAM>(e, dk);
                     double ll = -glm_draw_uterm<FAM>(e, cv[bi][r], dv[bi][r], dk);
                     ll = glm_row_on<FAM>(cv[bi][r], dv[bi][r]) ? ll : 0.0;  // weight 0: exactly nothing, whatever b() gave
                     pw_lse_add(am[bi][r], as[bi][r], ll);

@@ -225,6 +225,23 @@ int glm_build_disp(pbbi_potential* pot, int Dx, int64_t M, const double* X, cons
     return glm_upload(pot, GLM_V_DISPERSION, family, DP, M, t);
 }
 
+// pot->D = Dx + K - 1; lam and mu cover the K - 1 cutpoint rows.  The prior table: lam (DP) | mu (DP) | A_k (8) | A_k as built (8)
+// -- the second copy is what a likelihood power scales the first from (kernels_glm_loglik.hip).
+int glm_build_ordinal(pbbi_potential* pot, int Dx, int K, int64_t M, const double* X, const double* y, const double* weights,
+                      const double* offset, const double* lam, const double* mu) {
+    const int Dt = pot->D, DP = glm_padded_dim(Dt);
+    GlmTables t = glm_design_tables(Dx, DP, M, X);  // [X | 0]: the cutpoint rows meet zero columns
+    t.obs.resize((size_t)glm_obs_len(M));
+    double counts[8];
+    glm_pack_obs_ordinal(M, K, y, weights, offset, t.obs.data(), counts);
+    t.prior = glm_prior_vectors(Dt, DP, lam, mu);
+    t.prior.insert(t.prior.end(), counts, counts + 8);
+    t.prior.insert(t.prior.end(), counts, counts + 8);
+    pot->glm_terms = glm_terms_of(weights, offset, nullptr);
+    pot->glm_K = K;
+    return glm_upload(pot, GLM_V_ORDINAL, PBBI_GLM_ORDINAL, DP, M, t);
+}
+
 // pot->D = Dx + J.  penalty != NULL: the structured group priors (centred only), rank[j] into the table's n_j slots.
 int glm_build_hier(pbbi_potential* pot, int Dx, int64_t M, const double* X, const double* y, int family,
                    const double* weights, const double* offset, const double* trials, const double* lam, const double* mu,
@@ -991,6 +1008,23 @@ int pbbi_potential_create_glm_dispersion(int D, int64_t M, const double* X, cons
     return finish_or_destroy(glm_build_disp(*out, D, M, X, y, family, weights, offset, lam, mu, sample, theta), out);
 }
 
+int pbbi_potential_create_glm_ordinal(int D, int K, int64_t M, const double* X, const double* y, const double* weights,
+                                      const double* offset, const double* lam, const double* mu, int dtype, int device,
+                                      pbbi_potential** out) {
+    if (out) *out = nullptr;
+    if (!X || !y) return pbbi_fail(PBBI_ERR_INVALID, "X / y is NULL");
+    if (D < 1) return pbbi_fail(PBBI_ERR_INVALID, "D must be >= 1");
+    if (int rc = glm_check_obs_ordinal(M, K, y, weights, offset)) return rc;
+    if (int rc = glm_check_design(D, M, X)) return rc;
+    if (dtype == PBBI_F32)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "GLM potentials run on the fp64 matrix-core kernels: float64 only");
+    if (int rc = glm_check_ordinal_shape(D, K)) return rc;
+    if (int rc = glm_check_prior(D + K - 1, lam, mu)) return rc;
+    if (int rc = new_handle(KIND_GLM, D + K - 1, dtype, device, out)) return rc;
+    DeviceGuard guard(device);
+    return finish_or_destroy(glm_build_ordinal(*out, D, K, M, X, y, weights, offset, lam, mu), out);
+}
+
 static int glm_hier_check_dim(int D, int J, int family, int dtype, int parametrisation) {
     const bool nc = parametrisation == PBBI_HIER_NONCENTRED;
     const int dmax = glm_max_dim(nc ? GLM_V_HIER_NC : GLM_V_HIER, family);
@@ -1018,6 +1052,9 @@ int pbbi_potential_create_glm_hier_ex(int D, int64_t M, const double* X, const d
                                       const double* prior_mean, const int32_t* groups, int J, const double* log_scale_prior,
                                       int parametrisation, int dtype, int device, pbbi_potential** out) {
     if (out) *out = nullptr;
+    if (family == PBBI_GLM_ORDINAL)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "random effects for the ordinal family are not built: pbbi_potential_create_glm_ordinal "
+                                               "serves it with fixed priors");
     if (parametrisation != PBBI_HIER_CENTRED && parametrisation != PBBI_HIER_NONCENTRED)
         return pbbi_fail(PBBI_ERR_INVALID, "parametrisation must be PBBI_HIER_CENTRED (0) or PBBI_HIER_NONCENTRED (1)");
     if (!X || !y) return pbbi_fail(PBBI_ERR_INVALID, "X / y is NULL");
@@ -1036,6 +1073,9 @@ int pbbi_potential_create_glm_hier_q(int D, int64_t M, const double* X, const do
                                      const double* prior_mean, const int32_t* groups, int J, const double* log_scale_prior,
                                      const double* penalty, const double* rank, int dtype, int device, pbbi_potential** out) {
     if (out) *out = nullptr;
+    if (family == PBBI_GLM_ORDINAL)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "random effects for the ordinal family are not built: pbbi_potential_create_glm_ordinal "
+                                               "serves it with fixed priors");
     if (!X || !y) return pbbi_fail(PBBI_ERR_INVALID, "X / y is NULL");
     if (int rc = glm_check_hier(D, J, prior_precision, prior_mean, groups, log_scale_prior)) return rc;
     if (int rc = glm_check_obs(M, family, y, weights, offset, trials)) return rc;
@@ -1072,6 +1112,9 @@ int pbbi_potential_create_glm_hier_dispersion(int D, int64_t M, const double* X,
                                               const double* log_scale_prior, int parametrisation, int sample, double theta,
                                               const double* log_dispersion_prior, int dtype, int device, pbbi_potential** out) {
     if (out) *out = nullptr;
+    if (family == PBBI_GLM_ORDINAL)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "random effects for the ordinal family are not built: pbbi_potential_create_glm_ordinal "
+                                               "serves it with fixed priors");
     if (parametrisation != PBBI_HIER_CENTRED && parametrisation != PBBI_HIER_NONCENTRED)
         return pbbi_fail(PBBI_ERR_INVALID, "parametrisation must be PBBI_HIER_CENTRED (0) or PBBI_HIER_NONCENTRED (1)");
     if (!X || !y) return pbbi_fail(PBBI_ERR_INVALID, "X / y is NULL");
@@ -1144,6 +1187,20 @@ int pbbi_glm_pack_observations_dispersion(int64_t M, int family, const double* y
     if (int rc = glm_check_obs_disp(M, family, y, weights, offset)) return rc;
     if (out_len < len) return pbbi_fail(PBBI_ERR_INVALID, "out is shorter than the three streams");
     glm_pack_obs_disp(M, family, y, weights, offset, out);
+    return PBBI_OK;
+}
+
+int pbbi_glm_pack_observations_ordinal(int64_t M, int K, const double* y, const double* weights, const double* offset,
+                                       double* out, int64_t out_len, int64_t* len_out, double* counts_out) {
+    if (M < 1) return pbbi_fail(PBBI_ERR_INVALID, "M must be >= 1");
+    const int64_t len = glm_obs_len(M);
+    if (len_out) *len_out = len;
+    if (!out) return PBBI_OK;
+    if (int rc = glm_check_obs_ordinal(M, K, y, weights, offset)) return rc;
+    if (out_len < len) return pbbi_fail(PBBI_ERR_INVALID, "out is shorter than the three streams");
+    double counts[8];
+    glm_pack_obs_ordinal(M, K, y, weights, offset, out, counts);
+    if (counts_out) std::memcpy(counts_out, counts, sizeof(counts));
     return PBBI_OK;
 }
 
@@ -1626,6 +1683,14 @@ int pbbi_describe_run(const pbbi_potential* pot, int method, int64_t N, int64_t 
                                         "scaled copy of the state, the group sums of gL z reduced per chain)"
                                       : "centred: the group sums of squares reduced per chain)";
             }
+            d += (t & GLM_TERM_WEIGHTS) ? ", weights" : "";
+            d += (t & GLM_TERM_OFFSET) ? ", offset" : "";
+        } else if (v == GLM_V_ORDINAL) {
+            const int t = pot->glm_terms;
+            d += "; ordinal family (cumulative logit), " + std::to_string(pot->glm_K) + " categories: " +
+                 std::to_string(pot->glm_K - 1) + " sampled cutpoint rows (state rows " + std::to_string(pot->D - (pot->glm_K - 1)) +
+                 " .. " + std::to_string(pot->D - 1) + ": the first cutpoint and the log-gaps, each read by one chain sum per "
+                 "gradient; the observation's two cutpoints selected by its category, the cutpoints' gradients reduced per chain)";
             d += (t & GLM_TERM_WEIGHTS) ? ", weights" : "";
             d += (t & GLM_TERM_OFFSET) ? ", offset" : "";
         } else if (v == GLM_V_HIER || v == GLM_V_HIER_NC || v == GLM_V_HIER_Q) {

@@ -166,6 +166,26 @@ def pack_observations_dispersion(y, family="negbinomial", weights=None, offset=N
     return out.reshape(3, -1)
 
 
+def pack_observations_ordinal(y, categories, weights=None, offset=None):
+    """The three per-observation streams an OrdinalGLM handle keeps on the device, computed (and checked) on the host by
+    libpbbi.so, and the weighted category counts: ((3, L) array, (8,) array) -- c = weights, d = y (the category) and the
+    offset, each zero padded to L as for `pack_observations`; A_k = the sum of the weights of category k, 0 past `categories`."""
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if y.ndim != 1 or y.size < 1:
+        raise ValueError("y must be 1-D with at least one entry")
+    M, K = y.size, int(categories)
+    vec = [None if v is None else _vector(v, M, name, "M") for v, name in ((weights, "weights"), (offset, "offset"))]
+    n = C.c_int64()
+    _lib.call("pbbi_glm_pack_observations_ordinal", M, K, None, None, None, None, 0, C.byref(n), None)
+    out, counts = np.empty(n.value, dtype=np.float64), np.empty(8, dtype=np.float64)
+    try:
+        _lib.call("pbbi_glm_pack_observations_ordinal", M, K, _dptr(y), _dptr(vec[0]), _dptr(vec[1]), _dptr(out), out.size,
+                  C.byref(n), _dptr(counts))
+    except RuntimeError as e:
+        raise ValueError(str(e)) from None
+    return out.reshape(3, -1), counts
+
+
 def _vector(v, n, name, letter):
     v = np.asarray(v, dtype=np.float64)
     if v.ndim != 1 or v.size != n:
@@ -260,7 +280,7 @@ def _lgamma(x):
 def pointwise_constants(family, y, weights=None, trials=None):
     """k_i: the part of observation i's log-likelihood that depends on no parameter, which the kernels drop and `pointwise`
     adds on the host -- a_i log C(n_i, y_i) (logistic), -a_i lgamma(y_i + 1) (poisson, negbinomial), -a_i / 2 log 2 pi
-    (gaussian), -a_i log y_i (gamma); a_i the weights (the likelihood of observation i enters to the power a_i)."""
+    (gaussian), -a_i log y_i (gamma), 0 (ordinal: nothing is dropped); a_i the weights (the likelihood of observation i enters to the power a_i)."""
     y = np.asarray(y, dtype=np.float64)
     a = np.ones_like(y) if weights is None else np.asarray(weights, dtype=np.float64)
     if family == "logistic":
@@ -272,6 +292,8 @@ def pointwise_constants(family, y, weights=None, trials=None):
         return -0.5 * np.log(2.0 * np.pi) * a
     if family == "gamma":
         return -a * np.log(y)
+    if family == "ordinal":
+        return np.zeros_like(y)
     raise ValueError("pointwise_constants: unknown family %r" % (family,))
 
 
@@ -399,6 +421,10 @@ def _prior_layout(pot):
         m_t, l_t = pot.log_dispersion_prior
         mean.append([m_t]); prec.append([l_t])
         names.append("log_dispersion_prior")
+    if getattr(pot, "cutpoint_prior", None) is not None:
+        cp = np.asarray(pot.cutpoint_prior, dtype=np.float64)
+        mean.append(cp[:, 0]); prec.append(cp[:, 1])
+        names += ["cutpoint_prior[%d]" % j for j in range(cp.shape[0])]
     return np.concatenate(mean), np.concatenate(prec), names, D, J, groups
 
 
@@ -758,6 +784,135 @@ class DispersionGLM(_Tempered, _Metric, Potential):
             return samples, self.dispersion
         theta = samples[D]
         return samples[:D], (theta.exp() if hasattr(theta, "exp") and not isinstance(theta, np.ndarray) else np.exp(theta))
+
+
+ORDINAL_MAX_CATEGORIES = 8
+# the largest state dimension (coefficients + K - 1 cutpoint rows) an ordinal kernel is shipped for (glm_max_dim of
+# csrc/glm_host.cpp, profiles/glm_ordinal_resources.txt)
+ORDINAL_MAX_DIM = 64
+
+
+def _cutpoint_prior(v, K):
+    """`cutpoint_prior` checked: a (K - 1, 2) array of (mean, precision) -- row 0 of zeta_1 = kappa_1, rows 1 .. K-2 of the
+    log-gaps.  Given as ((m1, l1), (mg, lg)): one pair for the first cutpoint and one for every log-gap; or (K - 1, 2)."""
+    a = np.asarray(v, dtype=np.float64)
+    if a.shape == (2, 2) and K - 1 != 2:      # (K = 3: the two readings agree)
+        a = np.vstack([a[:1], np.repeat(a[1:], K - 2, axis=0)])
+    if a.shape != (K - 1, 2):
+        raise ValueError("cutpoint_prior must be ((mean, precision) of the first cutpoint, (mean, precision) of the log-gaps) "
+                         "or a (K - 1, 2) array of such pairs (K - 1 = %d; shape %s)" % (K - 1, a.shape))
+    if not (np.all(np.isfinite(a)) and np.all(a[:, 1] >= 0)):
+        raise ValueError("cutpoint_prior must hold finite means and finite precisions >= 0")
+    return a
+
+
+class OrdinalGLM(_Tempered, _Metric, Potential):
+    """-log posterior of ordinal (cumulative-logit, proportional-odds) regression: ordered categories y_i in {0 .. K-1} -- Likert
+    items, grades, severity scores -- with cutpoints kappa_1 < .. < kappa_{K-1} (kappa_0 = -inf, kappa_K = +inf):
+
+        P(y_i = k) = sigma(kappa_{k+1} - eta_i) - sigma(kappa_k - eta_i),    eta_i = x_i . w + o_i
+
+        pot = OrdinalGLM(X, stars)                          # categories = max(y) + 1
+        hmc = HMC(Ensemble(pot.numDimensions, N), 1.0, 0.05, None, potential=pot, rng="philox")
+        w, kappa = pot.split(samples)                       # (D, ...) coefficients, (K - 1, ...) ordered cutpoints
+        q0 = pot.unconstrain(w0, kappa0)                    # starting values from the natural scale
+
+    X carries NO intercept column: the cutpoints are the intercepts (a column of ones is not identified against them; X is
+    not tested for one).  The chain's state is [w (D rows); zeta (K - 1 rows)], numDimensions == D + K - 1, the cutpoint rows
+    last and unconstrained: zeta_1 = kappa_1, zeta_j = log(kappa_j - kappa_{j-1}), so the ordering holds by construction.
+    The priors are Gaussian on these rows and stated on zeta (no Jacobian term): `cutpoint_prior` is ((mean, precision) of
+    the first cutpoint, (mean, precision) of every log-gap), default ((0, 0.1), (0, 1)) -- kappa_1 ~ N(0, 10), each gap
+    log-normal around 1 -- or a (K - 1, 2) array of pairs, one per row.  `categories=None` takes int(max(y)) + 1; 2 <= K <= 8,
+    and a category without observations is allowed.  `prior_precision` is a scalar or a (D,) vector, `prior_mean` a (D,)
+    vector (default 0), `weights` (>= 0; a row of weight 0 is held out exactly) and `offset` (M,) vectors.  K = 2 is logistic
+    regression with intercept -kappa_1.
+
+    `pointwise` reports the expected category sum_j P(y_i >= j) as `mu_i`.  Works wherever `GLM` does (HMC in both rng modes,
+    Leapfrog / StormerVerlet, the diagonal metric and `adaptMassMatrix`, `loglik`, `LikelihoodTemperedSMC`); per-chain
+    trajectory lengths and GIST raise as for `GLM`; random effects are not built for this family.  float64; the state
+    dimension is at most ORDINAL_MAX_DIM.  It runs on csrc/kernels_glm.hip (FAM = 6 of k_glm<NT, FAM, true>)."""
+
+    kind = "glm"
+    family = "ordinal"
+    pointwise = _pointwise
+
+    def __init__(self, X, y, categories=None, prior_precision=1.0, prior_mean=None, weights=None, offset=None,
+                 cutpoint_prior=((0.0, 0.1), (0.0, 1.0)), dtype="float64", device=None):
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError("X must be 2-D: (M, D) with at least one row and one column")
+        M, D = X.shape
+        y = np.asarray(y, dtype=np.float64)
+        if y.ndim != 1 or y.size != M:
+            raise ValueError("X has %d rows, y must be 1-D with as many entries (shape %s)" % (M, y.shape))
+        if not np.all(np.isfinite(X)) or not np.all(np.isfinite(y)):
+            raise ValueError("X and y must be finite")
+        K = int(np.max(y)) + 1 if categories is None else int(categories)
+        if categories is None and K < 2:
+            K = 2
+        if not 2 <= K <= ORDINAL_MAX_CATEGORIES:
+            raise ValueError("OrdinalGLM serves 2 <= categories <= %d (got %d)" % (ORDINAL_MAX_CATEGORIES, K))
+        if not (np.all(y >= 0) and np.all(y < K) and np.all(y == np.floor(y))):
+            raise ValueError("ordinal: y must hold integer categories in [0, %d)" % K)
+        if weights is not None:
+            weights = _vector(weights, M, "weights", "M")
+            if not np.all(weights >= 0):
+                raise ValueError("weights must be >= 0")
+        if offset is not None:
+            offset = _vector(offset, M, "offset", "M")
+        lam = np.asarray(prior_precision, dtype=np.float64)
+        if lam.ndim == 0:
+            if not np.isfinite(lam):
+                raise ValueError("prior_precision must be finite and >= 0")
+            lam = np.full(D, float(lam))
+        else:
+            lam = _vector(lam, D, "prior_precision", "D")
+        if not np.all(lam >= 0):
+            raise ValueError("every prior_precision must be >= 0")
+        mu = np.zeros(D) if prior_mean is None else _vector(prior_mean, D, "prior_mean", "D")
+        cp = _cutpoint_prior(cutpoint_prior, K)
+        Dt = D + K - 1
+        if Dt > ORDINAL_MAX_DIM:
+            raise ValueError("OrdinalGLM serves a state dimension (coefficients + categories - 1) <= %d (got %d)"
+                             % (ORDINAL_MAX_DIM, Dt))
+        if np.dtype(dtype) != np.dtype("float64"):
+            raise ValueError("GLM potentials are float64 only")
+        X, y = np.ascontiguousarray(X), np.ascontiguousarray(y)
+        super().__init__(Dt, dtype, device)
+        self.X, self.y, self.weights, self.offset = X, y, weights, offset
+        self.prior_precision, self.prior_mean = lam, mu
+        self.categories, self.cutpoint_prior, self.numCoefficients = K, cp, D
+        lam_t = np.ascontiguousarray(np.r_[lam, cp[:, 1]])
+        mu_t = np.ascontiguousarray(np.r_[mu, cp[:, 0]])
+        _lib.call("pbbi_potential_create_glm_ordinal", D, K, M, _dptr(X), _dptr(y), _dptr(weights), _dptr(offset), _dptr(lam_t),
+                  _dptr(mu_t), self._dt, self.device, C.byref(self._handle))
+
+    def split(self, samples):
+        """(numDimensions, ...) -> (w, cutpoints): the (D, ...) coefficients (a view wherever the array allows one) and the
+        (K - 1, ...) cutpoints on the natural, ordered scale: kappa_j = zeta_1 + sum_{m = 2 .. j} exp(zeta_m)."""
+        D = self.numCoefficients
+        z = samples[D:self.numDimensions]
+        if isinstance(z, np.ndarray):
+            return samples[:D], np.cumsum(np.concatenate([z[:1], np.exp(z[1:])], axis=0), axis=0)
+        t = _device_torch()
+        return samples[:D], t.cumsum(t.cat([z[:1], z[1:].exp()], dim=0), dim=0)
+
+    def unconstrain(self, w, cutpoints):
+        """The inverse of `split`, for starting values: (D, ...) coefficients and (K - 1, ...) strictly increasing cutpoints ->
+        the (numDimensions, ...) state [w; kappa_1; log(kappa_j - kappa_{j-1})] (NumPy)."""
+        w, k = np.asarray(w, dtype=np.float64), np.asarray(cutpoints, dtype=np.float64)
+        if w.shape[0] != self.numCoefficients or k.shape[0] != self.categories - 1 or w.shape[1:] != k.shape[1:]:
+            raise ValueError("unconstrain: w must be (%d, ...) and cutpoints (%d, ...) with the same trailing shape"
+                             % (self.numCoefficients, self.categories - 1))
+        gaps = np.diff(k, axis=0)
+        if not (np.all(np.isfinite(k)) and np.all(gaps > 0)):
+            raise ValueError("unconstrain: the cutpoints must be finite and strictly increasing")
+        return np.concatenate([w, k[:1], np.log(gaps)], axis=0)
+
+
+def _device_torch():
+    from . import _device
+    return _device.torch()
 
 
 def _pair(v):

@@ -46,6 +46,12 @@ and the ratio to the centred kernel next to what the MFMA counts predict, 1 + (D
 each other at the shapes of --model dispersion and writes profiles/glm_gamma_bench.json: what each family's link costs on the
 same frame.
 
+--model ordinal times OrdinalGLM (K = 5; FAM = 6 of k_glm<NT, FAM, true>) beside the full logistic model at the same padded state
+dimension (16 and 64), alternating in one process at M, N and step sizes of --model dispersion, and writes
+profiles/glm_ordinal_bench.json: what the ordinal link -- two exp per observation, the select chains, the K - 1 per-chain
+reductions -- costs on the same kernel frame.  --model logistic times the logistic side alone (--out FILE); run on another build
+of the library (the parent commit's) its file is what --model ordinal --baseline FILE merges into the record.
+
 --model hierdisp times HierarchicalDispersionGLM(family="negbinomial", dispersion="sample") in both parametrisations (k_glm<NT,
 4, true, GLM_HIER_CENTRED / GLM_HIER_NC>) against the centred model as a CustomPotential and against DispersionGLM of [X | 0]
 with the group scales held at their true values -- the parent kernel at the same padded shape, so that ratio is the cost of
@@ -68,6 +74,8 @@ usage: tools/bench_glm.py [--shape small|large|all] [--K 32] [--repeats 5] [--gl
        tools/bench_glm.py --model softmax [--shape k3|k8|k8large|all]
        tools/bench_glm.py --model dispersion [--shape small|large|all]
        tools/bench_glm.py --model gamma [--shape small|large|all]
+       tools/bench_glm.py --model ordinal [--shape small|large|all] [--baseline FILE]
+       tools/bench_glm.py --model logistic [--shape small|large|all] [--build NAME] --out FILE
        tools/bench_glm.py --model hierq [--shape small|large|all]
        tools/bench_glm.py --model hierdisp [--shape small|large|all]
        tools/bench_glm.py --model pointwise [--shape small|large|all] [--slabs 8] [--repeats 5]
@@ -438,6 +446,79 @@ def bench_gamma(name, M, D, N, h, L, per_call, window, repeats, warm):
     out["gamma_over_gaussian_time_median"] = med["gamma"] / med["gaussian"]
     out["negbinomial_over_gamma_time_median"] = med["negbinomial"] / med["gamma"]
     out["gamma_lies_between"] = bool(med["gaussian"] <= med["gamma"] <= med["negbinomial"])
+    return out
+
+
+ORDINAL_K = 5
+
+
+def ordinal_problem(M, D, seed=0):
+    """Ordered categories (K = 5) from D covariates (no intercept column), offsets ~ N(0, 0.3), weights from {0.5, 1, 3}; and, for
+    the logistic side, the same X widened by K - 1 further covariates to the ordinal model's state dimension with the response
+    cut in two at the middle category."""
+    K = ORDINAL_K
+    rs = np.random.RandomState(seed)
+    X = rs.standard_normal((M, D)) / np.sqrt(D)
+    w = 0.7 * rs.standard_normal(D)
+    zeta = np.r_[-1.2, np.full(K - 2, -0.2)]
+    kappa = np.cumsum(np.r_[zeta[0], np.exp(zeta[1:])])
+    a = rs.choice([0.5, 1.0, 3.0], size=M)
+    o = 0.3 * rs.standard_normal(M)
+    y = ((rs.logistic(size=M) + X @ w + o)[:, None] > kappa[None, :]).sum(axis=1).astype(np.float64)
+    Xl = np.hstack([X, rs.standard_normal((M, K - 1)) / np.sqrt(D)])
+    return dict(X=X, y=y, weights=a, offset=o), dict(X=Xl, y=(y >= 2).astype(np.float64), weights=a, offset=o), np.r_[w, zeta], rs
+
+
+def ordinal_runners(M, D, N, h, L, per_call, W, sides):
+    """The runners of --model ordinal / logistic: OrdinalGLM (K = 5, state dimension D + 4) and the full logistic model at the
+    same padded state dimension, same weights, offsets, starts and draws."""
+    kwo, kwl, wt, rs = ordinal_problem(M, D)
+    DT = D + ORDINAL_K - 1
+    q0 = np.ascontiguousarray(wt[:, None] + 0.05 * rs.standard_normal((DT, N)))
+    runners = {}
+    if "ordinal" in sides:
+        runners["ordinal"] = Runner(P.OrdinalGLM(categories=ORDINAL_K, **kwo), DT, N, q0, h, L, per_call, W)
+    if "logistic" in sides:
+        ql = q0.copy()
+        ql[D:] = 0.05 * rs.standard_normal((ORDINAL_K - 1, N))
+        runners["logistic"] = Runner(P.GLM(family="logistic", **kwl), DT, N, ql, h, L, per_call, W)
+    return runners, DT
+
+
+def bench_ordinal(name, M, D, N, h, L, per_call, window, repeats, warm, sides=("ordinal", "logistic"), baseline=None):
+    """OrdinalGLM (K = 5) and the full logistic model at the same padded state dimension alternating in one process after warm-up
+    (M, N, h and the window lengths are --model dispersion's; D is 4 less, so that the state dimensions are its 16 and 64).  No
+    plugin side: what is measured is the cost of the ordinal link -- two exp, the select chains and the K - 1 reductions -- on the
+    same kernel frame.  sides = ("logistic",): that side alone (--model logistic), which run on another build of the library
+    gives the record `baseline` -- then merged here as logistic_baseline_*, with the ordinal kernel's time over it."""
+    W = window["dispersion"]
+    runners, DT = ordinal_runners(M, D - (ORDINAL_K - 2), N, h, L, per_call, W, sides)
+    for r in runners.values():
+        r.go(warm)
+    torch.cuda.synchronize()
+    series = {k: [] for k in runners}
+    for i in range(repeats):
+        for k, r in runners.items():   # alternating
+            series[k].append(r.timed())
+            print(f"# {name} repeat {i} {k}: {series[k][-1]:.4f} s", flush=True)
+    DP = glm.padded_dim(DT)
+    out = dict(shape=name, M=M, D=DT - (ORDINAL_K - 1), categories=ORDINAL_K, state_dimension=DT, DP=DP, chains=N, L=L, h=h,
+               iterations_per_call=per_call, iterations_per_window=W, repeats=repeats, warmup_iterations=warm,
+               timing="host clock over whole windows of pbbi_hmc_run calls (synchronised before and after)",
+               accept_rate={k: 1.0 - float(r.rej.float().mean().item()) for k, r in runners.items()})
+    flop_it = 4.0 * M * DP * (L + 1) * N
+    med = {}
+    for k, ts in series.items():
+        out[k + "_seconds"] = ts
+        out[k + "_step_chain_per_s"] = [W * L * N / t for t in ts]
+        med[k] = float(np.median(ts))
+        out[k + "_executed_tflops_median"] = flop_it * W / med[k] / 1e12
+    if "ordinal" in med and "logistic" in med:
+        out["ordinal_over_logistic_time_median"] = med["ordinal"] / med["logistic"]
+    if baseline is not None and "ordinal" in med:
+        out["logistic_baseline_seconds"] = baseline["logistic_seconds"]
+        out["logistic_baseline_build"] = baseline.get("build", "another build of the library")
+        out["ordinal_over_logistic_baseline_time_median"] = med["ordinal"] / float(np.median(baseline["logistic_seconds"]))
     return out
 
 
@@ -1099,7 +1180,10 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=None, help="default 4 (--model softmax: per shape)")
     ap.add_argument("--glm-only", action="store_true")
     ap.add_argument("--model", default="plain", choices=["plain", "rich", "softmax", "dispersion", "gamma", "hier", "hierq", "hierdisp",
-                                                         "pointwise", "loglik"])
+                                                         "pointwise", "loglik", "ordinal", "logistic"])
+    ap.add_argument("--baseline", default=None, help="--model ordinal: the output file of --model logistic run on another build "
+                                                     "of the library (the parent commit's), merged into the record")
+    ap.add_argument("--build", default=None, help="--model logistic: a name for the build measured, kept in the record")
     ap.add_argument("--slabs", type=int, default=8, help="--model pointwise / loglik: slabs of N draws")
     ap.add_argument("--parametrisation", default="centred", choices=["centred", "noncentred"],
                     help="--model hier: noncentred times the non-centred kernel against the centred one and the plugin")
@@ -1126,10 +1210,12 @@ if __name__ == "__main__":
                                results=sorted(results, key=lambda r: r["shape"], reverse=True)), f, indent=1)
                 f.write("\n")
         sys.exit(0)
-    if a.model in ("softmax", "dispersion", "gamma", "hier", "hierq", "hierdisp"):
+    if a.model in ("softmax", "dispersion", "gamma", "hier", "hierq", "hierdisp", "ordinal", "logistic"):
         table, fn, side = {"softmax": (SOFTMAX_SHAPES, bench_softmax, "softmax"),
                            "dispersion": (DISPERSION_SHAPES, bench_dispersion, "dispersion"),
                            "gamma": (DISPERSION_SHAPES, bench_gamma, "gamma"),
+                           "ordinal": (DISPERSION_SHAPES, bench_ordinal, "ordinal"),
+                           "logistic": (DISPERSION_SHAPES, bench_ordinal, "logistic"),
                            "hier": (HIER_SHAPES, bench_hier, "hier"),
                            "hierq": (HIERQ_SHAPES, bench_hierq, "hierq"),
                            "hierdisp": (HIER_DISP_SHAPES, bench_hier_dispersion, "centred")}[a.model]
@@ -1150,7 +1236,14 @@ if __name__ == "__main__":
                 cfg["repeats"] = a.repeats
             if a.warmup is not None:
                 cfg["warm"] = a.warmup
+            if a.model == "logistic":
+                cfg["sides"] = ("logistic",)
+            if a.model == "ordinal" and a.baseline:
+                with open(a.baseline) as f:
+                    cfg["baseline"] = [r for r in json.load(f)["results"] if r["shape"] == n][0]
             res = fn(n, L=a.L, **cfg)
+            if a.model == "logistic" and a.build:
+                res["build"] = a.build
             print(json.dumps(res))
             results.append(res)
             with open(a.out, "w") as f:
