@@ -42,6 +42,7 @@ draws of a (D, N, S) device view without forming an M x T matrix; a second poten
 from a proper prior and `pot.set_likelihood_power(beta)` the potential of p(w) L(w)^beta: the three pieces of
 `smc.LikelihoodTemperedSMC`, which tempers from the prior to the posterior and returns the log marginal likelihood.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -49,9 +50,10 @@ import numpy as np
 from . import _lib
 from .potential import Potential, _Metric, _dptr  # (_Metric: the mixin lives in potential.py)
 
-__all__ = ["GLM", "SoftmaxGLM", "DispersionGLM", "HierarchicalGLM", "HierarchicalDispersionGLM", "HIER_DISP_MAX_DIM",
+__all__ = ["GLM", "SoftmaxGLM", "DispersionGLM", "OrdinalGLM", "HierarchicalGLM", "HierarchicalDispersionGLM", "HIER_DISP_MAX_DIM",
            "pack_prior_groups_dispersion", "FAMILIES", "DISPERSION_FAMILIES", "HIER_MAX_DIM",
            "HIER_NC_MAX_DIM", "HIER_PARAMETRISATIONS", "HIER_MAX_GROUPS", "pack_design", "pack_observations", "pack_observations_dispersion", "pack_prior_groups",
+           "pack_observations_ordinal", "DISPERSION_MAX_DIM", "ORDINAL_MAX_DIM", "ORDINAL_MAX_CATEGORIES",
            "HIER_Q_MAX_DIM", "pack_penalty", "pack_metric", "padded_dim", "softmax_layout", "PointwiseResult", "pointwise_constants"]
 
 FAMILIES = {"logistic": _lib.GLM_LOGISTIC, "poisson": _lib.GLM_POISSON}
@@ -88,6 +90,45 @@ def padded_dim(D):
     return 16 if D <= 16 else 32 if D <= 32 else 64 if D <= 64 else 128
 
 
+def _iptr(arr):
+    return arr.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _exp(x):
+    """exp of a torch tensor or of a NumPy array, in its own array type."""
+    return x.exp() if hasattr(x, "exp") and not isinstance(x, np.ndarray) else np.exp(x)
+
+
+@contextlib.contextmanager
+def _host_errors():
+    """Whatever a host packer of libpbbi.so refuses (any RuntimeError) is a ValueError: a bad argument."""
+    try:
+        yield
+    except RuntimeError as e:
+        raise ValueError(str(e)) from None
+
+
+@contextlib.contextmanager
+def _device_errors():
+    """What a device entry refuses about its arguments (INVALID, UNSUPPORTED) is a ValueError; every other failure stays."""
+    try:
+        yield
+    except _lib.PbbiError as e:
+        if e.code in (_lib.ERR_INVALID, _lib.ERR_UNSUPPORTED):
+            raise ValueError(str(e)) from None
+        raise
+
+
+def _pack(name, scalars, arrays, also=()):
+    """The protocol of the host packers `name(*scalars, *arrays, out, out_len, &len, *also)`: one call with NULL arrays for
+    the length, one that fills a fresh array; `also` are further output arrays.  Returns the filled (flat) array."""
+    n = C.c_int64()
+    _lib.call(name, *scalars, *[None] * len(arrays), None, 0, C.byref(n), *[None] * len(also))
+    out = np.empty(n.value, dtype=np.float64)
+    _lib.call(name, *scalars, *[_dptr(v) for v in arrays], _dptr(out), out.size, C.byref(n), *[_dptr(v) for v in also])
+    return out
+
+
 def pack_metric(diag):
     """The table {m_d, 1 / m_d} a GLM handle with a diagonal metric keeps on the device and its kernel in LDS, computed
     (and checked: every entry finite and > 0) on the host by libpbbi.so (no GPU involved): array (DP, 2), {1, 1} on the
@@ -95,11 +136,7 @@ def pack_metric(diag):
     m = np.ascontiguousarray(diag, dtype=np.float64)
     if m.ndim != 1 or m.size < 1:
         raise ValueError("the metric must be a vector of D >= 1 masses")
-    n = C.c_int64()
-    _lib.call("pbbi_glm_pack_metric", m.size, None, None, 0, C.byref(n))
-    out = np.empty(n.value, dtype=np.float64)
-    _lib.call("pbbi_glm_pack_metric", m.size, _dptr(m), _dptr(out), out.size, C.byref(n))
-    return out.reshape(-1, 2)
+    return _pack("pbbi_glm_pack_metric", (m.size,), (m,)).reshape(-1, 2)
 
 
 def pack_design(X):
@@ -112,34 +149,22 @@ def pack_design(X):
         raise ValueError("X must be (M, D) with M >= 1")
     M, D = X.shape
     DP = padded_dim(D)
-    n = C.c_int64()
-    _lib.call("pbbi_glm_pack_design", D, M, None, None, 0, C.byref(n))
-    out = np.empty(n.value, dtype=np.float64)
-    _lib.call("pbbi_glm_pack_design", D, M, _dptr(X), _dptr(out), out.size, C.byref(n))
-    return out.reshape(-1, 2, DP * 16)
+    return _pack("pbbi_glm_pack_design", (D, M), (X,)).reshape(-1, 2, DP * 16)
 
 
 def pack_observations(y, family="logistic", weights=None, offset=None, trials=None):
     """The three per-observation streams the handle of the full model keeps on the device, computed (and
     checked) on the host by libpbbi.so: array (3, L) -- c = weights * trials, d = weights * y and the
     offset, each zero padded to L = 16 * (blocks of 16 observations, padded to a multiple of 4)."""
-    if family not in FAMILIES:
-        raise ValueError("family must be one of %s (got %r)" % (sorted(FAMILIES), family))
+    _known_family(family, FAMILIES)
     y = np.ascontiguousarray(y, dtype=np.float64)
     if y.ndim != 1 or y.size < 1:
         raise ValueError("y must be 1-D with at least one entry")
     M = y.size
     vec = [None if v is None else _vector(v, M, name, "M") for v, name in
            ((weights, "weights"), (offset, "offset"), (trials, "trials"))]
-    n = C.c_int64()
-    _lib.call("pbbi_glm_pack_observations", M, FAMILIES[family], None, None, None, None, None, 0, C.byref(n))
-    out = np.empty(n.value, dtype=np.float64)
-    try:
-        _lib.call("pbbi_glm_pack_observations", M, FAMILIES[family], _dptr(y), _dptr(vec[0]), _dptr(vec[1]),
-                  _dptr(vec[2]), _dptr(out), out.size, C.byref(n))
-    except RuntimeError as e:
-        raise ValueError(str(e)) from None
-    return out.reshape(3, -1)
+    with _host_errors():
+        return _pack("pbbi_glm_pack_observations", (M, FAMILIES[family]), (y, *vec)).reshape(3, -1)
 
 
 def pack_observations_dispersion(y, family="negbinomial", weights=None, offset=None):
@@ -147,23 +172,14 @@ def pack_observations_dispersion(y, family="negbinomial", weights=None, offset=N
     by libpbbi.so: array (3, L) -- c = weights, d = y (raw, not weights * y; family "gamma": log y, which is all its
     kernels need of y) and the offset, each zero padded to L as for `pack_observations`.  "gamma" requires y > 0.
     `HierarchicalDispersionGLM` keeps the same streams."""
-    if family not in DISPERSION_FAMILIES:
-        raise ValueError("family must be one of %s (got %r)" % (sorted(DISPERSION_FAMILIES), family))
+    _known_family(family, DISPERSION_FAMILIES)
     y = np.ascontiguousarray(y, dtype=np.float64)
     if y.ndim != 1 or y.size < 1:
         raise ValueError("y must be 1-D with at least one entry")
     M = y.size
     vec = [None if v is None else _vector(v, M, name, "M") for v, name in ((weights, "weights"), (offset, "offset"))]
-    fam = DISPERSION_FAMILIES[family]
-    n = C.c_int64()
-    _lib.call("pbbi_glm_pack_observations_dispersion", M, fam, None, None, None, None, 0, C.byref(n))
-    out = np.empty(n.value, dtype=np.float64)
-    try:
-        _lib.call("pbbi_glm_pack_observations_dispersion", M, fam, _dptr(y), _dptr(vec[0]), _dptr(vec[1]), _dptr(out),
-                  out.size, C.byref(n))
-    except RuntimeError as e:
-        raise ValueError(str(e)) from None
-    return out.reshape(3, -1)
+    with _host_errors():
+        return _pack("pbbi_glm_pack_observations_dispersion", (M, DISPERSION_FAMILIES[family]), (y, *vec)).reshape(3, -1)
 
 
 def pack_observations_ordinal(y, categories, weights=None, offset=None):
@@ -175,15 +191,14 @@ def pack_observations_ordinal(y, categories, weights=None, offset=None):
         raise ValueError("y must be 1-D with at least one entry")
     M, K = y.size, int(categories)
     vec = [None if v is None else _vector(v, M, name, "M") for v, name in ((weights, "weights"), (offset, "offset"))]
-    n = C.c_int64()
-    _lib.call("pbbi_glm_pack_observations_ordinal", M, K, None, None, None, None, 0, C.byref(n), None)
-    out, counts = np.empty(n.value, dtype=np.float64), np.empty(8, dtype=np.float64)
-    try:
-        _lib.call("pbbi_glm_pack_observations_ordinal", M, K, _dptr(y), _dptr(vec[0]), _dptr(vec[1]), _dptr(out), out.size,
-                  C.byref(n), _dptr(counts))
-    except RuntimeError as e:
-        raise ValueError(str(e)) from None
-    return out.reshape(3, -1), counts
+    counts = np.empty(8, dtype=np.float64)
+    with _host_errors():
+        return _pack("pbbi_glm_pack_observations_ordinal", (M, K), (y, *vec), also=(counts,)).reshape(3, -1), counts
+
+
+def _known_family(family, table):
+    if family not in table:
+        raise ValueError("family must be one of %s (got %r)" % (sorted(table), family))
 
 
 def _vector(v, n, name, letter):
@@ -195,26 +210,62 @@ def _vector(v, n, name, letter):
     return np.ascontiguousarray(v)
 
 
-def _validate(X, y, family, prior_precision, dtype, prior_mean=None, weights=None, offset=None, trials=None):
+def _design_shape(X, y):
+    """(X, y, M, D) as contiguous float64: X 2-D with at least one row and one column, y 1-D with one entry per row."""
     X = np.asarray(X, dtype=np.float64)
-    if X.ndim != 2:
-        raise ValueError("X must be 2-D: (M, D)")
+    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError("X must be 2-D: (M, D) with at least one row and one column")
     M, D = X.shape
-    if M < 1 or D < 1:
-        raise ValueError("X must have at least one row and one column")
     y = np.asarray(y, dtype=np.float64)
     if y.ndim != 1 or y.size != M:
         raise ValueError("X has %d rows, y must be 1-D with as many entries (shape %s)" % (M, y.shape))
-    if family not in FAMILIES:
-        raise ValueError("family must be one of %s (got %r)" % (sorted(FAMILIES), family))
+    return np.ascontiguousarray(X), np.ascontiguousarray(y), M, D
+
+
+def _design(X, y):
+    """The rule for X and y of every GLM class: `_design_shape`, and both finite."""
+    X, y, M, D = _design_shape(X, y)
     if not np.all(np.isfinite(X)) or not np.all(np.isfinite(y)):
         raise ValueError("X and y must be finite")
+    return X, y, M, D
+
+
+def _obs_vectors(weights, offset, M):
+    """`weights` ((M,), finite, >= 0) and `offset` ((M,), finite) checked, None where not given."""
     if weights is not None:
         weights = _vector(weights, M, "weights", "M")
         if not np.all(weights >= 0):
             raise ValueError("weights must be >= 0")
     if offset is not None:
         offset = _vector(offset, M, "offset", "M")
+    return weights, offset
+
+
+def _precision_vector(prior_precision, D):
+    """`prior_precision`, a scalar or a (D,) vector of finite values >= 0, as the (D,) vector."""
+    lam = np.asarray(prior_precision, dtype=np.float64)
+    if lam.ndim == 0:
+        if not np.isfinite(lam):
+            raise ValueError("prior_precision must be finite and >= 0")
+        lam = np.full(D, float(lam))
+    else:
+        lam = _vector(lam, D, "prior_precision", "D")
+    if not np.all(lam >= 0):
+        raise ValueError("every prior_precision must be >= 0")
+    return lam
+
+
+def _float64_only(dtype):
+    if np.dtype(dtype) != np.dtype("float64"):
+        raise ValueError("GLM potentials are float64 only")
+
+
+def _validate(X, y, family, prior_precision, dtype, prior_mean=None, weights=None, offset=None, trials=None):
+    # `_design`, with the family asked for between its shape and its value checks: the order this function has always had
+    _design_shape(X, y)
+    _known_family(family, FAMILIES)
+    X, y, M, D = _design(X, y)
+    weights, offset = _obs_vectors(weights, offset, M)
     if trials is not None:
         if family != "logistic":
             raise ValueError("trials belong to the logistic (binomial) family only")
@@ -241,9 +292,8 @@ def _validate(X, y, family, prior_precision, dtype, prior_mean=None, weights=Non
         prior_mean = _vector(prior_mean, D, "prior_mean", "D")
     if D > MAX_DIM:
         raise ValueError(f"GLM potentials serve D <= {MAX_DIM} (D = {D})")
-    if np.dtype(dtype) != np.dtype("float64"):
-        raise ValueError("GLM potentials are float64 only")
-    return np.ascontiguousarray(X), np.ascontiguousarray(y), lam, prior_mean, weights, offset, trials
+    _float64_only(dtype)
+    return X, y, lam, prior_mean, weights, offset, trials
 
 
 class PointwiseResult:
@@ -302,7 +352,7 @@ def _pointwise_slabs(pot, samples):
     a (D, N, S) device view of such slabs (getSamples(device_output=True), also sliced along S) without a copy."""
     from . import _device
     t = _device.torch()
-    natural = getattr(pot, "parametrisation", "centred") != "centred"
+    natural = pot.parametrisation != "centred"
 
     def rows(Dt):
         if Dt < pot.numDimensions:
@@ -356,18 +406,13 @@ def _pointwise(self, samples, ranges=0):
     M, T = self.y.size, S * N
     out = _device.empty((4, M), np.float64, self.device)
     ptr = [out[k].data_ptr() for k in range(4)]
-    try:
+    with _device_errors():
         _lib.call("pbbi_pointwise_glm", self.handle, sdn.data_ptr(), S, Dt, N, int(ranges), ptr[0], ptr[1],
                   ptr[2] if T >= 2 else None, ptr[3], _device.stream_ptr(self.device))
-    except _lib.PbbiError as e:
-        if e.code in (_lib.ERR_INVALID, _lib.ERR_UNSUPPORTED):
-            raise ValueError(str(e)) from None
-        raise
     lse, mean, var, mu = _device.to_numpy(out)
-    trials = getattr(self, "trials", None)
-    k = pointwise_constants(self.family, self.y, self.weights, trials)
-    if trials is not None:
-        mu = mu * trials
+    k = pointwise_constants(self.family, self.y, self.weights, self.trials)
+    if self.trials is not None:
+        mu = mu * self.trials
     return PointwiseResult(lse - np.log(T) + k, mean + k, var if T >= 2 else np.full(M, np.nan), mu, T)
 
 
@@ -388,14 +433,10 @@ def _loglik(self, samples, ranges=0, device_output=False):
     sdn, S, Dt, N = _pointwise_slabs(self, samples)
     out = _device.empty((S, N), np.float64, self.device)
     pot = self._power_target(build=False)
-    try:
+    with _device_errors():
         _lib.call("pbbi_loglik_glm", pot.handle, sdn.data_ptr(), S, Dt, N, int(ranges), out.data_ptr(),
                   _device.stream_ptr(self.device))
-    except _lib.PbbiError as e:
-        if e.code in (_lib.ERR_INVALID, _lib.ERR_UNSUPPORTED):
-            raise ValueError(str(e)) from None
-        raise
-    k = float(np.sum(pointwise_constants(self.family, self.y, self.weights, getattr(self, "trials", None))))
+    k = float(np.sum(pointwise_constants(self.family, self.y, self.weights, self.trials)))
     ll = (k - out).t()
     return ll if device_output else _device.to_numpy(ll.contiguous())
 
@@ -403,10 +444,7 @@ def _loglik(self, samples, ranges=0, device_output=False):
 def _prior_layout(pot):
     """(mean, precision, names, D, J, groups) of the rows of the state: what `sample_prior` draws from; the precision of a
     grouped coefficient is NaN (its scale is exp(t_j))."""
-    Dn = pot.numDimensions
-    D = getattr(pot, "numCoefficients", Dn)
-    J = getattr(pot, "numGroups", 0)
-    groups = getattr(pot, "groups", None)
+    D, J, groups = pot.numCoefficients, pot.numGroups, pot.groups
     lam = np.full(D, float(pot.prior_precision)) if np.ndim(pot.prior_precision) == 0 else np.array(pot.prior_precision, float)
     mu = np.zeros(D) if pot.prior_mean is None else np.asarray(pot.prior_mean, dtype=np.float64)
     names = ["prior_precision[%d]" % d for d in range(D)]
@@ -417,11 +455,11 @@ def _prior_layout(pot):
         tp = np.asarray(pot.log_scale_prior, dtype=np.float64)
         mean.append(tp[:, 0]); prec.append(tp[:, 1])
         names += ["log_scale_prior[%d]" % j for j in range(J)]
-    if getattr(pot, "sampled", False):
+    if pot.sampled:
         m_t, l_t = pot.log_dispersion_prior
         mean.append([m_t]); prec.append([l_t])
         names.append("log_dispersion_prior")
-    if getattr(pot, "cutpoint_prior", None) is not None:
+    if pot.cutpoint_prior is not None:
         cp = np.asarray(pot.cutpoint_prior, dtype=np.float64)
         mean.append(cp[:, 0]); prec.append(cp[:, 1])
         names += ["cutpoint_prior[%d]" % j for j in range(cp.shape[0])]
@@ -440,7 +478,7 @@ def _sample_prior(self, N, seed=0, draw_f64=True):
     N = int(N)
     if N < 1:
         raise ValueError("sample_prior: N must be >= 1")
-    if getattr(self, "penalty", None) is not None:
+    if self.penalty is not None:
         j = [j for j, Q in enumerate(self.penalty) if Q is not None][0]
         raise ValueError("sample_prior: group %d has a structured prior (penalty[%d]), which is not served" % (j, j))
     mean, prec, names, D, J, groups = _prior_layout(self)
@@ -460,12 +498,33 @@ def _sample_prior(self, N, seed=0, draw_f64=True):
     if grouped.any():
         rows = np.flatnonzero(grouped)
         rows_d = t.as_tensor(rows, device=q.device)
-        if getattr(self, "parametrisation", "centred") == "centred":
+        if self.parametrisation == "centred":
             trow = t.as_tensor(D + np.asarray(groups)[rows].astype(np.int64), device=q.device)
             q[rows_d] = mean_d[rows_d][:, None] + q[trow].exp() * z[rows_d]
         else:
             q[rows_d] = z[rows_d]
     return q
+
+
+class _GLMBase(Potential):
+    """What the six GLM classes share: the layout of the chain's state, declared.  Its rows are `numCoefficients` coefficients
+    (`groups`: the prior group of each, or None), `numGroups` group log-scales, one log-dispersion if `sampled`, and one row per
+    entry of `cutpoint_prior`.  `_prior_layout`, `pointwise`, `loglik`, `sample_prior` and smc.py read these attributes; a
+    class sets on its instances the ones in which it differs from the defaults here."""
+
+    kind = "glm"
+    trials = None
+    groups = None
+    numGroups = 0
+    sampled = False
+    cutpoint_prior = None
+    penalty = None
+    parametrisation = "centred"
+
+    def __getattr__(self, name):      # (asked only for what the instance and its classes do not have)
+        if name == "numCoefficients":
+            return self.numDimensions
+        raise AttributeError(name)
 
 
 class _Tempered:
@@ -492,12 +551,8 @@ class _Tempered:
         if beta_dev is None and not (np.isfinite(beta) and float(beta) > 0.0):
             raise ValueError("the likelihood power must be finite and > 0 (got %r)" % (beta,))
         pot = self._power_target()
-        try:
+        with _device_errors():
             _lib.call("pbbi_potential_set_likelihood_power", pot.handle, float(beta), beta_dev, _device.stream_ptr(self.device))
-        except _lib.PbbiError as e:
-            if e.code in (_lib.ERR_INVALID, _lib.ERR_UNSUPPORTED):
-                raise ValueError(str(e)) from None
-            raise
 
     @property
     def likelihood_power(self):
@@ -508,7 +563,7 @@ class _Tempered:
         return out.value
 
 
-class GLM(_Tempered, _Metric, Potential):
+class GLM(_Tempered, _Metric, _GLMBase):
     """-log posterior of the weights of a generalised linear model (see the module text).
 
         pot = GLM(X, y, family="logistic", prior_precision=1.0)
@@ -523,7 +578,6 @@ class GLM(_Tempered, _Metric, Potential):
     Works wherever a Potential does (HMC in both rng modes, Leapfrog / StormerVerlet, TemperedSMC,
     TemperingLadder).  Arguments are checked on the host before anything touches the GPU."""
 
-    kind = "glm"
     pointwise = _pointwise
 
     def __init__(self, X, y, family="logistic", prior_precision=1.0, prior_mean=None, weights=None, offset=None,
@@ -572,16 +626,14 @@ def softmax_layout(D, K):
     internal rows k * Dc .. k * Dc + Dc - 1.  Raises ValueError outside the supported shapes."""
     D, K = int(D), int(K)
     Dc, NT = C.c_int(), C.c_int()
-    try:
+    with _host_errors():
         _lib.call("pbbi_glm_softmax_layout", D, K, C.byref(Dc), C.byref(NT), None)
         row_map = np.empty(NT.value * 16, dtype=np.int32)
-        _lib.call("pbbi_glm_softmax_layout", D, K, C.byref(Dc), C.byref(NT), row_map.ctypes.data_as(C.POINTER(C.c_int32)))
-    except RuntimeError as e:
-        raise ValueError(str(e)) from None
+        _lib.call("pbbi_glm_softmax_layout", D, K, C.byref(Dc), C.byref(NT), _iptr(row_map))
     return Dc.value, NT.value, row_map
 
 
-class SoftmaxGLM(_Metric, Potential):
+class SoftmaxGLM(_Metric, _GLMBase):
     """-log posterior of the coefficients of K-class (multinomial logistic / softmax) regression:
 
         U(W) = sum_i [ logsumexp_k(x_i . W_k) - x_i . W_{y_i} ] + 0.5 sum_k sum_d lam_d W_kd^2,   y_i in {0 .. K-1}
@@ -604,18 +656,8 @@ class SoftmaxGLM(_Metric, Potential):
     Works wherever `GLM` does (HMC in both rng modes, Leapfrog / StormerVerlet, TemperedSMC, TemperingLadder,
     sampleStats).  Arguments are checked on the host before anything touches the GPU."""
 
-    kind = "glm"
-
     def __init__(self, X, y, classes=None, prior_precision=1.0, dtype="float64", device=None):
-        X = np.asarray(X, dtype=np.float64)
-        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
-            raise ValueError("X must be 2-D: (M, D) with at least one row and one column")
-        M, D = X.shape
-        y = np.asarray(y, dtype=np.float64)
-        if y.ndim != 1 or y.size != M:
-            raise ValueError("X has %d rows, y must be 1-D with as many entries (shape %s)" % (M, y.shape))
-        if not np.all(np.isfinite(X)) or not np.all(np.isfinite(y)):
-            raise ValueError("X and y must be finite")
+        X, y, M, D = _design(X, y)
         if not (np.all(y >= 0) and np.all(y == np.floor(y))):
             raise ValueError("labels must be integers >= 0")
         K = int(y.max()) + 1 if classes is None else int(classes)
@@ -625,16 +667,9 @@ class SoftmaxGLM(_Metric, Potential):
             raise ValueError("softmax regression needs classes >= 2 (classes = %d)" % K)
         if not np.all(y < K):
             raise ValueError("labels must be < classes = %d" % K)
-        lam = np.asarray(prior_precision, dtype=np.float64)
-        if lam.ndim == 0 and not np.isfinite(lam):
-            raise ValueError("prior_precision must be finite and >= 0")
-        lam = np.full(D, float(lam)) if lam.ndim == 0 else _vector(lam, D, "prior_precision", "D")
-        if not np.all(lam >= 0):
-            raise ValueError("every prior_precision must be >= 0")
+        lam = _precision_vector(prior_precision, D)
         softmax_layout(D, K)   # the shape rule, stated once: in libpbbi.so (host only); raises ValueError
-        if np.dtype(dtype) != np.dtype("float64"):
-            raise ValueError("GLM potentials are float64 only")
-        X, y, lam = np.ascontiguousarray(X), np.ascontiguousarray(y), np.ascontiguousarray(lam)
+        _float64_only(dtype)
         super().__init__(K * D, dtype, device)
         self.X, self.y, self.classes, self.prior_precision = X, y, K, lam
         self.family = "softmax"
@@ -654,28 +689,13 @@ class SoftmaxGLM(_Metric, Potential):
 
 def _validate_dispersion(X, y, family, weights, offset):
     """X, y and the per-observation vectors of a dispersion family, checked: (X, y, weights, offset) as float64 arrays."""
-    if family not in DISPERSION_FAMILIES:
-        raise ValueError("family must be one of %s (got %r)" % (sorted(DISPERSION_FAMILIES), family))
-    X = np.asarray(X, dtype=np.float64)
-    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
-        raise ValueError("X must be 2-D: (M, D) with at least one row and one column")
-    M, D = X.shape
-    y = np.asarray(y, dtype=np.float64)
-    if y.ndim != 1 or y.size != M:
-        raise ValueError("X has %d rows, y must be 1-D with as many entries (shape %s)" % (M, y.shape))
-    if not np.all(np.isfinite(X)) or not np.all(np.isfinite(y)):
-        raise ValueError("X and y must be finite")
+    _known_family(family, DISPERSION_FAMILIES)
+    X, y, M, D = _design(X, y)
     if family == "negbinomial" and not (np.all(y >= 0) and np.all(y == np.floor(y))):
         raise ValueError("negbinomial: y must hold non-negative integers")
     if family == "gamma" and not np.all(y > 0):
         raise ValueError("gamma: y must be > 0")
-    if weights is not None:
-        weights = _vector(weights, M, "weights", "M")
-        if not np.all(weights >= 0):
-            raise ValueError("weights must be >= 0")
-    if offset is not None:
-        offset = _vector(offset, M, "offset", "M")
-    return X, y, weights, offset
+    return (X, y) + _obs_vectors(weights, offset, M)
 
 
 def _dispersion_args(dispersion, log_dispersion_prior):
@@ -701,7 +721,7 @@ def _dispersion_args(dispersion, log_dispersion_prior):
     return sample, (None if sample else disp), theta, ((m_t, l_t) if sample else None)
 
 
-class DispersionGLM(_Tempered, _Metric, Potential):
+class DispersionGLM(_Tempered, _Metric, _GLMBase):
     """-log posterior of a GLM whose family has a free dispersion, with theta = log(dispersion):
 
         gaussian     y_i ~ N(eta_i, sigma^2 / a_i), sigma = exp(theta):
@@ -736,7 +756,6 @@ class DispersionGLM(_Tempered, _Metric, Potential):
     sampleStats); per-chain trajectory lengths and GIST raise as for `GLM`.  Arguments are checked on the host before
     anything touches the GPU.  It runs on csrc/kernels_glm.hip (FAM = 3, 4, 5 of k_glm<NT, FAM, true>)."""
 
-    kind = "glm"
     pointwise = _pointwise
 
     def __init__(self, X, y, family="negbinomial", dispersion="sample", log_dispersion_prior=None, prior_precision=1.0,
@@ -744,33 +763,22 @@ class DispersionGLM(_Tempered, _Metric, Potential):
         X, y, weights, offset = _validate_dispersion(X, y, family, weights, offset)
         M, D = X.shape
         sample, disp, theta, tprior = _dispersion_args(dispersion, log_dispersion_prior)
-        m_t, l_t = tprior if sample else (None, None)
-        lam = np.asarray(prior_precision, dtype=np.float64)
-        if lam.ndim == 0:
-            if not np.isfinite(lam):
-                raise ValueError("prior_precision must be finite and >= 0")
-            lam = np.full(D, float(lam))
-        else:
-            lam = _vector(lam, D, "prior_precision", "D")
-        if not np.all(lam >= 0):
-            raise ValueError("every prior_precision must be >= 0")
+        lam = _precision_vector(prior_precision, D)
         mu = np.zeros(D) if prior_mean is None else _vector(prior_mean, D, "prior_mean", "D")
         Dt = D + 1 if sample else D
         if Dt > DISPERSION_MAX_DIM[family]:
             raise ValueError("DispersionGLM(family=%r) serves a state dimension (coefficients%s) <= %d (got %d)"
                              % (family, " + 1 for the sampled dispersion" if sample else "", DISPERSION_MAX_DIM[family], Dt))
-        if np.dtype(dtype) != np.dtype("float64"):
-            raise ValueError("GLM potentials are float64 only")
-        X, y = np.ascontiguousarray(X), np.ascontiguousarray(y)
+        _float64_only(dtype)
         super().__init__(Dt, dtype, device)
         self.X, self.y, self.family, self.weights, self.offset = X, y, family, weights, offset
         self.prior_precision, self.prior_mean = lam, mu
         self.sampled = sample
         self.dispersion = "sample" if sample else disp
-        self.log_dispersion_prior = (m_t, l_t) if sample else None
+        self.log_dispersion_prior = tprior
         self.numCoefficients = D
-        lam_t = np.ascontiguousarray(np.r_[lam, l_t] if sample else lam)
-        mu_t = np.ascontiguousarray(np.r_[mu, m_t] if sample else mu)
+        lam_t = np.ascontiguousarray(np.r_[lam, tprior[1]] if sample else lam)
+        mu_t = np.ascontiguousarray(np.r_[mu, tprior[0]] if sample else mu)
         _lib.call("pbbi_potential_create_glm_dispersion", D, M, _dptr(X), _dptr(y), DISPERSION_FAMILIES[family],
                   _dptr(weights), _dptr(offset), _dptr(lam_t), _dptr(mu_t), int(sample), theta, self._dt, self.device,
                   C.byref(self._handle))
@@ -783,7 +791,7 @@ class DispersionGLM(_Tempered, _Metric, Potential):
         if not self.sampled:
             return samples, self.dispersion
         theta = samples[D]
-        return samples[:D], (theta.exp() if hasattr(theta, "exp") and not isinstance(theta, np.ndarray) else np.exp(theta))
+        return samples[:D], _exp(theta)
 
 
 ORDINAL_MAX_CATEGORIES = 8
@@ -806,7 +814,7 @@ def _cutpoint_prior(v, K):
     return a
 
 
-class OrdinalGLM(_Tempered, _Metric, Potential):
+class OrdinalGLM(_Tempered, _Metric, _GLMBase):
     """-log posterior of ordinal (cumulative-logit, proportional-odds) regression: ordered categories y_i in {0 .. K-1} -- Likert
     items, grades, severity scores -- with cutpoints kappa_1 < .. < kappa_{K-1} (kappa_0 = -inf, kappa_K = +inf):
 
@@ -832,21 +840,12 @@ class OrdinalGLM(_Tempered, _Metric, Potential):
     trajectory lengths and GIST raise as for `GLM`; random effects are not built for this family.  float64; the state
     dimension is at most ORDINAL_MAX_DIM.  It runs on csrc/kernels_glm.hip (FAM = 6 of k_glm<NT, FAM, true>)."""
 
-    kind = "glm"
     family = "ordinal"
     pointwise = _pointwise
 
     def __init__(self, X, y, categories=None, prior_precision=1.0, prior_mean=None, weights=None, offset=None,
                  cutpoint_prior=((0.0, 0.1), (0.0, 1.0)), dtype="float64", device=None):
-        X = np.asarray(X, dtype=np.float64)
-        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
-            raise ValueError("X must be 2-D: (M, D) with at least one row and one column")
-        M, D = X.shape
-        y = np.asarray(y, dtype=np.float64)
-        if y.ndim != 1 or y.size != M:
-            raise ValueError("X has %d rows, y must be 1-D with as many entries (shape %s)" % (M, y.shape))
-        if not np.all(np.isfinite(X)) or not np.all(np.isfinite(y)):
-            raise ValueError("X and y must be finite")
+        X, y, M, D = _design(X, y)
         K = int(np.max(y)) + 1 if categories is None else int(categories)
         if categories is None and K < 2:
             K = 2
@@ -854,30 +853,15 @@ class OrdinalGLM(_Tempered, _Metric, Potential):
             raise ValueError("OrdinalGLM serves 2 <= categories <= %d (got %d)" % (ORDINAL_MAX_CATEGORIES, K))
         if not (np.all(y >= 0) and np.all(y < K) and np.all(y == np.floor(y))):
             raise ValueError("ordinal: y must hold integer categories in [0, %d)" % K)
-        if weights is not None:
-            weights = _vector(weights, M, "weights", "M")
-            if not np.all(weights >= 0):
-                raise ValueError("weights must be >= 0")
-        if offset is not None:
-            offset = _vector(offset, M, "offset", "M")
-        lam = np.asarray(prior_precision, dtype=np.float64)
-        if lam.ndim == 0:
-            if not np.isfinite(lam):
-                raise ValueError("prior_precision must be finite and >= 0")
-            lam = np.full(D, float(lam))
-        else:
-            lam = _vector(lam, D, "prior_precision", "D")
-        if not np.all(lam >= 0):
-            raise ValueError("every prior_precision must be >= 0")
+        weights, offset = _obs_vectors(weights, offset, M)
+        lam = _precision_vector(prior_precision, D)
         mu = np.zeros(D) if prior_mean is None else _vector(prior_mean, D, "prior_mean", "D")
         cp = _cutpoint_prior(cutpoint_prior, K)
         Dt = D + K - 1
         if Dt > ORDINAL_MAX_DIM:
             raise ValueError("OrdinalGLM serves a state dimension (coefficients + categories - 1) <= %d (got %d)"
                              % (ORDINAL_MAX_DIM, Dt))
-        if np.dtype(dtype) != np.dtype("float64"):
-            raise ValueError("GLM potentials are float64 only")
-        X, y = np.ascontiguousarray(X), np.ascontiguousarray(y)
+        _float64_only(dtype)
         super().__init__(Dt, dtype, device)
         self.X, self.y, self.weights, self.offset = X, y, weights, offset
         self.prior_precision, self.prior_mean = lam, mu
@@ -894,7 +878,8 @@ class OrdinalGLM(_Tempered, _Metric, Potential):
         z = samples[D:self.numDimensions]
         if isinstance(z, np.ndarray):
             return samples[:D], np.cumsum(np.concatenate([z[:1], np.exp(z[1:])], axis=0), axis=0)
-        t = _device_torch()
+        from . import _device
+        t = _device.torch()
         return samples[:D], t.cumsum(t.cat([z[:1], z[1:].exp()], dim=0), dim=0)
 
     def unconstrain(self, w, cutpoints):
@@ -908,11 +893,6 @@ class OrdinalGLM(_Tempered, _Metric, Potential):
         if not (np.all(np.isfinite(k)) and np.all(gaps > 0)):
             raise ValueError("unconstrain: the cutpoints must be finite and strictly increasing")
         return np.concatenate([w, k[:1], np.log(gaps)], axis=0)
-
-
-def _device_torch():
-    from . import _device
-    return _device.torch()
 
 
 def _pair(v):
@@ -977,6 +957,14 @@ def _hier_prior(D, groups, log_scale_prior, prior_precision, prior_mean):
     return groups, J, tp, np.ascontiguousarray(lam), mu
 
 
+def _hier_args(parametrisation, groups):
+    """The two arguments both hierarchical constructors ask for before they look at the data."""
+    if not isinstance(parametrisation, str) or parametrisation not in HIER_PARAMETRISATIONS:
+        raise ValueError("parametrisation must be \"centred\" or \"noncentred\" (got %r)" % (parametrisation,))
+    if groups is None:
+        raise ValueError("groups is required: a (D,) vector of -1 (fixed prior) or group indices 0 .. J-1")
+
+
 def pack_prior_groups(groups, log_scale_prior=(0.0, 1.0), prior_precision=1.0, prior_mean=None):
     """The prior table a HierarchicalGLM handle keeps on the device and its kernel in LDS, computed (and checked) on the
     host by libpbbi.so: (table, n) -- table (2, DP) with DP = padded_dim(D + J): row 0 the `lam` slots (a fixed
@@ -986,11 +974,8 @@ def pack_prior_groups(groups, log_scale_prior=(0.0, 1.0), prior_precision=1.0, p
     groups, J, tp, lam, mu = _hier_prior(D, groups, log_scale_prior, prior_precision, prior_mean)
     DP = padded_dim(D + J)
     out, n = np.empty(2 * DP, dtype=np.float64), np.empty(J, dtype=np.float64)
-    try:
-        _lib.call("pbbi_glm_pack_prior_groups", D, J, _dptr(lam), _dptr(mu), groups.ctypes.data_as(C.POINTER(C.c_int32)),
-                  _dptr(tp), _dptr(out), _dptr(n))
-    except RuntimeError as e:
-        raise ValueError(str(e)) from None
+    with _host_errors():
+        _lib.call("pbbi_glm_pack_prior_groups", D, J, _dptr(lam), _dptr(mu), _iptr(groups), _dptr(tp), _dptr(out), _dptr(n))
     return out.reshape(2, DP), n
 
 
@@ -1095,14 +1080,10 @@ def pack_penalty(penalty, J):
     if not 1 <= J <= HIER_MAX_GROUPS:
         raise ValueError("J must be 1 .. %d (got %d)" % (HIER_MAX_GROUPS, J))
     DP = padded_dim(D + J)
-    n = C.c_int64()
-    _lib.call("pbbi_glm_pack_penalty", D, J, None, None, 0, C.byref(n))
-    out = np.empty(n.value, dtype=np.float64)
-    _lib.call("pbbi_glm_pack_penalty", D, J, _dptr(Q), _dptr(out), out.size, C.byref(n))
-    return out.reshape(DP // 16, DP // 8, 64, 2)
+    return _pack("pbbi_glm_pack_penalty", (D, J), (Q,)).reshape(DP // 16, DP // 8, 64, 2)
 
 
-class HierarchicalGLM(_Tempered, _Metric, Potential):
+class HierarchicalGLM(_Tempered, _Metric, _GLMBase):
     """-log posterior of a GLM (family "logistic" or "poisson", the full model of `GLM`: weights a_i, trials n_i,
     offsets o_i, eta_i = x_i . w + o_i) in which blocks of coefficients share a prior scale that is sampled:
 
@@ -1179,17 +1160,12 @@ class HierarchicalGLM(_Tempered, _Metric, Potential):
     sampleStats).  Arguments are checked on the host before anything touches the GPU.  It runs on csrc/kernels_glm.hip
     (k_glm<NT, FAM, true, HIER>)."""
 
-    kind = "glm"
-    parametrisation = "centred"
     pointwise = _pointwise
 
     def __init__(self, X, y, family="logistic", groups=None, log_scale_prior=(0.0, 1.0), prior_precision=1.0,
                  prior_mean=None, weights=None, offset=None, trials=None, dtype="float64", device=None,
                  parametrisation="centred", penalty=None, penalty_rank=None):
-        if not isinstance(parametrisation, str) or parametrisation not in HIER_PARAMETRISATIONS:
-            raise ValueError("parametrisation must be \"centred\" or \"noncentred\" (got %r)" % (parametrisation,))
-        if groups is None:
-            raise ValueError("groups is required: a (D,) vector of -1 (fixed prior) or group indices 0 .. J-1")
+        _hier_args(parametrisation, groups)
         # X, y and the per-observation vectors: GLM's rules (the prior is checked below, with the groups)
         X, y, _, _, a, o, n = _validate(X, y, family, 0.0, dtype, None, weights, offset, trials)
         M, D = X.shape
@@ -1202,28 +1178,30 @@ class HierarchicalGLM(_Tempered, _Metric, Potential):
         if D + J > dmax:
             raise ValueError("HierarchicalGLM(family=%r) serves a state dimension (coefficients + groups) <= %d (got %d + %d)"
                              % (family, dmax, D, J))
-        super().__init__(D + J, dtype, device)
-        self.parametrisation = parametrisation
-        self.X, self.y, self.family = X, y, family
-        self.weights, self.offset, self.trials = a, o, n
-        self.prior_precision, self.prior_mean = lam, mu
-        self.groups, self.log_scale_prior = groups, tp
-        self.numCoefficients, self.numGroups = D, J
-        self.levels = None
-        self.penalty, self.penalty_rank = Qs, ranks
+        self._set_hier_state(D + J, dtype, device, parametrisation, X, y, family, a, o, n, lam, mu, groups, tp, Qs, ranks)
+        model = (D, M, _dptr(X), _dptr(y), FAMILIES[family], _dptr(a), _dptr(o), _dptr(n), _dptr(lam), _dptr(mu), _iptr(groups),
+                 J, _dptr(tp))
+        where = (self._dt, self.device, C.byref(self._handle))
         if Qs is not None:
             rk = np.ascontiguousarray(ranks, dtype=np.float64)
-            _lib.call("pbbi_potential_create_glm_hier_q", D, M, _dptr(X), _dptr(y), FAMILIES[family], _dptr(a), _dptr(o),
-                      _dptr(n), _dptr(lam), _dptr(mu), groups.ctypes.data_as(C.POINTER(C.c_int32)), J, _dptr(tp), _dptr(Qfull),
-                      _dptr(rk), self._dt, self.device, C.byref(self._handle))
+            _lib.call("pbbi_potential_create_glm_hier_q", *model, _dptr(Qfull), _dptr(rk), *where)
         elif parametrisation == "centred":    # the entry point, and so the kernel, every call had before the keyword existed
-            _lib.call("pbbi_potential_create_glm_hier", D, M, _dptr(X), _dptr(y), FAMILIES[family], _dptr(a), _dptr(o),
-                      _dptr(n), _dptr(lam), _dptr(mu), groups.ctypes.data_as(C.POINTER(C.c_int32)), J, _dptr(tp), self._dt,
-                      self.device, C.byref(self._handle))
+            _lib.call("pbbi_potential_create_glm_hier", *model, *where)
         else:
-            _lib.call("pbbi_potential_create_glm_hier_ex", D, M, _dptr(X), _dptr(y), FAMILIES[family], _dptr(a), _dptr(o),
-                      _dptr(n), _dptr(lam), _dptr(mu), groups.ctypes.data_as(C.POINTER(C.c_int32)), J, _dptr(tp),
-                      HIER_PARAMETRISATIONS[parametrisation], self._dt, self.device, C.byref(self._handle))
+            _lib.call("pbbi_potential_create_glm_hier_ex", *model, HIER_PARAMETRISATIONS[parametrisation], *where)
+
+    def _set_hier_state(self, Dt, dtype, device, parametrisation, X, y, family, weights, offset, trials, lam, mu, groups, tp,
+                        penalty=None, ranks=None):
+        """Potential's own state (Dt rows) and the attributes every hierarchical potential carries."""
+        Potential.__init__(self, Dt, dtype, device)
+        self.parametrisation = parametrisation
+        self.X, self.y, self.family = X, y, family
+        self.weights, self.offset, self.trials = weights, offset, trials
+        self.prior_precision, self.prior_mean = lam, mu
+        self.groups, self.log_scale_prior = groups, tp
+        self.numCoefficients, self.numGroups = groups.size, tp.shape[0]
+        self.levels = None
+        self.penalty, self.penalty_rank = penalty, ranks
 
     def _scale_and_mean(self, q):
         """(exp(t) of each row's group, mu) shaped to broadcast against q[:D], in q's own array type; and the grouped mask."""
@@ -1270,7 +1248,7 @@ class HierarchicalGLM(_Tempered, _Metric, Potential):
         if self.parametrisation != "centred":
             samples = self.to_natural(samples)
         t = samples[D:D + self.numGroups]
-        return samples[:D], (t.exp() if hasattr(t, "exp") and not isinstance(t, np.ndarray) else np.exp(t))
+        return samples[:D], _exp(t)
 
     @staticmethod
     def random_intercept_design(X, labels, groups=None):
@@ -1364,11 +1342,9 @@ def pack_prior_groups_dispersion(groups, log_scale_prior=(0.0, 1.0), prior_preci
     DP = padded_dim(D + J + int(sample))
     dp = np.ascontiguousarray(dprior, dtype=np.float64) if sample else None
     out, n = np.empty(2 * DP, dtype=np.float64), np.empty(J, dtype=np.float64)
-    try:
-        _lib.call("pbbi_glm_pack_prior_groups_dispersion", D, J, _dptr(lam), _dptr(mu),
-                  groups.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(tp), int(sample), _dptr(dp), _dptr(out), _dptr(n))
-    except RuntimeError as e:
-        raise ValueError(str(e)) from None
+    with _host_errors():
+        _lib.call("pbbi_glm_pack_prior_groups_dispersion", D, J, _dptr(lam), _dptr(mu), _iptr(groups), _dptr(tp), int(sample),
+                  _dptr(dp), _dptr(out), _dptr(n))
     return out.reshape(2, DP), n
 
 
@@ -1419,10 +1395,7 @@ class HierarchicalDispersionGLM(HierarchicalGLM):
         if penalty is not None or penalty_rank is not None:
             raise ValueError("penalty= (structured group priors) is not built for HierarchicalDispersionGLM: it is served by "
                              "HierarchicalGLM (families logistic and poisson) only")
-        if not isinstance(parametrisation, str) or parametrisation not in HIER_PARAMETRISATIONS:
-            raise ValueError("parametrisation must be \"centred\" or \"noncentred\" (got %r)" % (parametrisation,))
-        if groups is None:
-            raise ValueError("groups is required: a (D,) vector of -1 (fixed prior) or group indices 0 .. J-1")
+        _hier_args(parametrisation, groups)
         if family in DISPERSION_FAMILIES and family not in HIER_DISP_MAX_DIM:
             raise ValueError("HierarchicalDispersionGLM serves the families %s: random effects for family=%r are not built "
                              "(DispersionGLM serves it)" % (sorted(HIER_DISP_MAX_DIM), family))
@@ -1436,24 +1409,14 @@ class HierarchicalDispersionGLM(HierarchicalGLM):
             raise ValueError("HierarchicalDispersionGLM(family=%r, parametrisation=%r) serves a state dimension (coefficients + "
                              "groups%s) <= %d (got %d): a kernel is shipped only if it builds without register spills to memory"
                              % (family, parametrisation, " + 1 for the sampled dispersion" if sample else "", dmax, Dt))
-        if np.dtype(dtype) != np.dtype("float64"):
-            raise ValueError("GLM potentials are float64 only")
-        X, y = np.ascontiguousarray(X), np.ascontiguousarray(y)
-        Potential.__init__(self, Dt, dtype, device)
-        self.parametrisation = parametrisation
-        self.X, self.y, self.family = X, y, family
-        self.weights, self.offset, self.trials = a, o, None
-        self.prior_precision, self.prior_mean = lam, mu
-        self.groups, self.log_scale_prior = groups, tp
-        self.numCoefficients, self.numGroups = D, J
-        self.levels = None
-        self.penalty, self.penalty_rank = None, None
+        _float64_only(dtype)
+        self._set_hier_state(Dt, dtype, device, parametrisation, X, y, family, a, o, None, lam, mu, groups, tp)
         self.sampled = sample
         self.dispersion = "sample" if sample else disp
         self.log_dispersion_prior = dprior
         dp = np.ascontiguousarray(dprior, dtype=np.float64) if sample else None
         _lib.call("pbbi_potential_create_glm_hier_dispersion", D, M, _dptr(X), _dptr(y), DISPERSION_FAMILIES[family], _dptr(a),
-                  _dptr(o), _dptr(lam), _dptr(mu), groups.ctypes.data_as(C.POINTER(C.c_int32)), J, _dptr(tp),
+                  _dptr(o), _dptr(lam), _dptr(mu), _iptr(groups), J, _dptr(tp),
                   HIER_PARAMETRISATIONS[parametrisation], int(sample), theta, _dptr(dp), self._dt, self.device,
                   C.byref(self._handle))
 
@@ -1465,4 +1428,4 @@ class HierarchicalDispersionGLM(HierarchicalGLM):
         if not self.sampled:
             return w, scales, self.dispersion
         theta = samples[self.numCoefficients + self.numGroups]
-        return w, scales, (theta.exp() if hasattr(theta, "exp") and not isinstance(theta, np.ndarray) else np.exp(theta))
+        return w, scales, _exp(theta)

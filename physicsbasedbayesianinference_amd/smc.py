@@ -280,7 +280,7 @@ class LikelihoodTemperedSMC:
         self.nstages = t
         self.betas = to_numpy(betas[1:t + 1]).copy()
         self.logZ = float(to_numpy(logz)[0])
-        k = pointwise_constants(pot.family, pot.y, pot.weights, getattr(pot, "trials", None))
+        k = pointwise_constants(pot.family, pot.y, pot.weights, pot.trials)
         self.logML = self.logZ + float(np.sum(k))
         r = to_numpy(rec[:t])
         self.logZ_increments, self.ess = r[:, 0].copy(), r[:, 1].copy()
@@ -293,7 +293,7 @@ class LikelihoodTemperedSMC:
         """The stage loop and the closing resample: launches only, plus -- adaptive schedule -- the one read of the next
         beta per stage.  Returns (stages, final state)."""
         pot, D, N, dev, S = self.pot, self.D, self.N, self.pot.device, self.max_stages
-        noncentred = getattr(pot, "parametrisation", "centred") != "centred"
+        noncentred = pot.parametrisation != "centred"
         b8, t, beta = 8, 0, 0.0
         while True:
             if t >= S:
