@@ -847,4 +847,7 @@ int pbbi_smc_resample_systematic(double* logw, int64_t N, uint64_t seed, uint64_
 #endif
 #include "pbbi_glm_metric.h"
 #include "pbbi_glm_ordinal.h"
+/* pbbi_glm_hessian(pot, q, ranges, hess_out, stream): the Hessian of a GLM handle's potential at one state (posterior mode,
+ * Laplace approximation), and its host-only twin pbbi_glm_hessian_check */
+#include "pbbi_glm_hessian.h"
 #endif /* PBBI_H */

@@ -308,6 +308,32 @@ class HMC:
     def _position_stream(self):
         return _lib.STREAM_POSITION | (_lib.STREAM_DRAW_F64 if self.draw_f64 else 0)
 
+    def _initial_state(self, q_state, qStd, seed, iter0, chain0, start=None):
+        """The chains' starting state into q_state (D, N), for the entry points that draw in the kernel (getSamples with
+        rng="philox", sampleChunks, sampleStats, adaptStepSize, adaptMassMatrix).  start=None: N(0, qStd^2) from the Philox
+        position stream at (iter0, chain0), the draw these entry points have always made.  Otherwise `start`, a (D, N)
+        float64 device tensor or NumPy array (e.g. LaplaceResult.sample of glm.GLM.laplace: chains over-dispersed around
+        the mode), is copied in -- converted to the potential's dtype -- and qStd is ignored."""
+        pot = self._pot
+        D, N = (int(v) for v in q_state.shape)
+        if start is None:
+            _lib.call("pbbi_philox_normal", seed, self._position_stream(), int(iter0), int(chain0), D, N, N,
+                      float(qStd), None, pot._dt, pot.device, q_state.data_ptr(), stream_ptr(pot.device))
+            return
+        import torch
+        if isinstance(start, torch.Tensor):
+            if not start.is_cuda or start.device.index != pot.device:
+                raise ValueError("start must live on device %d" % pot.device)
+        else:
+            start = np.asarray(start)
+        if tuple(start.shape) != (D, N):
+            raise ValueError("start must be (D, N) = (%d, %d), got %s" % (D, N, tuple(start.shape)))
+        if not isinstance(start, torch.Tensor):
+            start = as_device(start.astype(np.float64), pot.device, np.float64)
+        if start.dtype != torch.float64:
+            raise ValueError("start must be float64")
+        q_state.copy_(start)
+
     def ensembleWeights(self, q, p, temperature=None):
         """Normalised canonical weights of the ensemble, w_n = exp(-beta H_n) / sum_m exp(-beta H_m)
         with H = 0.5 p.p/mass + potential(q) (HMC.getWeights, src/HMC.py:86-104, normalised; the
@@ -423,7 +449,7 @@ class HMC:
         return run
 
     def getSamples(self, numSamples, temperature, qStd, rng=None, seed=None, device_output=False,
-                   chain0=0, iter0=0, host_stream=None, jitter=0.0, burn_in=0, per_chain_steps=False):
+                   chain0=0, iter0=0, host_stream=None, jitter=0.0, burn_in=0, per_chain_steps=False, start=None):
         """HMC.getSamples (src/HMC.py:123-183): returns (samples_hmc, momentum_hmc), each
         (D, N, numSamples) with the sample index fastest.
 
@@ -443,6 +469,7 @@ class HMC:
         include/pbbi.h) gives every CHAIN its own number of leapfrog steps in every iteration, uniform
         on [1, numSteps] from the Philox stream: randomised-length HMC per chain, inside the fused
         kernels (finished chains are masked out); self.steps holds the (S, N) counts.
+        start (rng="philox" only): the chains' starting state, see _initial_state.
         """
         pot = self._pot
         ens = self.ensemble
@@ -450,6 +477,8 @@ class HMC:
         if D != pot.numDimensions:
             raise ValueError(f"potential has D={pot.numDimensions}, ensemble has D={D}")
         rng = self.rng if rng is None else rng
+        if rng == "numpy" and start is not None:
+            raise ValueError("start needs rng='philox' (the parity mode replays the reference's stream)")
         seed = self.seed if seed is None else int(seed)
         L = self.integrator.numSteps
         h = float(self.stepSize)
@@ -488,8 +517,7 @@ class HMC:
         elif rng == "philox":
             kT = float(boltzmannConst * temperature)                         # src/ensemble.py:88
             q_state = empty((D, N), dt, dev)
-            _lib.call("pbbi_philox_normal", seed, self._position_stream(), int(iter0), int(chain0), D,
-                      N, N, float(qStd), None, pot._dt, dev, q_state.data_ptr(), stream)
+            self._initial_state(q_state, qStd, seed, iter0, chain0, start)
             if burn_in:
                 if jitter:
                     raise ValueError("burn_in and jitter cannot be combined in one call")
@@ -584,7 +612,7 @@ class HMC:
         return self._to_dns(samples), self._to_dns(momenta)
 
     def sampleChunks(self, numSamples, chunk, temperature, qStd, seed=None, chain0=0, iter0=0,
-                     spill_dir=None, momenta=False, stats=None):
+                     spill_dir=None, momenta=False, stats=None, start=None):
         """Generator over a long in-kernel-draw run in chunks of `chunk` iterations (SURVEY 8f row 4:
         at C2 scale 1000 draws are 64 GB, more than one wants resident or returned at once).  The
         chain state stays on the GPU between chunks and the Philox iteration counter continues,
@@ -595,7 +623,8 @@ class HMC:
         reference's (D, N, c) layout (momenta_XXXXX.npy when momenta=True).  stats (a stats.RunningStats of
         this ensemble's D and N) is fed every chunk before it is yielded: the run's mean, covariance, R-hat and
         ESS without more than one chunk resident.  stats may also be a list or tuple of sinks (RunningStats,
-        stats.RunningHistogram: anything with update), each fed every chunk in turn."""
+        stats.RunningHistogram: anything with update), each fed every chunk in turn.  start: the chains' starting state (_initial_state); the concatenated chunks are then those of
+        getSamples(numSamples, rng="philox", start=start)."""
         import os
         sinks = () if stats is None else tuple(stats) if isinstance(stats, (list, tuple)) else (stats,)
         pot, ens = self._pot, self.ensemble
@@ -609,8 +638,7 @@ class HMC:
         md = self._mass()
         mptr = md.data_ptr() if md is not None else None
         q_state = empty((D, N), dt, dev)
-        _lib.call("pbbi_philox_normal", seed, self._position_stream(), int(iter0), int(chain0), D, N, N,
-                  float(qStd), None, pot._dt, dev, q_state.data_ptr(), stream)
+        self._initial_state(q_state, qStd, seed, iter0, chain0, start)
         c_alloc = min(chunk, max(S, 1))
         samples = empty((c_alloc, D, N), dt, dev)
         mom = empty((c_alloc, D, N), dt, dev) if momenta else None
@@ -639,7 +667,7 @@ class HMC:
             yield s_view, m_view
 
     def sampleStats(self, numSamples, chunk, temperature, qStd, burn_in=0, max_lag=32, seed=None, chain0=0, iter0=0,
-                    hist=None):
+                    hist=None, start=None):
         """A long in-kernel-draw run reduced on the device as it goes: numSamples iterations in chunks of `chunk`
         into ONE reused (chunk, D, N) slab, every chunk accumulated into a stats.RunningStats (max_lag: the largest
         autocovariance lag kept), which is returned -- moments(), covariance(), rhat(), ess() of the whole run
@@ -648,7 +676,7 @@ class HMC:
         without a sample slab).  Nothing is read back between chunks: the launches of all chunks are queued one
         after the other, the reject count is summed on the device and read once at the end into acceptRate.
         hist (a stats.RunningHistogram of this ensemble's D and N) is fed every recorded chunk after the statistics,
-        queued in the same way: the run's quantiles and marginals beside its moments."""
+        queued in the same way: the run's quantiles and marginals beside its moments.  start: the chains' starting state (_initial_state)."""
         import torch
         pot, ens = self._pot, self.ensemble
         D, N = ens.numDimensions, ens.numParticles
@@ -669,8 +697,7 @@ class HMC:
         md = self._mass()
         mptr = md.data_ptr() if md is not None else None
         q_state = empty((D, N), dt, dev)
-        _lib.call("pbbi_philox_normal", seed, self._position_stream(), int(iter0), int(chain0), D, N, N,
-                  float(qStd), None, pot._dt, dev, q_state.data_ptr(), stream)
+        self._initial_state(q_state, qStd, seed, iter0, chain0, start)
         it = int(iter0)
         if burn_in:
             _lib.call("pbbi_hmc_run", pot.handle, self.integrator.method_id, q_state.data_ptr(), mptr, None, None,
@@ -764,7 +791,7 @@ class HMC:
             yield og_s.finish(), (og_m.finish() if momenta else None), self
 
     def adaptStepSize(self, temperature, qStd, target=0.8, iterations=60, seed=None, chain0=0,
-                      gamma=0.05, t0=10.0, kappa=0.75):
+                      gamma=0.05, t0=10.0, kappa=0.75, start=None):
         """Step-size adaptation by dual averaging (Hoffman & Gelman 2014, Alg. 5) on the
         ENSEMBLE-mean acceptance probability -- SURVEY 8f row 2 (planned in the reference's
         WeekPlan.md:16-17; described in NotesOnParticleBasedHMC.pdf 0.1.2), not a reference
@@ -772,7 +799,7 @@ class HMC:
         only the scalar mean(min(1, ratio)) leaves the GPU, all-reduced over the process group when
         the ensemble is sharded), keeps simulTime fixed (numSteps = int(simulTime/stepSize) follows
         the step), then sets self.stepSize / the integrator's to the averaged step and returns it.
-        The warm-up state is discarded."""
+        The warm-up state is discarded.  start: the warm-up's starting state (_initial_state)."""
         import torch
         pot, ens = self._pot, self.ensemble
         D, N = ens.numDimensions, ens.numParticles
@@ -789,8 +816,7 @@ class HMC:
         ratio = empty((1, N), dt, dev)  # burn-in form of pbbi_hmc_run: no sample slab
         md = self._mass()
         mptr = md.data_ptr() if md is not None else None
-        _lib.call("pbbi_philox_normal", seed, self._position_stream(), 0, int(chain0), D, N, N,
-                  float(qStd), None, pot._dt, dev, q_state.data_ptr(), stream)
+        self._initial_state(q_state, qStd, seed, 0, chain0, start)
         return self._dualAverage(q_state, ratio, mptr, kT, seed, chain0, 0, iterations, target, gamma, t0, kappa)
 
     def _dualAverage(self, q_state, ratio, mptr, kT, seed, chain0, iter0, iterations, target, gamma, t0, kappa):
@@ -850,7 +876,7 @@ class HMC:
         return self._pot.metric
 
     def adaptMassMatrix(self, temperature, qStd, windows=(25, 50, 100), target=0.8, step_iterations=40, chunk=25,
-                        seed=None, chain0=0, gamma=0.05, t0=10.0, kappa=0.75):
+                        seed=None, chain0=0, gamma=0.05, t0=10.0, kappa=0.75, start=None):
         """Windowed warm-up of the diagonal metric (Stan's scheme on the ENSEMBLE).  From a fresh start (positions drawn
         as adaptStepSize draws them) and the potential's current metric (the unit metric when it has none), for each
         window in turn, the chain state kept from one window to the next:
@@ -864,7 +890,7 @@ class HMC:
         other adapters, with one run of iteration counters over all phases.  Leaves stepSize and numSteps set (simulTime
         is kept) and returns the metric.  The warm-up state is discarded.  Potentials as for setMassMatrix: GLM and
         user-defined ones (CustomPotential, callables traced to source; trace_potential(..., prefer="source") for a
-        quadratic lambda), ValueError otherwise."""
+        quadratic lambda), ValueError otherwise.  start: the warm-up's starting state (_initial_state) in place of the fresh draw."""
         pot, ens = self._pot, self.ensemble
         D, N = ens.numDimensions, ens.numParticles
         if not hasattr(pot, "set_metric"):
@@ -882,8 +908,7 @@ class HMC:
         ratio = empty((1, N), dt, dev)
         md = self._mass()
         mptr = md.data_ptr() if md is not None else None
-        _lib.call("pbbi_philox_normal", seed, self._position_stream(), 0, int(chain0), D, N, N,
-                  float(qStd), None, pot._dt, dev, q_state.data_ptr(), stream)
+        self._initial_state(q_state, qStd, seed, 0, chain0, start)
         chunk = max(1, int(chunk))
         samples = empty((min(chunk, max(windows)), D, N), dt, dev)
         flags = self._flags() & ~_lib.COMPAT_P_FROM_OLDQ

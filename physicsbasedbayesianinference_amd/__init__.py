@@ -17,6 +17,7 @@ from .integrator import Integrator, Leapfrog, StormerVerlet
 from .HMC import HMC
 from .custom import CustomPotential
 from .glm import GLM, SoftmaxGLM, DispersionGLM, OrdinalGLM, HierarchicalGLM, HierarchicalDispersionGLM, pack_observations_dispersion, pack_prior_groups
+from .laplace import LaplaceResult
 from .stats import RunningHistogram, RunningStats
 from .smc import LikelihoodTemperedSMC
 from . import trace
@@ -26,6 +27,6 @@ __all__ = ["Ensemble", "HMC", "Integrator", "Leapfrog", "StormerVerlet", "Potent
            "Harmonic", "GaussianDiag", "StandardGaussian", "GaussianDense", "Rosenbrock",
            "harmonicPotentialND", "linear_regression_posterior", "CustomPotential", "GLM", "SoftmaxGLM", "DispersionGLM", "OrdinalGLM",
            "HierarchicalGLM", "HierarchicalDispersionGLM", "pack_observations_dispersion", "pack_prior_groups", "RunningStats",
-           "RunningHistogram", "LikelihoodTemperedSMC",
+           "RunningHistogram", "LikelihoodTemperedSMC", "LaplaceResult",
            "trace", "grad", "trace_potential"]
 __version__ = "0.1.0"

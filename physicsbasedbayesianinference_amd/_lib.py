@@ -150,6 +150,13 @@ ORDINAL_PROTOTYPES = {
     "pbbi_glm_pack_observations_ordinal": [_i64, _i, _dp, _dp, _dp, _dp, _i64, C.POINTER(C.c_int64), _dp],
 }
 
+# ... and the Hessian of a GLM handle at one state (include/pbbi_glm_hessian.h; laplace.py): the order of its rejections is spelt
+# out in tests/test_glm_hessian_host.py
+HESSIAN_PROTOTYPES = {
+    "pbbi_glm_hessian": [_vp, _vp, _i, _vp, _vp],
+    "pbbi_glm_hessian_check": [_i, _i, _i, _vp, _vp, _i],
+}
+
 _lib = None
 
 
@@ -168,7 +175,7 @@ def load():
     # dependency to that already-loaded copy instead of mapping a second runtime.
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, argtypes in {**PROTOTYPES, **HOST_PACKER_PROTOTYPES, **ORDINAL_PROTOTYPES}.items():
+    for name, argtypes in {**PROTOTYPES, **HOST_PACKER_PROTOTYPES, **ORDINAL_PROTOTYPES, **HESSIAN_PROTOTYPES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI and this table drift apart
         fn.argtypes = argtypes
         fn.restype = C.c_int

@@ -299,6 +299,33 @@ static void loglik_rules() {
     EXPECT(glm_check_loglik(1, PBBI_GLM_LOGISTIC, 5, p, u, 2000000000, 5, (int64_t)1 << 40, 0) == PBBI_OK);
 }
 
+// every rule of pbbi_glm_hessian's arguments, in the order the checker states them; the pointers are only compared with NULL
+static void hessian_rules() {
+    Buf<double> s = dbuf(1, 0.0), o = dbuf(1, 0.0);
+    const void *q = s.get(), *h = o.get();
+    for (int fam : {(int)PBBI_GLM_LOGISTIC, (int)PBBI_GLM_POISSON, (int)PBBI_GLM_GAUSSIAN, (int)PBBI_GLM_NEGBINOMIAL, (int)PBBI_GLM_GAMMA})
+        for (int ranges : {0, 1, 65535}) EXPECT(glm_check_hessian(1, fam, false, q, h, ranges) == PBBI_OK);
+    EXPECT(glm_check_hessian(0, PBBI_GLM_SOFTMAX, true, nullptr, nullptr, -1) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("handle is NULL") != std::string::npos);
+    EXPECT(glm_check_hessian(2, PBBI_GLM_SOFTMAX, true, nullptr, nullptr, -1) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("q is NULL") != std::string::npos);
+    EXPECT(glm_check_hessian(2, PBBI_GLM_SOFTMAX, true, q, nullptr, -1) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("hess_out is NULL") != std::string::npos);
+    EXPECT(glm_check_hessian(2, PBBI_GLM_SOFTMAX, true, q, h, -1) == PBBI_ERR_INVALID);
+    EXPECT(glm_check_hessian(2, PBBI_GLM_SOFTMAX, true, q, h, 65536) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("ranges must be") != std::string::npos);
+    EXPECT(glm_check_hessian(2, PBBI_GLM_SOFTMAX, true, q, h, 0) == PBBI_ERR_UNSUPPORTED);
+    EXPECT(g_error.find("not a GLM handle") != std::string::npos && g_error.find(GLM_HESSIAN_RULE) != std::string::npos);
+    EXPECT(glm_check_hessian(1, PBBI_GLM_SOFTMAX, true, q, h, 0) == PBBI_ERR_UNSUPPORTED);
+    EXPECT(g_error.find("softmax") != std::string::npos);
+    EXPECT(glm_check_hessian(1, PBBI_GLM_ORDINAL, true, q, h, 0) == PBBI_ERR_UNSUPPORTED);
+    EXPECT(g_error.find("ordinal") != std::string::npos);
+    EXPECT(glm_check_hessian(1, PBBI_GLM_LOGISTIC, true, q, h, 0) == PBBI_ERR_UNSUPPORTED);
+    EXPECT(g_error.find("hierarchical") != std::string::npos && g_error.find(GLM_HESSIAN_RULE) != std::string::npos);
+    EXPECT(glm_check_hessian(1, 99, false, q, h, 0) == PBBI_ERR_UNSUPPORTED);
+    EXPECT(g_error.find("unknown GLM family") != std::string::npos);
+}
+
 // every rule of pbbi_potential_set_likelihood_power, in the checker's order
 static void power_rules() {
     for (int fam : {(int)PBBI_GLM_LOGISTIC, (int)PBBI_GLM_POISSON, (int)PBBI_GLM_GAUSSIAN, (int)PBBI_GLM_NEGBINOMIAL}) {
@@ -357,6 +384,7 @@ int main() {
     softmax_shapes();
     pointwise_rules();
     loglik_rules();
+    hessian_rules();
     power_rules();
     // what is shipped (the one statement the entries and the launch read)
     EXPECT(glm_max_dim(GLM_V_PLAIN, PBBI_GLM_LOGISTIC) == 128 && glm_max_dim(GLM_V_FULL, PBBI_GLM_POISSON) == 128);

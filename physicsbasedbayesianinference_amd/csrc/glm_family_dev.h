@@ -130,6 +130,111 @@ __device__ __forceinline__ void glm_link_disp(double eta, double cv, double yv, 
     }
 }
 
+// ---- second derivatives: what k_glm_hess (kernels_glm_hessian.hip) takes.  New functions beside the ones above, which they do
+// not call: k_glm, k_glm_pw and k_glm_ll read none of these.
+//
+// psi'(x) for x > 0, in the style of glm_psi: the recurrence psi'(x) = psi'(x + 1) + 1/x^2, two steps at a time (one division
+// per pair), then the asymptotic series 1/x + 1/(2x^2) + sum B_2k / x^(2k+1) through x^-15.  The first term left out is
+// 3617 / (510 x^17): 4.2e-13 at 6, 7.1e-17 at 10.  The Hessian takes psi' in differences (psi'(phi) - psi'(y + phi)) whose size
+// is far below either term, so the recurrence runs up to an argument >= 10 (>= 6 would leave 2e-12 of the term); at most five
+// pairs.  glm_psi_far is psi by the same recurrence to >= 10 (first term left out of glm_psi's series: 3617 / (8160 x^16),
+// 4.4e-17 at 10), for the same reason: dU/dtheta's own psi difference is differentiated here.
+__device__ __forceinline__ double glm_trigamma(double x) {
+    double acc = 0.0;
+    while (x < 10.0) {
+        const double x1 = x + 1.0, den = x * x1;
+        acc += (x * x + x1 * x1) / (den * den);  // 1/x^2 + 1/(x + 1)^2
+        x += 2.0;
+    }
+    const double r = 1.0 / x, r2 = r * r;
+    const double tail = r2 * (1.0 / 6 - r2 * (1.0 / 30 - r2 * (1.0 / 42 - r2 * (1.0 / 30 - r2 * (5.0 / 66 -
+                        r2 * (691.0 / 2730 - r2 * (7.0 / 6)))))));
+    return acc + (r + r2 * 0.5 + r * tail);
+}
+__device__ __forceinline__ double glm_psi_far(double x) {
+    double acc = 0.0;
+    while (x < 10.0) {
+        acc -= (2.0 * x + 1.0) / (x * (x + 1.0));
+        x += 2.0;
+    }
+    const double r = 1.0 / x, r2 = r * r;
+    const double tail = r2 * (1.0 / 12 - r2 * (1.0 / 120 - r2 * (1.0 / 252 - r2 * (1.0 / 240 - r2 * (1.0 / 132 -
+                        r2 * (691.0 / 32760 - r2 * (1.0 / 12)))))));
+    return acc + ((log(x) - 0.5 * r) - tail);
+}
+
+// h = d2U_i/deta2 of the canonical families (cv = a_i n_i): c sigma (1 - sigma), c exp(eta)
+template <int FAM>
+__device__ __forceinline__ double glm_hess_rich(double eta, double cv) {
+    if constexpr (FAM == PBBI_GLM_LOGISTIC) {
+        const double e = exp(-fabs(eta));
+        const double inv = 1.0 / (1.0 + e);
+        return cv * ((e * inv) * inv);
+    } else {
+        return cv * exp(eta);
+    }
+}
+
+// what a dispersion family's second derivatives form once per evaluation
+//   gaussian:     a = tau = exp(-2 theta)
+//   negbinomial:  a = phi = exp(theta), b = psi(phi), c = phi psi'(phi)
+//   gamma:        a = alpha = exp(theta), b = (psi(alpha) - theta - 1) + (alpha psi'(alpha) - 1)
+template <int FAM>
+__device__ __forceinline__ GlmDispChain glm_hess_chain(double theta) {
+    GlmDispChain k{theta, 0.0, 0.0, 0.0};
+    if constexpr (FAM == PBBI_GLM_GAUSSIAN) {
+        k.a = exp(-2.0 * theta);
+    } else if constexpr (FAM == PBBI_GLM_GAMMA) {
+        k.a = exp(theta);
+        k.b = ((glm_psi_far(k.a) - theta) - 1.0) + (k.a * glm_trigamma(k.a) - 1.0);
+    } else {
+        static_assert(FAM == PBBI_GLM_NEGBINOMIAL, "a dispersion family");
+        k.a = exp(theta);
+        k.b = glm_psi_far(k.a);
+        k.c = k.a * glm_trigamma(k.a);
+    }
+    return k;
+}
+
+// the dispersion families' h = d2U_i/deta2, kx = d2U_i/deta dtheta and tt = d2U_i/dtheta2 (cv = a_i, yv = y_i; gamma: log y_i)
+//   gaussian     e = y - eta:  h = a tau,  kx = 2 a tau e,  tt = 2 a tau e^2
+//   negbinomial  s = sigma(eta - theta), sp = softplus(eta - theta), yp = y + phi:
+//                h = a yp s (1 - s),  kx = a [phi s - yp s (1 - s)],
+//                tt = a { phi [psi(phi) - psi(yp) + sp - s] + phi [phi psi'(phi) - phi psi'(yp)] - phi s^2 + y s (1 - s) }
+//   gamma        z = eta - log y:  h = a alpha exp(-z),  kx = a alpha (1 - exp(-z)),
+//                tt = a alpha [ (psi(alpha) - theta - 1 + z + exp(-z)) + alpha psi'(alpha) - 1 ]
+template <int FAM>
+__device__ __forceinline__ void glm_hess_disp(double eta, double cv, double yv, const GlmDispChain& k, double& h, double& kx,
+                                              double& tt) {
+    if constexpr (FAM == PBBI_GLM_GAUSSIAN) {
+        const double r = yv - eta;
+        const double tr = k.a * r;
+        h = cv * k.a;
+        kx = cv * (2.0 * tr);
+        tt = cv * (2.0 * (tr * r));
+    } else if constexpr (FAM == PBBI_GLM_GAMMA) {
+        const double z = eta - yv;
+        const double e = exp(-z);
+        h = cv * (k.a * e);
+        kx = cv * (k.a * (1.0 - e));
+        tt = cv * (k.a * (k.b + (z + e)));
+    } else {
+        static_assert(FAM == PBBI_GLM_NEGBINOMIAL, "a dispersion family");
+        const double z = eta - k.theta;
+        const double e = exp(-fabs(z));
+        const double ope = 1.0 + e;
+        const double inv = 1.0 / ope;
+        const double s = z >= 0.0 ? inv : e * inv;
+        const double ss1 = (e * inv) * inv;  // s (1 - s)
+        const double sp = (z > 0.0 ? z : 0.0) + log(ope);
+        const double yp = yv + k.a;
+        h = cv * (yp * ss1);
+        kx = cv * (k.a * s - yp * ss1);
+        tt = cv * (((k.a * (((k.b - glm_psi_far(yp)) + sp) - s) + k.a * (k.c - k.a * glm_trigamma(yp))) - k.a * (s * s)) +
+                   yv * ss1);
+    }
+}
+
 // ---- ordinal (cumulative-logit) regression: K ordered categories, cutpoints kappa_1 < .. < kappa_{K-1} carried by the chain as
 // zeta_1 = kappa_1, zeta_m = log(kappa_m - kappa_{m-1}) (include/pbbi.h has the model).  What a chain forms once per gradient
 // evaluation from its K - 1 zeta rows z[0 .. K-2] (z[j] = zeta_{j+1}; entries past K - 1 are not read), before the likelihood walk:

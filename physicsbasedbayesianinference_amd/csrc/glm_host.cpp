@@ -474,6 +474,33 @@ int glm_check_loglik(int handle, int family, int state_dim, const void* sdn, con
     return glm_check_draws("pbbi_loglik_glm: ", handle, family, state_dim, sdn, out == nullptr, S, Dt, N, ranges, false);
 }
 
+// ---- the Hessian at one state -----------------------------------------------------------------------------------
+const char* const GLM_HESSIAN_RULE = "pbbi_glm_hessian serves the handles of pbbi_potential_create_glm, _glm_ex and "
+                                     "_glm_dispersion (families logistic, poisson, gaussian, negbinomial, gamma; float64; "
+                                     "theta sampled or held)";
+
+// The rules of pbbi_glm_hessian, in the order it states them: the arguments first, then the handle's kind.
+int glm_check_hessian(int handle, int family, bool hierarchical, const void* q, const void* out, int ranges) {
+    const std::string entry = "pbbi_glm_hessian: ";
+    if (handle == 0) return pbbi_fail(PBBI_ERR_INVALID, "potential handle is NULL");
+    if (!q) return pbbi_fail(PBBI_ERR_INVALID, "q is NULL");
+    if (!out) return pbbi_fail(PBBI_ERR_INVALID, "hess_out is NULL");
+    if (ranges < 0 || ranges > 65535)
+        return pbbi_fail(PBBI_ERR_INVALID, "ranges must be 0 (the library chooses) or 1 .. 65535 (ranges = " +
+                                               std::to_string(ranges) + ")");
+    if (handle != 1) return pbbi_fail(PBBI_ERR_UNSUPPORTED, entry + "not a GLM handle: " + GLM_HESSIAN_RULE);
+    if (family == PBBI_GLM_SOFTMAX)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, entry + "a softmax handle is not served: " + GLM_HESSIAN_RULE);
+    if (family == PBBI_GLM_ORDINAL)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, entry + "an ordinal handle is not served: " + GLM_HESSIAN_RULE);
+    if (hierarchical)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, entry + "a hierarchical handle (sampled group scales) is not served: " +
+                                                   GLM_HESSIAN_RULE);
+    if (!glm_canonical(family) && !glm_disp(family))
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, entry + "unknown GLM family: " + GLM_HESSIAN_RULE);
+    return PBBI_OK;
+}
+
 // ---- the likelihood power ---------------------------------------------------------------------------------------
 const char* const GLM_POWER_RULE = "a likelihood power is served on the handles that keep observation streams: "
                                    "pbbi_potential_create_glm_ex, _glm_dispersion, _glm_hier, _glm_hier_ex, _glm_hier_q and "

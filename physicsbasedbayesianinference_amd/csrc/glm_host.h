@@ -107,6 +107,10 @@ int glm_check_pointwise(int handle, int family, int state_dim, const void* sdn, 
 // ---- the likelihood energy of each draw (kernels_glm_loglik.hip): every argument rule of pbbi_loglik_glm, `handle` as above
 int glm_check_loglik(int handle, int family, int state_dim, const void* sdn, const void* out, int S, int Dt, int64_t N,
                      int ranges);
+// ---- the Hessian at one state (kernels_glm_hessian.hip): every argument rule of pbbi_glm_hessian, `handle` as above;
+// hierarchical: the handle has group log-scales (every GLM_V_HIER* variant)
+extern const char* const GLM_HESSIAN_RULE;
+int glm_check_hessian(int handle, int family, bool hierarchical, const void* q, const void* out, int ranges);
 // ---- the likelihood power: every argument rule of pbbi_potential_set_likelihood_power.  has_streams: the handle keeps the
 // c | d | o streams (every GLM handle but the plain model's and the softmax's); beta is read only when it comes from the host
 extern const char* const GLM_POWER_RULE;

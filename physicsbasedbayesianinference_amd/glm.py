@@ -49,6 +49,7 @@ import numpy as np
 
 from . import _lib
 from .potential import Potential, _Metric, _dptr  # (_Metric: the mixin lives in potential.py)
+from .laplace import laplace as _laplace           # (bound on GLM and DispersionGLM alone)
 
 __all__ = ["GLM", "SoftmaxGLM", "DispersionGLM", "OrdinalGLM", "HierarchicalGLM", "HierarchicalDispersionGLM", "HIER_DISP_MAX_DIM",
            "pack_prior_groups_dispersion", "FAMILIES", "DISPERSION_FAMILIES", "HIER_MAX_DIM",
@@ -579,6 +580,7 @@ class GLM(_Tempered, _Metric, _GLMBase):
     TemperingLadder).  Arguments are checked on the host before anything touches the GPU."""
 
     pointwise = _pointwise
+    laplace = _laplace
 
     def __init__(self, X, y, family="logistic", prior_precision=1.0, prior_mean=None, weights=None, offset=None,
                  trials=None, dtype="float64", device=None):
@@ -757,6 +759,7 @@ class DispersionGLM(_Tempered, _Metric, _GLMBase):
     anything touches the GPU.  It runs on csrc/kernels_glm.hip (FAM = 3, 4, 5 of k_glm<NT, FAM, true>)."""
 
     pointwise = _pointwise
+    laplace = _laplace
 
     def __init__(self, X, y, family="negbinomial", dispersion="sample", log_dispersion_prior=None, prior_precision=1.0,
                  prior_mean=None, weights=None, offset=None, dtype="float64", device=None):
