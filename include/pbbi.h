@@ -505,6 +505,28 @@ int pbbi_potential_set_metric_diag(pbbi_potential* pot, const double* mass_diag,
  * handle has none. */
 int pbbi_potential_get_metric_diag(const pbbi_potential* pot, double* out, int out_len, int* has_out);
 /* pbbi_glm_pack_metric, the host-only packer and checker of that table, is declared in pbbi_glm_metric.h (included at the end). */
+/* A dense metric (mass matrix) on a GLM handle.  With M symmetric positive definite over the D = pbbi_potential_dim(pot) rows of
+ * the state (a sampled log-dispersion among them), M = L L^T (L lower, positive diagonal), C = M^-1 and the per-chain mass m_n of
+ * a call, chain n has the mass matrix m_n M:
+ *     draw    p = sqrt(m_n kT) L z           (z: the Philox normals drawn without a metric, same counters, same precision rule)
+ *     velocity v = C p / m_n,   kick v -= c h C g / m_n,   drift q += h v
+ *     kinetic energy K = 0.5 p^T C p / m_n = 0.5 p . v
+ * in every call the diagonal metric serves (above); uploaded momenta are p as given, v_out is the velocity above,
+ * pbbi_potential_eval does not see it.  The natural choice is the posterior precision (the Hessian at the mode): every
+ * frequency of a Gaussian posterior is then 1, whatever the correlation between its rows.  The dense identity reproduces the
+ * handle without a metric bit for bit.  The device keeps the three images of pbbi_glm_pack_metric_dense (pbbi_glm_metric.h); the
+ * dense-metric instantiations of k_glm hold C in LDS for the launch (8 DP^2 bytes) and form C g on the fp64 matrix cores.
+ * A handle carries at most ONE metric: setting either kind removes the other, and NULL to either entry removes whichever is
+ * there.  Like the diagonal one it lives on the handle: two samplers that share a handle share the metric.
+ * M: (D x D) doubles on the host, row-major, under the rules of pbbi_glm_pack_metric_dense (PBBI_ERR_INVALID); D must equal
+ * pbbi_potential_dim(pot).  Served: the handles of pbbi_potential_create_glm, _glm_ex and _glm_dispersion, float64, state
+ * dimension <= 64.  Every other handle -- no GLM handle, softmax, ordinal, hierarchical, a wider state -- is refused with
+ * PBBI_ERR_UNSUPPORTED and the reason, before the device is touched. */
+int pbbi_potential_set_metric_dense(pbbi_potential* pot, const double* M, int D);
+/* Copies the handle's dense metric, as it was given, into out (D x D doubles, out_len >= D^2; out may be NULL).  *has_out <- 1
+ * when the handle carries a dense metric, 0 when it does not -- a handle with a diagonal metric answers 0 here, and one with a
+ * dense metric answers 0 to pbbi_potential_get_metric_diag. */
+int pbbi_potential_get_metric_dense(const pbbi_potential* pot, double* out, int64_t out_len, int* has_out);
 int pbbi_potential_destroy(pbbi_potential* pot);
 int pbbi_potential_dim(const pbbi_potential* pot);
 int pbbi_potential_dtype(const pbbi_potential* pot);

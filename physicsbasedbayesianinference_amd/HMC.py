@@ -204,6 +204,16 @@ def regularized_variance(var, n):
     return n / (n + 5.0) * np.asarray(var, dtype=np.float64) + 1e-3 * 5.0 / (n + 5.0)
 
 
+def regularized_covariance(cov, n):
+    """Stan's shrinkage of a warm-up window's covariance estimate towards 1e-3 I: n / (n + 5) * cov + 1e-3 * 5 / (n + 5) * I,
+    n the draws per chain in the window.  The dense metric of HMC.adaptMassMatrix(dense=True) is its inverse."""
+    n = float(n)
+    cov = np.asarray(cov, dtype=np.float64)
+    if cov.ndim != 2 or cov.shape[0] != cov.shape[1]:
+        raise ValueError("regularized_covariance: cov must be a square matrix")
+    return n / (n + 5.0) * (0.5 * (cov + cov.T)) + 1e-3 * 5.0 / (n + 5.0) * np.eye(cov.shape[0])
+
+
 class HMC:
     def __init__(self, ensemble, simulTime, stepSize, density, potential=None, gradient=None,
                  method="Leapfrog", compat=True, rng="numpy", seed=0, verbose=True, kdk_fma=None,
@@ -479,6 +489,9 @@ class HMC:
         rng = self.rng if rng is None else rng
         if rng == "numpy" and start is not None:
             raise ValueError("start needs rng='philox' (the parity mode replays the reference's stream)")
+        if rng == "numpy" and getattr(getattr(pot, "metric", None), "ndim", 0) == 2:
+            raise ValueError("a potential with a dense metric needs rng=\"philox\": the host stream draws p = sqrt(m kT) z and "
+                             "does not see the metric's factor L")
         seed = self.seed if seed is None else int(seed)
         L = self.integrator.numSteps
         h = float(self.stepSize)
@@ -858,6 +871,9 @@ class HMC:
     def setMassMatrix(self, diag):
         """Attach a diagonal metric to the potential (one mass > 0 per row of the state; None removes it): row d of
         chain n then has mass ensemble.mass[n] * diag[d] in the draw, the kick and the kinetic energy of every call.
+        A 2-D (D, D) array is a DENSE metric instead: chain n has the mass matrix ensemble.mass[n] * M, M symmetric positive
+        definite -- laplace()'s `fit.dense_metric`, the posterior precision, is the idiom beside `fit.metric`.  It is served
+        on GLM and DispersionGLM potentials up to 64 rows and needs rng="philox"; a potential carries one metric at a time.
         The metric lives on the potential's handle, so every sampler that shares the potential shares it -- two samplers
         built on the same Python callable included: they share the traced potential (the trace cache) and hence the metric.
         Served on GLM potentials (glm.py) and on user-defined ones: custom.CustomPotential, and every callable that trace.py
@@ -870,13 +886,13 @@ class HMC:
 
     @property
     def massMatrix(self):
-        """The potential's diagonal metric (a copy) or None; ValueError for a potential that cannot carry one."""
+        """The potential's metric (a copy: 1-D diagonal or (D, D) dense) or None; ValueError for a potential that cannot carry one."""
         if not hasattr(self._pot, "set_metric"):
             raise ValueError(self._NO_METRIC + type(self._pot).__name__)
         return self._pot.metric
 
     def adaptMassMatrix(self, temperature, qStd, windows=(25, 50, 100), target=0.8, step_iterations=40, chunk=25,
-                        seed=None, chain0=0, gamma=0.05, t0=10.0, kappa=0.75, start=None):
+                        seed=None, chain0=0, gamma=0.05, t0=10.0, kappa=0.75, start=None, dense=False):
         """Windowed warm-up of the diagonal metric (Stan's scheme on the ENSEMBLE).  From a fresh start (positions drawn
         as adaptStepSize draws them) and the potential's current metric (the unit metric when it has none), for each
         window in turn, the chain state kept from one window to the next:
@@ -890,7 +906,16 @@ class HMC:
         other adapters, with one run of iteration counters over all phases.  Leaves stepSize and numSteps set (simulTime
         is kept) and returns the metric.  The warm-up state is discarded.  Potentials as for setMassMatrix: GLM and
         user-defined ones (CustomPotential, callables traced to source; trace_potential(..., prefer="source") for a
-        quadratic lambda), ValueError otherwise.  start: the warm-up's starting state (_initial_state) in place of the fresh draw."""
+        quadratic lambda), ValueError otherwise.  start: the warm-up's starting state (_initial_state) in place of the fresh draw.
+
+        dense=True adapts the DENSE metric by the same scheme: steps 3 to 5 are the pooled COVARIANCE of the window
+        (RunningStats.covariance), M = regularized_covariance(cov, n)^-1 by a host Cholesky factorisation, and set_metric(M).
+        It starts from the potential's metric as a dense one (the identity when it has none, diag(m) for a diagonal one) and
+        raises ValueError where the potential refuses a dense metric (GLM and DispersionGLM up to 64 rows carry one).
+
+        With dense=True the metric changes only when the warm-up completes: an empty ensemble, a window that diverged
+        (FloatingPointError) or any other failure leaves the potential with the metric it had on entry (so a potential that
+        had none, or a diagonal one, does not come out needing rng="philox").  dense=False makes the calls it always made."""
         pot, ens = self._pot, self.ensemble
         D, N = ens.numDimensions, ens.numParticles
         if not hasattr(pot, "set_metric"):
@@ -898,41 +923,65 @@ class HMC:
         windows = [int(w) for w in windows]
         if not windows or min(windows) < 2:
             raise ValueError("windows must hold at least one length >= 2")
+        if dense:
+            m0 = pot.metric
+            # the refusal first, before any warm-up: the current metric restated as a dense one (exact: the dense identity and
+            # a dense diagonal run what the handle ran)
+            try:
+                pot.set_metric(np.eye(D) if m0 is None else np.diag(m0) if m0.ndim == 1 else m0)
+            except _lib.PbbiError as e:
+                raise ValueError(str(e)) from None
         if N == 0:
+            if dense:
+                pot.set_metric(m0)
             return pot.metric
-        seed = ((self.seed if seed is None else int(seed)) ^ WARMUP_SEED_MASK) & 0xFFFFFFFFFFFFFFFF
-        dev, dt = pot.device, pot.dtype
-        stream = stream_ptr(dev)
-        kT = float(boltzmannConst * temperature)
-        q_state = empty((D, N), dt, dev)
-        ratio = empty((1, N), dt, dev)
-        md = self._mass()
-        mptr = md.data_ptr() if md is not None else None
-        self._initial_state(q_state, qStd, seed, 0, chain0, start)
-        chunk = max(1, int(chunk))
-        samples = empty((min(chunk, max(windows)), D, N), dt, dev)
-        flags = self._flags() & ~_lib.COMPAT_P_FROM_OLDQ
-        it = 0
-        for w in windows:
+        try:
+            seed = ((self.seed if seed is None else int(seed)) ^ WARMUP_SEED_MASK) & 0xFFFFFFFFFFFFFFFF
+            dev, dt = pot.device, pot.dtype
+            stream = stream_ptr(dev)
+            kT = float(boltzmannConst * temperature)
+            q_state = empty((D, N), dt, dev)
+            ratio = empty((1, N), dt, dev)
+            md = self._mass()
+            mptr = md.data_ptr() if md is not None else None
+            self._initial_state(q_state, qStd, seed, 0, chain0, start)
+            chunk = max(1, int(chunk))
+            samples = empty((min(chunk, max(windows)), D, N), dt, dev)
+            flags = self._flags() & ~_lib.COMPAT_P_FROM_OLDQ
+            it = 0
+            for w in windows:
+                self._dualAverage(q_state, ratio, mptr, kT, seed, chain0, it, step_iterations, target, gamma, t0, kappa)
+                it += int(step_iterations)
+                stats = RunningStats(D, N, max_lag=0, device=dev)
+                h, L = float(self.stepSize), int(self.integrator.numSteps)
+                done = 0
+                while done < w:
+                    c = min(chunk, w - done)
+                    _lib.call("pbbi_hmc_run", pot.handle, self.integrator.method_id, q_state.data_ptr(), mptr,
+                              samples.data_ptr(), None, None, None, N, N, h, L, c, flags, seed, it + 1 + done, int(chain0),
+                              kT, stream)
+                    stats.update(samples[:c])
+                    done += c
+                it += w
+                if dense:
+                    cov = stats.covariance()[1]
+                    if not np.all(np.isfinite(cov)):
+                        raise FloatingPointError("adaptMassMatrix: the warm-up window diverged (non-finite covariance)")
+                    Lc = np.linalg.cholesky(regularized_covariance(cov, w))     # positive definite: the shrinkage adds a multiple of I
+                    Li = np.linalg.solve(Lc, np.eye(D))
+                    M = Li.T @ Li
+                    pot.set_metric(0.5 * (M + M.T))
+                    continue
+                var = stats.moments()[1]
+                if not np.all(np.isfinite(var)):
+                    raise FloatingPointError("adaptMassMatrix: the warm-up window diverged (non-finite variance)")
+                pot.set_metric(1.0 / regularized_variance(var, w))
             self._dualAverage(q_state, ratio, mptr, kT, seed, chain0, it, step_iterations, target, gamma, t0, kappa)
-            it += int(step_iterations)
-            stats = RunningStats(D, N, max_lag=0, device=dev)
-            h, L = float(self.stepSize), int(self.integrator.numSteps)
-            done = 0
-            while done < w:
-                c = min(chunk, w - done)
-                _lib.call("pbbi_hmc_run", pot.handle, self.integrator.method_id, q_state.data_ptr(), mptr,
-                          samples.data_ptr(), None, None, None, N, N, h, L, c, flags, seed, it + 1 + done, int(chain0),
-                          kT, stream)
-                stats.update(samples[:c])
-                done += c
-            it += w
-            var = stats.moments()[1]
-            if not np.all(np.isfinite(var)):
-                raise FloatingPointError("adaptMassMatrix: the warm-up window diverged (non-finite variance)")
-            pot.set_metric(1.0 / regularized_variance(var, w))
-        self._dualAverage(q_state, ratio, mptr, kT, seed, chain0, it, step_iterations, target, gamma, t0, kappa)
-        return pot.metric
+            return pot.metric
+        except BaseException:
+            if dense:               # a dense warm-up that did not finish leaves the potential's metric as it found it
+                pot.set_metric(m0)
+            raise
 
     def adaptTrajectoryLength(self, temperature, qStd, iterations=12, max_steps=None, quantile=0.5,
                               seed=None, chain0=0):

@@ -90,6 +90,9 @@ PROTOTYPES = {
     # the diagonal metric of a GLM handle (glm.py `set_metric`, HMC.adaptMassMatrix)
     "pbbi_potential_set_metric_diag": [_vp, _dp, _i],
     "pbbi_potential_get_metric_diag": [_vp, _dp, _i, C.POINTER(C.c_int)],
+    # ... and the dense one (a 2-D `set_metric`, HMC.adaptMassMatrix(dense=True))
+    "pbbi_potential_set_metric_dense": [_vp, _dp, _i],
+    "pbbi_potential_get_metric_dense": [_vp, _dp, _i64, C.POINTER(C.c_int)],
     "pbbi_potential_destroy": [_vp],
     "pbbi_potential_dim": [_vp],
     "pbbi_potential_dtype": [_vp],
@@ -141,6 +144,8 @@ PROTOTYPES = {
 # PROTOTYPES as an entry whose order of rejections it spells out; this packer's rules are tests/test_glm_metric_host.py's.
 HOST_PACKER_PROTOTYPES = {
     "pbbi_glm_pack_metric": [_i, _dp, _dp, _i64, C.POINTER(C.c_int64)],   # the diagonal metric's table (glm.pack_metric)
+    # the dense metric's three images (glm.pack_metric_dense); its rules are tests/test_glm_dense_metric_host.py's
+    "pbbi_glm_pack_metric_dense": [_i, _dp, _dp, _i64, C.POINTER(C.c_int64)],
 }
 
 # ... and the two entries of ordinal regression (include/pbbi_glm_ordinal.h): the order of their rejections is spelt out in

@@ -376,8 +376,60 @@ static void metric_tables() {
     EXPECT(glm_metric_max_dim(GLM_V_SOFTMAX, PBBI_GLM_SOFTMAX, 0, 64, 2) == 0 && glm_metric_max_dim(GLM_V_SOFTMAX, PBBI_GLM_SOFTMAX, 0, 32, 4) == 128);
 }
 
+// the dense metric's images: 3 DP^2 doubles, C | L | M in A-fragment order, over an exactly-sized (D x D) matrix and an exactly-
+// sized output; the first entry of each image is its [0][0], the last (lane 63, e = 1 of the last K-step pair of the last block)
+// its [DP - 1][DP - 1]
+static void dense_metric_images() {
+    for (int D : {1, 5, 16, 17, 33, 64}) {
+        const int DP = glm_padded_dim(D);
+        const int64_t len = 3 * (int64_t)DP * DP;
+        int64_t n = -1;
+        EXPECT(pbbi_glm_pack_metric_dense(D, nullptr, nullptr, 0, &n) == PBBI_OK && n == len && glm_metric_dense_len(D) == len);
+        // tridiagonal, diagonally dominant: 2 + (i % 3) on the diagonal, -0.5 beside it
+        Buf<double> M = dbuf((int64_t)D * D, 0.0);
+        for (int i = 0; i < D; ++i) {
+            M[(size_t)i * D + i] = 2.0 + (double)(i % 3);
+            if (i + 1 < D) M[(size_t)i * D + i + 1] = M[(size_t)(i + 1) * D + i] = -0.5;
+        }
+        EXPECT(glm_check_metric_dense(D, M.get()) == PBBI_OK);
+        Buf<double> out = dbuf(len, -7.0);
+        EXPECT(pbbi_glm_pack_metric_dense(D, M.get(), out.get(), len, &n) == PBBI_OK && n == len);
+        const size_t sq = (size_t)DP * DP;
+        EXPECT(out[2 * sq] == 2.0 && out[sq] == std::sqrt(2.0));
+        const double last = D == DP ? M[(size_t)D * D - 1] : 1.0;
+        EXPECT(out[3 * sq - 1] == last);
+        if (D < DP) EXPECT(out[sq - 1] == 1.0 && out[2 * sq - 1] == 1.0);  // the identity on the padding
+        for (int64_t i = 0; i < len; ++i)
+            if (!std::isfinite(out[(size_t)i]) || out[(size_t)i] == -7.0) { EXPECT(!"an entry of the images was left unwritten"); break; }
+        EXPECT(pbbi_glm_pack_metric_dense(D, M.get(), out.get(), len - 1, &n) == PBBI_ERR_INVALID && g_error.find("shorter") != std::string::npos);
+        EXPECT(pbbi_glm_pack_metric_dense(D, nullptr, out.get(), len, &n) == PBBI_ERR_INVALID);
+        // the rules, in their order: finite, symmetric, positive definite
+        const double keep = M[(size_t)D * D - 1];
+        M[(size_t)D * D - 1] = NAN;
+        EXPECT(glm_check_metric_dense(D, M.get()) == PBBI_ERR_INVALID && g_error.find("finite") != std::string::npos);
+        M[(size_t)D * D - 1] = -keep;
+        EXPECT(glm_check_metric_dense(D, M.get()) == PBBI_ERR_INVALID && g_error.find("positive definite") != std::string::npos);
+        M[(size_t)D * D - 1] = keep;
+        if (D > 1) {
+            M[1] += 1e-6;
+            EXPECT(glm_check_metric_dense(D, M.get()) == PBBI_ERR_INVALID && g_error.find("symmetric") != std::string::npos);
+            M[1] -= 1e-6;
+        }
+        EXPECT(glm_check_metric_dense(D, M.get()) == PBBI_OK);
+    }
+    EXPECT(pbbi_glm_pack_metric_dense(0, nullptr, nullptr, 0, nullptr) == PBBI_ERR_UNSUPPORTED);
+    EXPECT(pbbi_glm_pack_metric_dense(65, nullptr, nullptr, 0, nullptr) == PBBI_ERR_UNSUPPORTED && glm_check_metric_dense(65, nullptr) == PBBI_ERR_UNSUPPORTED);
+    // which dense-metric kernels ship: the plain and full models and the dispersion families up to 64 rows, nothing else
+    EXPECT(glm_dense_metric_max_dim(GLM_V_PLAIN, PBBI_GLM_LOGISTIC) == 64 && glm_dense_metric_max_dim(GLM_V_FULL, PBBI_GLM_POISSON) == 64);
+    for (int f : {PBBI_GLM_GAUSSIAN, PBBI_GLM_NEGBINOMIAL, PBBI_GLM_GAMMA}) EXPECT(glm_dense_metric_max_dim(GLM_V_DISPERSION, f) == 64);
+    for (int v : {(int)GLM_V_SOFTMAX, (int)GLM_V_HIER, (int)GLM_V_HIER_NC, (int)GLM_V_HIER_Q, (int)GLM_V_HIER_DISPERSION, (int)GLM_V_ORDINAL, 99})
+        for (int f = 0; f < 7; ++f) EXPECT(glm_dense_metric_max_dim(v, f) == 0);
+    EXPECT(glm_dense_metric_max_rows(PBBI_GLM_ORDINAL, true, 0) == 0 && glm_dense_metric_max_rows(PBBI_GLM_LOGISTIC, true, 1) == 0);
+}
+
 int main() {
     metric_tables();
+    dense_metric_images();
     design_and_observations();
     hierarchical_tables();
     penalties();

@@ -97,6 +97,13 @@ static void glm_pack_p1(int KS, int64_t b, const At& at, double* P1) {
                 P1[((size_t)s2 * 64 + l) * 2 + e] = at(16 * b + lo, 4 * (2 * s2 + e) + hi);
     }
 }
+// a (DP x DP) matrix as the A operand of a product with the state: DP / 16 blocks of 16 rows, each in that order -- the penalty of
+// the structured group priors and the three images of the dense metric
+template <class At>
+static void glm_pack_square(int DP, const At& at, double* out) {
+    const int KS = DP / 4;
+    for (int b = 0; b < DP / 16; ++b) glm_pack_p1(KS, b, at, out + (size_t)b * KS * 64);
+}
 // ... at a padded dimension DP >= D of the caller's: the image of [X | 0]
 void glm_pack_dp(int D, int DP, int64_t M, const double* X, double* out) {
     const int NT = DP / 16, KS = DP / 4;
@@ -423,11 +430,120 @@ int glm_check_penalty(int D, int J, const int32_t* groups, const double* penalty
 // The image of the (DP x DP) penalty the kernel keeps in LDS, DP = glm_padded_dim(D + J): DP / 16 blocks of 16 rows, each in
 // the first product's A-fragment order (glm_pack_p1), (Q + Q^T) / 2 on rows and columns < D and zero beyond.
 void glm_pack_penalty(int D, int J, const double* penalty, double* out) {
-    const int DP = glm_padded_dim(D + J), KS = DP / 4;
+    const int DP = glm_padded_dim(D + J);
     auto at = [&](int64_t i, int d) -> double {
         return (i < D && d < D) ? 0.5 * (penalty[(size_t)i * D + d] + penalty[(size_t)d * D + i]) : 0.0;
     };
-    for (int b = 0; b < DP / 16; ++b) glm_pack_p1(KS, b, at, out + (size_t)b * KS * 64);
+    glm_pack_square(DP, at, out);
+}
+
+// ---- the dense metric ---------------------------------------------------------------------------------------------
+int glm_dense_metric_max_dim(int variant, int family) {
+    int rows = 0;
+    switch (variant) {
+        case GLM_V_PLAIN: rows = glm_dense_metric_max_rows(family, false, 0); break;
+        case GLM_V_FULL:
+        case GLM_V_DISPERSION: rows = glm_dense_metric_max_rows(family, true, 0); break;
+        default: return 0;  // softmax, ordinal and every hierarchical variant: no dense-metric kernel is built
+    }
+    const int parent = glm_max_dim(variant, family);
+    return rows < parent ? rows : parent;
+}
+
+// The lower Cholesky factor of the symmetric (D x D) matrix a (row-major) into l (zero above the diagonal); false where a pivot
+// is not > 0 (or not a number): the matrix is not positive definite.
+static bool glm_cholesky(int D, const std::vector<double>& a, std::vector<double>& l) {
+    l.assign((size_t)D * D, 0.0);
+    for (int j = 0; j < D; ++j) {
+        double piv = a[(size_t)j * D + j];
+        for (int k = 0; k < j; ++k) piv -= l[(size_t)j * D + k] * l[(size_t)j * D + k];
+        if (!(piv > 0.0) || !std::isfinite(piv)) return false;
+        const double ljj = std::sqrt(piv);
+        l[(size_t)j * D + j] = ljj;
+        for (int i = j + 1; i < D; ++i) {
+            double s = a[(size_t)i * D + j];
+            for (int k = 0; k < j; ++k) s -= l[(size_t)i * D + k] * l[(size_t)j * D + k];
+            l[(size_t)i * D + j] = s / ljj;
+        }
+    }
+    return true;
+}
+
+// (M + M^T) / 2 of the caller's matrix
+static std::vector<double> glm_symmetrised(int D, const double* M) {
+    std::vector<double> a((size_t)D * D);
+    for (int i = 0; i < D; ++i)
+        for (int j = 0; j < D; ++j) a[(size_t)i * D + j] = 0.5 * (M[(size_t)i * D + j] + M[(size_t)j * D + i]);
+    return a;
+}
+
+// the dense metric's rule on the dimension, stated once for the checker and for the packer's length call
+static int glm_check_metric_dense_dim(int D) {
+    if (D < 1 || D > 64)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "dense metric: need 1 <= D <= 64 (D = " + std::to_string(D) + "): the kernels keep the "
+                                               "(DP x DP) inverse in LDS, 8 DP^2 bytes");
+    return PBBI_OK;
+}
+
+int glm_check_metric_dense(int D, const double* M) {
+    if (int rc = glm_check_metric_dense_dim(D)) return rc;
+    if (!M) return pbbi_fail(PBBI_ERR_INVALID, "dense metric: M is NULL");
+    double big = 0.0, asym = 0.0;
+    for (int i = 0; i < D; ++i)
+        for (int j = 0; j < D; ++j) {
+            const double v = M[(size_t)i * D + j];
+            if (!std::isfinite(v))
+                return pbbi_fail(PBBI_ERR_INVALID, "dense metric: M must be finite (entry " + std::to_string(i) + ", " + std::to_string(j) + ")");
+            big = std::fmax(big, std::fabs(v));
+            asym = std::fmax(asym, std::fabs(v - M[(size_t)j * D + i]));
+        }
+    if (asym > 1e-12 * big) return pbbi_fail(PBBI_ERR_INVALID, "dense metric: M must be symmetric (max|M - M^T| <= 1e-12 max|M|)");
+    std::vector<double> l;
+    if (!glm_cholesky(D, glm_symmetrised(D, M), l))
+        return pbbi_fail(PBBI_ERR_INVALID, "dense metric: M must be positive definite (the Cholesky factorisation met a pivot <= 0)");
+    return PBBI_OK;
+}
+
+int64_t glm_metric_dense_len(int D) { return 3 * (int64_t)glm_padded_dim(D) * glm_padded_dim(D); }
+
+// C = M^-1 | L | M, each (DP x DP) in the first product's A-fragment order (glm_pack_square), the identity on rows and columns >=
+// D.  The caller has run glm_check_metric_dense.  C from the factor: column j of L^-1 by forward substitution, C = L^-T L^-1.
+void glm_pack_metric_dense(int D, const double* M, double* out) {
+    const int DP = glm_padded_dim(D);
+    const std::vector<double> a = glm_symmetrised(D, M);
+    std::vector<double> l, li((size_t)D * D, 0.0), c((size_t)D * D, 0.0);
+    glm_cholesky(D, a, l);
+    for (int j = 0; j < D; ++j)
+        for (int i = j; i < D; ++i) {
+            double s = i == j ? 1.0 : 0.0;
+            for (int k = j; k < i; ++k) s -= l[(size_t)i * D + k] * li[(size_t)k * D + j];
+            li[(size_t)i * D + j] = s / l[(size_t)i * D + i];
+        }
+    for (int i = 0; i < D; ++i)
+        for (int j = 0; j <= i; ++j) {
+            double s = 0.0;
+            for (int k = i; k < D; ++k) s += li[(size_t)k * D + i] * li[(size_t)k * D + j];
+            c[(size_t)i * D + j] = c[(size_t)j * D + i] = s;
+        }
+    const std::vector<double>* src[3] = {&c, &l, &a};
+    for (int m = 0; m < 3; ++m) {
+        const std::vector<double>& v = *src[m];
+        auto at = [&](int64_t i, int d) -> double { return (i < D && d < D) ? v[(size_t)i * D + d] : (i == d ? 1.0 : 0.0); };
+        glm_pack_square(DP, at, out + (size_t)m * DP * DP);
+    }
+}
+
+// the exported packer and checker (include/pbbi_glm_metric.h): the images' length first (out = NULL), the checks before anything
+// is written
+int pbbi_glm_pack_metric_dense(int D, const double* M, double* out, int64_t out_len, int64_t* len_out) {
+    if (int rc = glm_check_metric_dense_dim(D)) return rc;
+    const int64_t len = glm_metric_dense_len(D);
+    if (len_out) *len_out = len;
+    if (!out) return PBBI_OK;
+    if (int rc = glm_check_metric_dense(D, M)) return rc;
+    if (out_len < len) return pbbi_fail(PBBI_ERR_INVALID, "out is shorter than the dense metric's images");
+    glm_pack_metric_dense(D, M, out);
+    return PBBI_OK;
 }
 
 // ---- pointwise log-likelihood over draws ------------------------------------------------------------------------

@@ -68,6 +68,26 @@ int glm_metric_max_dim(int variant, int family, int hier_nc, int dp, int K);
 // ---- the diagonal metric's table: {m_d, 1 / m_d} of the DP = glm_padded_dim(D) rows, {1, 1} past D (2 DP doubles)
 int glm_check_metric(int D, const double* mass_diag);  // every entry finite and > 0
 void glm_pack_metric(int D, const double* mass_diag, double* out);
+// ... and glm_metric_max_rows' sibling for the dense metric (METRIC = GLM_METRIC_DENSE of k_glm): the largest PADDED row count (16,
+// 32, 64; 0 = none) at which the dense twin of k_glm<NT, family, rich, hier> builds without scratch at its parent's waves per SIMD
+// (profiles/glm_dense_metric_resources.txt).  The C image alone is 8 DP^2 bytes of LDS, 128 KiB at 128 rows: nothing there.  The
+// hierarchical kernels and the ordinal family are not built with it.  constexpr: the launch switch instantiates by it,
+// pbbi_potential_set_metric_dense refuses by it.
+constexpr int glm_dense_metric_max_rows(int family, bool rich, int hier) {
+    if (hier != 0) return 0;
+    if (glm_canonical(family)) return 64;
+    return rich && glm_disp(family) ? 64 : 0;
+}
+// the same question asked of a handle: the largest state dimension its variant's dense-metric kernels serve (0 = none)
+int glm_dense_metric_max_dim(int variant, int family);
+// ---- the dense metric: a (D x D) symmetric positive-definite mass matrix M = L L^T, C = M^-1.  glm_check_metric_dense: 1 <= D <=
+// 64 (PBBI_ERR_UNSUPPORTED), every entry finite, max|M - M^T| <= 1e-12 max|M| (the penalty's rule; (M + M^T) / 2 is used), the
+// Cholesky factorisation completes with every pivot > 0 (PBBI_ERR_INVALID) -- in that order.  glm_pack_metric_dense: three (DP x
+// DP) images, DP = glm_padded_dim(D), in the first product's A-fragment order (the penalty's writer): C, L and M, each the
+// identity on the padding rows and columns; 3 DP^2 doubles.
+int glm_check_metric_dense(int D, const double* M);
+int64_t glm_metric_dense_len(int D);
+void glm_pack_metric_dense(int D, const double* M, double* out);
 
 // ---- the design matrix
 int glm_padded_dim(int D);                   // 16, 32, 64 or 128

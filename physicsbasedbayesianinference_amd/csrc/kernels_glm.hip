@@ -120,6 +120,7 @@
 #include "pbbi_chain.h"
 
 int glm_launch_metric(const pbbi_potential* pot, const void* glm_prm, hipStream_t stream);  // glm_prm: a GlmPrm of this file
+int glm_launch_metric_dense(const pbbi_potential* pot, const void* glm_prm, hipStream_t stream);  // (kernels_glm_dense_metric.hip)
 
 namespace {
 
@@ -195,8 +196,19 @@ template <class Prm>
 struct GlmPrmMetric : Prm {
     const double* metric;  // {m_d, 1 / m_d} of each of the DP rows, {1, 1} past D (glm_pack_metric, glm_host.cpp)
 };
-template <int FAM, bool RICH, int HIER, bool METRIC>
-using GlmKernelArgs = std::conditional_t<METRIC, GlmPrmMetric<typename GlmArgs<FAM, RICH, HIER>::type>, typename GlmArgs<FAM, RICH, HIER>::type>;
+// the dense metric's (METRIC = GLM_METRIC_DENSE of k_glm): the same arguments plus the three images
+template <class Prm>
+struct GlmPrmMetricDense : Prm {
+    const double* dimg;  // C = M^-1 | L | M, each (DP x DP) in the first product's A-fragment order (glm_pack_metric_dense, glm_host.cpp)
+};
+// METRIC of k_glm: no metric, the diagonal one, the dense one.  (ints, not an unnamed enum: they are compared in the kernels'
+// signature, an unnamed type there enters the mangled name, and the host and device passes number unnamed types differently --
+// the host would register a name the code object does not hold)
+constexpr int GLM_METRIC_NONE = 0, GLM_METRIC_DIAG = 1, GLM_METRIC_DENSE = 2;
+template <int FAM, bool RICH, int HIER, int METRIC>
+using GlmKernelArgs = std::conditional_t<METRIC == GLM_METRIC_DENSE, GlmPrmMetricDense<typename GlmArgs<FAM, RICH, HIER>::type>,
+                                         std::conditional_t<METRIC == GLM_METRIC_DIAG, GlmPrmMetric<typename GlmArgs<FAM, RICH, HIER>::type>,
+                                                            typename GlmArgs<FAM, RICH, HIER>::type>>;
 enum { GLM_HMC = 0, GLM_INTEGRATE = 1, GLM_EVAL = 2, GLM_ENERGY = 3, GLM_RATIO = 4 };
 
 template <int NT>
@@ -381,7 +393,11 @@ __device__ __forceinline__ void glm_grad(const typename GlmArgs<FAM, RICH, HIER>
 // The dispersion families with a hierarchical prior (centred and non-centred) need no case of their own: all twelve build without
 // scratch at their families' counts (profiles/glm_hier_dispersion_resources.txt).
 // The Gamma family runs at the Gaussian's counts, DP = 128 included (profiles/glm_gamma_resources.txt).
-constexpr int glm_waves_per_simd(int NT, int fam, int hier) {
+// The dense metric's twins run at their parents' counts but for the Poisson kernels at DP = 64: those parents reach two waves by
+// register count under a bound of one, and their dense twins, left at that bound, take 285 registers; asked for two they build in
+// 254 without scratch (profiles/glm_dense_metric_resources.txt).
+constexpr int glm_waves_per_simd(int NT, int fam, int hier, int metric = GLM_METRIC_NONE) {
+    if (metric == GLM_METRIC_DENSE && NT == 4 && fam == PBBI_GLM_POISSON) return 2;
     if (fam == PBBI_GLM_ORDINAL) return 1;  // at the logistic's two waves the 16- and 32-row kernels reserve 212 / 324 bytes of scratch
     return (NT <= 2 && !(NT == 2 && (fam == PBBI_GLM_NEGBINOMIAL || (hier == GLM_HIER_NC && fam == PBBI_GLM_LOGISTIC)))) ? 2 : 1;
 }
@@ -394,9 +410,37 @@ constexpr int glm_waves_per_simd(int NT, int fam, int hier) {
 // used -- KS more values per lane in registers would cost the DP = 64 and 128 kernels theirs.  It enters the draw (p = z sqrt(m_n
 // m_d kT)), the velocity (v = p / (m_n m_d)), the kick (ck / m_d), p = v m_n m_d at the end and both kinetic energies (sum p^2 /
 // m_d, then / m_n); the drift, the gradient and U never see it.  Every one of these is today's operation with one more factor, so
-// a table of ones multiplies by exactly 1.0 and the run is today's bit for bit.  METRIC = false: nothing of it is compiled.
-template <int NT, int FAM, bool RICH, int HIER = GLM_HIER_NONE, bool METRIC = false>
-__global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_glm(GlmKernelArgs<FAM, RICH, HIER, METRIC> prm) {
+// a table of ones multiplies by exactly 1.0 and the run is today's bit for bit.  METRIC = GLM_METRIC_NONE: nothing of it is compiled.
+//
+// The dense metric (METRIC = GLM_METRIC_DENSE; pbbi_potential_set_metric_dense): chain n has the mass matrix m_n M, M = L L^T, C =
+// M^-1 (include/pbbi.h has the model).  vh stays the velocity.  C sits in LDS behind plds for the launch (clds, 8 DP^2 bytes in the
+// first product's A-fragment order, like the penalty of GLM_HIER_Q); L and M are used once per iteration and their fragments are
+// read straight from memory.  A state register is the B operand of a K-step as it sits and tile t of the product comes out with
+// register r = row 16t + 4r + g, so no value moves between lanes:
+//   draw      p = L (z sqrt(m_n kT))      into gacc (dead before the first gradient), then vh
+//   velocity  C p into gacc; pp = sum p_s (C p)_s is formed THERE, where both are in hand; vh = (C p) / m_n
+//   kick      the rows' gradients (likelihood and prior) go into gacc in place; C g tile by tile with gacc as the B operand, the
+//             four registers of the tile kicked and drifted at once -- one output tile is live at a time
+//   the end   p = m_n (M v) into gacc (dead after the last kick); pp = sum p_s (m_n v_s), C p = m_n v being what v is
+// The kinetic energy is 0.5 pp / m_n as without a metric.  With M = I every product is exact and every other operation is the one
+// of the kernel without a metric on the same values: the dense identity reproduces it bit for bit.  Padding rows: the images are
+// the identity there, their momenta, gradients and velocities are exact zeros.
+template <int KS, class Bop>
+__device__ __forceinline__ v4f64 glm_square_tile(const v2f64* __restrict__ A, int t, const Bop& b) {  // A: the image + lane
+    v4f64 acc = v4f64{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s2 = 0; s2 < KS / 2; ++s2) {
+        const v2f64 a = A[(t * (KS / 2) + s2) * 64];
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, b(2 * s2), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, b(2 * s2 + 1), acc, 0, 0, 0);
+    }
+    return acc;
+}
+template <int NT, int FAM, bool RICH, int HIER = GLM_HIER_NONE, int METRIC_KIND = GLM_METRIC_NONE>
+__global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER, METRIC_KIND)) k_glm(GlmKernelArgs<FAM, RICH, HIER, METRIC_KIND> prm) {
+    constexpr bool METRIC = METRIC_KIND == GLM_METRIC_DIAG;  // (the diagonal metric's statements below read as they always have)
+    constexpr bool DENSE = METRIC_KIND == GLM_METRIC_DENSE;
+    static_assert(!DENSE || (HIER == GLM_HIER_NONE && FAM != PBBI_GLM_ORDINAL && NT <= 4), "the dense metric: no hierarchical prior, not the ordinal family, DP <= 64");
     static_assert(RICH || !glm_disp(FAM), "the dispersion families live on the full model's frame");
     static_assert(HIER == GLM_HIER_NONE || RICH, "the hierarchical prior lives on the full model's frame");
     static_assert(HIER != GLM_HIER_Q || !glm_disp(FAM), "structured group priors: logistic and poisson only");
@@ -413,7 +457,9 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
     // ordinal family: then {A_k, 0}, 8 entries
     constexpr bool ORD = FAM == PBBI_GLM_ORDINAL;
     constexpr int PL = RICH ? DP + (HAS_NJ ? 4 : 0) + (HIER == GLM_HIER_Q ? DP * DP / 2 : 0) + (ORD ? 8 : 0) : 0;
-    __shared__ __attribute__((aligned(16))) v2f64 plds[PL + (METRIC ? DP : 0) > 0 ? PL + (METRIC ? DP : 0) : 1];
+    // DENSE: behind plds the C image instead (clds below), DP^2 / 2 entries
+    constexpr int ML = METRIC ? DP : DENSE ? DP * DP / 2 : 0;
+    __shared__ __attribute__((aligned(16))) v2f64 plds[PL + ML > 0 ? PL + ML : 1];
     if constexpr (RICH) {
         for (int i = threadIdx.x; i < DP; i += BLOCK) plds[i] = v2f64{prm.prior[i], prm.prior[DP + i]};
         if constexpr (HAS_NJ)
@@ -424,12 +470,17 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
             const v2f64* __restrict__ qsrc = reinterpret_cast<const v2f64*>(prm.qimg);
             for (int i = threadIdx.x; i < DP * DP / 2; i += BLOCK) plds[DP + 4 + i] = qsrc[i];
         }
-        if constexpr (!METRIC) __syncthreads();
+        if constexpr (!METRIC && !DENSE) __syncthreads();
     }
     [[maybe_unused]] v2f64* const mlds = plds + PL;
     if constexpr (METRIC) {
         const v2f64* __restrict__ msrc = reinterpret_cast<const v2f64*>(prm.metric);
         for (int i = threadIdx.x; i < DP; i += BLOCK) mlds[i] = msrc[i];
+        __syncthreads();
+    }
+    if constexpr (DENSE) {
+        const v2f64* __restrict__ csrc = reinterpret_cast<const v2f64*>(prm.dimg);
+        for (int i = threadIdx.x; i < DP * DP / 2; i += BLOCK) mlds[i] = csrc[i];
         __syncthreads();
     }
     const int lane = threadIdx.x & 63;
@@ -485,6 +536,13 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
                 }
             }
         }
+        if constexpr (DENSE) {  // p = L (z sqrt(m_n kT)), L's fragments from memory
+            const v2f64* __restrict__ LA = reinterpret_cast<const v2f64*>(prm.dimg) + DP * DP / 2 + lane;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) gacc[t] = glm_square_tile<KS>(LA, t, [&](int s) { return vh[s]; });
+#pragma unroll
+            for (int s = 0; s < KS; ++s) vh[s] = gacc[s >> 2][s & 3];
+        }
         u = rng_uniform(prm.seed, prm.iter, chain);
         if (have_pout && !(prm.flags & PBBI_COMPAT_P_FROM_OLDQ) && valid) {
             // non-compat: a rejected chain reports its drawn momentum; park the draw now
@@ -502,18 +560,24 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
 #pragma unroll
     for (int s = 0; s < KS; ++s) q[s] = load_row(qin, vin, s4in, s);
     double pp_old = 0.0;
+    if constexpr (DENSE) {  // C p into gacc while p is the operand; sum_s p_s (C p)_s
+#pragma unroll
+        for (int t = 0; t < NT; ++t) gacc[t] = glm_square_tile<KS>(mlds + lane, t, [&](int s) { return vh[s]; });
+    }
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
         if constexpr (METRIC) pp_old = fma(vh[s] * mlds[4 * s + g].y, vh[s], pp_old);  // sum_d p_d^2 / m_d
+        else if constexpr (DENSE) pp_old = fma(vh[s], gacc[s >> 2][s & 3], pp_old);
         else pp_old = fma(vh[s], vh[s], pp_old);
     }
     // (the sum is FORMED here: left to the compiler it is sunk to the accept test, and the drawn momenta and the table's
     //  entries stay in registers across the whole trajectory -- 388 bytes of scratch at DP = 128)
-    if constexpr (METRIC) pp_old = vgpr_fresh(pp_old);
+    if constexpr (METRIC || DENSE) pp_old = vgpr_fresh(pp_old);
     if (traj) {
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
             if constexpr (METRIC) vh[s] *= minv * mlds[4 * s + g].y;  // v = p / (m_n m_d)
+            else if constexpr (DENSE) vh[s] = gacc[s >> 2][s & 3] * minv;  // v = C p / m_n
             else vh[s] *= minv;  // v = p/m
         }
     }
@@ -722,6 +786,8 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
                 const v2f64 pm = plds[4 * s + g];
                 dq[s] = (pm.x < 0.0) ? q[s] - pm.y : 0.0;
             }
+            // (the product below is glm_square_tile's, the form the dense metric shares; it stays written out here so that these
+            // kernels keep the code they have)
             // Q dq tile by tile: register r of tile t is row 16t + 4r + g of this lane's chain.  Consumed at once: the
             // lane's share of S_j and tau_j (Q dq) into the gradient of member rows.
             const v2f64* __restrict__ QA = plds + (DP + 4) + lane;
@@ -831,10 +897,26 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
                 } else {
                     gt = fma(lam, q[s], gacc[t][r]);
                 }
-                if constexpr (METRIC) vh[s] = fma(-gt, ck * mlds[4 * s + gm].y, vh[s]);  // (ck != 0 here: no 0 * inf)
-                else vh[s] = fma(-gt, ck, vh[s]);
-                q[s] = fma(vh[s], hd, q[s]);
+                if constexpr (DENSE) {
+                    gacc[t][r] = gt;  // the row's whole gradient in place: the B operand of C g below
+                } else {
+                    if constexpr (METRIC) vh[s] = fma(-gt, ck * mlds[4 * s + gm].y, vh[s]);  // (ck != 0 here: no 0 * inf)
+                    else vh[s] = fma(-gt, ck, vh[s]);
+                    q[s] = fma(vh[s], hd, q[s]);
+                }
             }
+        if constexpr (DENSE) {  // C g tile by tile, the tile's four rows kicked and drifted at once
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const v4f64 cg = glm_square_tile<KS>(mlds + lane, t, [&](int s) { return gacc[s >> 2][s & 3]; });
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int s = 4 * t + r;
+                    vh[s] = fma(-cg[r], ck, vh[s]);
+                    q[s] = fma(vh[s], hd, q[s]);
+                }
+            }
+        }
     }
 
     if (mode == GLM_EVAL) {
@@ -880,11 +962,17 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
         return;
     }
     if (mode == GLM_INTEGRATE) {  // in place q, p; optional Integrator.v
+        if constexpr (DENSE) {  // p = m_n (M v), M's fragments from memory
+            const v2f64* __restrict__ MA = reinterpret_cast<const v2f64*>(prm.dimg) + DP * DP + lane;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) gacc[t] = glm_square_tile<KS>(MA, t, [&](int s) { return vh[s]; });
+        }
         if (valid) {
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
                 store_row(qout, vout, s4out, s, q[s]);
-                if constexpr (METRIC) store_row(pout, vout, s4out, s, (prm.mass ? vh[s] * m : vh[s]) * mlds[4 * s + vgpr_fresh(g)].x);
+                if constexpr (DENSE) store_row(pout, vout, s4out, s, prm.mass ? gacc[s >> 2][s & 3] * m : gacc[s >> 2][s & 3]);
+                else if constexpr (METRIC) store_row(pout, vout, s4out, s, (prm.mass ? vh[s] * m : vh[s]) * mlds[4 * s + vgpr_fresh(g)].x);
                 else store_row(pout, vout, s4out, s, prm.mass ? vh[s] * m : vh[s]);
             }
             if (prm.v_out) {
@@ -900,8 +988,19 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
     double pp_new = 0.0;
     [[maybe_unused]] int ge = g;
     if constexpr (METRIC) ge = vgpr_fresh(g);  // (read again, as at the kick)
+    if constexpr (DENSE) {  // M v into gacc while v is the operand
+        const v2f64* __restrict__ MA = reinterpret_cast<const v2f64*>(prm.dimg) + DP * DP + lane;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) gacc[t] = glm_square_tile<KS>(MA, t, [&](int s) { return vh[s]; });
+    }
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
+        if constexpr (DENSE) {  // p = m_n (M v) and C p = m_n v: sum_s p_s (C p)_s; vh now holds p
+            const double cp = prm.mass ? vh[s] * m : vh[s];
+            vh[s] = prm.mass ? gacc[s >> 2][s & 3] * m : gacc[s >> 2][s & 3];
+            pp_new = fma(vh[s], cp, pp_new);
+            continue;
+        }
         if (prm.mass) vh[s] *= m;  // p = v*m; vh now holds p
         if constexpr (METRIC) {
             const v2f64 md = mlds[4 * s + ge];
@@ -918,6 +1017,11 @@ __global__ void __launch_bounds__(BLOCK, glm_waves_per_simd(NT, FAM, HIER)) k_gl
     // so the step that rejects a fifth of the proposals is close to the one that diverges, and a chain that accepted a NaN never
     // leaves it: here a NaN energy is an infinite one, a rejected proposal.
     if constexpr (FAM == PBBI_GLM_ORDINAL) newH = (newH == newH) ? newH : __builtin_inf();
+    // dense metric: a gradient row that overflowed at the last evaluation is an infinite momentum and an infinite energy in the
+    // kernels without a product (rejected); through C g it meets the zeros of the image as 0 * inf, a NaN in every row of the chain,
+    // a NaN energy and an ACCEPTED proposal.  A NaN energy is an infinite one here too: the proposal is rejected as it is there,
+    // with the ratio 0 it has there.
+    if constexpr (DENSE) newH = (newH == newH) ? newH : __builtin_inf();
     const double ratio = exp((oldH - newH) * pbbi_accept_beta(prm.flags, prm.kT));
     const bool reject = metropolis_reject(ratio, u);
     const bool compat = (prm.flags & PBBI_COMPAT_P_FROM_OLDQ) != 0;
@@ -992,24 +1096,33 @@ Prm glm_prm_hier(const pbbi_potential* pot, const GlmPrm& prm) {
 
 // One case per variant of handle (glm_host.h), each building the one argument struct its kernels take.  A variant, family or
 // padded dimension with no shipped kernel launches nothing and is PBBI_ERR_UNSUPPORTED.
-template <bool GLM_METRIC_PASS>
+template <int GLM_METRIC_PASS>  // GLM_METRIC_NONE / _DIAG / _DENSE: the one kind of kernel this pass instantiates
 int glm_launch_pass(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t stream) {
     const dim3 grid((unsigned)((prm.N + CHAINS_PER_WG - 1) / CHAINS_PER_WG)), block(BLOCK);
     const int NT = pot->glm_DP / 16, fam = pot->glm_family;
     bool done = false;
 // a handle without a metric launches the kernel it always has; one with a metric the METRIC twin of the same case, which
-// takes the same arguments plus the table
+// takes the same arguments plus the table (the dense metric: plus the images), where that twin is shipped
 #define GLM_CASE(NT_, FAM_, RICH_, HIER_, PRM_)                                                             \
     if (NT == NT_ && fam == FAM_) {                                                                         \
-        if constexpr (!GLM_METRIC_PASS) {                                                                   \
+        if constexpr (GLM_METRIC_PASS == GLM_METRIC_NONE) {                                                 \
             hipLaunchKernelGGL((k_glm<NT_, FAM_, RICH_, HIER_>), grid, block, 0, stream, PRM_);             \
-        } else if constexpr (16 * NT_ <= glm_metric_max_rows(FAM_, RICH_, HIER_)) {                         \
-            GlmPrmMetric<std::decay_t<decltype(PRM_)>> am{};                                                \
-            static_cast<std::decay_t<decltype(PRM_)>&>(am) = PRM_;                                          \
-            am.metric = (const double*)pot->d_glm_metric;                                                   \
-            hipLaunchKernelGGL((k_glm<NT_, FAM_, RICH_, HIER_, true>), grid, block, 0, stream, am);         \
+            done = true;                                                                                    \
+        } else if constexpr (GLM_METRIC_PASS == GLM_METRIC_DIAG) {                                          \
+            if constexpr (16 * NT_ <= glm_metric_max_rows(FAM_, RICH_, HIER_)) {                            \
+                GlmPrmMetric<std::decay_t<decltype(PRM_)>> am{};                                            \
+                static_cast<std::decay_t<decltype(PRM_)>&>(am) = PRM_;                                      \
+                am.metric = (const double*)pot->d_glm_metric;                                               \
+                hipLaunchKernelGGL((k_glm<NT_, FAM_, RICH_, HIER_, GLM_METRIC_DIAG>), grid, block, 0, stream, am); \
+                done = true;                                                                                \
+            }                                                                                               \
+        } else if constexpr (16 * NT_ <= glm_dense_metric_max_rows(FAM_, RICH_, HIER_)) {                   \
+            GlmPrmMetricDense<std::decay_t<decltype(PRM_)>> ad{};                                           \
+            static_cast<std::decay_t<decltype(PRM_)>&>(ad) = PRM_;                                          \
+            ad.dimg = (const double*)pot->d_glm_metric_dense;                                               \
+            hipLaunchKernelGGL((k_glm<NT_, FAM_, RICH_, HIER_, GLM_METRIC_DENSE>), grid, block, 0, stream, ad); \
+            done = true;                                                                                    \
         }                                                                                                   \
-        done = !GLM_METRIC_PASS || 16 * NT_ <= glm_metric_max_rows(FAM_, RICH_, HIER_);                     \
     }
 // (K_ is the case list's kernel of the variant in hand.  The lists keep the order they have always had: it is the order in which
 // the kernels are instantiated and laid out in the code object.)
@@ -1088,7 +1201,8 @@ int glm_launch_pass(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t st
 #ifndef PBBI_GLM_METRIC_TU
 // the existing case lists here, the METRIC lists in a translation unit of their own (kernels_glm_metric.hip, see the end)
 int glm_launch(const pbbi_potential* pot, const GlmPrm& prm, hipStream_t stream) {
-    if (!pot->d_glm_metric) return glm_launch_pass<false>(pot, prm, stream);
+    if (pot->d_glm_metric_dense) return glm_launch_metric_dense(pot, &prm, stream);
+    if (!pot->d_glm_metric) return glm_launch_pass<GLM_METRIC_NONE>(pot, prm, stream);
     return glm_launch_metric(pot, &prm, stream);
 }
 
@@ -1108,9 +1222,15 @@ int glm_run(const Args& a, int mode) {
 // PBBI_GLM_METRIC_TU and includes it): with both lists in one module the compiler lays the kernels without a metric out
 // differently -- 15 of the 53 move by a register or two although their code is the same text -- and the kernels of a handle
 // without a metric must stay what they are.  That unit holds the METRIC case lists and this entry, nothing else.
-#ifdef PBBI_GLM_METRIC_TU
+// The dense metric's instantiations are a third unit for the same reason (kernels_glm_dense_metric.hip defines PBBI_GLM_METRIC_TU
+// as 2): the diagonal metric's kernels stay what they are too.
+#if defined(PBBI_GLM_METRIC_TU) && PBBI_GLM_METRIC_TU == 2
+int glm_launch_metric_dense(const pbbi_potential* pot, const void* glm_prm, hipStream_t stream) {
+    return glm_launch_pass<GLM_METRIC_DENSE>(pot, *static_cast<const GlmPrm*>(glm_prm), stream);
+}
+#elif defined(PBBI_GLM_METRIC_TU)
 int glm_launch_metric(const pbbi_potential* pot, const void* glm_prm, hipStream_t stream) {
-    return glm_launch_pass<true>(pot, *static_cast<const GlmPrm*>(glm_prm), stream);
+    return glm_launch_pass<GLM_METRIC_DIAG>(pot, *static_cast<const GlmPrm*>(glm_prm), stream);
 }
 #else
 

@@ -104,6 +104,7 @@ int new_handle(int kind, int D, int dtype, int device, pbbi_potential** out) {
     p->glm_variant = GLM_V_PLAIN;  // (means something on a KIND_GLM handle only, and its builder sets it)
     p->d_glm_metric = nullptr; p->glm_metric_diag = nullptr;
     p->d_glm_obs0 = nullptr; p->glm_power = 1.0;
+    p->d_glm_metric_dense = nullptr; p->glm_metric_dense = nullptr;
     *out = p;
     return PBBI_OK;
 }
@@ -1231,6 +1232,14 @@ int pbbi_glm_pack_design(int D, int64_t M, const double* X, double* out, int64_t
     return PBBI_OK;
 }
 
+// lets a handle's dense metric go (under the caller's DeviceGuard)
+static void drop_metric_dense(pbbi_potential* pot) {
+    if (pot->d_glm_metric_dense) (void)hipFree(pot->d_glm_metric_dense);
+    pot->d_glm_metric_dense = nullptr;
+    delete[] pot->glm_metric_dense;
+    pot->glm_metric_dense = nullptr;
+}
+
 // The diagonal metric of a GLM or user-defined handle (include/pbbi.h).  Every rule before the device is touched; the new table
 // is uploaded before the old one is let go, so a failure leaves the handle as it was.
 int pbbi_potential_set_metric_diag(pbbi_potential* pot, const double* mass_diag, int D) {
@@ -1240,7 +1249,8 @@ int pbbi_potential_set_metric_diag(pbbi_potential* pot, const double* mass_diag,
         return pbbi_fail(PBBI_ERR_UNSUPPORTED, "a diagonal metric is served on GLM handles only (the METRIC instantiations of k_glm "
                                                "and k_glm_softmax)");
     DeviceGuard guard(pot->device);
-    if (!mass_diag) {
+    if (!mass_diag) {  // a handle carries at most one metric: NULL removes whichever it has
+        drop_metric_dense(pot);
         if (pot->d_glm_metric) PBBI_HIP(hipFree(pot->d_glm_metric));
         pot->d_glm_metric = nullptr;
         delete[] pot->glm_metric_diag;
@@ -1291,6 +1301,59 @@ int pbbi_potential_set_metric_diag(pbbi_potential* pot, const double* mass_diag,
     delete[] pot->glm_metric_diag;
     pot->d_glm_metric = fresh;
     pot->glm_metric_diag = keep;
+    drop_metric_dense(pot);  // setting either kind removes the other
+    return PBBI_OK;
+}
+
+// The dense metric of a GLM handle (include/pbbi.h).  Every rule before the device is touched; the new images are uploaded before
+// the old ones are let go, so a failure leaves the handle as it was.
+int pbbi_potential_set_metric_dense(pbbi_potential* pot, const double* M, int D) {
+    if (!pot) return pbbi_fail(PBBI_ERR_INVALID, "potential handle is NULL");
+    if (pot->kind != KIND_GLM || pot->glm_DP == 0)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "a dense metric is served on GLM handles only (the dense-metric instantiations of k_glm)");
+    if (!M) return pbbi_potential_set_metric_diag(pot, nullptr, 0);
+    if (pot->dtype != PBBI_F64) return pbbi_fail(PBBI_ERR_UNSUPPORTED, "dense metric: float64 handles only");
+    const int top = glm_dense_metric_max_dim(pot->glm_variant, pot->glm_family);
+    if (top == 0)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "dense metric: served on the handles of pbbi_potential_create_glm, _glm_ex and "
+                                               "_glm_dispersion (logistic, poisson, gaussian, negbinomial, gamma); no dense-metric "
+                                               "kernel is built for softmax, ordinal and hierarchical handles");
+    if (D != pot->D)
+        return pbbi_fail(PBBI_ERR_INVALID, "dense metric: D must equal the handle's state dimension (D = " + std::to_string(D) +
+                                               ", state dimension " + std::to_string(pot->D) + ")");
+    if (pot->D > top)
+        return pbbi_fail(PBBI_ERR_UNSUPPORTED, "dense metric: state dimension " + std::to_string(pot->D) + ", served up to " +
+                                                   std::to_string(top) + " -- the kernels keep the (DP x DP) inverse in LDS, 8 DP^2 "
+                                                   "bytes, and a twin that would spill registers to memory is not shipped");
+    if (int rc = glm_check_metric_dense(D, M)) return rc;
+    DeviceGuard guard(pot->device);
+    std::vector<double> img((size_t)glm_metric_dense_len(D));  // glm_DP = glm_padded_dim(D) on these variants
+    glm_pack_metric_dense(D, M, img.data());
+    void* fresh = nullptr;
+    if (int rc = upload(img.data(), img.size(), PBBI_F64, &fresh)) return rc;
+    double* keep = new (std::nothrow) double[(size_t)D * D];
+    if (!keep) {
+        (void)hipFree(fresh);
+        return pbbi_fail(PBBI_ERR_INVALID, "out of host memory");
+    }
+    std::memcpy(keep, M, sizeof(double) * (size_t)D * D);
+    drop_metric_dense(pot);
+    pot->d_glm_metric_dense = fresh;
+    pot->glm_metric_dense = keep;
+    if (pot->d_glm_metric) (void)hipFree(pot->d_glm_metric);  // setting either kind removes the other
+    pot->d_glm_metric = nullptr;
+    delete[] pot->glm_metric_diag;
+    pot->glm_metric_diag = nullptr;
+    return PBBI_OK;
+}
+
+int pbbi_potential_get_metric_dense(const pbbi_potential* pot, double* out, int64_t out_len, int* has_out) {
+    if (!pot) return pbbi_fail(PBBI_ERR_INVALID, "potential handle is NULL");
+    const bool has = pot->kind == KIND_GLM && pot->glm_metric_dense != nullptr;
+    if (has_out) *has_out = has ? 1 : 0;
+    if (!has || !out) return PBBI_OK;
+    if (out_len < (int64_t)pot->D * pot->D) return pbbi_fail(PBBI_ERR_INVALID, "out is shorter than the square of the handle's state dimension");
+    std::memcpy(out, pot->glm_metric_dense, sizeof(double) * (size_t)pot->D * pot->D);
     return PBBI_OK;
 }
 
@@ -1309,9 +1372,10 @@ int pbbi_potential_destroy(pbbi_potential* pot) {
     DeviceGuard guard(pot->device);
     for (void* p : {pot->d_mean, pot->d_prec, pot->d_frag, pot->d_mean_pad, pot->d_big_PT, pot->d_big_mu,
                     pot->d_sfrag, pot->d_smean, pot->d_params, pot->d_glm_img, pot->d_glm_y, pot->d_glm_obs, pot->d_glm_prior,
-                    pot->d_glm_qimg, pot->d_glm_metric, pot->d_glm_obs0})
+                    pot->d_glm_qimg, pot->d_glm_metric, pot->d_glm_obs0, pot->d_glm_metric_dense})
         if (p) (void)hipFree(p);
     delete[] pot->glm_metric_diag;
+    delete[] pot->glm_metric_dense;
     if (pot->plugin) (void)dlclose(pot->plugin);
     delete pot;
     return PBBI_OK;
@@ -1768,6 +1832,10 @@ int pbbi_describe_run(const pbbi_potential* pot, int method, int64_t N, int64_t 
     if (pot->kind == KIND_GLM && pot->d_glm_metric)
         d += "; diagonal metric: row d of chain n has mass m_n m_d, the METRIC instantiation of the kernel with the table {m_d, "
              "1 / m_d} resident in LDS (draw, kick and kinetic energy)";
+    if (pot->kind == KIND_GLM && pot->d_glm_metric_dense)
+        d += "; dense metric: chain n has the mass matrix m_n M, the dense-metric instantiation of the kernel with the (" +
+             std::to_string(pot->glm_DP) + " x " + std::to_string(pot->glm_DP) + ") inverse resident in LDS in A-fragment order, "
+             "C g one more fp64 MFMA product per gradient (L z at the draw and M v at the end read from memory)";
     d += "; iterations per launch: up to " + std::to_string(fuse < 1 ? 1 : fuse);
     if (flags & PBBI_DRAW_F64) d += "; momentum draw: double precision";
     snprintf(out, (size_t)out_len, "%s", d.c_str());

@@ -89,6 +89,10 @@ struct pbbi_potential {
     // never tempered, which then runs the bits it always has
     void* d_glm_obs0;   // d_glm_obs as built (power 1); d_glm_obs itself then holds c = beta c0 (| d = beta d0)
     double glm_power;   // the power as set from the host; NaN when it was read from the device
+    // the dense metric (pbbi_potential_set_metric_dense).  (Appended.)  NULL / NULL on a handle without one; a handle carries at
+    // most one metric, so these two and the two of the diagonal metric above are never set together
+    void* d_glm_metric_dense;   // C = M^-1 | L | M, three (glm_DP x glm_DP) images in A-fragment order (glm_pack_metric_dense)
+    double* glm_metric_dense;   // the D x D entries as given, on the host (pbbi_potential_get_metric_dense)
 };
 
 // ---- error plumbing ---------------------------------------------------------

@@ -55,7 +55,7 @@ __all__ = ["GLM", "SoftmaxGLM", "DispersionGLM", "OrdinalGLM", "HierarchicalGLM"
            "pack_prior_groups_dispersion", "FAMILIES", "DISPERSION_FAMILIES", "HIER_MAX_DIM",
            "HIER_NC_MAX_DIM", "HIER_PARAMETRISATIONS", "HIER_MAX_GROUPS", "pack_design", "pack_observations", "pack_observations_dispersion", "pack_prior_groups",
            "pack_observations_ordinal", "DISPERSION_MAX_DIM", "ORDINAL_MAX_DIM", "ORDINAL_MAX_CATEGORIES",
-           "HIER_Q_MAX_DIM", "pack_penalty", "pack_metric", "padded_dim", "softmax_layout", "PointwiseResult", "pointwise_constants"]
+           "HIER_Q_MAX_DIM", "pack_penalty", "pack_metric", "pack_metric_dense", "padded_dim", "softmax_layout", "PointwiseResult", "pointwise_constants"]
 
 FAMILIES = {"logistic": _lib.GLM_LOGISTIC, "poisson": _lib.GLM_POISSON}
 DISPERSION_FAMILIES = {"gaussian": _lib.GLM_GAUSSIAN, "negbinomial": _lib.GLM_NEGBINOMIAL,
@@ -138,6 +138,18 @@ def pack_metric(diag):
     if m.ndim != 1 or m.size < 1:
         raise ValueError("the metric must be a vector of D >= 1 masses")
     return _pack("pbbi_glm_pack_metric", (m.size,), (m,)).reshape(-1, 2)
+
+
+def pack_metric_dense(M):
+    """The three images a GLM handle with a dense metric keeps on the device, computed (and checked: D <= 64, finite,
+    symmetric to 1e-12 of the largest entry, positive definite) on the host by libpbbi.so (no GPU involved): array (3, DP
+    DP / 2, 64, 2) -- C = inv(M), the lower Cholesky factor L and M itself, each padded with the identity to DP rows and
+    laid out like pack_penalty's image, [t * DP / 8 + s2][lane][e] = A[16 t + (lane & 15)][4 (2 s2 + e) + (lane >> 4)]."""
+    m = np.ascontiguousarray(M, dtype=np.float64)
+    if m.ndim != 2 or m.shape[0] != m.shape[1] or m.shape[0] < 1:
+        raise ValueError("the dense metric must be a (D, D) matrix, D >= 1")
+    with _host_errors():
+        return _pack("pbbi_glm_pack_metric_dense", (m.shape[0],), (m,)).reshape(3, -1, 64, 2)
 
 
 def pack_design(X):

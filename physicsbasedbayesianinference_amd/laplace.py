@@ -2,6 +2,7 @@
 
     fit = pot.laplace()                       # damped Newton to the mode; fit.mode, fit.stderr, fit.log_evidence
     hmc.setMassMatrix(fit.metric)             # a metric from the curvature before the first draw
+    hmc.setMassMatrix(fit.dense_metric)       # ... or the dense one: correlated rows as well as badly scaled ones
     hmc.getSamples(S, T, 0.0, rng="philox", start=fit.sample(N, spread=1.5))   # chains over-dispersed around the mode
 
 The hot path is the Hessian X^T Lambda(eta) X of the potential at one state, on the fp64 matrix cores over the design image the
@@ -29,6 +30,7 @@ class LaplaceResult:
         covariance    hessian^-1
         stderr        sqrt(diag(covariance))
         metric        1 / diag(covariance): what HMC.setMassMatrix takes
+        dense_metric  (hessian + hessian^T) / 2: the dense metric HMC.setMassMatrix takes (GLM, DispersionGLM up to 64 rows)
         log_evidence  the Laplace log p(y)
         sample(N)     N draws of N(mode, spread^2 covariance) as a device tensor
 
@@ -71,6 +73,12 @@ class LaplaceResult:
     @property
     def metric(self):
         return 1.0 / np.diag(self.covariance)
+
+    @property
+    def dense_metric(self):
+        """The Hessian, symmetrised: the posterior precision of the approximation, what HMC.setMassMatrix takes as a DENSE
+        metric -- it removes the correlation between rows as well as their scales (`metric` removes the scales alone)."""
+        return 0.5 * (self.hessian + self.hessian.T)
 
     @property
     def log_evidence(self):

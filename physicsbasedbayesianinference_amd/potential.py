@@ -109,15 +109,26 @@ class Potential:
 class _Metric:
     """The diagonal metric of a handle that carries one (pbbi_potential_set_metric_diag: the GLM classes of glm.py and
     custom.CustomPotential): row d of chain n has mass m_n m_d in the draw, the kick and the kinetic energy of every sampler
-    call on this potential.  It lives on the handle, so every sampler that shares the potential shares it."""
+    call on this potential.  It lives on the handle, so every sampler that shares the potential shares it.
+
+    A 2-D (D, D) array is the DENSE metric instead (pbbi_potential_set_metric_dense: GLM and DispersionGLM up to 64 rows):
+    chain n has the mass matrix m_n M, M symmetric positive definite -- the posterior precision, LaplaceResult.dense_metric,
+    is the natural choice.  A handle carries at most one metric: setting either kind removes the other."""
 
     def set_metric(self, diag):
-        """diag: one mass > 0 per row of the state (for a GLM: coefficients, group log-scales, a sampled log-dispersion), or
-        None to remove the metric.  Checked on the host before anything touches the GPU."""
+        """diag: one mass > 0 per row of the state (for a GLM: coefficients, group log-scales, a sampled log-dispersion), a
+        (D, D) symmetric positive-definite mass matrix over those rows, or None to remove the metric.  Checked on the host
+        before anything touches the GPU."""
         if diag is None:
             _lib.call("pbbi_potential_set_metric_diag", self.handle, None, 0)
             return
         m = np.ascontiguousarray(diag, dtype=np.float64)
+        if m.ndim == 2:
+            if m.shape != (self.numDimensions, self.numDimensions):
+                raise ValueError(f"a dense metric must be ({self.numDimensions}, {self.numDimensions}), one row and column per "
+                                 f"row of the state, got shape {m.shape}")
+            _lib.call("pbbi_potential_set_metric_dense", self.handle, _dptr(m), m.shape[0])
+            return
         if m.ndim != 1 or m.size != self.numDimensions:
             raise ValueError(f"the metric must hold one mass per row of the state ({self.numDimensions}), got shape {m.shape}")
         if not (np.all(np.isfinite(m)) and np.all(m > 0.0)):
@@ -126,10 +137,14 @@ class _Metric:
 
     @property
     def metric(self):
-        """The metric as set (a copy), or None."""
+        """The metric as set (a copy): 1-D for the diagonal one, (D, D) for the dense one; None without one."""
         out = np.empty(self.numDimensions, dtype=np.float64)
         has = C.c_int(0)
         _lib.call("pbbi_potential_get_metric_diag", self.handle, _dptr(out), out.size, C.byref(has))
+        if has.value:
+            return out
+        out = np.empty((self.numDimensions, self.numDimensions), dtype=np.float64)
+        _lib.call("pbbi_potential_get_metric_dense", self.handle, _dptr(out), out.size, C.byref(has))
         return out if has.value else None
 
 
