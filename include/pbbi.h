@@ -54,6 +54,33 @@
  *     (csrc/pbbi_rng.h, oracle/pbbi_oracle.c); exact N(0,1) on a 2^-52 grid with tails to 8.57 sigma.
  *   Metropolis uniform of a chain: block = 0xFFFFFFFF, stream = PBBI_STREAM_UNIFORM,
  *     u = ((x1:x0)>>11) * 2^-53 in [0,1).
+ *   Predictive replicates (pbbi_predictive_glm; csrc/glm_sample_dev.h, restated in NumPy with SciPy's distribution
+ *     functions by tests/glm_predictive_ref.py): stream = PBBI_STREAM_PREDICTIVE.  The block of (draw t, observation i,
+ *     index b) is counter (chain = i, block = b, iteration = t), t = s * N + n the global draw index (S * N <= 2^32), so a
+ *     replicate depends on (seed, t, i) alone.  The uniform of a block: u = ((x1:x0 >> 11) + 0.5) * 2^-53 in double arithmetic, never 0 (and 1 only for
+ *     the one k = 2^53 - 1, where the sum rounds up: every sampler below is defined at u = 1); the
+ *     normal of a block: the FIRST normal (z_even) of the double-precision Box-Muller above.  eta = x_i . w_t + o_i.
+ *     Every sampler is exact; none is replaced by a normal approximation:
+ *       gaussian     y = eta + exp(theta) / sqrt(a_i) * z,  z the normal of block 0.
+ *       poisson, logistic (binomial n_i), negbinomial (mean mu = exp(eta), shape phi = exp(theta), p = phi / (phi + mu)):
+ *                    inversion of the uniform of block 0 over the support enumerated from the mode outwards: m, m + 1, m - 1,
+ *                    m + 2, m - 2, ..., points outside the support skipped; y = the first point at which the accumulated
+ *                    mass reaches u (cum >= u).  m = floor(mu); min(n, floor((n + 1) p)); max(0, floor((phi - 1) mu / phi)).
+ *                    The mass at m from glm_lgamma, its neighbours by the one-division ratio recurrences f(k + 1) / f(k) =
+ *                    mu / (k + 1); (n - k) r / (k + 1), r = exp(eta); (k + phi) q / (k + 1), q = mu / (mu + phi), and their
+ *                    inverses.  The walk ends when the terms on both sides are 0 and returns the last point visited that had
+ *                    positive mass.  n_i = 1: y = 1 if u < p, else 0, without a walk.  O(sigma) steps per value: a
+ *                    distribution whose VARIANCE is above 2^20 (mu; n p (1 - p); mu + mu^2 / phi) is NOT SERVED and gives
+ *                    NaN, as does a walk longer than 2^20 rounds (only a shape phi -> 0 gets there); a rejection sampler for
+ *                    large means would be a different stream number.
+ *       ordinal      inversion of the uniform of block 0 over the K cumulative probabilities sigma(kappa_j - eta) in category
+ *                    order: y = the first category whose cumulative probability is >= u.
+ *       gamma        shape alpha = exp(theta), mean mu = exp(eta).  Marsaglia-Tsang: d = alpha - 1/3 (alpha + 2/3 when
+ *                    alpha < 1), c = 1 / sqrt(9 d); attempt j = 0, 1, ... takes z = the normal of block 2j and u = the uniform
+ *                    of block 2j + 1, v = (1 + c z)^3, and accepts if v > 0 and log u < z^2 / 2 + d - d v + d log v;
+ *                    y = d v mu / alpha, times u'^(1 / alpha) with u' the uniform of block 0x80000000 when alpha < 1.  After
+ *                    64 attempts the value is NaN.
+ *     A non-finite eta or mean gives NaN.
  *   The integer part is bit-identical to oracle/pbbi_oracle.c; the single-precision
  *   transcendental part agrees with the host mirror to ~1e-6 absolute.
  */
@@ -114,6 +141,7 @@ enum {
 enum { PBBI_STREAM_MOMENTUM = 0, PBBI_STREAM_POSITION = 1, PBBI_STREAM_UNIFORM = 2, PBBI_STREAM_STEPS = 3,
        PBBI_STREAM_SWAP = 4, /* replica-exchange uniforms (pbbi_replica_exchange) */
        PBBI_STREAM_RESAMPLE = 5, /* the stage uniform of systematic resampling (pbbi_smc_resample_systematic) */
+       PBBI_STREAM_PREDICTIVE = 6, /* posterior predictive replicates (pbbi_predictive_glm; "Predictive replicates" above) */
        /* OR-ed into pbbi_philox_normal's rng_stream: the draw PBBI_DRAW_F64 selects in pbbi_hmc_run */
        PBBI_STREAM_DRAW_F64 = 0x100 };
 
@@ -456,6 +484,40 @@ int pbbi_loglik_glm(const pbbi_potential* pot, const void* samples_sdn, int S, i
  * with NULL. */
 int pbbi_loglik_glm_check(int handle, int family, int state_dim, const void* samples, const void* ulik_out, int S, int Dt,
                           int64_t N, int ranges);
+/* Posterior predictive replicates of a GLM handle, drawn on the device (csrc/kernels_glm_predictive.hip: pbbi_loglik_glm's
+ * frame -- a wave keeps 16 draws in registers and walks the observation blocks, eta on the fp64 matrix cores -- with the
+ * family samplers of the RNG contract's section "Predictive replicates" in the lane).  For each of the S * N draws t = s * N + n
+ * and each observation i one replicate y_rep ~ p(y | draw t), reduced per draw over the observations of weight a_i != 0:
+ *     stats_out[k * S * N + t], k =    0  sum of (y_rep - centre)          1  sum of (y_rep - centre)^2
+ *                                      2  min y_rep      3  max y_rep      4  number of y_rep <= cut
+ *                                      5  sum of log f(y_rep_i | draw t)   6  sum of log f(y_i | draw t)
+ * 5 and 6 are the full proper log densities by one code path, the terms pbbi_pointwise_glm leaves to its caller included
+ * (log C(n, y); -lgamma(y + 1); the Gaussian constant; -log y), UNWEIGHTED except for the Gaussian family, where a_i is a
+ * precision weight (variance sigma^2 / a_i); in the other families a weight changes no replicate's distribution.
+ * aux: the image y | n | a on the device -- three runs of 16 * ceil(M / 64) * 4 doubles, zero padded: the response, the
+ * binomial trials (1 elsewhere) and the weight.  The handle's own streams are not read, except its offset (0 for a handle of
+ * pbbi_potential_create_glm); a likelihood power on the handle changes nothing.  samples_sdn, Dt, the rows that are read and
+ * `ranges` (over the observation blocks): as for pbbi_loglik_glm.
+ * yrep_out: NULL (keep = 0), or a (keep, M) matrix on the device that receives the replicates of draws t < keep; a row with
+ * a_i = 0 is NaN there.  Neither the statistics nor yrep_out depend on `ranges`, on the order tiles run in or on whether yrep_out
+ * is given -- a replicate is a function of (seed, t, i) -- except that the SUMS (0, 1, 5, 6) add their ranges in index order, so
+ * another `ranges` may change their last bits (integer-valued sums are exact); for a given `ranges` every bit repeats.
+ * A non-finite eta or mean gives a NaN replicate; so does a DISCRETE replicate whose distribution has variance above 2^20,
+ * which is not served (the inversion walks O(sigma) points per value), and a Gamma value none of whose 64 attempts accepts.  A
+ * NaN replicate makes statistics 0, 1, 2, 3 and 5 of its own draw NaN, and no other draw's.
+ * Rules, in this order, the first nine those of pbbi_loglik_glm without its output: NULL handle, NULL samples, S < 1, N < 1,
+ * ranges outside 0 .. 65535: PBBI_ERR_INVALID; a handle that is no GLM handle, a softmax handle, an unknown family:
+ * PBBI_ERR_UNSUPPORTED; Dt below the state dimension; NULL aux; NULL stats_out; S * N > 2^32; keep outside 0 .. S * N; keep > 0
+ * without yrep_out or yrep_out with keep = 0; centre or cut not finite; keep * M > 2^28: PBBI_ERR_INVALID.  All before the device
+ * is touched.  Shipped: the 22 shapes of pbbi_loglik_glm; none reserves scratch memory. */
+int pbbi_predictive_glm(const pbbi_potential* pot, const void* samples_sdn, int S, int Dt, int64_t N, uint64_t seed,
+                        const double* aux, double centre, double cut, int ranges, double* stats_out, int64_t keep,
+                        double* yrep_out, void* stream);
+/* Those rules alone but the last (it needs the handle's M), on the HOST, for a handle described by value (as
+ * pbbi_pointwise_glm_check); the pointers are only compared with NULL; yrep_given != 0: yrep_out is given. */
+int pbbi_predictive_glm_check(int handle, int family, int state_dim, const void* samples, const void* aux,
+                              const void* stats_out, int S, int Dt, int64_t N, int ranges, int64_t keep, int yrep_given,
+                              double centre, double cut);
 /* The likelihood power of a GLM handle: the handle's potential becomes -log [ p(w) L(w)^beta ] (prior terms untouched), the path
  * from the prior (beta -> 0) to the posterior (beta = 1) of likelihood-tempered SMC.  Raising the likelihood to the power beta is
  * multiplying every observation weight a_i by beta, so no kernel changes: a small kernel writes c <- beta c0 on the handle's

@@ -16,7 +16,7 @@ from .potential import (GaussianDense, GaussianDiag, Harmonic, Potential, Rosenb
 from .integrator import Integrator, Leapfrog, StormerVerlet
 from .HMC import HMC
 from .custom import CustomPotential
-from .glm import GLM, SoftmaxGLM, DispersionGLM, OrdinalGLM, HierarchicalGLM, HierarchicalDispersionGLM, pack_observations_dispersion, pack_prior_groups
+from .glm import GLM, SoftmaxGLM, DispersionGLM, OrdinalGLM, HierarchicalGLM, HierarchicalDispersionGLM, pack_observations_dispersion, pack_prior_groups, PredictiveResult
 from .laplace import LaplaceResult
 from .stats import RunningHistogram, RunningStats
 from .smc import LikelihoodTemperedSMC
@@ -27,6 +27,6 @@ __all__ = ["Ensemble", "HMC", "Integrator", "Leapfrog", "StormerVerlet", "Potent
            "Harmonic", "GaussianDiag", "StandardGaussian", "GaussianDense", "Rosenbrock",
            "harmonicPotentialND", "linear_regression_posterior", "CustomPotential", "GLM", "SoftmaxGLM", "DispersionGLM", "OrdinalGLM",
            "HierarchicalGLM", "HierarchicalDispersionGLM", "pack_observations_dispersion", "pack_prior_groups", "RunningStats",
-           "RunningHistogram", "LikelihoodTemperedSMC", "LaplaceResult",
+           "RunningHistogram", "LikelihoodTemperedSMC", "LaplaceResult", "PredictiveResult",
            "trace", "grad", "trace_potential"]
 __version__ = "0.1.0"

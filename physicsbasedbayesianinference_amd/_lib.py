@@ -28,6 +28,7 @@ DRAW_F64 = 32            # momenta drawn in double precision (include/pbbi.h)
 STREAM_MOMENTUM, STREAM_POSITION, STREAM_UNIFORM, STREAM_STEPS = 0, 1, 2, 3
 STREAM_SWAP = 4
 STREAM_RESAMPLE = 5      # the stage uniform of systematic resampling (pbbi_smc_resample_systematic)
+STREAM_PREDICTIVE = 6    # posterior predictive replicates (pbbi_predictive_glm)
 STREAM_DRAW_F64 = 0x100  # OR-ed into pbbi_philox_normal's rng_stream: the draw DRAW_F64 selects
 
 
@@ -84,6 +85,9 @@ PROTOTYPES = {
     # smc.LikelihoodTemperedSMC; csrc/kernels_glm_loglik.hip)
     "pbbi_loglik_glm": [_vp, _vp, _i, _i, _i64, _i, _vp, _vp],
     "pbbi_loglik_glm_check": [_i, _i, _i, _vp, _vp, _i, _i, _i64, _i],
+    # posterior predictive replicates and their per-draw statistics (glm.py `predictive`; csrc/kernels_glm_predictive.hip)
+    "pbbi_predictive_glm": [_vp, _vp, _i, _i, _i64, _u64, _vp, _d, _d, _i, _vp, _i64, _vp, _vp],
+    "pbbi_predictive_glm_check": [_i, _i, _i, _vp, _vp, _vp, _i, _i, _i64, _i, _i64, _i, _d, _d],
     "pbbi_potential_set_likelihood_power": [_vp, _d, _vp, _vp],
     "pbbi_potential_get_likelihood_power": [_vp, _dp],
     "pbbi_likelihood_power_check": [_i, _i, _i, _d, _i],

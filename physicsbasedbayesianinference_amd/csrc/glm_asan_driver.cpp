@@ -299,6 +299,37 @@ static void loglik_rules() {
     EXPECT(glm_check_loglik(1, PBBI_GLM_LOGISTIC, 5, p, u, 2000000000, 5, (int64_t)1 << 40, 0) == PBBI_OK);
 }
 
+// the rules pbbi_predictive_glm adds to those it shares (above), in the order the checker states them
+static void predictive_rules() {
+    Buf<double> s = dbuf(1, 0.0);
+    const void* p = s.get();
+    const double nan = std::nan("");
+    EXPECT(glm_check_predictive(1, PBBI_GLM_POISSON, 5, p, p, p, 3, 5, 150, 0, 0, false, 1.5, 0.0) == PBBI_OK);
+    EXPECT(glm_check_predictive(1, PBBI_GLM_ORDINAL, 9, p, p, p, 1, 9, (int64_t)1 << 32, 65535, 450, true, -1.5, 2.0) == PBBI_OK);
+    EXPECT(glm_check_predictive(1, PBBI_GLM_SOFTMAX, 6, p, nullptr, nullptr, 3, 6, 150, 0, -1, true, nan, nan) == PBBI_ERR_UNSUPPORTED);
+    EXPECT(g_error.find("pbbi_predictive_glm: a softmax handle") != std::string::npos);
+    EXPECT(glm_check_predictive(1, PBBI_GLM_POISSON, 5, p, nullptr, nullptr, 3, 5, (int64_t)1 << 32, 0, -1, true, nan, nan) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("aux is NULL") != std::string::npos);
+    EXPECT(glm_check_predictive(1, PBBI_GLM_POISSON, 5, p, p, nullptr, 3, 5, (int64_t)1 << 32, 0, -1, true, nan, nan) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("stats_out is NULL") != std::string::npos);
+    EXPECT(glm_check_predictive(1, PBBI_GLM_POISSON, 5, p, p, p, 3, 5, (int64_t)1 << 32, 0, -1, true, nan, nan) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("S * N must be <= 2^32") != std::string::npos);
+    EXPECT(glm_check_predictive(1, PBBI_GLM_POISSON, 5, p, p, p, 2000000000, 5, (int64_t)1 << 40, 0, 0, false, 0.0, 0.0) == PBBI_ERR_INVALID);
+    EXPECT(glm_check_predictive(1, PBBI_GLM_POISSON, 5, p, p, p, 3, 5, 150, 0, 451, true, nan, nan) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("keep must be in") != std::string::npos);
+    EXPECT(glm_check_predictive(1, PBBI_GLM_POISSON, 5, p, p, p, 3, 5, 150, 0, 5, false, nan, nan) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("keep > 0 needs yrep_out") != std::string::npos);
+    EXPECT(glm_check_predictive(1, PBBI_GLM_POISSON, 5, p, p, p, 3, 5, 150, 0, 0, true, nan, nan) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("yrep_out needs keep > 0") != std::string::npos);
+    EXPECT(glm_check_predictive(1, PBBI_GLM_POISSON, 5, p, p, p, 3, 5, 150, 0, 0, false, nan, nan) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("centre must be finite") != std::string::npos);
+    EXPECT(glm_check_predictive(1, PBBI_GLM_POISSON, 5, p, p, p, 3, 5, 150, 0, 0, false, 0.0, INFINITY) == PBBI_ERR_INVALID);
+    EXPECT(g_error.find("cut must be finite") != std::string::npos);
+    EXPECT(glm_check_predictive_keep(0, (int64_t)1 << 40) == PBBI_OK && glm_check_predictive_keep(1 << 14, 1 << 14) == PBBI_OK);
+    EXPECT(glm_check_predictive_keep((1 << 14) + 1, 1 << 14) == PBBI_ERR_INVALID && g_error.find("keep * M") != std::string::npos);
+    EXPECT(glm_check_predictive_keep((int64_t)1 << 40, (int64_t)1 << 40) == PBBI_ERR_INVALID);   // no overflow of the product
+}
+
 // every rule of pbbi_glm_hessian's arguments, in the order the checker states them; the pointers are only compared with NULL
 static void hessian_rules() {
     Buf<double> s = dbuf(1, 0.0), o = dbuf(1, 0.0);
@@ -436,6 +467,7 @@ int main() {
     softmax_shapes();
     pointwise_rules();
     loglik_rules();
+    predictive_rules();
     hessian_rules();
     power_rules();
     // what is shipped (the one statement the entries and the launch read)

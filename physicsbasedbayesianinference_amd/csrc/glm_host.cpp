@@ -590,6 +590,34 @@ int glm_check_loglik(int handle, int family, int state_dim, const void* sdn, con
     return glm_check_draws("pbbi_loglik_glm: ", handle, family, state_dim, sdn, out == nullptr, S, Dt, N, ranges, false);
 }
 
+// ---- posterior predictive replicates ----------------------------------------------------------------------------
+// The rules pbbi_predictive_glm shares with the two entries above first (glm_check_draws: no output rule, no var_out), then its own.
+int glm_check_predictive(int handle, int family, int state_dim, const void* sdn, const void* aux, const void* stats_out, int S,
+                         int Dt, int64_t N, int ranges, int64_t keep, bool yrep_given, double centre, double cut) {
+    if (int rc = glm_check_draws("pbbi_predictive_glm: ", handle, family, state_dim, sdn, false, S, Dt, N, ranges, false)) return rc;
+    if (!aux) return pbbi_fail(PBBI_ERR_INVALID, "aux is NULL");
+    if (!stats_out) return pbbi_fail(PBBI_ERR_INVALID, "stats_out is NULL");
+    const int64_t two32 = (int64_t)1 << 32;
+    if (N > two32 || (int64_t)S * N > two32)  // S < 2^31 and N <= 2^32: the product is below 2^63
+        return pbbi_fail(PBBI_ERR_INVALID, "S * N must be <= 2^32: the draw index is the 32-bit iteration word of the counter "
+                                           "(S = " + std::to_string(S) + ", N = " + std::to_string(N) + ")");
+    if (keep < 0 || keep > (int64_t)S * N)
+        return pbbi_fail(PBBI_ERR_INVALID, "keep must be in 0 .. S * N (keep = " + std::to_string(keep) + ")");
+    if ((keep > 0) != yrep_given)
+        return pbbi_fail(PBBI_ERR_INVALID, keep > 0 ? "keep > 0 needs yrep_out" : "yrep_out needs keep > 0: pass NULL");
+    if (!std::isfinite(centre)) return pbbi_fail(PBBI_ERR_INVALID, "centre must be finite");
+    if (!std::isfinite(cut)) return pbbi_fail(PBBI_ERR_INVALID, "cut must be finite");
+    return PBBI_OK;
+}
+
+int glm_check_predictive_keep(int64_t keep, int64_t M) {
+    const int64_t cap = (int64_t)1 << 28;
+    if (keep > 0 && (keep > cap || keep * M > cap))
+        return pbbi_fail(PBBI_ERR_INVALID, "keep * M must be <= 2^28 values of yrep_out (keep = " + std::to_string(keep) +
+                                               ", M = " + std::to_string(M) + ")");
+    return PBBI_OK;
+}
+
 // ---- the Hessian at one state -----------------------------------------------------------------------------------
 const char* const GLM_HESSIAN_RULE = "pbbi_glm_hessian serves the handles of pbbi_potential_create_glm, _glm_ex and "
                                      "_glm_dispersion (families logistic, poisson, gaussian, negbinomial, gamma; float64; "

@@ -127,6 +127,12 @@ int glm_check_pointwise(int handle, int family, int state_dim, const void* sdn, 
 // ---- the likelihood energy of each draw (kernels_glm_loglik.hip): every argument rule of pbbi_loglik_glm, `handle` as above
 int glm_check_loglik(int handle, int family, int state_dim, const void* sdn, const void* out, int S, int Dt, int64_t N,
                      int ranges);
+// ---- posterior predictive replicates (kernels_glm_predictive.hip): every argument rule of pbbi_predictive_glm that needs no
+// handle, `handle` as above -- glm_check_draws' first, then aux, stats_out, S * N <= 2^32, keep, centre, cut -- and the one that
+// needs the handle's M (keep * M <= 2^28), which the entry checks right after them
+int glm_check_predictive(int handle, int family, int state_dim, const void* sdn, const void* aux, const void* stats_out, int S,
+                         int Dt, int64_t N, int ranges, int64_t keep, bool yrep_given, double centre, double cut);
+int glm_check_predictive_keep(int64_t keep, int64_t M);
 // ---- the Hessian at one state (kernels_glm_hessian.hip): every argument rule of pbbi_glm_hessian, `handle` as above;
 // hierarchical: the handle has group log-scales (every GLM_V_HIER* variant)
 extern const char* const GLM_HESSIAN_RULE;

@@ -38,6 +38,8 @@ in its quadratic form (random walks, difference penalties of splines, ICAR), Q_j
 per observation the log pointwise predictive density, the WAIC penalty and the posterior predictive mean, reduced over all
 draws of a (D, N, S) device view without forming an M x T matrix; a second potential on held-out data takes the same draws.
 
+`pot.predictive(samples)` draws one replicate data set per draw in the kernel (csrc/kernels_glm_predictive.hip) and returns per-draw
+test statistics and posterior predictive p-values (a `PredictiveResult`).
 `pot.loglik(samples)` is the total log-likelihood of each draw (csrc/kernels_glm_loglik.hip), `pot.sample_prior(N)` exact draws
 from a proper prior and `pot.set_likelihood_power(beta)` the potential of p(w) L(w)^beta: the three pieces of
 `smc.LikelihoodTemperedSMC`, which tempers from the prior to the posterior and returns the log marginal likelihood.
@@ -55,7 +57,7 @@ __all__ = ["GLM", "SoftmaxGLM", "DispersionGLM", "OrdinalGLM", "HierarchicalGLM"
            "pack_prior_groups_dispersion", "FAMILIES", "DISPERSION_FAMILIES", "HIER_MAX_DIM",
            "HIER_NC_MAX_DIM", "HIER_PARAMETRISATIONS", "HIER_MAX_GROUPS", "pack_design", "pack_observations", "pack_observations_dispersion", "pack_prior_groups",
            "pack_observations_ordinal", "DISPERSION_MAX_DIM", "ORDINAL_MAX_DIM", "ORDINAL_MAX_CATEGORIES",
-           "HIER_Q_MAX_DIM", "pack_penalty", "pack_metric", "pack_metric_dense", "padded_dim", "softmax_layout", "PointwiseResult", "pointwise_constants"]
+           "HIER_Q_MAX_DIM", "pack_penalty", "pack_metric", "pack_metric_dense", "padded_dim", "softmax_layout", "PointwiseResult", "pointwise_constants", "PredictiveResult"]
 
 FAMILIES = {"logistic": _lib.GLM_LOGISTIC, "poisson": _lib.GLM_POISSON}
 DISPERSION_FAMILIES = {"gaussian": _lib.GLM_GAUSSIAN, "negbinomial": _lib.GLM_NEGBINOMIAL,
@@ -335,6 +337,91 @@ class PointwiseResult:
                                                                                  self.p_waic, self.waic)
 
 
+class PredictiveResult:
+    """What `predictive` returns.  Per draw, (N, S) NumPy arrays of the test statistics of that draw's replicate data set y_rep
+    (over the observations of weight != 0): `mean`, `var` (the population variance), `min`, `max`, `frac_le_cut` (the share of
+    y_rep <= cut), `loglik_rep` = log p(y_rep | draw) and `loglik_obs` = log p(y | draw) (full proper log densities).
+    `observed`: a dict of the same statistics of the data y themselves ("mean", "var", "min", "max", "frac_le_cut").
+    `yrep`: the replicates of the first `keep` draws, (keep, M) with NaN on rows of weight 0, or None.  `T`: the number of draws."""
+
+    NAMES = ("mean", "var", "min", "max", "frac_le_cut")
+
+    def __init__(self, mean, var, min, max, frac_le_cut, loglik_rep, loglik_obs, observed, yrep=None):
+        self.mean, self.var, self.min, self.max, self.frac_le_cut = mean, var, min, max, frac_le_cut
+        self.loglik_rep, self.loglik_obs, self.observed, self.yrep = loglik_rep, loglik_obs, dict(observed), yrep
+        self.T = int(np.size(mean))
+
+    def pvalue(self, name):
+        """The posterior predictive p-value of a statistic: the share of draws with T(y_rep) >= T(y), `name` one of "mean",
+        "var", "min", "max", "frac_le_cut"; for "loglik" the discrepancy is the log density itself, which depends on the
+        draw: the share of draws with log p(y_rep | draw) <= log p(y | draw).  Draws whose statistic is NaN count as not
+        meeting the condition."""
+        if name == "loglik":
+            return float(np.mean(self.loglik_rep <= self.loglik_obs))
+        if name not in self.NAMES:
+            raise ValueError("pvalue: unknown statistic %r (one of %s, \"loglik\")" % (name, ", ".join(map(repr, self.NAMES))))
+        return float(np.mean(getattr(self, name) >= self.observed[name]))
+
+    def __repr__(self):
+        return "PredictiveResult(T=%d, %s)" % (self.T, ", ".join("p_%s=%.3g" % (n, self.pvalue(n)) for n in self.NAMES))
+
+
+def _predictive_aux(pot):
+    """(aux, on): the image y | n | a of pbbi_predictive_glm -- three runs zero padded to a multiple of 64 observations -- and
+    the mask of the rows of weight != 0."""
+    y = np.asarray(pot.y, dtype=np.float64).ravel()
+    M = y.size
+    a = np.ones(M) if pot.weights is None else np.asarray(pot.weights, dtype=np.float64)
+    n = np.ones(M) if pot.trials is None else np.asarray(pot.trials, dtype=np.float64)
+    aux = np.zeros((3, (M + 63) // 64 * 64))
+    aux[0, :M], aux[1, :M], aux[2, :M] = y, n, a
+    return aux, a != 0.0
+
+
+def _predictive(self, samples, seed=0, keep=0, cut=0.0, ranges=0):
+    """Posterior predictive checks, drawn on the device (csrc/kernels_glm_predictive.hip): for every draw one replicate data set
+    y_rep ~ p(y | draw) at the potential's own design, reduced in the kernel to per-draw test statistics -- no M x T matrix
+    unless `keep` asks for one.
+
+        r = pot.predictive(s[:, :, 500:])                # r.pvalue("var"), r.pvalue("max"), r.pvalue("frac_le_cut"): zeros
+        y_new = GLM(X_new, dummy_y).predictive(s, keep=200).yrep       # replicates at new inputs, (200, len(X_new))
+
+    `samples` as for `pointwise`.  `seed`: the replicate of (draw t, observation i) is a function of (seed, t, i) alone (the
+    RNG contract of include/pbbi.h, stream PBBI_STREAM_PREDICTIVE), t counted over the draws of THIS call in the order slab,
+    chain.  `keep`: the replicates of the first `keep` draws (in that order) come back as `yrep`, (keep, M).  `cut`: the
+    threshold of `frac_le_cut` (0: the share of zeros of count data).  `ranges` as for `loglik`.  The samplers are exact
+    (inversion from the mode for the count families, Marsaglia-Tsang for the gamma); a DISCRETE replicate whose distribution
+    has a variance above 2^20 is not served and is NaN, as is one with a non-finite linear predictor, and a NaN replicate makes
+    its own draw's mean, var, min, max and loglik_rep NaN.  Weights: a row of weight 0 takes no part (NaN in `yrep`); otherwise
+    a weight changes a replicate's distribution only for the gaussian family, where it is a precision weight (variance
+    sigma^2 / a_i); the log densities are unweighted but for that.  Returns a `PredictiveResult`."""
+    from . import _device
+    sdn, S, Dt, N = _pointwise_slabs(self, samples)
+    M, T, keep = self.y.size, S * N, int(keep)
+    aux, on = _predictive_aux(self)
+    n_on = int(np.count_nonzero(on))
+    if not n_on:
+        raise ValueError("predictive: every observation has weight 0")
+    yo = np.asarray(self.y, dtype=np.float64).ravel()[on]
+    centre = float(np.mean(yo))
+    aux_d = _device.as_device(aux, self.device, np.float64)
+    stats = _device.empty((7, T), np.float64, self.device)
+    if 0 < keep <= T and keep * M > 1 << 28:       # (the library's own rule, before the buffer is asked for)
+        raise ValueError("predictive: keep * M must be <= 2^28 values of yrep (keep = %d, M = %d)" % (keep, M))
+    yrep = _device.empty((keep, M), np.float64, self.device) if 0 < keep <= T else None
+    with _device_errors():
+        _lib.call("pbbi_predictive_glm", self.handle, sdn.data_ptr(), S, Dt, N, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                  aux_d.data_ptr(), centre, float(cut), int(ranges), stats.data_ptr(), keep,
+                  yrep.data_ptr() if yrep is not None else None, _device.stream_ptr(self.device))
+    s = _device.to_numpy(stats)
+    per = lambda v: np.ascontiguousarray(v.reshape(S, N).T)      # (N, S), as `loglik`
+    d1 = s[0] / n_on
+    observed = dict(mean=centre, var=float(np.mean((yo - centre) ** 2)), min=float(yo.min()), max=float(yo.max()),
+                    frac_le_cut=float(np.mean(yo <= float(cut))))
+    return PredictiveResult(per(centre + d1), per(s[1] / n_on - d1 * d1), per(s[2]), per(s[3]), per(s[4] / n_on), per(s[5]),
+                            per(s[6]), observed, None if yrep is None else _device.to_numpy(yrep))
+
+
 def _lgamma(x):
     import math
     return np.array([math.lgamma(v) for v in np.asarray(x, dtype=np.float64).ravel()]).reshape(np.shape(x))
@@ -592,6 +679,7 @@ class GLM(_Tempered, _Metric, _GLMBase):
     TemperingLadder).  Arguments are checked on the host before anything touches the GPU."""
 
     pointwise = _pointwise
+    predictive = _predictive
     laplace = _laplace
 
     def __init__(self, X, y, family="logistic", prior_precision=1.0, prior_mean=None, weights=None, offset=None,
@@ -771,6 +859,7 @@ class DispersionGLM(_Tempered, _Metric, _GLMBase):
     anything touches the GPU.  It runs on csrc/kernels_glm.hip (FAM = 3, 4, 5 of k_glm<NT, FAM, true>)."""
 
     pointwise = _pointwise
+    predictive = _predictive
     laplace = _laplace
 
     def __init__(self, X, y, family="negbinomial", dispersion="sample", log_dispersion_prior=None, prior_precision=1.0,
@@ -857,6 +946,7 @@ class OrdinalGLM(_Tempered, _Metric, _GLMBase):
 
     family = "ordinal"
     pointwise = _pointwise
+    predictive = _predictive
 
     def __init__(self, X, y, categories=None, prior_precision=1.0, prior_mean=None, weights=None, offset=None,
                  cutpoint_prior=((0.0, 0.1), (0.0, 1.0)), dtype="float64", device=None):
@@ -1176,6 +1266,7 @@ class HierarchicalGLM(_Tempered, _Metric, _GLMBase):
     (k_glm<NT, FAM, true, HIER>)."""
 
     pointwise = _pointwise
+    predictive = _predictive
 
     def __init__(self, X, y, family="logistic", groups=None, log_scale_prior=(0.0, 1.0), prior_precision=1.0,
                  prior_mean=None, weights=None, offset=None, trials=None, dtype="float64", device=None,

@@ -69,6 +69,12 @@ launches, ranges = 0) on the plain logistic model against the same vector from t
 link elementwise, a sum over the observations: loglik_torch), alternating in one process, at the same two shapes and slabs.  It
 writes profiles/glm_loglik_bench.json.
 
+--model predictive times pbbi_predictive_glm (csrc/kernels_glm_predictive.hip: one Poisson replicate per draw and observation
+and the seven per-draw statistics) against the same statistics from torch.poisson and torch ops over chunks of draws
+(predictive_torch), alternating in one process after two warm-up calls, at the two shapes of SHAPES with --slabs 8 slabs of N
+draws; and the kernel alone with the means scaled up, for the cost of the inversion's O(sigma) walk.  It writes
+profiles/glm_predictive_bench.json.
+
 usage: tools/bench_glm.py [--shape small|large|all] [--K 32] [--repeats 5] [--glm-only] [--out FILE]
        tools/bench_glm.py --model rich [--custom] [--label NAME] [--shape ...]
        tools/bench_glm.py --model softmax [--shape k3|k8|k8large|all]
@@ -80,6 +86,7 @@ usage: tools/bench_glm.py [--shape small|large|all] [--K 32] [--repeats 5] [--gl
        tools/bench_glm.py --model hierdisp [--shape small|large|all]
        tools/bench_glm.py --model pointwise [--shape small|large|all] [--slabs 8] [--repeats 5]
        tools/bench_glm.py --model loglik [--shape small|large|all] [--slabs 8] [--repeats 5]
+       tools/bench_glm.py --model predictive [--shape small|large|all] [--slabs 8] [--repeats 5]
        tools/bench_glm.py --model hier [--parametrisation centred|noncentred] [--shape small|large|all]  (noncentred: also mid)
 """
 import argparse
@@ -1137,6 +1144,99 @@ def bench_loglik(name, M, D, N, S, repeats, warm):
                 max_rel_difference_kernel_vs_torch=agree)
 
 
+def predictive_torch(X, y, sdn, chunk, centre, cut):
+    """The baseline of --model predictive: the same seven per-draw statistics from torch ops on the same device -- matmul over
+    chunks of `chunk` draws (an M x chunk matrix at a time), torch.poisson for the replicates, the Poisson log density of the
+    replicates and of y elementwise, reductions over the observations."""
+    S, D, N = sdn.shape
+    out = torch.empty((7, S, N), dtype=torch.float64, device=sdn.device)
+    lgy = torch.lgamma(y + 1.0)[:, None]
+    for s in range(S):
+        for n0 in range(0, N, chunk):
+            eta = X @ sdn[s, :, n0:n0 + chunk]
+            mu = eta.exp()
+            rep = torch.poisson(mu)
+            d = rep - centre
+            o = out[:, s, n0:n0 + chunk]
+            o[0], o[1], o[2], o[3] = d.sum(dim=0), (d * d).sum(dim=0), rep.amin(dim=0), rep.amax(dim=0)
+            o[4] = (rep <= cut).sum(dim=0)
+            o[5] = (rep * eta - mu - torch.lgamma(rep + 1.0)).sum(dim=0)
+            o[6] = (y[:, None] * eta - mu - lgy).sum(dim=0)
+    return out
+
+
+def bench_predictive(name, M, D, N, S, repeats, warm):
+    """pbbi_predictive_glm (both launches, ranges = 0, no yrep_out) against predictive_torch on S slabs of N draws of the plain
+    Poisson model, alternating in one process after `warm` calls of each; both sides produce the seven statistics of all S * N
+    draws.  A timed window is several calls (at least a quarter of a second) and one synchronisation; times are per call.  The
+    replicates differ (two generators), so the sides are held together by statistic 6, which draws nothing, and by the means of
+    statistic 0 over all draws.  `kernel_ns_per_value_by_mean_shift`: the kernel alone with every mean multiplied by exp(shift) --
+    what the O(sigma) walk of the inversion costs as the means grow."""
+    from physicsbasedbayesianinference_amd import _device
+    rs = np.random.RandomState(0)
+    X = rs.standard_normal((M, D)) / np.sqrt(D)
+    w = 0.5 * rs.standard_normal(D)
+    y = rs.poisson(np.exp(X @ w + 1.0)).astype(np.float64)
+    X = np.ascontiguousarray(np.c_[X[:, :D - 1], np.ones(M)])      # the last column an intercept; its coefficient 1
+    w[D - 1] = 1.0
+    pot = P.GLM(X, y, family="poisson")
+    sdn = torch.from_numpy(np.ascontiguousarray(w[None, :, None] + 0.1 * rs.standard_normal((S, D, N)))).to("cuda:0")
+    Xd, yd = torch.from_numpy(X).to("cuda:0"), torch.from_numpy(y).to("cuda:0")
+    chunk = N
+    while M * chunk > 2 ** 25 and chunk % 2 == 0:     # an M x chunk matrix of at most 256 MiB (N is a power of two)
+        chunk //= 2
+    T, centre, cut = S * N, float(y.mean()), 0.0
+    aux = torch.from_numpy(glm._predictive_aux(pot)[0]).to("cuda:0")
+    out = torch.empty((7, T), dtype=torch.float64, device="cuda:0")
+    st = _device.stream_ptr(0)
+
+    def kernel(draws=sdn):
+        _lib.call("pbbi_predictive_glm", pot.handle, draws.data_ptr(), S, D, N, 1, aux.data_ptr(), centre, cut, 0, out.data_ptr(),
+                  0, None, st)
+        return out
+
+    def baseline():
+        return predictive_torch(Xd, yd, sdn, chunk, centre, cut).reshape(7, T)
+
+    def window(f, calls):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            f()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / calls
+
+    sides = {"kernel": kernel, "torch": baseline}
+    for _ in range(warm):
+        got = [f().cpu().numpy() for f in sides.values()]
+    agree = float(np.max(np.abs(got[0][6] - got[1][6])) / max(1.0, float(np.max(np.abs(got[1][6])))))
+    mean_rep = [float(centre + g[0].mean() / M) for g in got]
+    calls = max(1, int(np.ceil(0.25 / window(kernel, 1))))
+    series = {k: [] for k in sides}
+    for i in range(repeats):
+        for k, f in sides.items():   # alternating
+            series[k].append(window(f, calls))
+            print(f"# {name} repeat {i} {k}: {series[k][-1]:.6f} s per call ({calls} calls)", flush=True)
+    tk, tt = np.array(series["kernel"]), np.array(series["torch"])
+    eta_max = float((Xd @ sdn[0]).max().item())
+    by_shift = {}
+    for shift in (0.0, 2.0, 4.0, 8.0):      # the intercept's coefficient moved: means times 1, 7.4, 55, 2981
+        moved = sdn.clone()
+        moved[:, D - 1, :] += shift
+        kernel(moved)
+        ts = [window(lambda: kernel(moved), max(1, calls // 4)) for _ in range(3)]
+        by_shift["%g" % shift] = dict(largest_fitted_mean=float(np.exp(eta_max + shift)), ns_per_value=float(np.median(ts) / (M * T) * 1e9),
+                                      nan_draws=int(torch.isnan(out[0]).sum().item()))
+    return dict(shape=name, family="poisson", M=M, D=D, DP=glm.padded_dim(D), slabs=S, chains=N, draws=T, torch_chunk=chunk,
+                calls_per_window=calls, kernel_seconds=series["kernel"], torch_seconds=series["torch"],
+                kernel_median_seconds=float(np.median(tk)), torch_median_seconds=float(np.median(tt)),
+                kernel_range_seconds=[float(tk.min()), float(tk.max())], torch_range_seconds=[float(tt.min()), float(tt.max())],
+                kernel_ns_per_value=float(np.median(tk) / (M * T) * 1e9), torch_ns_per_value=float(np.median(tt) / (M * T) * 1e9),
+                largest_fitted_mean=float(np.exp(eta_max)), kernel_ns_per_value_by_mean_shift=by_shift,
+                ratio_median=float(np.median(tt) / np.median(tk)), ratio_worst_case=float(tt.min() / tk.max()),
+                mean_replicate_kernel_and_torch=mean_rep, max_rel_difference_loglik_obs_kernel_vs_torch=agree)
+
+
 def bench_shape(name, M, D, N, h, L, K, repeats, warm, glm_only):
     X, y, w, rs = problem(M, D)
     q0 = np.ascontiguousarray(w[:, None] + 0.3 * rs.standard_normal((D, N)))
@@ -1180,19 +1280,19 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=None, help="default 4 (--model softmax: per shape)")
     ap.add_argument("--glm-only", action="store_true")
     ap.add_argument("--model", default="plain", choices=["plain", "rich", "softmax", "dispersion", "gamma", "hier", "hierq", "hierdisp",
-                                                         "pointwise", "loglik", "ordinal", "logistic"])
+                                                         "pointwise", "loglik", "predictive", "ordinal", "logistic"])
     ap.add_argument("--baseline", default=None, help="--model ordinal: the output file of --model logistic run on another build "
                                                      "of the library (the parent commit's), merged into the record")
     ap.add_argument("--build", default=None, help="--model logistic: a name for the build measured, kept in the record")
-    ap.add_argument("--slabs", type=int, default=8, help="--model pointwise / loglik: slabs of N draws")
+    ap.add_argument("--slabs", type=int, default=8, help="--model pointwise / loglik / predictive: slabs of N draws")
     ap.add_argument("--parametrisation", default="centred", choices=["centred", "noncentred"],
                     help="--model hier: noncentred times the non-centred kernel against the centred one and the plugin")
     ap.add_argument("--custom", action="store_true", help="--model rich: also the full model as a CustomPotential")
     ap.add_argument("--label", default="rich_vs_plain", help="--model rich: key of the record in the output file")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.model in ("pointwise", "loglik"):
-        bench_pw = bench_pointwise if a.model == "pointwise" else bench_loglik
+    if a.model in ("pointwise", "loglik", "predictive"):
+        bench_pw = {"pointwise": bench_pointwise, "loglik": bench_loglik, "predictive": bench_predictive}[a.model]
         a.out = a.out or os.path.join(ROOT, "profiles", "glm_%s_bench.json" % a.model)
         names = list(SHAPES) if a.shape == "all" else [a.shape]
         results = []
